@@ -1,4 +1,4 @@
-"""bench.py's host-side pieces without a GPU: the synthetic workload, the CPU-baseline leg, and the
+"""bench.py's host-side pieces without a GPU: the synthetic workload, the output dump, the CPU-baseline leg, and the
 refusal to run (rather than fall back) when no GPU is present."""
 import json
 import os
@@ -20,6 +20,44 @@ def test_shear_layer_shape_and_slab_consistency():
     assert u[:, 12].max() == pytest.approx(0., abs=1e-7)            # shear layers at ny/4 and 3ny/4
     r2, u2, v2 = bench.shear_layer(64, 48, 16, 16)                   # a slab sees the same rows
     assert np.array_equal(u2, u[:, 16:32]) and np.array_equal(v2, v[:, 16:32])
+
+
+@pytest.mark.parametrize("nx,ny", [(40, 24), (1100, 1000)])
+def test_dump_outputs_writes_the_same_cells_whatever_the_slabs(tmp_path, nx, ny):
+    """--dump-outputs: every cell of a small lattice, a fixed sample of DUMP_CELLS on a larger one, the same arrays from one rank
+    as from two (rank 0 assembles what all_gather_object brings)."""
+    import bench
+    rng = np.random.default_rng(1)
+    f = np.asfortranarray(rng.random((nx, ny, 9), dtype=np.float32))
+    g = {"f": f, "rho": np.asfortranarray(f.sum(axis=2)), "u": np.asfortranarray(f[:, :, 1]), "v": np.asfortranarray(f[:, :, 2])}
+    rows = lambda y0, h: {k: np.asfortranarray(a[:, y0:y0 + h]) for k, a in g.items()}     # noqa: E731
+
+    class TwoRanks(object):
+        def __init__(self, other):
+            self.other, self.sent = other, None
+
+        def get_world_size(self):
+            return 2
+
+        def all_gather_object(self, out, obj):
+            self.sent = obj
+            out[:] = [obj, self.other if self.other is not None else obj]
+
+    whole = tmp_path / "whole"
+    whole.mkdir()
+    bench.dump_outputs(str(whole), rows(0, ny), nx, ny, 0, ny, 0, None)
+    rank1 = TwoRanks(None)
+    bench.dump_outputs(str(tmp_path), rows(13, ny - 13), nx, ny, 13, ny - 13, 1, rank1)
+    assert not list(tmp_path.glob("*.npy"))                          # only rank 0 writes
+    bench.dump_outputs(str(tmp_path), rows(0, 13), nx, ny, 0, 13, 0, TwoRanks(rank1.sent))
+    cells = nx * ny
+    idx = np.arange(cells) if cells <= bench.DUMP_CELLS else \
+        np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, cells, bench.DUMP_CELLS))
+    for k in ("f", "rho", "u", "v"):
+        a = np.load(str(whole / (k + ".npy")))
+        assert a.dtype == np.float32 and a.shape[0] == min(cells, bench.DUMP_CELLS)
+        assert np.array_equal(a, g[k][idx % nx, idx // nx]), k
+        assert np.array_equal(np.load(str(tmp_path / (k + ".npy"))), a), k
 
 
 def test_cpu_baseline_leg_reports_the_contract_keys():

@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --calibrate 5 --min-timed-s 0.2 $*"
+BENCH="python3 $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --calibrate 5 --min-timed-s 0.2 $*"
 # The tuner's choice is pinned: an un-profiled run tunes and writes LB_TUNE_CACHE, the profiled runs read it (lb_autotune takes a cached
 # result over) -- the summaries then hold the kernel the un-profiled line names, not whatever wins under the profiler's overhead.
 export LB_TUNE_CACHE=$OUT/tune_cache.txt
