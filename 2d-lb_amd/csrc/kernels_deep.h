@@ -31,18 +31,11 @@
 namespace {
 
 // The skirt is D - 1 cells deep, i.e. whole lanes of four cells that are computed and never stored, at either end of a strip
-#ifdef LB_DEEP_SKIRT_LANES                               // (experiment: more skirt than needed, e.g. 4 lanes = strips 224 cells = 7 x 128 B apart)
-constexpr int deep_skirt_lanes(int D) { return LB_DEEP_SKIRT_LANES; }
-#else
 constexpr int deep_skirt_lanes(int D) { return (D - 1 + 3) / 4; }
-#endif
 constexpr int deep_valid(int D) { return STRIP_W - 8 * deep_skirt_lanes(D); }           // cells stored per strip and row (D = 6..9: 240)
 constexpr int deep_strips(int nx, int D) { return (nx + deep_valid(D) - 1) / deep_valid(D); }
 // Where a wave's state lives, per depth (see the header comment): windows in registers, rows gathered ahead
-#ifndef LB_DEEP_RW
-#define LB_DEEP_RW 1                    // (2: the form of round 5's first D = 7 kernel, for tools/r06/rw2_check.sh)
-#endif
-constexpr int deep_rw(int D) { return LB_DEEP_RW; }
+constexpr int deep_rw(int D) { return 1; }
 constexpr int DEEP_WSLOTS = 8;          // LDS slots of a stage window
 constexpr int deep_pfd(int D) { return 1; }
 // Code footprint (two CUs share a 64 KB instruction cache; a lone wave has nobody to cover its fetch misses; 8192^2, k MLUPS,
@@ -51,14 +44,11 @@ constexpr int deep_pfd(int D) { return 1; }
 // the loop) pay without an obstacle mask (periodic 435 against 412, cavity 403 / 383) and cost with one (periodic + mask 350 against
 // 368, pipe + mask 4096^2 250 / 263); a code path of their own for the strips without a wall column (no per-lane wall test: -36
 // instructions per row) costs more in footprint than it saves (pipe 337 against 393 with pairs, 388 / 384 without): off.
-// Since the row in flight sits in accumulation registers (LB_DEEP_MANUAL below) no buffers swap roles any more, the pairs only
+// Since the row in flight sits in accumulation registers (deep_row_issue below) no buffers swap roles any more, the pairs only
 // make the ring slots immediate: periodic 458 against 452 k, but the walled kernels (2,600 instructions per iteration: the pair of
 // pairs of the two waves is ~62 KB of code) now lose by them: pipe 8192^2 392 against 384, cavity 418 / 406, pipe 4096^2 337 / 329
-// (profiles/r05_pairs_ab.txt).  Mode 1: pairs in periodic boxes without a mask only (2: wherever there is no mask; 0: nowhere).
-#ifndef LB_DEEP_PAIRS_MODE
-#define LB_DEEP_PAIRS_MODE 1
-#endif
-constexpr bool deep_pairs(bool mask, int bc) { return LB_DEEP_PAIRS_MODE == 2 ? !mask : (LB_DEEP_PAIRS_MODE == 1 ? !mask && bc == LB_BC_PERIODIC : false); }
+// (profiles/r05_pairs_ab.txt).  Hence pairs in periodic boxes without a mask only.
+constexpr bool deep_pairs(bool mask, int bc) { return !mask && bc == LB_BC_PERIODIC; }
 
 template <int RW, int NL>
 struct DeepState {
@@ -114,9 +104,6 @@ __device__ __forceinline__ void deep_publish(f4a (*W)[64], int lane, int gs, con
 // itself: a resource (its base: a source row's start moved one float down, so that the displaced planes need no negative offset;
 // three per gathered row, one per stored row), a scalar offset per plane (eight loop-invariant scalars) and a small immediate
 // (0 / 4 / 8 bytes: pulled from the left / same column / from the right); the lane offset is one register for all.
-#ifndef LB_DEEP_BUFFER
-#define LB_DEEP_BUFFER 1
-#endif
 // Extent of every resource: the whole 32-bit range.  A raw buffer access is range-checked as offset >= num_records - soffset, and the
 // scalar offset carries the plane: up to 8 planes x 4 bytes, which in the planar layout (LB_FLAG_PLANAR) of an 8192^2 lattice is 2.16 GB
 // -- with 2 GiB of records (round 5) plane 8 of such a lattice would have read zeros and dropped its stores.  The host admits a
@@ -144,46 +131,42 @@ __device__ __forceinline__ void deep_row_load(const StepArgs &a, int r, int x4, 
     o.hsolid = false;
     o.hxc = -1;
     if (o.have) {
-        if (LB_DEEP_BUFFER) {
-            const long long P = a.pitch, S = a.plane;
-            const float *s = a.src;
-            const int yl = o.rr;
-            o.wp = WrapPatch{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (BC == LB_BC_PERIODIC) {                     // (the seam lanes' wrap elements: as gather_issue)
-                const int c = a.nx - 1 - x4;
-                const bool wrap_w = x4 == 0, wrap_e = c >= 0 && c < 4;
-                if (wrap_w) {
-                    o.wp.p1 = s[1 * S + (long long)yl * P + a.nx - 1];
-                    o.wp.p5 = s[5 * S + (long long)ym * P + a.nx - 1];
-                    o.wp.p8 = s[8 * S + (long long)yp * P + a.nx - 1];
-                }
-                if (wrap_e) {
-                    o.wp.w3 = s[3 * S + (long long)yl * P];
-                    o.wp.w6 = s[6 * S + (long long)ym * P];
-                    o.wp.w7 = s[7 * S + (long long)yp * P];
-                }
+        const long long P = a.pitch, S = a.plane;
+        const float *s = a.src;
+        const int yl = o.rr;
+        o.wp = WrapPatch{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (BC == LB_BC_PERIODIC) {                     // (the seam lanes' wrap elements: as gather_issue)
+            const int c = a.nx - 1 - x4;
+            const bool wrap_w = x4 == 0, wrap_e = c >= 0 && c < 4;
+            if (wrap_w) {
+                o.wp.p1 = s[1 * S + (long long)yl * P + a.nx - 1];
+                o.wp.p5 = s[5 * S + (long long)ym * P + a.nx - 1];
+                o.wp.p8 = s[8 * S + (long long)yp * P + a.nx - 1];
             }
-            // one resource per source row (the row itself, the rows its cy = +1 / cy = -1 links come from: wrapped by step1_rows where
-            // the box is periodic), each based one float BELOW the row start: the immediate is 0 / 4 / 8 for a pull from the left / the
-            // same column / the right; the scalar offset is the plane's
-            const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc(deep_uniform(s + (long long)yl * P - 1), 0, DEEP_NUM_RECORDS, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(deep_uniform(s + (long long)ym * P - 1), 0, DEEP_NUM_RECORDS, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(deep_uniform(s + (long long)yp * P - 1), 0, DEEP_NUM_RECORDS, 0x00020000);
-            const unsigned S4 = (unsigned)a.plane * 4u;
-            const int vo = x4 * 4;
-            o.q[0] = deep_buf_load(r0, vo, 0, 4);
-            o.q[1] = deep_buf_load(r0, vo, (int)(S4), 0);
-            o.q[2] = deep_buf_load(rm, vo, (int)(2u * S4), 4);
-            o.q[3] = deep_buf_load(r0, vo, (int)(3u * S4), 8);
-            o.q[4] = deep_buf_load(rp, vo, (int)(4u * S4), 4);
-            o.q[5] = deep_buf_load(rm, vo, (int)(5u * S4), 0);
-            o.q[6] = deep_buf_load(rm, vo, (int)(6u * S4), 8);
-            o.q[7] = deep_buf_load(rp, vo, (int)(7u * S4), 8);
-            o.q[8] = deep_buf_load(rp, vo, (int)(8u * S4), 0);
-            if (MASK) o.mk = *reinterpret_cast<const uc4 *>(lane_ptr(a.mask + (long long)yl * a.fpitch, x4));
-        } else {
-            gather_issue<BC, MASK, false>(a, x4, o.rr, ym, yp, o.q, o.mk, o.wp);
+            if (wrap_e) {
+                o.wp.w3 = s[3 * S + (long long)yl * P];
+                o.wp.w6 = s[6 * S + (long long)ym * P];
+                o.wp.w7 = s[7 * S + (long long)yp * P];
+            }
         }
+        // one resource per source row (the row itself, the rows its cy = +1 / cy = -1 links come from: wrapped by step1_rows where
+        // the box is periodic), each based one float BELOW the row start: the immediate is 0 / 4 / 8 for a pull from the left / the
+        // same column / the right; the scalar offset is the plane's
+        const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc(deep_uniform(s + (long long)yl * P - 1), 0, DEEP_NUM_RECORDS, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(deep_uniform(s + (long long)ym * P - 1), 0, DEEP_NUM_RECORDS, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(deep_uniform(s + (long long)yp * P - 1), 0, DEEP_NUM_RECORDS, 0x00020000);
+        const unsigned S4 = (unsigned)a.plane * 4u;
+        const int vo = x4 * 4;
+        o.q[0] = deep_buf_load(r0, vo, 0, 4);
+        o.q[1] = deep_buf_load(r0, vo, (int)(S4), 0);
+        o.q[2] = deep_buf_load(rm, vo, (int)(2u * S4), 4);
+        o.q[3] = deep_buf_load(r0, vo, (int)(3u * S4), 8);
+        o.q[4] = deep_buf_load(rp, vo, (int)(4u * S4), 4);
+        o.q[5] = deep_buf_load(rm, vo, (int)(5u * S4), 0);
+        o.q[6] = deep_buf_load(rm, vo, (int)(6u * S4), 8);
+        o.q[7] = deep_buf_load(rp, vo, (int)(7u * S4), 8);
+        o.q[8] = deep_buf_load(rp, vo, (int)(8u * S4), 0);
+        if (MASK) o.mk = *reinterpret_cast<const uc4 *>(lane_ptr(a.mask + (long long)yl * a.fpitch, x4));
     } else {
         o.wp = WrapPatch{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -205,13 +188,11 @@ __device__ __forceinline__ void deep_row_load(const StepArgs &a, int r, int x4, 
 // issues them; none in the filling iterations --: vector-memory operations of a wave complete in issue order (loads and stores count
 // together), "all but the N youngest are done" is then exactly "the row has arrived".  A count too SMALL only waits longer; one too
 // LARGE would read registers still in flight, hence: N is 0 wherever the iteration before was not a steady one (deep_march drains the
-// counter once before its loop), and LB_DIAG builds, whose ablation bits skip loads and stores, do not use this path.
-#ifndef LB_DEEP_MANUAL
+// counter once before its loop), and LB_DIAG builds, whose ablation bits skip loads and stores, do not use this path (deep_row_load).
 #ifdef LB_DIAG
-#define LB_DEEP_MANUAL 0
+constexpr bool DEEP_MANUAL = false;
 #else
-#define LB_DEEP_MANUAL LB_DEEP_BUFFER
-#endif
+constexpr bool DEEP_MANUAL = true;
 #endif
 __device__ __forceinline__ u4v deep_rsrc_words(const float *p)
 {
@@ -274,9 +255,6 @@ __device__ __forceinline__ void deep_row_take(Row1 &o)
 #define LB_DEEP_TAKE_OUTS "={a[0:3]}"(o.q[0]), "={a[4:7]}"(o.q[1]), "={a[8:11]}"(o.q[2]), "={a[12:15]}"(o.q[3]), \
                           "={a[16:19]}"(o.q[4]), "={a[20:23]}"(o.q[5]), "={a[24:27]}"(o.q[6]), "={a[28:31]}"(o.q[7]), "={a[32:35]}"(o.q[8])
     if (N == 0) asm volatile("s_waitcnt vmcnt(0)" : LB_DEEP_TAKE_OUTS :: "memory");
-#ifdef LB_DEEP_TIMING_NO_WAIT                        // timing only, wrong results: what the wait itself costs
-    else if (N == 9) asm volatile("s_waitcnt vmcnt(63)" : LB_DEEP_TAKE_OUTS :: "memory");
-#endif
     else if (N == 9) asm volatile("s_waitcnt vmcnt(9)" : LB_DEEP_TAKE_OUTS :: "memory");
     else asm volatile("s_waitcnt vmcnt(12)" : LB_DEEP_TAKE_OUTS :: "memory");
 #undef LB_DEEP_TAKE_OUTS
@@ -445,9 +423,7 @@ __device__ __forceinline__ void deep_stage(const StepArgs &a, const DeepCtx &cx,
                 if (!(a.diag & (1 << 22)))
 #endif
                 if (cx.store_lane) {
-                    float *d = a.dst + (long long)r * a.pitch;     // row start, uniform
-                    if (LB_DEEP_BUFFER) deep_row_store(a, r, x4, t);
-                    else store_row9<false>(a.nts != 0, d, a.plane, x4, t);
+                    deep_row_store(a, r, x4, t);
                     if (MACRO) {
                         const long long m = (long long)r * a.fpitch;
                         store4<false>(lane_ptr(a.rho + m, x4), r4);
@@ -504,7 +480,7 @@ __device__ __forceinline__ void deep_iter(const StepArgs &a, const DeepCtx &cx, 
         if (ROLE == DEEP_FRONT) {
             deep_row_take_lds<BC, MASK>(cx.dma, lane, cur);
             deep_row_issue_lds<BC, MASK>(a, row_at(min(i + 1, cx.n_iter - 1)), x4, cx.dma_off, nxt);
-        } else if (PFD && LB_DEEP_MANUAL) {
+        } else if (PFD && DEEP_MANUAL) {
             deep_row_take<BC, MASK, (NST < D ? 0 : (MACRO ? 12 : 9))>(cur);
             deep_row_issue<BC, MASK>(a, row_at(min(i + 1, cx.n_iter - 1)), x4, nxt);
         } else if (PFD) deep_row_load<BC, MASK>(a, row_at(min(i + 1, cx.n_iter - 1)), x4, nxt);
@@ -557,11 +533,11 @@ __device__ __forceinline__ void deep_march(const StepArgs &a, const int x0, cons
     DeepState<RW, D - 1 - RW> st = {};
     auto row_at = [&](int p) { return DOWN ? ym - 1 - p : ym + p; };
     Row1 ra, rb;
-    if (PFD && LB_DEEP_MANUAL) deep_row_issue<BC, MASK>(a, row_at(0), cx.x4, ra);
+    if (PFD && DEEP_MANUAL) deep_row_issue<BC, MASK>(a, row_at(0), cx.x4, ra);
     else if (PFD) deep_row_load<BC, MASK>(a, row_at(0), cx.x4, ra);
     deep_fill<BC, MASK, MACRO, D, RW, PFD, DOWN, 1>(a, cx, st, ra, rb);
     // (the steady iterations wait with the count of a steady iteration's stores: the first one has none behind it)
-    if (PFD && LB_DEEP_MANUAL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (PFD && DEEP_MANUAL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (PFD == 1 && !deep_pairs(MASK, BC)) {
         // one iteration per trip; the row gathered ahead moves into place (position D - 1 is in ra or rb by its parity)
         if ((D - 1) & 1) ra = rb;
@@ -581,21 +557,13 @@ __device__ __forceinline__ void deep_march(const StepArgs &a, const int x0, cons
     } else {
         for (int i = D - 1; i < cx.n_iter; ++i) deep_iter<BC, MASK, MACRO, D, RW, PFD, DOWN, D>(a, cx, i, st, ra, ra);
     }
-    if (PFD && LB_DEEP_MANUAL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the row gathered behind the last position)
+    if (PFD && DEEP_MANUAL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the row gathered behind the last position)
 }
 
 // Launch geometry as k_step5 / k_step6: one workgroup = one segment pair of one strip (two waves), XCD-transposed order, shorter
 // segments for the two wall-column strips.  LDS: (D - 1 - RW) x 8 KiB per wave.
-// (LB_DEEP_OCC2: timing probes only -- two workgroups per SIMD pair where the depth's registers and LDS allow it, e.g. D = 4:
-//  tools/r06/occ2_probe.sh, profiles/r06_experiments.txt section 5)
-#ifndef LB_DEEP_OCC2
-#define LB_DEEP_OCC2 0
-#endif
-#ifndef LB_DEEP_KATTR
-#define LB_DEEP_KATTR
-#endif
 template <int BC, bool MASK, bool MACRO, int D, int RW, int PFD>
-__global__ __launch_bounds__(64 * STEP4_WAVES, ((PFD && !LB_DEEP_OCC2) ? 1 : 2)) LB_DEEP_KATTR void k_deep(const StepArgs a, int strips, int seg_rows, int nsegs, int row_end)
+__global__ __launch_bounds__(64 * STEP4_WAVES, PFD ? 1 : 2) void k_deep(const StepArgs a, int strips, int seg_rows, int nsegs, int row_end)
 {
     __shared__ f4a lds_win[STEP4_WAVES][(D - 1 - RW) * DEEP_WSLOTS][64];
     const int wy = __builtin_amdgcn_readfirstlane(threadIdx.y);

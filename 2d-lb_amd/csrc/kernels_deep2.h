@@ -174,11 +174,8 @@ __global__ __launch_bounds__(64 * DEEP2_WAVES, 2) void k_deep2(const StepArgs a,
     __shared__ f4a lds_ho[2][DEEP_HO_SLOTS][64];
     // 0 front-down, 1 front-up, 2 back-down, 3 back-up.  A workgroup's wave w lands on SIMD w, and the two workgroups of a CU are (in
     // launch order) 256 apart: every other 256 workgroups take the roles two waves on, so that a SIMD holds a front wave (four stages
-    // and the gather) AND a back wave (three stages and the stores), not two of a kind -- LB_DEEP2_SWAP 0: off (A/B).
-#ifndef LB_DEEP2_SWAP
-#define LB_DEEP2_SWAP 1
-#endif
-    const int wy = (__builtin_amdgcn_readfirstlane(threadIdx.y) + (LB_DEEP2_SWAP ? ((blockIdx.x >> 8) & 1) * 2 : 0)) & 3;
+    // and the gather) AND a back wave (three stages and the stores), not two of a kind.
+    const int wy = (__builtin_amdgcn_readfirstlane(threadIdx.y) + ((blockIdx.x >> 8) & 1) * 2) & 3;
     const int item = xcd_item(blockIdx.x, gridDim.x);
 #ifdef LB_DIAG
     const unsigned long long diag_t0 = __builtin_amdgcn_s_memrealtime();     // 100 MHz

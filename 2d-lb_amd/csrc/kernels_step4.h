@@ -400,7 +400,7 @@ __device__ __forceinline__ void march4_iter(const StepArgs &a, const March4Ctx &
         if (a.diag & 1048576) {
             // timing only (wrong results): a FIFTH stage's worth of work -- a window load and push on W2 again, the gather with its
             // six cross-lane moves, a halo-cell stage, a collide -- to price five steps per pass before building them
-            // (tools/r04_fifth_stage.sh, profiles/r04_experiments.txt section 9)
+            // (profiles/r04_experiments.txt section 9)
             Window w2b;
             lds_window_load(W2, lane, it, w2b);
             f4a q3b[9];

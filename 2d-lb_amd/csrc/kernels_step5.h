@@ -5,7 +5,7 @@
 // kernel moves its bytes at the ceiling of the marching waves' access pattern (~6.0 TB/s counted, 1.08 x the compulsory bytes),
 // and its vector ALU idles a third of the time.  A launch costs about the same whatever it computes per row, so the way up is a
 // FIFTH time step per pass -- provided the kernel keeps eight waves per CU (timing probe on the diagnostic build,
-// tools/r04_fifth_stage.sh: with a third LDS window, i.e. six waves per CU, the gain is gone -- for k_step4's halo-lane form, which
+// profiles/r04_experiments.txt section 9: with a third LDS window, i.e. six waves per CU, the gain is gone -- for k_step4's halo-lane form, which
 // the probe ran; THIS kernel turned out to run as fast at six waves per CU, which is what kernels_step6.h builds on).  Hence: the windows between steps
 // 1/2 AND 2/3 in registers (2 x 36), those between 3/4 and 4/5 in LDS (the 36 KB per workgroup k_step4 uses).
 //
@@ -13,7 +13,7 @@
 // lanes" -- a third of its vector instructions, 27 registers of delay lines, and with four cells per side and stage the first
 // version of this kernel spilled (1.37 ms instead of 0.88 ms per 8192^2 launch: profiles/r04_experiments.txt section 10).  Here a
 // wave's 64 lanes x 4 cells ARE the strip and its skirt: strips were laid 248 cells apart and started 4 cells early (since the end of
-// round 5: 240 apart, 8 early, LB_STEP5_ALIGN64 below), step s is
+// round 5: 240 apart, 8 early, STEP5_SKIRT below), step s is
 // right for the cells at least s - 1 away from either end (what is wrong creeps in one cell per step), so after step 5 lanes
 // 1..62 hold 248 good cells and lanes 0 and 63 are never stored.  No halo cells, no delay lines, no exchange between the halo
 // lanes of a pair; the price is 256 / 248 = +3.2 % rows read and computed (the halo lanes read those cells, too) and row starts
@@ -26,17 +26,14 @@
 
 namespace {
 
-// LB_STEP5_ALIGN64 (round 5, default): strips 240 cells = 15 x 64 bytes apart instead of 248 = 15.5 x 64 -- two lanes of skirt per
+// Round 5: strips 240 cells = 15 x 64 bytes apart instead of 248 = 15.5 x 64 -- two lanes of skirt per
 // side, of which the inner one is computed right and not stored --, so that every strip's stores begin and end on 64-byte boundaries.
 // With 248 every other seam cut a 64-byte sector into two parts written at different times; k_deep with its seams at 8-byte offsets
 // lost 12-23 % to that (profiles/r05_experiments.txt section 23).  (The counted HBM bytes do not show it -- 1.06 x compulsory before
 // and after, profiles/pmc_traffic.json --, the launch time does: 8192^2 1030 -> 894 us by rocprofv3.)  One box, 248 | 240 apart, k MLUPS: periodic 8192^2 334-350 | 375, pipe 8192^2
 // 351 | 369-376, cavity 3072^2 287-291 | 296-297, velocity inlet 4096^2 266-267 | 270-273; 4096^2 and below +-1 %
 // (profiles/r05_step5_align64_ab.txt): 3 % more strips, no partial sectors.
-#ifndef LB_STEP5_ALIGN64
-#define LB_STEP5_ALIGN64 1
-#endif
-constexpr int STEP5_SKIRT = LB_STEP5_ALIGN64 ? 8 : 4;   // cells a strip starts before / ends behind its stored cells (= one lane)
+constexpr int STEP5_SKIRT = 8;                          // cells a strip starts before / ends behind its stored cells (= one lane)
 constexpr int STEP5_VALID = STRIP_W - 2 * STEP5_SKIRT;  // 248 cells stored per strip and row
 
 struct March5State {
@@ -54,29 +51,18 @@ struct March5Ctx {
 // gather of the next stage for my 4 cells from a window {d0,d1,d3,g2,g5,g6} and the newest row q; what lanes 0 / 63 take
 // from beyond the wave is their own value: wrong, and never within reach of a stored cell
 // (the neighbour lane's element by a DPP move -- wave_shr:1 / wave_shl:1, one vector-ALU pass; lanes 0 / 63, which have no such
-//  neighbour, get 0.0: as wrong as their own value, and as far from every stored cell.  Round 5; until then -- and with
-//  -DLB_SKIRT_BPERMUTE -- by ds_bpermute: an LDS-queue round trip per element, 36 per row of six stages.  Bitwise equal, same speed
-//  at two waves per SIMD, +2 % at one: profiles/r05_experiments.txt)
-#ifndef LB_SKIRT_BPERMUTE
-#define LB_SKIRT_DPP 1
-#endif
+//  neighbour, get 0.0: as wrong as their own value, and as far from every stored cell.  Round 5; until then by ds_bpermute: an
+//  LDS-queue round trip per element, 36 per row of six stages.  Bitwise equal, same speed at two waves per SIMD, +2 % at one:
+//  profiles/r05_experiments.txt)
 __device__ __forceinline__ float wave_from_left(float v)
 {
-#ifdef LB_SKIRT_DPP
     const int i = __builtin_bit_cast(int, v);
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, i, 0x138, 0xf, 0xf, true));
-#else
-    return __shfl_up(v, 1);
-#endif
 }
 __device__ __forceinline__ float wave_from_right(float v)
 {
-#ifdef LB_SKIRT_DPP
     const int i = __builtin_bit_cast(int, v);
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, i, 0x130, 0xf, 0xf, true));
-#else
-    return __shfl_down(v, 1);
-#endif
 }
 __device__ __forceinline__ f4a skirt_left(f4a v) { return f4a{wave_from_left(v.w), v.x, v.y, v.z}; }
 __device__ __forceinline__ f4a skirt_right(f4a v) { return f4a{v.y, v.z, v.w, wave_from_right(v.x)}; }
@@ -238,7 +224,7 @@ __device__ __forceinline__ void march5(const StepArgs &a, const int x0, const in
     // values are never within reach of a stored cell: the wall column's rule rebuilds what it pulled from them)
     // (periodic: only the first lane beyond the last column is anybody's skirt; the lanes behind it -- the last strip of 8192
     //  columns stores 8 cells -- read what that lane reads, i.e. the same cache lines, instead of 240 more columns)
-    if (BC == LB_BC_PERIODIC) cx.x4 = xr < 0 ? xr + a.nx : (xr >= a.nx ? (LB_STEP5_ALIGN64 && xr - a.nx < 8 ? xr - a.nx : (LB_STEP5_ALIGN64 ? 4 : 0)) : xr);
+    if (BC == LB_BC_PERIODIC) cx.x4 = xr < 0 ? xr + a.nx : (xr >= a.nx ? (xr - a.nx < 8 ? xr - a.nx : 4) : xr);
     else cx.x4 = min(max(xr, 0), (a.nx - 1) & ~3);
     cx.store_lane = cx.lane >= STEP5_SKIRT / 4 && cx.lane <= 63 - STEP5_SKIRT / 4 && xr < a.nx;
     cx.ym = ym; cx.n_iter = len + 4; cx.wy = wy; cx.slot = slot;

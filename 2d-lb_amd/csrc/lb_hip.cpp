@@ -183,12 +183,6 @@ struct lb_sim {
         int h = 0;
     } peer_nb[2];                                   // [0] = south, [1] = north
     unsigned long long peer_timeout_ticks = 0;
-    // CYCLE_GRAPH_CYCLES halo cycles of lb_run captured into one hipGraph (peer transport; LB_CYCLE_GRAPH=1)
-    hipGraph_t cyc_graph = nullptr;
-    hipGraphExec_t cyc_exec = nullptr;
-    int cyc_key = -1;
-    bool cyc_failed = false;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int diag = 0;
     bool xchg_inline = false;   // slabs, split bands: the exchange on the COMPUTE stream, between the interior launches (lb_set_exchange_inline)
     int slab_flavour = -1;      // slabs, seven-step cycle: 0 k_deep<7>, 1 k_deep2<7> (lb_set_slab_cycle(8)), -1 automatic (k_deep2 under RCCL)
@@ -252,7 +246,7 @@ StepArgs step_args(const lb_sim *s, int row_begin, int row_step, int row_count)
     a.ghost_n = (s->multi_slab() && (periodic || s->p.y0 + s->H < s->p.ny)) ? 1 : 0;
     a.seg_stride = 0;
     a.edge_seg_rows = 0;
-    a.tile_launch_order = (s->variant >= 0 && (s->variant & 8192)) ? 1 : 0;    // (A/B switch: explicit variants only)
+    a.tile_launch_order = (s->variant >= 0 && (s->variant & VAR_TILE_LAUNCH_ORDER)) ? 1 : 0;    // (A/B switch: explicit variants only)
     a.diag = s->diag;
     a.prio_turns = 0;      // (set by launch_step2 from the variant)
     a.nts = 0;
@@ -283,24 +277,24 @@ int effective_variant(const lb_sim *s)
     //  170 MB (periodic 1536^2) 306 | 298, 302 MB (2048^2) 369 | 363, pipe 2048^2 291 | 295; 338 MB -- the reference's 3751 x 1251 case --
     //  274-285 | 292-293 (two rounds, both depths), 415 MB: periodic 2400^2 385 | 388, pipe 337 against 308, cavity + mask 298 against 276:
     //  the threshold is 320 MB now)
-    int v = pair_bytes >= 3.2e8 ? ((s->p.flags & LB_FLAG_PLANAR) ? 9 : 1) : 16;
+    int v = pair_bytes >= 3.2e8 ? ((s->p.flags & LB_FLAG_PLANAR) ? VAR_NT_STORES | VAR_ROWS_2 : VAR_NT_STORES) : VAR_XCD_ORDER;
     // from 1024^2 cells: three steps per pass (110 k MLUPS at 1024^2 against 87 k single-step); from 1280^2:
     // four (125 k at 1280^2, 158 k at 1536^2, 170 k at 2048^2, 220 k from 3072^2), whole grids and slabs alike,
     // in every boundary family, with and without obstacles (profiles/r01_sweep_variants.txt,
     // profiles/r01_slab_proxy_1gpu.txt).  Smaller grids: single step, replayed through a hipGraph.
-    if (cells >= 1024.0 * 1024.0) v = (v & ~16) | 32 | 64;
-    if (cells >= 1280.0 * 1280.0) v |= 256;
+    if (cells >= 1024.0 * 1024.0) v = (v & ~VAR_XCD_ORDER) | VAR_STEP2 | VAR_STEP3;
+    if (cells >= 1280.0 * 1280.0) v |= VAR_STEP4;
     // ... and five wherever four are (k_step5, overlapping strips: periodic 2048^2 298 against 250 k MLUPS, 4096^2 315 against 289 k,
     // 8192^2 327-346 against 306-319 k; pipe 8192^2 346 against 309 k: profiles/r04_experiments.txt section 10), in every family,
     // whole grids and slabs (cycle_depth) alike
-    if (cells >= 1280.0 * 1280.0) v |= 4096;
+    if (cells >= 1280.0 * 1280.0) v |= VAR_STEP5;
     // ... and six / seven (k_deep, round 5: ONE wave per SIMD with the next row's gather in flight; kernels_deep.h) on the large whole
     // grids.  k MLUPS, k_step5 / k_deep<6> / k_deep<7>, one box (profiles/r05_size_sweep.txt): periodic 2048^2 281 / 283 / 279,
     // 2560^2 282 / 290 / 302, 4096^2 314 / 345 / 358, 8192^2 342 / 411 / 432 (other boxes: 346 / 436 / 459); pipe 3072^2 280 / 252 / 255,
     // 4096^2 303 / 318 / 323, 6144^2 303 / 370 / 371, 8192^2 333 / 387 / 394; cavity 4096^2 324 / 319 / 322, 6144^2 303 / 368 / 366;
     // with a (dense, random 1 %) obstacle mask -- 32 selects per row and stage that a lone wave pays in full --: periodic 2560^2
     // 254 / 244 / 261, 8192^2 338 / 347 / 368; pipe 4096^2 293 / 270 / 280, 6144^2 295 / 298 / 321; cavity 6144^2 321 / 305 / 322.
-    // With the gathered row waited for by hand (kernels_deep.h, LB_DEEP_MANUAL; profiles/r05_size_sweep2.txt, another box): periodic
+    // With the gathered row waited for by hand (kernels_deep.h, deep_row_issue; profiles/r05_size_sweep2.txt, another box): periodic
     // 1536^2 253 / 252 / 263, 2048^2 279 / 309 / 307, 3072^2 290 / 314 / 327; with a mask 1536^2 229 / 236 / 248, 2560^2 272 / 256 / 292;
     // pipe 3584^2 296 / 277 / 288, 4096^2 310 / 318 / 329; cavity 3584^2 296 / 299 / 301; pipe + mask 3584^2 280 / 259 / 264, 4096^2
     // 291 / 293 / 298 (config 5's image: 297 / 296 / 307), 5120^2 282 / 327 / 335; cavity + mask 4096^2 292 / 302 / 309.  Whole grids
@@ -331,17 +325,17 @@ int effective_variant(const lb_sim *s)
                                           : (whole_grid ? 1700.0 : 3800.0);
     // (not the velocity-inlet family: its wall-row bands stop at five steps and k_deep has no instantiation for it)
     if (cells >= deep_side * deep_side && s->p.bc_mode != LB_BC_VELOCITY_INLET) {
-        v |= 16384 | 32768;     // (slabs: inside the twelve- / fourteen-step halo cycle, cycle_depth)
-        if (whole_grid && !s->multi_slab() && !periodic_box && cells < 2900.0 * 2900.0) v |= 65536;
+        v |= VAR_STEP6 | VAR_STEP7;     // (slabs: inside the twelve- / fourteen-step halo cycle, cycle_depth)
+        if (whole_grid && !s->multi_slab() && !periodic_box && cells < 2900.0 * 2900.0) v |= VAR_DEEP2;
     }
     // Periodic whole grids without a mask, tiles | k_step5 | k_deep<6> | k_deep<7>, k MLUPS, 1680-step runs (profiles/r06q_periodic_small_sweep.txt):
     // 1024^2 214 | 186 | 205 | 195, 1152^2 220 | 227 | 246 | 239, 1280^2 234 | 256 | 263 | 258, 1408^2 242 | 266 | 291 | 287, 1536^2 245 | 291 | 310 | 308,
     // 1792^2 254 | 319 | 364 | 359, 2048^2 210 | 293 | 340 | 364: six steps per pass from 1100^2 cells, seven from 1900^2 (use_tile_kernel:
     // the tiles below 1100^2).
     if (periodic_box && whole_grid && !s->multi_slab() && !s->has_mask) {
-        v &= ~(16384 | 32768);
-        if (cells >= 1100.0 * 1100.0) v |= 256 | 4096 | 16384;
-        if (cells >= 1900.0 * 1900.0) v |= 32768;
+        v &= ~(VAR_STEP6 | VAR_STEP7);
+        if (cells >= 1100.0 * 1100.0) v |= VAR_STEP4 | VAR_STEP5 | VAR_STEP6;
+        if (cells >= 1900.0 * 1900.0) v |= VAR_STEP7;
     }
     return v;
 }
@@ -353,8 +347,8 @@ int launch_step(lb_sim *s, int row_begin, int row_step, int row_count, bool macr
     macro = macro && !lazy_macro(s);       // (no fused kernel stores rho, u, v on a handle that rebuilds them on demand)
     const StepArgs a = step_args(s, row_begin, row_step, row_count);
     const int variant = effective_variant(s);
-    const int rpb_sel = (variant >> 2) & 3;          // bits 2-3: rows per block 0 -> 4, 1 -> 1, 2 -> 2
-    const int rows_per_block = rpb_sel == 1 ? 1 : (rpb_sel == 2 ? 2 : 4);
+    const int rpb_sel = variant & VAR_ROWS;
+    const int rows_per_block = rpb_sel == VAR_ROWS_1 ? 1 : (rpb_sel == VAR_ROWS_2 ? 2 : 4);
     const int waves_x = 4 / rows_per_block;          // waves side by side in x
     dim3 block(64 * waves_x, rows_per_block);
     const int lanes_x = (int)(s->pitch / 4);
@@ -366,11 +360,11 @@ int launch_step(lb_sim *s, int row_begin, int row_step, int row_count, bool macr
 
 // A marching launch of `depth` time steps per pass (k_step2 ... k_step5, k_deep), by the translation unit that instantiates that depth.
 // k_step4 gathers one row ahead where that fits in 256 registers without scratch (step4_prefetch, kernels_step4.h: every
-// instantiation without an obstacle mask but the D2Q9i fork's); variant bit 10 switches it off (A/B runs).
+// instantiation without an obstacle mask but the D2Q9i fork's); VAR_STEP4_NO_AHEAD switches it off (A/B runs).
 bool deep2_chosen(const lb_sim *s)
 {
     if (s->multi_slab() && s->slab_flavour >= 0) return s->slab_flavour == 1;      // lb_set_slab_cycle(7) / (8): the caller's word
-    if (s->variant >= 0) return (s->variant & 65536) != 0;
+    if (s->variant >= 0) return (s->variant & VAR_DEEP2) != 0;
     // Slabs without the caller's word (above: the ranks' collective tuner): by transport.  Beside k_deep<7> (2 x 80 KB of
     // LDS per CU, lone waves) RCCL's send / receive kernel waits for places and slows what it shares SIMDs with; k_deep2<7>'s launches
     // (2 x 72 KB, waves in pairs per SIMD) do not run longer for it, though it still takes most of a launch beside them: one slab of 4 | 2 of an 8192^2 lattice over RCCL 381-392 | 402-450 k MLUPS by k_deep, 443-444 | 466 k by
@@ -378,7 +372,7 @@ bool deep2_chosen(const lb_sim *s)
     // (profiles/r06s_slab_proxy_deep2.txt).  Every rank of a run shares the transport, so the ranks agree.
     if (s->multi_slab()) return s->comm != nullptr && !s->peer_connected;
     if (s->tuned_steps) return s->tuned_steps == 7 && s->tuned_wpc == 8;       // lb_autotune's word
-    return (effective_variant(s) & 65536) != 0;                                // the size table's
+    return (effective_variant(s) & VAR_DEEP2) != 0;                                // the size table's
 }
 
 bool launch_march(const lb_sim *s, hipStream_t st, const StepArgs &a, int items, int strips, int seg_rows, int nsegs, int row_end,
@@ -393,12 +387,12 @@ bool launch_march(const lb_sim *s, hipStream_t st, const StepArgs &a, int items,
     g.strips = strips; g.seg_rows = seg_rows; g.nsegs = nsegs; g.row_end = row_end;
     const int bc = kernel_bc(s);
     // (false: the unit has no instantiation for this boundary family -- k_deep / k_deep2 and the velocity-inlet family)
-    // k_deep2: four waves per workgroup -- asked for (variant bit 16) or found faster by lb_autotune (seven steps at "eight waves per CU")
+    // k_deep2: four waves per workgroup -- asked for (VAR_DEEP2) or found faster by lb_autotune (seven steps at "eight waves per CU")
     if (depth == 7 && deep2_chosen(s)) return lbk_launch_deep2_7(bc, s->has_mask, macro, g, a);
     if (depth == 7) return lbk_launch_deep7(bc, s->has_mask, macro, g, a);
     if (depth == 6) return lbk_launch_deep6(bc, s->has_mask, macro, g, a);
     if (depth == 5) lbk_launch_march5(bc, s->has_mask, macro, g, a);
-    else if (depth == 4) lbk_launch_march4(bc, s->has_mask, macro, !(effective_variant(s) & 1024), g, a);
+    else if (depth == 4) lbk_launch_march4(bc, s->has_mask, macro, !(effective_variant(s) & VAR_STEP4_NO_AHEAD), g, a);
     else lbk_launch_march23(depth, bc, s->has_mask, macro, g, a);
     return true;
 }
@@ -467,13 +461,10 @@ int launch_step2(lb_sim *s, hipStream_t st, int row_begin, int row_end, bool mac
         a.seg_stride = seg_stride;
     } else {
         // as many wave-items as the chip holds at once (waves per CU from the kernel's register
-        // budget; tunable), each marching an equal share of the rows
-        // (lb_autotune's waves per CU belong to the depth it found fastest: the shallower launches of a run's remainder keep 8)
-        int waves_per_cu = (s->tuned_wpc > 0 && depth == s->tuned_steps) ? s->tuned_wpc : 8;
-        static const int wpc_env = getenv("LB_STEP2_WAVES_PER_CU") ? atoi(getenv("LB_STEP2_WAVES_PER_CU")) : 0;   // tuning knob
-        if (wpc_env > 0) waves_per_cu = wpc_env;
-        if (depth >= 6) waves_per_cu = 4;        // (k_deep: one wave per SIMD -- 512 registers, 36 KB of LDS per wave)
-        if (depth >= 6 && wpc_env > 0) waves_per_cu = wpc_env;
+        // budget), each marching an equal share of the rows
+        // (lb_autotune's waves per CU belong to the depth it found fastest: the shallower launches of a run's remainder keep 8;
+        //  k_deep: one wave per SIMD -- 512 registers, 36 KB of LDS per wave)
+        const int waves_per_cu = depth >= 6 ? 4 : ((s->tuned_wpc > 0 && depth == s->tuned_steps) ? s->tuned_wpc : 8);
         // (k_step4: an item is a PAIR of segments, marched by the two waves of a workgroup from its middle line: two
         //  wave slots each; `capacity`, `segs`, `seg_rows` then count pairs)
         const int per_item = (depth >= 4) ? STEP4_WAVES : 1;
@@ -492,7 +483,6 @@ int launch_step2(lb_sim *s, hipStream_t st, int row_begin, int row_end, bool mac
         // rows cost edge_cost times an interior strip's: the boundary rule of one cell per row and stage -- measured per
         // wave, tools/wave_timeline.py: +18 % pipe, +10..16 % cavity; the velocity-inlet columns also read the stored u, v),
         // within the same number of wave slots: pipe / cavity +5..8 %, velocity inlet +19..30 % (profiles/r02_experiments.txt)
-        static const double edge_env = getenv("LB_EDGE_COST") ? atof(getenv("LB_EDGE_COST")) : 0.0;          // tuning knob
         // (k_step5 has no halo-lane work, so the wall column's rule weighs more in its rows: velocity inlet, 8192^2, edge cost 1.2:
         //  301-305 k MLUPS, 1.6: 306-310 k, 2.0: 322-339 k, 2.5: 329-348 k, 3.0: 321-328 k; 4096^2: 252 / 274 / 290 / 298 / 276 k;
         //  pipe and cavity stay at 1.2: profiles/r04_experiments.txt section 10)
@@ -504,8 +494,7 @@ int launch_step2(lb_sim *s, hipStream_t st, int row_begin, int row_end, bool mac
         //  memory counter at every call --: 1.8 | 2.0 | 2.2 | 2.5 | 3.2, k MLUPS, k_deep<7>: pipe 8192^2 394 | 419 | 420 | 416 | 420, 6144^2
         //  410 | 413 | 419 | 402 | 388, 4096^2 333 | 351 | 347 | 349 | 325; cavity 4096^2 346 | 351 | 353 | 350 | 328; config 5's image 4096^2
         //  310 | 320 | 320 | 309 | 289; k_deep<6> pipe 8192^2 381 | 406 | 403 | 406 | 407: profiles/r05_edge_cost_scan2.txt -> 2.1)
-        const double edge_cost = edge_env > 0.0 ? edge_env
-                                 : (s->p.bc_mode == LB_BC_VELOCITY_INLET ? (depth == 5 ? 2.3 : 1.6) : (depth >= 6 ? 2.1 : 1.2));
+        const double edge_cost = s->p.bc_mode == LB_BC_VELOCITY_INLET ? (depth == 5 ? 2.3 : 1.6) : (depth >= 6 ? 2.1 : 1.2);
         if (depth >= 4 && s->p.bc_mode != LB_BC_PERIODIC && strips >= 4 && edge_cost > 1.0 && segs * strips >= capacity / 2) {
             // the split of the wave slots between interior strips (segs_i pairs each) and the two wall-column strips (segs_e each) that
             // finishes first: min over segs_i of max(rows_i, edge_cost x rows_e).  (Until round 5: segs_i = capacity / (strips - 2 +
@@ -539,10 +528,9 @@ int launch_step2(lb_sim *s, hipStream_t st, int row_begin, int row_end, bool mac
         }
     }
     const int items = strips * segs + extra_items;
-    const bool nts = (variant & 1) != 0;
-    // k_step4: the two waves of a SIMD take turns at the higher issue priority (see the kernel); variant bit 11 = off
-    static const int turn_bit = getenv("LB_PRIO_TURN_BIT") ? atoi(getenv("LB_PRIO_TURN_BIT")) : 13;    // tuning knob
-    a.prio_turns = (variant & 2048) ? 0 : turn_bit;
+    const bool nts = (variant & VAR_NT_STORES) != 0;
+    // k_step4: the two waves of a SIMD take turns at the higher issue priority (see the kernel), in turns of 2^13 ticks of the 100 MHz clock; VAR_NO_PRIO_TURNS = off
+    a.prio_turns = (variant & VAR_NO_PRIO_TURNS) ? 0 : 13;
     a.nts = nts ? 1 : 0;                       // (the marching kernels take it at run time)
     if (!launch_march(s, st, a, items, strips, seg_rows, segs, row_end, macro, depth))
         return fail(LB_ERR_STATE, "no %d-step kernel for this boundary family (the caller's schedule must not ask for one)", depth);
@@ -563,8 +551,7 @@ int tile_shape_of(const lb_sim *s)
     // (two cells per thread from 576^2 -- 900^2 until the rings were stepped by whole waves: one / two cells per thread, MLUPS,
     //  periodic 512^2 122-124 / 123 k, 640^2 125-128 / 133-135 k, 768^2 145 / 156 k, 896^2 152 / 170 k; cavity 512^2 110 / 107 k,
     //  640^2 112 / 121 k, 896^2 139 / 156 k: profiles/r03_experiments.txt section 16)
-    static const long long cpt2_env = getenv("LB_TILE_CPT2_SIDE") ? atoll(getenv("LB_TILE_CPT2_SIDE")) : 576;     // tuning knob
-    if (cells >= cpt2_env * cpt2_env) return 0;
+    if (cells >= 576LL * 576) return 0;
     return cells >= 330LL * 330 ? 1 : 2;
 }
 
@@ -914,7 +901,7 @@ int exchange_peer(lb_sim *s, int which, hipStream_t q, const HaloTables &T)
 int exchange_halo(lb_sim *s, int which, hipStream_t q, const HaloTables &T)
 {
     // (lb_exchange_timing: what an exchange takes on its stream -- pack / push, the transfer, the wait for the neighbours, unpack)
-    // (not inside a stream capture -- LB_CYCLE_GRAPH=1 --: timing events cannot be recorded into a graph)
+    // (not inside a stream capture: timing events cannot be recorded into a graph)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (s->xt_on) (void)hipStreamIsCapturing(q, &cap);
     const bool timed = s->xt_on && cap == hipStreamCaptureStatusNone && s->xt_count < lb_sim::XT_RING;
@@ -1049,18 +1036,18 @@ int slab_step_join(lb_sim *s)
 int cycle_depth(const lb_sim *s, int h)
 {
     const int v = effective_variant(s);
-    if (!(v & 64) || (v & 128) || !step3_applicable(s, h) || h < 32) return 0;
+    if (!(v & VAR_STEP3) || (v & VAR_NO_CYCLE) || !step3_applicable(s, h) || h < 32) return 0;
     // (lb_set_slab_cycle: the caller's choice -- the ranks of a run time the candidates together and agree, bench.py / slabs.py --
     //  wherever that depth can run; elsewhere the automatic one)
     if (s->forced_cycle >= 3 && s->forced_cycle <= MAX_DEPTH && h >= 16 * s->forced_cycle &&
         !(s->forced_cycle >= 6 && s->p.bc_mode == LB_BC_VELOCITY_INLET))
         return s->forced_cycle;
     // (k_deep on slabs, round 5: the fourteen- / twelve-step cycle, ghost zone as deep)
-    if ((v & 32768) && (v & 16384) && (v & 4096) && (v & 256) && h >= 112) return 7;
-    if ((v & 16384) && (v & 4096) && (v & 256) && h >= 96) return 6;
+    if ((v & VAR_STEP7) && (v & VAR_STEP6) && (v & VAR_STEP5) && (v & VAR_STEP4) && h >= 112) return 7;
+    if ((v & VAR_STEP6) && (v & VAR_STEP5) && (v & VAR_STEP4) && h >= 96) return 6;
     // (k_step5 on slabs: the ten-step cycle, ghost zone ten rows deep)
-    if ((v & 4096) && (v & 256) && h >= 80) return 5;
-    return ((v & 256) && h >= 64) ? 4 : 3;
+    if ((v & VAR_STEP5) && (v & VAR_STEP4) && h >= 80) return 5;
+    return ((v & VAR_STEP4) && h >= 64) ? 4 : 3;
 }
 const HaloTables &cycle_halo(int depth)
 {
@@ -1095,8 +1082,7 @@ int launch_bands(lb_sim *s, hipStream_t st, int lo_s, int hi_s, int lo_n, int hi
 //   E1b  rows [D, D+B)       of the next cycle: reads rows [0, 2D+B) only, no ghost row -- does not wait for the exchange
 //   E1a  rows [-D, D)        the one launch that reads the ghost rows: waits for ev_halo
 // so the exchange has from the end of E2a to the start of E1a, more than a whole launch, and every workgroup slot stays busy.
-// LB_BAND_EXTRA=<rows> fixes B (0 = the bands of rounds 3-5), LB_BAND_SLACK=<iterations> the head start, LB_SPLIT_BANDS=0 keeps
-// each band one launch (lb_run_group and the captured cycles always do).
+// (lb_run_group keeps each band one launch.)
 // (Which transport.  RCCL's pack, send / receive, unpack take 30-160 us and never fitted a thick band's head start: one launch per band
 //  331-341 | 356-357 | 363-380 k MLUPS per GPU at 8 | 4 | 2 slabs of a strong-scaled 8192^2, split 353-388 | 372-386 | 420-445
 //  (profiles/r06_slab_proxy_split.txt).  The peer transport's exchange is one push kernel, ~16 us, and on that box one launch per band
@@ -1105,25 +1091,15 @@ int launch_bands(lb_sim *s, hipStream_t st, int lo_s, int hi_s, int lo_n, int hi
 //  split 397-399 | 449-453 | 470-474 | 484 = 0.92 | 0.97 | 0.98 | 0.99 of the plain grids of those sizes
 //  (profiles/r06_slab_proxy_peer_split_ab.txt; bench.py --force-slab-path: 415 k one launch, 467 k split).  With one launch per band
 //  the next E1 queues behind E2 AND the exchange on one stream, and whether that chain keeps up with the interior depends on the box's
-//  issue rate; split, nothing of a band but its outer 2D rows waits for anything.  Hence split for both transports; LB_SPLIT_BANDS=0
-//  keeps each band one launch.)
-bool split_bands(const lb_sim *)
-{
-    static const int forced = getenv("LB_SPLIT_BANDS") ? (atoi(getenv("LB_SPLIT_BANDS")) != 0) : -1;
-    return forced != 0;
-}
-
+//  issue rate; split, nothing of a band but its outer 2D rows waits for anything.  Hence split for both transports.)
 int band_extra(const lb_sim *s, int D, bool split = false)
 {
     if (D < 4) return 0;                                // (k_step2 / k_step3: one wave per strip and band, a few rows: as they were)
-    static const int fixed = getenv("LB_BAND_EXTRA") ? atoi(getenv("LB_BAND_EXTRA")) : -1;         // tuning knobs
-    static const double slack_env = getenv("LB_BAND_SLACK") ? atof(getenv("LB_BAND_SLACK")) : -1.0;
     // (one launch per band: the exchange must fit into the head start; split: only the launch gaps of the two parts do)
-    const double slack = slack_env >= 0.0 ? slack_env : (split ? 3.0 : 8.0);
+    const double slack = split ? 3.0 : 8.0;
     const int H = s->H;
     const int room = (H - 4 * D) / 2 - 8;               // the interior of the second launch keeps at least 16 rows
     if (room <= 0) return 0;
-    if (fixed >= 0) return std::min(fixed & ~1, room & ~1);
     const int strips = D >= 6 ? deep_strips(s->p.nx, D) : (D == 5 ? step5_strips(s->p.nx) : (s->p.nx + STRIP_W - 1) / STRIP_W);
     const int wpc = D >= 6 ? 4 : 8;
     const int segs = std::max(1, (s->cu_count * wpc - 2 * strips * STEP4_WAVES) / STEP4_WAVES / strips);    // interior pairs per strip
@@ -1188,14 +1164,14 @@ int slab_cycle_second(lb_sim *s, bool macro, int D, bool split = false)
 
 // Which fused depths a whole-grid handle may use: the variant bits (explicit or from the size heuristic), or --
 // once lb_autotune has timed this grid -- everything applicable up to the depth it found fastest.
-// Four steps per pass through LDS tiles (k_tile4) instead of the marching kernels: asked for (variant bit 9),
+// Four steps per pass through LDS tiles (k_tile4) instead of the marching kernels: asked for (VAR_TILES),
 // found fastest by lb_autotune, or -- automatic -- on whole grids below ~1400^2 cells and on grids the marching
 // kernels do not serve (27 k MLUPS at 256^2, 82 k at 512^2, 120 k at 1024^2, 138 k at 1280^2, against 19 / 57 /
 // 113 / 129 k; from 1536^2 the marching kernel wins, 163 against 153 k: profiles/r01_sweep_variants.txt).
 bool use_tile_kernel(const lb_sim *s)
 {
     if (!tile_applicable(s)) return false;
-    if (s->variant >= 0) return (s->variant & 512) != 0;
+    if (s->variant >= 0) return (s->variant & VAR_TILES) != 0;
     if (s->tuned_steps) return s->tuned_wpc < 0;
     // (walled boxes likewise: pipe 24 / 74 / 112 / 123 k at 256^2 / 512^2 / 1024^2 / 1280^2 against 16.5 / 55 / 95 / 113 k;
     //  marching from 1536^2: 136 against 130 k)
@@ -1224,8 +1200,8 @@ int whole_grid_depths(const lb_sim *s)
                           step4_applicable(s) && s->tuned_steps >= 4, step5_applicable(s) && s->tuned_steps >= 5,
                           deep_applicable(s) && s->tuned_steps >= 6, deep_applicable(s) && s->tuned_steps >= 7);
     const int v = effective_variant(s);
-    return depth_mask((v & 32) && step2_applicable(s), (v & 64) && step3_applicable(s), (v & 256) && step4_applicable(s),
-                      (v & 4096) && step5_applicable(s), (v & 16384) && deep_applicable(s), (v & 32768) && deep_applicable(s));
+    return depth_mask((v & VAR_STEP2) && step2_applicable(s), (v & VAR_STEP3) && step3_applicable(s), (v & VAR_STEP4) && step4_applicable(s),
+                      (v & VAR_STEP5) && step5_applicable(s), (v & VAR_STEP6) && deep_applicable(s), (v & VAR_STEP7) && deep_applicable(s));
 }
 
 // A d-step pass (d = 3, 4, 5) of the velocity-inlet family.  Rows [d, ny-d) depend on nothing the wall rows do within d steps:
@@ -1466,8 +1442,8 @@ int corners_patch(lb_sim *s, int which)
 int autotune_quick_cost(const lb_sim *s) { return 11 * 2 * (small_grid(s) ? 36 : 12) + 2 * 2 * 10 + 2 * 2 * 14 + 1; }
 
 // the Cython path runs four steps per launch through LDS tiles (k1_tile4) unless the grid is too small for them or an
-// explicit variant without bit 9 asks for single steps (k1_fstep)
-bool cython_tiles(const lb_sim *s) { return s->p.nx >= 64 && s->H >= 64 && (s->variant < 0 || (s->variant & 512)); }
+// explicit variant without VAR_TILES asks for single steps (k1_fstep)
+bool cython_tiles(const lb_sim *s) { return s->p.nx >= 64 && s->H >= 64 && (s->variant < 0 || (s->variant & VAR_TILES)); }
 
 // ---- what lb_autotune found, remembered across handles and processes (opt-in: LB_TUNE_CACHE) ------------------------------------
 // The kernel choice of a handle that was never tuned is a table of size thresholds measured on a pool of boxes that differ by +-5 %,
@@ -1677,29 +1653,15 @@ int lb_create(const lb_params *p, lb_sim **out)
     //  communication stream at the highest priority, a queue pool of its own, pushed the EDGE stream onto the interior's queue in
     //  bench.py's process structure, 370 -> 230 k MLUPS: profiles/r06_experiments.txt section 10c, r06h_bench_comm_prio.txt.)
     CREATE_TRY(hipStreamCreateWithFlags(&s->comm_stream, hipStreamNonBlocking));
-    {
-        // The edge stream (edge bands, halo push / RCCL) at NORMAL priority, like the other two.  Rounds 1-2 created it at the
-        // device's highest priority; with it, ~2 % of random slab partitions run through lb_run_group with events alone differed from
-        // the undivided run when four other processes kept the GPU busy (17 of ~900, tools/slab_stress.py), none of 1650 without,
-        // while a stand-alone stress of HIP's cross-queue ordering finds nothing (tools/queue_order_repro.hip) and an audit of
-        // every read-after-write and write-after-read pair of the cycle finds every one ordered.  The
-        // priority bought nothing measurable (profiles/r03_experiments.txt section 6), so the product has no such stream and
-        // no switch for one; the DIAGNOSTIC build (-DLB_DIAG, never loaded by the product) keeps LB_EDGE_PRIO=1 as the
-        // known-bad control for tools/slab_stress.py.
-        // (Rounds 3-5 passed the FIRST value hipDeviceGetStreamPriorityRange returns -- the LEAST priority, not the normal one the
-        //  comment claimed: the edge bands, which gate the halo, ran on a low-priority queue.  Round 6: no priority argument at all.)
-        bool high = false;
-#ifdef LB_DIAG
-        high = getenv("LB_EDGE_PRIO") && atoi(getenv("LB_EDGE_PRIO")) == 1;
-#endif
-        if (high) {
-            int least = 0, greatest = 0;
-            (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-            CREATE_TRY(hipStreamCreateWithPriority(&s->edge_stream, hipStreamNonBlocking, greatest));
-        } else {
-            CREATE_TRY(hipStreamCreateWithFlags(&s->edge_stream, hipStreamNonBlocking));
-        }
-    }
+    // The edge stream (edge bands, halo push / RCCL) at NORMAL priority, like the other two.  Rounds 1-2 created it at the
+    // device's highest priority; with it, ~2 % of random slab partitions run through lb_run_group with events alone differed from
+    // the undivided run when four other processes kept the GPU busy (17 of ~900, tools/slab_stress.py), none of 1650 without,
+    // while a stand-alone stress of HIP's cross-queue ordering finds nothing (tools/queue_order_repro.hip) and an audit of
+    // every read-after-write and write-after-read pair of the cycle finds every one ordered.  The
+    // priority bought nothing measurable (profiles/r03_experiments.txt section 6), so there is no such stream and no switch for one.
+    // (Rounds 3-5 passed the FIRST value hipDeviceGetStreamPriorityRange returns -- the LEAST priority, not the normal one the
+    //  comment claimed: the edge bands, which gate the halo, ran on a low-priority queue.  Round 6: no priority argument at all.)
+    CREATE_TRY(hipStreamCreateWithFlags(&s->edge_stream, hipStreamNonBlocking));
     const unsigned ev_flags = hipEventDisableTiming;
     CREATE_TRY(hipEventCreateWithFlags(&s->ev_boundary, ev_flags));
     CREATE_TRY(hipEventCreateWithFlags(&s->ev_halo, ev_flags));
@@ -1757,10 +1719,6 @@ int lb_destroy(lb_sim *s)
     if (s->comm_stream) (void)hipStreamSynchronize(s->comm_stream);
     if (s->edge_stream) (void)hipStreamSynchronize(s->edge_stream);
     drop_graph(s);
-    if (s->cyc_exec) (void)hipGraphExecDestroy(s->cyc_exec);
-    if (s->cyc_graph) (void)hipGraphDestroy(s->cyc_graph);
-    for (hipEvent_t e : {s->ev_fork, s->ev_join})
-        if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->xt_ev)
         if (e) (void)hipEventDestroy(e);
     for (lb_sim::PeerNb &nb : s->peer_nb)
@@ -1874,7 +1832,7 @@ int lb_exchange_stats(lb_sim *s, int64_t *n_exchanges, double *total_ms, double 
     if (max_ms) *max_ms = mx;
     const int D = s->multi_slab() ? cycle_depth(s, s->min_h > 0 ? s->min_h : s->H) : 0;
     if (cycle_depth_out) *cycle_depth_out = D;
-    if (band_rows) *band_rows = D ? 2 * D + band_extra(s, D, split_bands(s)) : 0;
+    if (band_rows) *band_rows = D ? 2 * D + band_extra(s, D, true) : 0;
     s->xt_count = s->xt_dropped = 0;
     return LB_OK;
 }
@@ -2313,86 +2271,22 @@ int lb_halo_floats(lb_sim *s)
 }
 
 namespace {
-constexpr int CYCLE_GRAPH_CYCLES = 4;
-
-// one halo cycle: E1 + C1, E2 + C2, exchange of the 2D edge rows (see slab_cycle_first).  split: the exchange on the communication
+// one halo cycle of lb_run: E1 + C1, E2 + C2 in split bands, exchange of the 2D edge rows (see slab_cycle_first) on the communication
 // stream, behind the outer part of E2 (ev_edge) and in front of the outer part of the next E1 (ev_halo).
-int slab_cycle_one(lb_sim *s, int D, bool last_of_run, const HaloTables &T, bool split)
+int slab_cycle_one(lb_sim *s, int D, bool last_of_run, const HaloTables &T)
 {
     int rc;
-    if ((rc = slab_cycle_first(s, D, false, split))) return rc;
+    if ((rc = slab_cycle_first(s, D, false, true))) return rc;
     s->cur ^= 1;
-    if ((rc = slab_cycle_second(s, last_of_run, D, split))) return rc;
+    if ((rc = slab_cycle_second(s, last_of_run, D, true))) return rc;
     s->cur ^= 1;
-    if (split) {
-        // (xchg_inline: on the compute stream, i.e. behind C2 and in front of the next C1 -- beside the tail of E2b at most)
-        hipStream_t xq = s->xchg_inline ? s->stream : s->comm_stream;
-        HIP_TRY(hipStreamWaitEvent(xq, s->ev_edge, 0));
-        if ((rc = exchange_halo(s, s->cur, xq, T))) return rc;
-        HIP_TRY(hipEventRecord(s->ev_halo, xq));
-    } else {
-        if ((rc = exchange_halo(s, s->cur, s->edge_stream, T))) return rc;
-    }
+    // (xchg_inline: on the compute stream, i.e. behind C2 and in front of the next C1 -- beside the tail of E2b at most)
+    hipStream_t xq = s->xchg_inline ? s->stream : s->comm_stream;
+    HIP_TRY(hipStreamWaitEvent(xq, s->ev_edge, 0));
+    if ((rc = exchange_halo(s, s->cur, xq, T))) return rc;
+    HIP_TRY(hipEventRecord(s->ev_halo, xq));
     HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_boundary, 0));
     return LB_OK;
-}
-
-bool cycle_graph_wanted(const lb_sim *s)
-{
-    static const bool on = getenv("LB_CYCLE_GRAPH") && atoi(getenv("LB_CYCLE_GRAPH")) != 0;
-    return on && s->peer_connected && !s->cyc_failed;
-}
-
-// CYCLE_GRAPH_CYCLES halo cycles as ONE graph launch.  Captured once per (lattice parity, depth, mask, variant): both queues
-// of the handle are captured -- the edge stream forks off the compute stream at the top and joins it at the bottom --, so the
-// cross-queue waits inside become graph edges; between two graph launches the two queues are joined (once per
-// 8 D CYCLE_GRAPH_CYCLES / 2 time steps instead of never: the price of replaying).  A capture the runtime refuses is not an
-// error: the caller falls back to eager launches.
-int slab_cycle_graph(lb_sim *s, int D, const HaloTables &T)
-{
-    const int key = (s->cur & 1) | (s->has_mask ? 2 : 0) | (D << 2) | (effective_variant(s) << 5);
-    if (!s->ev_fork) {
-        HIP_TRY(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
-    }
-    if (!s->cyc_exec || s->cyc_key != key) {
-        if (s->cyc_exec) (void)hipGraphExecDestroy(s->cyc_exec);
-        if (s->cyc_graph) (void)hipGraphDestroy(s->cyc_graph);
-        s->cyc_exec = nullptr;
-        s->cyc_graph = nullptr;
-        if (hipStreamBeginCapture(s->stream, hipStreamCaptureModeRelaxed) != hipSuccess) {
-            (void)hipGetLastError();
-            s->cyc_failed = true;
-            return LB_OK;
-        }
-        int rc = LB_OK;
-        const int cur0 = s->cur;
-        hipError_t e = hipEventRecord(s->ev_fork, s->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s->edge_stream, s->ev_fork, 0);
-        for (int c = 0; c < CYCLE_GRAPH_CYCLES && !rc && e == hipSuccess; ++c) rc = slab_cycle_one(s, D, false, T, false);
-        if (e == hipSuccess) e = hipEventRecord(s->ev_join, s->edge_stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s->stream, s->ev_join, 0);
-        s->cur = cur0;
-        hipGraph_t g = nullptr;
-        const hipError_t e2 = hipStreamEndCapture(s->stream, &g);
-        if (rc || e != hipSuccess || e2 != hipSuccess || !g || hipGraphInstantiate(&s->cyc_exec, g, nullptr, nullptr, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            if (g) (void)hipGraphDestroy(g);
-            s->cyc_exec = nullptr;
-            s->cyc_failed = true;
-            return LB_OK;
-        }
-        s->cyc_graph = g;
-        s->cyc_key = key;
-    }
-    // whatever the edge stream still has in flight (the exchange before the first cycle) precedes the graph, and what it is
-    // given afterwards follows it
-    HIP_TRY(hipEventRecord(s->ev_join, s->edge_stream));
-    HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_join, 0));
-    HIP_TRY(hipGraphLaunch(s->cyc_exec, s->stream));
-    HIP_TRY(hipEventRecord(s->ev_fork, s->stream));
-    HIP_TRY(hipStreamWaitEvent(s->edge_stream, s->ev_fork, 0));
-    return LB_OK;                                       // (an even number of launches: cur is unchanged)
 }
 }  // namespace
 
@@ -2421,7 +2315,7 @@ int lb_run(lb_sim *s, int n_steps)
         }
         // n = 4a + rem: the remainder first, step by step (k1_fstep: four cells per lane, 16-byte accesses, at the streaming
         // ceiling of a pass that moves 72 B per cell), then a launches of four steps each through LDS tiles (k1_tile4);
-        // grids too small for tiles, or LB_VARIANT / lb_set_variant bit 9 clear with an explicit variant: single steps only
+        // grids too small for tiles, or LB_VARIANT / lb_set_variant without VAR_TILES with an explicit variant: single steps only
         const dim3 blk(64, 4), grd((unsigned)((s->pitch / 4 + 63) / 64), (unsigned)((s->H + 3) / 4));
         // (rounds 4-5 also had a five-step marching form, k1_step5: bitwise right, slower than the tiles at the reference's sizes --
         //  3751 x 1251 with the cylinder 136 against 174 k MLUPS --, diagnostic build only in round 5, removed in round 6)
@@ -2488,28 +2382,17 @@ int lb_run(lb_sim *s, int n_steps)
             if ((rc = exchange_halo(s, s->cur, s->edge_stream, T))) return rc;
             s->ghost_depth = 2 * D;
         }
-        // (peer transport, LB_CYCLE_GRAPH=1: CYCLE_GRAPH_CYCLES cycles at a time replayed from a captured hipGraph -- the cycle's
-        //  kernel arguments never change, the exchange counters live on the device: slab_cycle_graph)
-        while (left >= 2 * D * CYCLE_GRAPH_CYCLES + 2 * D && cycle_graph_wanted(s)) {
-            if ((rc = slab_cycle_graph(s, D, T))) return rc;
-            if (!s->cyc_exec) break;                    // (capture refused: eager launches below)
-            left -= 2 * D * CYCLE_GRAPH_CYCLES;
-            s->ghost_depth = 2 * D;
-        }
         // (the exchanges of the cycles below run on the communication stream, each behind the outer edge rows of its cycle and in front
         //  of the next cycle's; whatever the edge stream has done so far -- the exchange above -- precedes the first of them)
-        const bool split = split_bands(s);
-        if (split) {
-            HIP_TRY(hipEventRecord(s->ev_halo, s->edge_stream));
-            HIP_TRY(hipStreamWaitEvent(s->xchg_inline ? s->stream : s->comm_stream, s->ev_halo, 0));
-        }
+        HIP_TRY(hipEventRecord(s->ev_halo, s->edge_stream));
+        HIP_TRY(hipStreamWaitEvent(s->xchg_inline ? s->stream : s->comm_stream, s->ev_halo, 0));
         for (; left >= 2 * D; left -= 2 * D) {
-            if ((rc = slab_cycle_one(s, D, left == 2 * D, T, split))) return rc;
+            if ((rc = slab_cycle_one(s, D, left == 2 * D, T))) return rc;
             s->ghost_depth = 2 * D;
         }
         if (left >= D) {
             const bool last = (left == D);
-            if ((rc = slab_cycle_first(s, D, last, split))) return rc;
+            if ((rc = slab_cycle_first(s, D, last, true))) return rc;
             HIP_TRY(hipEventRecord(s->ev_boundary, s->edge_stream));      // the edge bands of the new lattice are complete
             s->cur ^= 1;
             left -= D;
@@ -2518,14 +2401,14 @@ int lb_run(lb_sim *s, int n_steps)
             HIP_TRY(hipStreamWaitEvent(s->edge_stream, s->ev_interior, 0));
         }
         // (whatever follows on the edge stream follows the last exchange of the cycles)
-        if (split) HIP_TRY(hipStreamWaitEvent(s->edge_stream, s->ev_halo, 0));
+        HIP_TRY(hipStreamWaitEvent(s->edge_stream, s->ev_halo, 0));
     }
     if (left > 0 && s->ghost_depth < 3) {
         // ghost rows of the current lattice: exchange once before the first step
         if ((rc = exchange_halo(s, s->cur, s->edge_stream, HALO3))) return rc;
     }
-    const bool two = (effective_variant(s) & 32) && step2_applicable(s, hmin);
-    const bool three = (effective_variant(s) & 64) && step3_applicable(s, hmin);
+    const bool two = (effective_variant(s) & VAR_STEP2) && step2_applicable(s, hmin);
+    const bool three = (effective_variant(s) & VAR_STEP3) && step3_applicable(s, hmin);
     const bool stepped = left > 0;
     while (left > 0) {
         const int adv = next_advance(s, depth_mask(two, three), left);
@@ -2637,8 +2520,8 @@ int lb_run_group(lb_sim **sims, int count, int n_steps)
     bool two = true, three = true;
     int D = MAX_DEPTH;
     for (int i = 0; i < count; ++i) {
-        two = two && (effective_variant(sims[i]) & 32) && step2_applicable(sims[i], hmin);
-        three = three && (effective_variant(sims[i]) & 64) && step3_applicable(sims[i], hmin);
+        two = two && (effective_variant(sims[i]) & VAR_STEP2) && step2_applicable(sims[i], hmin);
+        three = three && (effective_variant(sims[i]) & VAR_STEP3) && step3_applicable(sims[i], hmin);
         D = std::min(D, cycle_depth(sims[i], hmin));
     }
     int left = n_steps;
@@ -2839,7 +2722,8 @@ int lb_comm_init(lb_sim *s, const void *unique_id_128, int rank, int nranks)
     //  (profiles/r06c_slab_proxy_channels.txt, timeline profiles/r06c_slab_timeline_rccl_4.txt).  The per-communicator form of that cap,
     //  ncclConfig_t::maxCTAs through ncclCommInitRankConfig, is accepted and IGNORED by RCCL 2.26 / 2.27 (59 workgroups still:
     //  profiles/r06c_slab_timeline_rccl_4_cap8.txt), and the environment variable is read once per process at the first communicator's
-    //  creation -- usually the caller's.  So it is the caller's to set before anything touches RCCL: bench.py does, INTEGRATION.md says so.)
+    //  creation -- usually the caller's.  So the cap is the caller's to set before anything touches RCCL; neither this library nor
+    //  bench.py sets it, and INTEGRATION.md explains why RCCL's default is left alone.)
     NCCL_TRY(g_rccl.CommInitRank(&s->comm, nranks, id, rank));
     s->rank = rank;
     s->nranks = nranks;
@@ -3065,8 +2949,8 @@ int lb_steps_per_launch(lb_sim *s)
         const int v = effective_variant(s);
         const int h = s->min_h > 0 ? s->min_h : s->H;
         if (cycle_depth(s, h)) n = cycle_depth(s, h);
-        else if ((v & 64) && step3_applicable(s, h)) n = 3;
-        else if ((v & 32) && step2_applicable(s, h)) n = 2;
+        else if ((v & VAR_STEP3) && step3_applicable(s, h)) n = 3;
+        else if ((v & VAR_STEP2) && step2_applicable(s, h)) n = 2;
     }
     return n;
 }

@@ -331,7 +331,8 @@ int lb_copy_calibration(lb_sim *s, int nontemporal, int64_t *bytes_moved);
  * the velocity-inlet family; automatic from 1100^2 (six steps; seven from 1900^2) periodic (1250^2 with obstacle-mask cells; slabs: 2400^2) / 1700^2 walled (slabs: 3800^2) cells), bit 16
  * (with bits 14, 15) the seven-step launches by k_deep2 -- two waves per strip and direction, two waves per SIMD (round 6; automatic on walled whole grids of 1700^2 ... 2900^2 cells, one of lb_autotune's candidates), bit 13
  * the LDS-tile kernel takes its tiles in launch order instead of one band of tile rows per XCD (bits 10, 11, 13: A/B
- * switches of things on by default).  Results never depend on it (bitwise); the ranks of one run must use the same value. */
+ * switches of things on by default).  Results never depend on it (bitwise); the ranks of one run must use the same value.
+ * The library's own names for these bits: VariantBits in 2d-lb_amd/csrc/launchers.h. */
 int lb_set_variant(lb_sim *s, int variant);
 /* Slab handles (round 6; new work, the reference is single-device: opencl_dim.py:229-240).  Depth of the fused kernel the halo cycle
  * of lb_run runs on (the cycle is 2 x depth time steps between two exchanges): 0 = automatic (the size thresholds of

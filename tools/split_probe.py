@@ -3,8 +3,7 @@
 them) fill the tail of the marching kernel's launches?  A launch of k_step4 is one round of resident waves and ends with its
 slowest wave (wave slots busy ~92 % of a launch); with G slabs on G compute streams the next launch of one slab can start while
 another slab's launch drains.  Prints MLUPS of the whole grid for G = 1 (plain handle) and G in --slabs.
-    python tools/split_probe.py [--n 8192] [--ny 8192] [--slabs 2,4] [--steps 192]
-(LB_STEP2_WAVES_PER_CU in the environment sizes every launch for that many waves per CU.)"""
+    python tools/split_probe.py [--n 8192] [--ny 8192] [--slabs 2,4] [--steps 192]"""
 import argparse
 import os
 import sys
@@ -33,7 +32,7 @@ def main():
     for _ in range(3):
         ms = one.timed_run(a.steps)
         best = max(best, a.n * ny * a.steps / (ms * 1e-3) / 1e6)
-    print("%d x %d %s, wpc=%s: plain handle %.1f MLUPS [%s]" % (a.n, ny, a.bc, os.environ.get("LB_STEP2_WAVES_PER_CU", "8"), best, one.hot_kernel()), flush=True)
+    print("%d x %d %s: plain handle %.1f MLUPS [%s]" % (a.n, ny, a.bc, best, one.hot_kernel()), flush=True)
     one.close()
     for g in [int(x) for x in a.slabs.split(",")]:
         ring = LocalSlabRing(a.n, ny, 1.7, g, bc=a.bc)
@@ -50,8 +49,8 @@ def main():
                 s.sync()
             el = time.perf_counter() - t0
             best = max(best, a.n * ny * a.steps / el / 1e6)
-        print("%d x %d %s, wpc=%s: %d virtual slabs through lb_run_group %.1f MLUPS (host clock, %d steps; %d steps per launch)"
-              % (a.n, ny, a.bc, os.environ.get("LB_STEP2_WAVES_PER_CU", "8"), g, best, a.steps, ring.slabs[0].steps_per_launch()), flush=True)
+        print("%d x %d %s: %d virtual slabs through lb_run_group %.1f MLUPS (host clock, %d steps; %d steps per launch)"
+              % (a.n, ny, a.bc, g, best, a.steps, ring.slabs[0].steps_per_launch()), flush=True)
         for s in ring.slabs:
             s.close()
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-wave timeline of one k_step4 / k_deep launch (diagnostic build, LB_DIAG bit 12): when each wave started and ended, on which
-XCD / CU / SIMD.  Usage (GPU box): [LB_TIMELINE_BC=pipe] [LB_TIMELINE_DEPTH=6|7] python tools/wave_timeline.py [n] [waves_per_cu]"""
+XCD / CU / SIMD.  Usage (GPU box): [LB_TIMELINE_BC=pipe] [LB_TIMELINE_DEPTH=6|7] python tools/wave_timeline.py [n]"""
 import os
 import sys
 
@@ -10,8 +10,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "2d-lb_amd"), ROOT]
 os.environ["LB_LIB"] = os.environ.get("LB_TIMELINE_LIB") or os.path.join(ROOT, "2d-lb_amd", "LB_D2Q9", "liblbhip_diag.so")
 os.environ["LB_DIAG"] = os.environ.get("LB_DIAG", "4096")
-if len(sys.argv) > 2:
-    os.environ["LB_STEP2_WAVES_PER_CU"] = sys.argv[2]
 
 
 def main():
@@ -32,7 +30,7 @@ def main():
     u = np.ascontiguousarray(raw.T).view(np.uint32).reshape(-1)          # device order: [y][x]
     # device rows are pitch floats long; host rows nx: with nx % 64 == 0 they coincide
     strips = (n + 255) // 256 if depth == 4 else (n + 239) // 240      # (k_step5, k_deep: 240 apart)
-    wpc = int(os.environ.get("LB_STEP2_WAVES_PER_CU", "8" if depth == 4 else "4"))
+    wpc = 8 if depth < 6 else 4                   # (the waves per CU the library sizes the launch for: launch_step2)
     cap = 256 * wpc // 2                          # an item = a pair of segments = one workgroup of two waves (up / down)
     segs = max(cap // strips, 1)
     seg_rows = max(-(-ny // segs), 8)
