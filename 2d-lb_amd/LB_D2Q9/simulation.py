@@ -209,7 +209,8 @@ class Simulation(object):
         every kernel); pass wait=False to only enqueue (never blocks the host).  A blocking run of at least four
         times the tuning pass (4 x 361 + 7 = 1451 steps; 4 x 889 + 7 on grids <= 768^2) first times the candidate kernel
         configurations on its own first steps (lb_autotune_quick: they are bitwise equivalent, the trajectory is
-        unchanged) and keeps the fastest for this grid; shorter runs use the size heuristic (or call autotune())."""
+        unchanged; the pass advances at most (n - 7) // 4 steps, a runner-up's longer comparison included) and keeps the
+        fastest for this grid; shorter runs use the size heuristic (or call autotune())."""
         n = int(num_iterations)
         if wait and n > 0:
             # (the pass costs 361 steps, 889 on grids <= 768^2, some of them in configurations several times slower than

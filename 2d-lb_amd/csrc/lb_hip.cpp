@@ -32,6 +32,7 @@
 #include <dlfcn.h>
 #include <unistd.h>
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <initializer_list>
 #include <map>
@@ -1272,10 +1273,11 @@ int run_whole_grid(lb_sim *s, int n_steps, bool final_macro = true)
 // bitwise identical results, so tuning advances the simulation like any other steps): four-, three- and
 // two-step marching kernels at 8 and 4 waves per CU, and the single-step kernel.  Which one wins depends
 // on the grid's aspect ratio, the mask and the boundary family (wide, short pipes favour fewer, longer
-// segments: +20 % at 3751 x 1251).  Returns the number of steps advanced, or a negative status.
+// segments: +20 % at 3751 x 1251).  Returns the number of steps advanced, or a negative status.  max_steps: the caller's budget --
+// the rounds are the caller's to fit into it (autotune_quick_cost), the runner-up pass below is skipped where it would not fit.
 void tune_cache_store(const lb_sim *s);                 // (LB_TUNE_CACHE, below)
 
-int autotune_whole_grid(lb_sim *s, int rounds)
+int autotune_whole_grid(lb_sim *s, int rounds, int max_steps)
 {
     struct Cand { int steps, wpc; };
     // (k_step4 at 8192^2 on one box: 4 waves per CU 189 k MLUPS, 6: 243 k, 8: 232 k, 12: 210 k -- profiles/r02_experiments.txt)
@@ -1344,13 +1346,15 @@ int autotune_whole_grid(lb_sim *s, int rounds)
         if (usable[c] && (best < 0 || ms_min[c] < best_ms)) { best = c; best_ms = ms_min[c]; }
     // A runner-up within 5 % (round 5: k_step5 and k_deep<7> on config 5, 19.7 against 19.1 steps per ms -- the choice flipped from run to
     // run, the rocprofv3 profile and the driver's line named different kernels): the two once more over samples four times as long, three
-    // rounds alternating, minimum of each.
+    // rounds alternating, minimum of each.  Only where the caller's budget holds it and the closing step below: 3 x 4 x (14 + 14) = 336
+    // steps for the two seven-step kernels, which lb_autotune_quick(h, 361) has no room for (its rounds alone take up to 360 + 1).
     if (best >= 0 && !small_grid(s)) {
         int second = -1;
         for (int c = 0; c < NC; ++c)
             if (usable[c] && c != best && (cands[c].steps != cands[best].steps || cands[c].steps == 7) &&       // (7: k_deep<7> against k_deep2<7>)
                 (second < 0 || ms_min[c] < ms_min[second])) second = c;
-        if (second >= 0 && ms_min[second] < 1.05f * best_ms) {
+        if (second >= 0 && ms_min[second] < 1.05f * best_ms &&
+            3 * 4 * (per_of(cands[best]) + per_of(cands[second])) <= max_steps - used - 1) {
             float again[2] = {1e30f, 1e30f};
             const int pair[2] = {best, second};
             for (int r = 0; r < 3; ++r)
@@ -1437,8 +1441,9 @@ int corners_patch(lb_sim *s, int which)
     return LB_OK;
 }
 
-// steps a quick (one-round) tuning pass consumes at most: 11 candidates x 2 samples x 12 (36) steps, 2 x 2 x 10, + 1
-// (an upper bound: every candidate usable)
+// steps a quick (one-round) tuning pass consumes at most: 11 candidates x 2 samples x 12 (36) steps, 2 x 2 x 10, 2 x 2 x 14, + 1
+// (an upper bound: every candidate usable).  The runner-up pass of autotune_whole_grid is not counted: it only runs where the
+// budget it is given holds it, and lb_autotune_quick gives it max_steps, so the quick pass never advances more than max_steps.
 int autotune_quick_cost(const lb_sim *s) { return 11 * 2 * (small_grid(s) ? 36 : 12) + 2 * 2 * 10 + 2 * 2 * 14 + 1; }
 
 // the Cython path runs four steps per launch through LDS tiles (k1_tile4) unless the grid is too small for them or an
@@ -2968,7 +2973,7 @@ int lb_autotune(lb_sim *s)
     //  kernel the un-profiled run before it chose: tools/gpu_profile.sh)
     if (!s->tune_cache_checked && s->variant < 0 && !s->tuned_steps && tune_cache_apply(s)) return 0;
     DeviceGuard guard(s->p.device);
-    return autotune_whole_grid(s, 6);
+    return autotune_whole_grid(s, 6, INT_MAX);        // (unbounded: the runner-up pass always runs when it applies)
 }
 
 int lb_autotune_quick(lb_sim *s, int max_steps)
@@ -2979,7 +2984,7 @@ int lb_autotune_quick(lb_sim *s, int max_steps)
     if (!s->tune_cache_checked && tune_cache_apply(s)) return 0;       // (LB_TUNE_CACHE: an earlier handle of this shape was tuned)
     if (!autotune_applies(s) || s->variant >= 0 || s->tuned_steps || max_steps < autotune_quick_cost(s)) return 0;
     DeviceGuard guard(s->p.device);
-    return autotune_whole_grid(s, 1);
+    return autotune_whole_grid(s, 1, max_steps);
 }
 
 int lb_hot_kernel(lb_sim *s, char *buf, int buflen)

@@ -304,7 +304,8 @@ int lb_autotune(lb_sim *s);
 /* The same with one sample per candidate, for callers that are about to run max_steps steps anyway and
  * will wait for them (the Python classes' blocking run()): tunes only when the handle is untuned, the
  * variant automatic and the pass (361 steps; 889 on grids <= 768^2) fits into max_steps; returns the number
- * of steps advanced, 0 when it did nothing.
+ * of steps advanced, 0 when it did nothing, and never more than max_steps: the longer comparison of a runner-up
+ * within 5 % (lb_autotune's) is made only when max_steps has room for it as well.
  *
  * Environment: LB_TUNE_CACHE=<file> (or "mem": this process only) remembers every result of lb_autotune / lb_autotune_quick under
  * the handle's shape (GPU, grid, rows owned, boundary family, mask or not, layout flags, semantics; one text line each) and lets the

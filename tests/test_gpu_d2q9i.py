@@ -93,9 +93,9 @@ def test_d2q9i_every_fused_kernel_bitwise_and_vs_oracle(lbhip, oracle, nx, ny, m
         s.set_f(f0)
         s.run(5); s.run(3)
         outs.append(s.get_fields(("f", "rho", "u", "v")))
-    for o in outs[1:]:
+    for variant, o in zip(variants[1:], outs[1:]):
         for k in o:
-            assert np.array_equal(outs[0][k], o[k]), k
+            assert np.array_equal(outs[0][k], o[k]), (variant, k)
     ref = oracle.O2Sim(nx, ny, 1.0, oracle.BC_PIPE, 1.0002, 1., mask=mask, d2q9i=True)
     ref.set_f(f0)
     ref.run(8)

@@ -47,24 +47,36 @@ def test_config2_lid_driven_cavity_1024_vs_oracle(lbhip, oracle):
 
 
 @pytest.mark.parametrize("variant,steps", [(9, 2), (33, 2), (97, 3), (353, 4), (353, 8), (4449, 5), (4449, 10), (20833, 6), (20833, 12),
-                                           (-1, 4), (-1, 7), (-1, 14)])
+                                           (-1, 4), (-1, 7), (-1, 14), (119137, 7), (119137, 14), ("tuned", 7)])
 def test_config3_kelvin_helmholtz_4096_vs_oracle(lbhip, oracle, variant, steps):
     """4096x4096 periodic double shear layer against the oracle: single-, two-, three-, four- and five-step kernels
     (353 = k_step4, 4449 = k_step5, 20833 = k_deep<6> forced, -1 = the automatic choice, which is k_deep<7> at this size: the kernel
-    bench.py times; 4 steps of it = its remainder launch, k_step4), one and two launches of the four- ... seven-step kernel."""
+    bench.py times; 4 steps of it = its remainder launch, k_step4), one and two launches of the four- ... seven-step kernel; k_deep2<7>
+    forced (119137) and whatever autotune() picks (the bench's sequence: tune, then the initial state again)."""
     from LB_D2Q9.simulation import Simulation
     import bench
     n = 4096
     rho, u, v = bench.shear_layer(n, n, 0, n, U=0.05)
     f0 = equilibrium(rho, u, v)
     sim = Simulation(n, n, 1.8, bc="periodic")
-    sim.set_variant(variant)
-    if variant in (353, 4449, 20833, -1):
-        assert sim.steps_per_launch() == {353: 4, 4449: 5, 20833: 6, -1: 7}[variant]
+    if variant == "tuned":
+        sim.set_f(f0)
+        assert sim.autotune() > 0
+        tuned = sim.hot_kernel()
+        print("4096^2: the tuner picked", tuned)
+        assert sim.plan_launches(steps) == [7] and ("k_deep<7>" in tuned or "k_deep2<7>" in tuned), tuned
+    else:
+        sim.set_variant(variant)
+    if variant in (353, 4449, 20833, -1, 119137):
+        assert sim.steps_per_launch() == {353: 4, 4449: 5, 20833: 6, -1: 7, 119137: 7}[variant]
+    if variant in (-1, 119137):
+        assert ("k_deep2<7>" if variant == 119137 else "k_deep<7>") in sim.hot_kernel()
+    if variant == 119137:
+        assert sim.plan_launches(steps) == [7] * (steps // 7)
     sim.set_f(f0)
     ref = oracle.O2Sim(n, n, 1.8, oracle.BC_PERIODIC)
     ref.set_f(f0)
-    sim.run(steps); ref.run(steps)
+    sim.run(steps); ref.run(steps, openmp=variant in (119137, "tuned"))
     # the contract's bound for this many steps (contract_tol: n x the single-step bounds of SURVEY 8c, not fitted to a kernel);
     # measured at 4096^2, round 5's arithmetic (= round 4's): 4 steps f 3.3e-7 rho 1.01e-6; 8 steps f 6.9e-7 rho 1.25e-6
     tol = contract_tol(steps)
@@ -96,39 +108,68 @@ def test_config4_shear_layer_8192_properties(lbhip):
 
 
 def test_config4_shear_layer_8192_default_kernel_vs_oracle(lbhip, oracle):
-    """8192x8192, the bench workload, the bench's initial state, the kernel the bench times (k_deep<7> on segment pairs: one
-    launch = 7 steps, two launches = 14) DIRECTLY against the oracle at the size the metric is quoted on -- the same-size field
-    comparison the reference's own check makes (testing/Bryan/opencl_check_03.ipynb:593, 778).  The oracle runs its
-    -fopenmp build (same bits as the serial one: tests/test_oracle_golden.py).  Bounds: the contract's, n x the single-step ones
-    (contract_tol); the measured margins are printed."""
+    """8192x8192, the bench workload, the bench's initial state, the kernels the bench times (k_deep<7> or k_deep2<7> on segment pairs:
+    one launch = 7 steps, two launches = 14) DIRECTLY against the oracle at the size the metric is quoted on -- the same-size field
+    comparison the reference's own check makes (testing/Bryan/opencl_check_03.ipynb:593, 778).  Three handles against one oracle run:
+    (a) the static default, k_deep<7>; (b) k_deep2<7> forced (variant 119137); (c) the bench's own sequence -- autotune(), the initial
+    state again, run -- whichever of the two the tuner picks, which must also be the bits of (a) or (b).  The oracle runs its -fopenmp
+    build (same bits as the serial one: tests/test_oracle_golden.py).  Bounds: the contract's, n x the single-step ones (contract_tol);
+    the measured margins are printed."""
     from LB_D2Q9.simulation import Simulation
     import bench
     n = 8192
-    sim = Simulation(n, n, 1.7, bc="periodic")
-    assert sim.steps_per_launch() == 7 and "k_deep<7>" in sim.hot_kernel()
-    sim.init_equilibrium(*bench.shear_layer(n, n, 0, n))          # f = feq, built on the device, as bench.py does
-    f0 = sim.get_fields(("f",))["f"]
+    fields = bench.shear_layer(n, n, 0, n)
+    sims = {}
+    for name, variant in (("default", -1), ("k_deep2<7>", 119137), ("tuned", -1)):
+        sim = Simulation(n, n, 1.7, bc="periodic")
+        sim.set_variant(variant)
+        sim.init_equilibrium(*fields)                              # f = feq, built on the device, as bench.py does
+        if name == "tuned":
+            assert sim.autotune() > 0                              # bench.py: autotune(), then the initial state again
+            sim.init_equilibrium(*fields)
+        sims[name] = sim
+    del fields
+    assert sims["default"].steps_per_launch() == 7 and "k_deep<7>" in sims["default"].hot_kernel()
+    assert sims["k_deep2<7>"].steps_per_launch() == 7 and "k_deep2<7>" in sims["k_deep2<7>"].hot_kernel()
+    tuned = sims["tuned"].hot_kernel()
+    twin = "k_deep2<7>" if "k_deep2<7>" in tuned else "default"
+    print("8192^2: the tuner picked", tuned)
+    assert sims["tuned"].steps_per_launch() == 7 and ("k_deep<7>" in tuned or "k_deep2<7>" in tuned), tuned
+    f0 = sims["default"].get_fields(("f",))["f"]
     ref = oracle.O2Sim(n, n, 1.7, oracle.BC_PERIODIC)
     ref.set_f(f0)
     del f0
     done = 0
     for steps in (7, 14):
         tol = contract_tol(steps)
-        sim.run(steps - done)
         ref.run(steps - done, openmp=True)
+        kept = None
+        for name in ("default", "k_deep2<7>", "tuned"):           # one handle's fields on the host at a time (+ the tuned one's twin)
+            sim = sims[name]
+            assert sim.plan_launches(steps - done) == [7], (name, sim.plan_launches(steps - done))
+            sim.run(steps - done)
+            g = sim.get_fields(("f", "rho", "u", "v"))
+            # (nx, ny, 9) F-ordered on the GPU side is the oracle's (9, ny, nx) C-ordered array: compare without copies
+            gf = np.asarray(g["f"]).transpose(2, 1, 0)
+            assert gf.flags.c_contiguous
+            meas = {"f": max(maxdiff(gf[k9], ref.f[k9]) for k9 in range(9))}      # (plane by plane: no 5 GB float64 temporaries)
+            for k in ("rho", "u", "v"):
+                meas[k] = maxdiff(np.asarray(g[k]).T, getattr(ref, k))
+            report = ", ".join("%s %.2e / %.1e" % (k, meas[k], tol[k]) for k in ("f", "rho", "u", "v"))
+            print("8192^2, %s, %d steps, measured / bound: %s" % (name, steps, report))
+            for k in meas:
+                assert meas[k] <= tol[k], (name, steps, k, report)
+            del gf
+            if name == twin:
+                kept = g
+            elif name == "tuned":
+                for k in g:
+                    assert np.array_equal(g[k], kept[k]), (twin, steps, k)
+            del g
+        del kept
         done = steps
-        g = sim.get_fields(("f", "rho", "u", "v"))
-        # (nx, ny, 9) F-ordered on the GPU side is the oracle's (9, ny, nx) C-ordered array: compare without copies
-        gf = np.asarray(g["f"]).transpose(2, 1, 0)
-        assert gf.flags.c_contiguous
-        meas = {"f": max(maxdiff(gf[k9], ref.f[k9]) for k9 in range(9))}      # (plane by plane: no 5 GB float64 temporaries)
-        for k in ("rho", "u", "v"):
-            meas[k] = maxdiff(np.asarray(g[k]).T, getattr(ref, k))
-        report = ", ".join("%s %.2e / %.1e" % (k, meas[k], tol[k]) for k in ("f", "rho", "u", "v"))
-        print("8192^2, %d steps, measured / bound: %s" % (steps, report))
-        for k in meas:
-            assert meas[k] <= tol[k], (steps, k, report)
-        del g
+    for sim in sims.values():
+        sim.close()
     assert float(np.abs(ref.u).max()) > 0.03                       # the shear layer is there
 
 
@@ -200,7 +241,8 @@ def test_planar_layout_8192_deep_kernels_equal_single_step_kernel_bitwise(lbhip)
 def test_full_size_families_default_and_four_step_kernel_equal_single_step_kernel_bitwise(lbhip, bc, masked):
     """8192 x 8192 in the other boundary families, with and without an obstacle mask (the instantiations of k_step5 and k_step4
     the periodic bench never runs: wall rules on the boundary cell, lanes beyond the box, mask history registers): default
-    kernel (k_deep<7> at this size: 4 + 4, 3 steps), six-, five- and four-step kernel against the single-step kernel, bit for bit."""
+    kernel (k_deep<7> at this size: 4 + 4, 3 steps), six-, five- and four-step kernel and k_deep2<7> (119137: what the tuner may pick)
+    against the single-step kernel, bit for bit."""
     from LB_D2Q9.simulation import Simulation
     import bench
     n = 8192
@@ -210,17 +252,24 @@ def test_full_size_families_default_and_four_step_kernel_equal_single_step_kerne
         if bc != "periodic":
             mask[0, :] = mask[-1, :] = False
             mask[:, 0] = mask[:, -1] = False
-    out = []
-    for variant in (-1, 9, 353, 4449, 20833):
+    want = None
+    for variant in (9, -1, 353, 4449, 20833, 119137):       # (each result against the single-step kernel's as it arrives)
         sim = Simulation(n, n, 1.6, bc=bc, inlet_rho=1.0005, lid_u=0.05, obstacle_mask=mask)
         sim.set_variant(variant)
-        assert sim.steps_per_launch() == {9: 1, -1: 7, 353: 4, 4449: 5, 20833: 6}[variant]
+        assert sim.steps_per_launch() == {9: 1, -1: 7, 353: 4, 4449: 5, 20833: 6, 119137: 7}[variant]
+        if variant in (-1, 119137):
+            assert ("k_deep2<7>" if variant == 119137 else "k_deep<7>") in sim.hot_kernel(), sim.hot_kernel()
         sim.init_equilibrium(*bench.shear_layer(n, n, 0, n))
         sim.run(14)
         sim.run(3)
-        out.append(sim.get_fields(("f",))["f"])
+        f = sim.get_fields(("f",))["f"]
         sim.close()
-    assert np.all(np.isfinite(out[0])) and all(np.array_equal(o, out[1]) for o in out)
+        if want is None:
+            assert np.all(np.isfinite(f))
+            want = f
+        else:
+            assert np.array_equal(f, want), variant
+        del f
 
 
 @pytest.mark.parametrize("bc,nx,ny,masked", [("pipe", 3751, 1251, True), ("cavity", 2048, 2048, False),
@@ -311,7 +360,9 @@ def test_one_slab_of_eight_as_a_ring_of_its_own_equals_the_plain_grid_bitwise(lb
 
 def test_config5_porous_obstacles_4096_vs_oracle(lbhip, oracle):
     """4096x4096 pipe flow through the reference's obstacle image (docs/CS205_obstacle_4.tif rescaled
-    by nearest neighbour), bounce-back mask, two steps against the oracle + a longer sanity run."""
+    by nearest neighbour), bounce-back mask, against the oracle at 3, 7 and 17 steps + a longer sanity run.  Three handles: the static
+    choice (k_deep<7>), k_deep2<7> forced -- what bench.py's line for this configuration runs after tuning, the build the compiler gives
+    32 B/lane of scratch -- and an autotuned one; the two others also bit for bit the static handle's."""
     from LB_D2Q9.masks import obstacle_mask_from_tiff
     from LB_D2Q9.simulation import Simulation
     n = 4096
@@ -322,16 +373,50 @@ def test_config5_porous_obstacles_4096_vs_oracle(lbhip, oracle):
     rin = 1.001
     ramp = oracle.density_ramp(n, n, rin, 1.)
     f0 = equilibrium(ramp.astype(np.float64), np.zeros((n, n)), np.zeros((n, n)))
-    sim = Simulation(n, n, 1.0, bc="pipe", inlet_rho=rin, outlet_rho=1., obstacle_mask=mask)
-    ref = oracle.O2Sim(n, n, 1.0, oracle.BC_PIPE, rin, 1., mask=mask)
-    sim.set_f(f0); ref.set_f(f0)
+    sims = {}
+    for name, variant in (("static", -1), ("k_deep2<7>", 119137), ("tuned", -1)):
+        sims[name] = s = Simulation(n, n, 1.0, bc="pipe", inlet_rho=rin, outlet_rho=1., obstacle_mask=mask)
+        s.set_variant(variant)
+        s.set_f(f0)
+        if name == "tuned":                           # bench.py's sequence: tune on live steps, then the initial state again
+            assert s.autotune() > 0
+            s.set_f(f0)
+            print("config 5: the tuner picked", s.hot_kernel())
+            assert "<PIPE, MASK>" in s.hot_kernel()
+    sim = sims["static"]
     assert sim.steps_per_launch() == 7 and "k_deep<7>" in sim.hot_kernel()     # (walled + mask: k_deep from 4000^2 cells)
-    sim.run(3); ref.run(3)                            # remainder launch: k_step3
-    assert_fields_close(sim.get_fields(("f", "rho", "u", "v")), ref.get_fields(), dict(f=5e-7, rho=1e-6, u=1e-6, v=1e-6))
-    sim.run(4); ref.run(4)                            # remainder launch: k_step4<PIPE, MASK>
-    assert_fields_close(sim.get_fields(("f", "rho", "u", "v")), ref.get_fields(), dict(f=1e-6, rho=1e-6, u=1e-6, v=1e-6))
-    sim.run(10); ref.run(10)                          # the plan's launches of k_deep<PIPE, MASK> (and a remainder launch)
-    assert_fields_close(sim.get_fields(("f", "rho", "u", "v")), ref.get_fields(), dict(f=2.5e-6, rho=2.5e-6, u=2.5e-6, v=2.5e-6))
+    assert sims["k_deep2<7>"].steps_per_launch() == 7 and "k_deep2<7>" in sims["k_deep2<7>"].hot_kernel()
+    ref = oracle.O2Sim(n, n, 1.0, oracle.BC_PIPE, rin, 1., mask=mask)
+    ref.set_f(f0)
+    done = 0
+    # 3 steps: remainder launch k_step3; 7: + k_step4<PIPE, MASK>; 17: the static handle's plan of ten steps (k_step4 + k_deep<6>), the
+    # others' 3 + 7 -- one launch of the seven-step kernel (k_deep2<7><PIPE, MASK> on the forced handle) -- against the same oracle state
+    for steps, tol in ((3, dict(f=5e-7, rho=1e-6, u=1e-6, v=1e-6)), (7, dict(f=1e-6, rho=1e-6, u=1e-6, v=1e-6)),
+                       (17, dict(f=2.5e-6, rho=2.5e-6, u=2.5e-6, v=2.5e-6))):
+        ref.run(steps - done)
+        want = ref.get_fields()
+        first = None
+        for name, s in sims.items():
+            if steps - done == 10 and name != "static":
+                if name == "k_deep2<7>":
+                    assert s.plan_launches(7) == [7]
+                s.run(3)
+                s.run(7)
+            else:
+                s.run(steps - done)
+            g = s.get_fields(("f", "rho", "u", "v"))
+            print("config 5, %s, %d steps:" % (name, steps))
+            assert_fields_close(g, want, tol)
+            if first is None:
+                first = g
+            else:
+                for k in g:
+                    assert np.array_equal(g[k], first[k]), (name, steps, k)
+            del g
+        del want, first
+        done = steps
+    sims["k_deep2<7>"].close()
+    sims["tuned"].close()
     sim.run(183)
     g = sim.get_fields(("rho", "u", "v"))
     assert np.all(np.isfinite(g["rho"])) and abs(g["rho"].mean() - 1.0005) < 1e-3

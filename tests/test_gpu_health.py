@@ -33,14 +33,16 @@ def host_health(f):
     return int((~ok).sum()), float(np.sqrt(3.0 * usq[ok].max())), float(rho[ok].sum())
 
 
+@pytest.mark.parametrize("nx,ny", [(1216, 320), (2048, 2048)], ids=["1216x320", "2048x2048"])
 @pytest.mark.parametrize("bc", ["periodic", "pipe", "cavity"])
 @pytest.mark.parametrize("masked", [False, True])
-def test_deep_kernels_store_the_single_step_kernels_fields_when_eager(lbhip, bc, masked):
-    """k_deep<6> / k_deep<7> instantiated with MACRO (a handle that stores rho, u, v with the last launch of every run: the reference-named
-    classes do) -- the launch whose hand-written wait counts twelve stores instead of nine -- against the single-step kernel on such a
-    handle: populations and stored fields, bit for bit, over runs whose last launch is a deep one."""
+def test_deep_kernels_store_the_single_step_kernels_fields_when_eager(lbhip, bc, masked, nx, ny):
+    """k_deep<6> / k_deep<7> / k_deep2<7> instantiated with MACRO (a handle that stores rho, u, v with the last launch of every run: the
+    reference-named classes do) -- the launch whose hand-written wait counts twelve stores instead of nine -- against the single-step kernel
+    on such a handle: populations and stored fields, bit for bit, over runs whose last launch is a deep one.  At 2048^2 also the automatic
+    choice, which is where the size table serves these builds: k_deep2<7> in the walled families (1700^2 to 2900^2 cells), k_deep<7>
+    in the periodic box."""
     from LB_D2Q9.simulation import Simulation
-    nx, ny = 1216, 320
     rng = np.random.default_rng(77)
     f0 = _random_state(rng, nx, ny)
     mask = None
@@ -49,19 +51,26 @@ def test_deep_kernels_store_the_single_step_kernels_fields_when_eager(lbhip, bc,
         if bc != "periodic":
             mask[0, :] = mask[-1, :] = False
             mask[:, 0] = mask[:, -1] = False
-    out = []
-    for variant in (0, 97 | 256 | 4096 | 16384, 97 | 256 | 4096 | 16384 | 32768, 97 | 256 | 4096 | 16384 | 32768 | 65536):
+    want = None
+    deep6, deep7, deep2 = 97 | 256 | 4096 | 16384, 97 | 256 | 4096 | 16384 | 32768, 97 | 256 | 4096 | 16384 | 32768 | 65536
+    variants = (0, deep6, deep7, deep2) + ((-1,) if nx * ny >= 2048 * 2048 else ())
+    for variant in variants:
         s = Simulation(nx, ny, 1.6, bc=bc, obstacle_mask=mask, eager_macro=True, inlet_rho=1.002, lid_u=0.04)
         s.set_variant(variant)
         if variant:
-            assert "k_deep" in s.hot_kernel()
+            kernel = {deep6: "k_deep<6>", deep7: "k_deep<7>", deep2: "k_deep2<7>",
+                      -1: "k_deep<7>" if bc == "periodic" else "k_deep2<7>"}[variant]
+            assert s.steps_per_launch() == (6 if variant == deep6 else 7) and kernel in s.hot_kernel(), (variant, s.hot_kernel())
         s.set_f(f0)
         for n in (7, 14, 6, 13, 1):
             s.run(n)
-        out.append(s.get_fields(("f", "rho", "u", "v")))
+        got = s.get_fields(("f", "rho", "u", "v"))
         s.close()
-    for k in out[0]:
-        assert np.array_equal(out[0][k], out[1][k]) and np.array_equal(out[0][k], out[2][k]), k
+        if want is None:
+            want = got
+            continue
+        for k in want:
+            assert np.array_equal(want[k], got[k]), (variant, k)
 
 
 @pytest.mark.parametrize("bc,kw", FAMILIES)

@@ -217,25 +217,26 @@ def test_two_step_kernel_equals_single_step_kernel(lbhip, oracle, bc, nx, ny, ma
     kw = dict(inlet_rho=1.004, lid_u=0.06)
     sims = []
     # single step / two-step / + NT stores / three-step (+ two-step remainder) / four-step (+ remainders) /
-    # four steps through LDS tiles (+ single-step remainders) / five-step on overlapping strips (+ remainders)
-    for variant in (0, 32, 33, 97, 97 | 256, 512, 97 | 256 | 4096, 97 | 256 | 4096 | 16384, 97 | 256 | 4096 | 16384 | 32768,
-                    97 | 256 | 4096 | 16384 | 32768 | 65536):                     # (the last one: k_deep2)
+    # four steps through LDS tiles (+ single-step remainders) / five-step on overlapping strips (+ remainders) /
+    # k_deep<6> / k_deep<7> / k_deep2<7>
+    variants = (0, 32, 33, 97, 97 | 256, 512, 97 | 256 | 4096, 97 | 256 | 4096 | 16384, 97 | 256 | 4096 | 16384 | 32768,
+                97 | 256 | 4096 | 16384 | 32768 | 65536)
+    for variant in variants:
         s = Simulation(nx, ny, 1.6, bc=bc, obstacle_mask=mask, **kw)
         s.set_variant(variant)
         assert s.steps_per_launch() == {0: 1, 32: 2, 33: 2, 97: 3, 353: 4, 512: 4, 4449: 5, 20833: 6, 53601: 7, 119137: 7}[variant]
+        if variant & 16384:
+            assert ("k_deep2<7>" if variant & 65536 else "k_deep<%d>" % s.steps_per_launch()) in s.hot_kernel(), variant
         s.set_f(f0)
         s.run(7)                      # 7 = 1+2+2+2 (two-step) = 1+3+3 (three-step) = 3+4 (four-step) = 2+5 (five-step) = 1+6 = 7
         s.run(4)                      # 4 = 2+2 = 1+3 = 4
         sims.append(s.get_fields(("f", "rho", "u", "v")))
     for k in ("f", "rho", "u", "v"):
-        assert np.array_equal(sims[0][k], sims[1][k]), k          # -ffp-contract=on: same rounding in every kernel
         assert np.array_equal(sims[1][k], sims[2][k]), k          # NT stores never change results
-        assert np.array_equal(sims[0][k], sims[3][k]), k          # three steps per pass: still bitwise
-        assert np.array_equal(sims[0][k], sims[4][k]), k          # four steps per pass (LDS windows): still bitwise
-        assert np.array_equal(sims[0][k], sims[5][k]), k          # four steps per pass (LDS tiles): still bitwise
-        assert np.array_equal(sims[0][k], sims[6][k]), k          # five steps per pass (overlapping strips): still bitwise
-        assert np.array_equal(sims[0][k], sims[7][k]), k          # six steps per pass (k_deep<6>, one wave per SIMD): still bitwise
-        assert np.array_equal(sims[0][k], sims[8][k]), k          # seven steps per pass (k_deep<7>): still bitwise
+    # -ffp-contract=on: same rounding in every kernel -- every variant above, bit for bit the single-step kernel's
+    for variant, o in zip(variants[1:], sims[1:]):
+        for k in ("f", "rho", "u", "v"):
+            assert np.array_equal(sims[0][k], o[k]), (variant, k)
     code = {"pipe": oracle.BC_PIPE, "periodic": oracle.BC_PERIODIC, "cavity": oracle.BC_CAVITY}[bc]
     o = oracle.O2Sim(nx, ny, 1.6, code, 1.004, 1., 0.06, 1., mask=mask)
     o.set_f(f0)
@@ -354,7 +355,8 @@ def test_five_and_six_step_kernel_strip_boundaries(lbhip, bc, nx):
         mask[0, :] = mask[-1, :] = False
         mask[:, 0] = mask[:, -1] = False
     out = []
-    for variant in (0, 97 | 256 | 4096, 97 | 256 | 4096 | 16384, 97 | 256 | 4096 | 16384 | 32768, 97 | 256 | 4096 | 16384 | 32768 | 65536):
+    variants = (0, 97 | 256 | 4096, 97 | 256 | 4096 | 16384, 97 | 256 | 4096 | 16384 | 32768, 97 | 256 | 4096 | 16384 | 32768 | 65536)
+    for variant in variants:
         s = Simulation(nx, ny, 1.55, bc=bc, obstacle_mask=mask, inlet_rho=1.003, lid_u=0.05)
         s.set_variant(variant)
         if variant:
@@ -365,8 +367,9 @@ def test_five_and_six_step_kernel_strip_boundaries(lbhip, bc, nx):
         s.run(7)
         out.append(s.get_fields(("f", "rho", "u", "v")))
         s.close()
-    for k in out[0]:
-        assert np.array_equal(out[0][k], out[1][k]) and np.array_equal(out[0][k], out[2][k]) and np.array_equal(out[0][k], out[3][k]), k
+    for variant, o in zip(variants[1:], out[1:]):
+        for k in out[0]:
+            assert np.array_equal(out[0][k], o[k]), (variant, k)
 
 
 @pytest.mark.parametrize("bc,nx,ny", [("pipe", 96, 64), ("periodic", 64, 96), ("cavity", 130, 70), ("periodic", 256, 256),
@@ -718,6 +721,44 @@ def test_pipe_flow_cylinder_docs_case_vs_oracle(lbhip, oracle):
     assert np.allclose(phys["u"], sim.get_fields()["u"] * (sim.delta_x / sim.delta_t) * (sim.L / sim.T))
 
 
+def test_pipe_flow_cylinder_published_case_vs_oracle(lbhip, oracle):
+    """The reference's published benchmark case (docs/python_cython_opencl_comparison.ipynb; bench.py's reference-case arguments:
+    3751 x 1251 cells) through the drop-in class: an eager-macro handle whose lattice pair is above the non-temporal-store threshold,
+    for which the size table picks k_deep2<7><PIPE, MASK> (walled whole grids from 1700^2 to 2900^2 cells).  21 steps = three launches
+    of it, against the oracle within the contract's bound, and bit for bit a second instance run by the single-step kernel."""
+    from LB_D2Q9.dimensionless import opencl_dim as lb
+    kw = dict(diameter=1., rho=1., viscosity=1., pressure_grad=-10., pipe_length=3., N=125)
+    cyl = dict(cylinder_center=[.75, .5], cylinder_radius=.1)
+    steps = 21
+    np.random.seed(1234)
+    sim = lb.Pipe_Flow_Cylinder(verbose=False, **cyl, **kw)
+    np.random.seed(1234)
+    single = lb.Pipe_Flow_Cylinder(verbose=False, **cyl, **kw)
+    single._sim.set_variant(0)
+    np.random.seed(1234)
+    perturb = 1. + .001 * np.random.randn(sim.nx, sim.ny, 9)
+    ref = oracle.O2Sim.pipe_flow(perturb=perturb, **cyl, **kw)
+    del perturb
+    assert (sim.nx, sim.ny) == (ref.nx, ref.ny) == (3751, 1251)
+    assert np.array_equal(sim.obstacle_mask_host.astype(bool), ref.mask.T.astype(bool))
+    name = sim._sim.hot_kernel()
+    assert sim._sim.steps_per_launch() == 7 and "k_deep2<7>" in name and "<PIPE, MASK>" in name, name
+    assert 7 in sim._sim.plan_launches(steps), sim._sim.plan_launches(steps)
+    g0 = sim.get_fields()
+    assert np.array_equal(g0["f"], ref.get_fields()["f"])          # identical initial populations
+    assert np.array_equal(g0["f"], single.get_fields()["f"])
+    del g0
+    sim.run(steps)
+    ref.run(steps, openmp=True)
+    single.run(steps)
+    got = sim.get_fields()
+    print("published case, %d steps:" % steps)
+    assert_fields_close(got, ref.get_fields(), contract_tol(steps))
+    want = single.get_fields()
+    for k in ("f", "rho", "u", "v"):
+        assert np.array_equal(got[k], want[k]), k
+
+
 @pytest.mark.parametrize("bc", ["pipe", "periodic", "cavity"])
 def test_small_grid_graph_replay_equals_eager_steps(lbhip, bc):
     """Grids <= 768^2 replay 16 captured single-step launches per hipGraph launch inside run(n);
@@ -877,6 +918,40 @@ def test_autotune_is_transparent(lbhip, oracle):
     ref2.set_variant(0); ref2.set_f(f0); ref2.run(2900)
     for k in ("f", "rho", "u", "v"):
         assert np.array_equal(b.get_fields((k,))[k], ref2.get_fields((k,))[k]), k
+
+
+QUICK_TUNE_STEPS = 361      # the quick tuning pass on grids above 768^2 (include/lb_hip.h, lb_autotune_quick)
+
+
+def test_quick_autotune_advances_at_most_max_steps(lbhip):
+    """lb_autotune_quick(h, max_steps) advances at most max_steps steps -- also where the two seven-step kernels finish within 5 % of
+    each other, so that lb_autotune would time them once more over longer samples: 4096^2 periodic (lb_hip.cpp, autotune_whole_grid).
+    A caller that passes exactly the pass's cost gets back at most that; the state is the single-step kernel's after that many steps.
+    Then Simulation.run(4 x 361 + 7), the shortest run that tunes itself on such a grid, bit for bit 1451 single steps."""
+    from LB_D2Q9.simulation import Simulation
+    n = 4096
+    f0 = _random_state(np.random.default_rng(361), n, n)
+    ref = Simulation(n, n, 1.7, bc="periodic")
+    ref.set_variant(0)
+    ref.set_f(f0)
+    a = Simulation(n, n, 1.7, bc="periodic")
+    a.set_f(f0)
+    used = a._lib.lb_autotune_quick(a._h, QUICK_TUNE_STEPS)
+    print("lb_autotune_quick(h, %d) advanced %d steps, picked %s" % (QUICK_TUNE_STEPS, used, a.hot_kernel()))
+    assert 0 < used <= QUICK_TUNE_STEPS
+    ref.run(used)
+    for k in ("f", "rho", "u", "v"):
+        assert np.array_equal(a.get_fields((k,))[k], ref.get_fields((k,))[k]), k
+    a.close()
+    steps = 4 * QUICK_TUNE_STEPS + 7
+    b = Simulation(n, n, 1.7, bc="periodic")
+    b.set_f(f0)
+    b.run(steps)
+    print("run(%d) on a fresh handle: %s" % (steps, b.hot_kernel()))
+    ref.set_f(f0)
+    ref.run(steps)
+    for k in ("f", "rho", "u", "v"):
+        assert np.array_equal(b.get_fields((k,))[k], ref.get_fields((k,))[k]), k
 
 
 @pytest.mark.parametrize("family", ["pipe_mask", "velocity_inlet", "cython", "d2q9i", "periodic_halo"])
