@@ -6,7 +6,7 @@
 
 hipcc cross-compiles without a GPU; the .so is git-ignored but travels with the tree.  One translation unit per kernel
 family (csrc/launchers.h), compiled in parallel; objects under 2d-lb_amd/build/ (git- and gpurun-ignored) are reused while
-neither their source nor any header is newer.
+neither their source nor any header is newer.  The host side is cut by concern (csrc/host.h); plan.cpp, the launch planner, is plain C++.
 """
 import os
 import shutil
@@ -20,7 +20,8 @@ HDR = os.path.join(os.path.dirname(HERE), "include", "lb_hip.h")
 OUT = os.path.join(HERE, "LB_D2Q9", "liblbhip.so")
 OBJ = os.path.join(HERE, "build")
 # (largest first: the pool starts them in this order)
-UNITS = ["deep7.cpp", "deep2.cpp", "deep6.cpp", "march5.cpp", "march4.cpp", "lb_hip.cpp", "march23.cpp", "tile.cpp", "step1.cpp"]
+UNITS = ["deep7.cpp", "deep2.cpp", "deep6.cpp", "march5.cpp", "march4.cpp", "lb_hip.cpp", "march23.cpp", "tile.cpp", "step1.cpp",
+         "slab.cpp", "tune.cpp", "launch.cpp", "transport.cpp", "plan.cpp"]
 # -ffp-contract=on: a*b+c fuses to an FMA only inside one source expression, so every kernel instantiation (single step,
 # multi-step, slab edge rows) -- in whichever translation unit -- rounds identically: results are bitwise independent of the
 # kernel variant and of the slab partition.

@@ -1,6 +1,6 @@
 // d2q9_cell.h -- device-side arithmetic of one D2Q9 cell (boundary rules, obstacle swap, moments,
 // equilibrium, BGK relaxation) and the vector load/store helpers shared by every kernel.
-// Included by lb_hip.cpp only (one translation unit); see the header comment there for the
+// Included by every translation unit of the library; see the header comment of lb_hip.cpp for the
 // reference lines each function follows.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,0 +1,159 @@
+// host.h -- what the host-side translation units of liblbhip.so share: the handle, error reporting, the RCCL entry points and the
+// functions one unit offers the others.  Who holds what:
+//   plan.cpp       the launch planner (plan.h): every decision that is arithmetic over PlanInputs; no HIP
+//   launch.cpp     kernel arguments and launches of the fused kernels, hipGraph replay, a whole grid's run
+//   slab.cpp       halo tables, pack / unpack, the exchanges, a slab's halo cycle and run, lb_run_group, lb_step_*, lb_halo_*
+//   transport.cpp  the RCCL loader, lb_comm_*, lb_peer_*
+//   tune.cpp       lb_autotune* and what they found, remembered (LB_TUNE_CACHE)
+//   lb_hip.cpp     create / destroy / setters, state transfer, the un-fused phases, lb_run, lb_run_batch, lb_check, timers
+// Small kernels are emitted by the one unit that includes their header: kernels_phases.h + kernels_check.h by lb_hip.cpp,
+// kernels_halo.h by slab.cpp.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <algorithm>
+
+#include "../../include/lb_hip.h"
+#include "cpu_backend.h"
+#include "plan.h"
+#include "launchers.h"          // StepArgs; the fused kernels are instantiated in their own translation units
+
+namespace {
+
+constexpr int MASK_GHOST = LB_MASK_HALO_ROWS;   // mask rows kept of each neighbouring slab (step 1 of row -13)
+constexpr int GUARD = 512; // floats in front of / behind each lattice allocation (the marching kernels' last
+                           // strip reads up to 257 cells past a row's end, every kernel 1 cell before its start)
+
+}  // namespace
+
+struct lb_sim : PlanInputs {
+    lbcpu::CpuPipe *cpu = nullptr;   // device = LB_DEVICE_CPU: the host backend (cpu_backend.h); every device member below stays empty
+    float *lat[2] = {nullptr, nullptr};   // raw allocations (with guards)
+    int cur = 0;                // lattice holding f
+    int stepping = 0;           // 1 between lb_step_boundary and lb_step_finish
+    float *feq = nullptr;       // raw allocation, lazily created
+    float *rho = nullptr, *u = nullptr, *v = nullptr;
+    float *stage = nullptr;     // [H][pitch], lazily: one plane on its way between the host and interleaved rows (lattice_plane_*)
+    float *vi_corner = nullptr; // VELOCITY_INLET: the eight corner links nothing ever writes (bc_vel_cell), device
+    uint8_t *mask_raw = nullptr, *mask = nullptr;   // [H+2*MASK_GHOST][pitch] + guards; mask -> row 0
+    bool feq_valid = false;     // feq buffer consistent with rho,u,v
+    bool macro_valid = true;    // rho,u,v hold the last step's fields (false: to be rebuilt from the populations, ensure_macro)
+    void *check_part = nullptr; // CheckPartial records (kernels_check.h, typed in lb_hip.cpp): one per workgroup of k_macro_check + the folded result behind them
+    long long check_cap = 0;
+    hipStream_t own_stream = nullptr, stream = nullptr, comm_stream = nullptr, edge_stream = nullptr;
+    hipEvent_t ev_boundary = nullptr, ev_interior = nullptr, ev_halo = nullptr, ev_packed = nullptr, ev_edge = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
+    ncclComm_t comm = nullptr;
+    int rank = 0, nranks = 1;
+    float *halo_buf = nullptr;  // 4 x HALO_SEGS_DEEP (117) x nx floats: send north, send south, recv south, recv north (ensure_halo_buf)
+    int ghost_depth = 0;        // ghost rows of lat[cur] hold this many of the neighbours' edge rows (0, 3, 6 or 8)
+    hipGraph_t graph = nullptr;            // GRAPH_STEPS single-step launches, captured for small grids
+    hipGraphExec_t graph_exec = nullptr;
+    int graph_key = -1;                    // state the capture is valid for (cur, mask, variant)
+    hipStream_t graph_stream = nullptr;
+    bool graph_failed = false;
+    // peer transport (lb_peer_export / lb_peer_connect): my flag block, the neighbours' flag blocks and lattices as mapped here
+    unsigned long long *peer_flags = nullptr;
+    bool peer_flags_fine = false;
+    struct PeerNb {
+        unsigned long long *flags = nullptr;
+        float *lat_raw[2] = {nullptr, nullptr};     // base of the neighbour's allocations as mapped into this process
+        bool mapped = false;                        // (opened through IPC: to be closed; false: the same process / shared with the other side)
+        long long plane = 0, rowp = 0;
+        int h = 0;
+    } peer_nb[2];                                   // [0] = south, [1] = north
+    unsigned long long peer_timeout_ticks = 0;
+    int diag = 0;
+    bool xchg_inline = false;   // slabs, split bands: the exchange on the COMPUTE stream, between the interior launches (lb_set_exchange_inline)
+    // lb_exchange_timing: a pair of timing events around every halo exchange of lb_run, on the stream that carries it
+    static constexpr int XT_RING = 256;
+    bool xt_on = false;
+    hipEvent_t xt_ev[2 * XT_RING] = {};
+    int xt_count = 0, xt_dropped = 0;
+    bool tune_cache_checked = false;    // LB_TUNE_CACHE has been consulted for this handle's present shape (lb_set_mask resets it)
+    int64_t bytes = 0;
+
+    float *origin(int which) const { return lat[which] + GUARD + GHOST * rowp; }   // plane 0, row 0, x 0
+    float *feq_origin() const { return feq + GUARD + GHOST * rowp; }
+    bool peer_connected() const { return transport == SLAB_PEER; }
+};
+
+#pragma GCC visibility push(hidden)         // (internal to the library: only lb_* is exported)
+
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) { (void)hipGetDevice(&prev); (void)hipSetDevice(dev); }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+int fail(int code, const char *fmt, ...);       // records the message lb_last_error returns (this thread's); returns code
+
+#define HIP_TRY(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return fail(LB_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),     \
+                        __FILE__, __LINE__);                                                   \
+    } while (0)
+
+// Handles of the CPU backend: an entry point either has a host form or refuses.
+#define CPU_UNSUPPORTED(s, name)                                                                            \
+    do {                                                                                                    \
+        if ((s) && (s)->cpu) return fail(LB_ERR_STATE, "%s is not available on the CPU backend", name);      \
+    } while (0)
+
+// ---- transport.cpp: RCCL, loaded lazily so that single-GPU use never touches librccl ---------------------------------------------
+struct Rccl {
+    void *lib = nullptr;
+    ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
+    ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
+    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
+    ncclResult_t (*GroupStart)() = nullptr;
+    ncclResult_t (*GroupEnd)() = nullptr;
+    ncclResult_t (*Send)(const void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
+    ncclResult_t (*Recv)(void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
+    ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
+    const char *(*GetErrorString)(ncclResult_t) = nullptr;
+};
+extern Rccl g_rccl;
+int rccl_load();
+
+#define NCCL_TRY(expr)                                                                        \
+    do {                                                                                      \
+        ncclResult_t r_ = (expr);                                                             \
+        if (r_ != ncclSuccess)                                                                \
+            return fail(LB_ERR_COMM, "%s failed: %s", #expr, g_rccl.GetErrorString(r_));      \
+    } while (0)
+
+// ---- launch.cpp ------------------------------------------------------------------------------------------------------------------
+StepArgs step_args(const lb_sim *s, int row_begin, int row_step, int row_count);
+// the single-step kernel over local rows row_begin + i*row_step, i < row_count
+int launch_step(lb_sim *s, int row_begin, int row_step, int row_count, bool macro);
+// A marching launch (k_step2 ... k_step5, k_deep: `depth` time steps per pass) over output rows [row_begin, row_end).
+struct MarchRows {
+    hipStream_t stream = nullptr;
+    int row_begin = 0, row_end = 0;
+    int depth = 2;
+    bool macro = false;         // the rho, u, v epilogue
+    MarchBands bands;           // edge bands: fixed segments; count == 0: one balanced round of resident waves (plan_march)
+    int reserve = 0;            // wave slots left to a band launch running beside this one
+};
+int launch_marching(lb_sim *s, const MarchRows &r);
+void drop_graph(lb_sim *s);
+// n time steps on a whole-grid handle
+int run_whole_grid(lb_sim *s, int n_steps, bool final_macro = true);
+
+// ---- slab.cpp --------------------------------------------------------------------------------------------------------------------
+int ensure_halo_buf(lb_sim *s);         // the send / receive buffers of the halo exchange (also lb_check's scratch across ranks)
+int peer_check_error(lb_sim *s);
+int run_slab(lb_sim *s, int n_steps);   // lb_run on a slab handle
+extern const size_t peer_flag_bytes;    // a handle's flag block of the peer transport (kernels_halo.h)
+
+// ---- tune.cpp --------------------------------------------------------------------------------------------------------------------
+bool tune_cache_apply(lb_sim *s);       // takes over a remembered result (LB_TUNE_CACHE); true if the handle is tuned afterwards
+
+#pragma GCC visibility pop

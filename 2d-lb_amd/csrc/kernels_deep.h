@@ -30,10 +30,7 @@
 
 namespace {
 
-// The skirt is D - 1 cells deep, i.e. whole lanes of four cells that are computed and never stored, at either end of a strip
-constexpr int deep_skirt_lanes(int D) { return (D - 1 + 3) / 4; }
-constexpr int deep_valid(int D) { return STRIP_W - 8 * deep_skirt_lanes(D); }           // cells stored per strip and row (D = 6..9: 240)
-constexpr int deep_strips(int nx, int D) { return (nx + deep_valid(D) - 1) / deep_valid(D); }
+// (deep_skirt_lanes, deep_valid, deep_strips -- the skirt of a strip and what is left to store: plan_consts.h)
 // Where a wave's state lives, per depth (see the header comment): windows in registers, rows gathered ahead
 constexpr int deep_rw(int D) { return 1; }
 constexpr int DEEP_WSLOTS = 8;          // LDS slots of a stage window
@@ -107,7 +104,7 @@ __device__ __forceinline__ void deep_publish(f4a (*W)[64], int lane, int gs, con
 // Extent of every resource: the whole 32-bit range.  A raw buffer access is range-checked as offset >= num_records - soffset, and the
 // scalar offset carries the plane: up to 8 planes x 4 bytes, which in the planar layout (LB_FLAG_PLANAR) of an 8192^2 lattice is 2.16 GB
 // -- with 2 GiB of records (round 5) plane 8 of such a lattice would have read zeros and dropped its stores.  The host admits a
-// lattice to these kernels only while (8 planes + a row) x 4 bytes < 4 GiB (marching_planes_fit, lb_hip.cpp).
+// lattice to these kernels only while (8 planes + a row) x 4 bytes < 4 GiB (marching_planes_fit, plan.cpp).
 constexpr int DEEP_NUM_RECORDS = -1;                     // 0xffffffff bytes
 // (a resource must live in scalar registers; where the compiler cannot see that a row's base is wave-uniform it wraps every access in
 //  a "waterfall" loop over the distinct values -- 15 of them per row pair in the first form of this code: say so explicitly)

@@ -1,11 +1,12 @@
 // kernels_fused.h -- the hot path: k_step (one time step per launch), k_step2 / k_step3 (two / three
 // time steps per launch: wave-private strips marching in y with register windows) and the float4
-// copy used for calibration.  Included by lb_hip.cpp only.
+// copy used for calibration.  Included by every translation unit (launchers.h); each instantiates what it launches.
 #pragma once
 #include <type_traits>
 #include "d2q9_cell.h"
+#include "plan_consts.h"     // STRIP_W, LB_BC_PIPE_I: shared with the launch planner
 
-// (external linkage: the argument block crosses translation units -- the host side in lb_hip.cpp fills it, the launchers of
+// (external linkage: the argument block crosses translation units -- the host side (step_args, launch.cpp) fills it, the launchers of
 //  launchers.h, one translation unit per kernel family, hand it to their kernels)
 struct StepArgs {
     const float *src;      // plane 0, row 0, x 0 of the lattice being read
@@ -40,11 +41,6 @@ struct BatchArgs {
 };
 
 namespace {
-
-
-// Template value of the PIPE family run with the kernels of the reference's D2Q9i.cl fork (lb_params.semantics =
-// LB_SEM_OPENCL_D2Q9I); not a public lb_bc_mode.
-constexpr int LB_BC_PIPE_I = 4;
 
 // The family's boundary rule for one cell (w, e, s, n: it lies in column 0 / nx-1, row 0 / ny-1).
 template <int BC>
@@ -219,7 +215,7 @@ template <bool NTS>
 __device__ __forceinline__ void store_row9(bool nts, float *d, long long S, int x4, const f4a (&t)[9])
 {
     // Addressing: ONE scalar base (the row) and a 32-bit per-lane offset that carries the plane as well -- (x + k S) * 4 bytes
-    // stays below 4 GB for every lattice the marching kernels are launched on (marching_planes_fit, lb_hip.cpp).  With nine
+    // stays below 4 GB for every lattice the marching kernels are launched on (marching_planes_fit, plan.cpp).  With nine
     // bases d + k S the compiler, once the two branches below share them, computes nine 64-bit per-lane addresses in front of the
     // branch (instruction selection works block by block and then sees nine opaque pointers): 18 registers and 36 vector adds
     // per row.  The lane offset passes through an empty asm in either branch so that the sums are not shared either.
@@ -443,8 +439,7 @@ __global__ __launch_bounds__(256) void k_step_batch(const BatchArgs b)
 // full aligned 1 KiB.  (A first version used lanes 0/63 as halo lanes and advanced strips by 248
 // cells: simpler, but its 992-byte store segments and 34-instead-of-32 strips cost 10-18 %:
 // tools/ablate.py, profiles/r01_ablation.txt.)  HBM traffic per two updates of a cell: 9 reads +
-// 9 writes (+2 rows per segment), i.e. ~37 B per lattice update instead of 72.
-constexpr int STRIP_W = 256;       // cells per wave-row
+// 9 writes (+2 rows per segment), i.e. ~37 B per lattice update instead of 72.  (STRIP_W = 256 cells per wave-row: plan_consts.h)
 
 // Workgroup -> work item order of the marching kernels.  Workgroups are dealt round-robin over the 8
 // XCDs; transposing every 8x8 block of workgroup ids puts 8 consecutive items (= up to 32 adjacent

@@ -1,4 +1,4 @@
-// kernels_step4.h -- four time steps per pass.  Included by lb_hip.cpp after kernels_fused.h.
+// kernels_step4.h -- four time steps per pass.  Included after kernels_fused.h by the units that instantiate it or build on it (march4.cpp, march5.cpp, deep*.cpp).
 //
 // The march of k_step3 with one more stage.  Per iteration i a wave loads one row and runs step 1 on it, step 2 on the
 // row loaded one iteration earlier, step 3 on the one before, step 4 on the one before that (stored).  The window
@@ -170,8 +170,6 @@ __device__ __forceinline__ void stage_gather(const Window &w, const f4a (&q)[9],
     t[D::Cn] = from_right(q[D::Cn], htm_new, lane);
     t[D::Bn] = from_left(q[D::Bn], htm_new, lane);
 }
-
-constexpr int STEP4_WAVES = 2;      // waves per workgroup = the two directions of a segment pair: 2 x 2 windows x 9 KiB of LDS
 
 // what the halo lanes of the two waves hand each other across the middle line: [receiving wave][stage][value][halo lane]
 struct HaloXchg {

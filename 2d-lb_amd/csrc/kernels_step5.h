@@ -1,4 +1,4 @@
-// kernels_step5.h -- FIVE time steps per pass.  Included by lb_hip.cpp after kernels_step4.h, whose building blocks it uses
+// kernels_step5.h -- FIVE time steps per pass.  Included after kernels_step4.h, whose building blocks it uses
 // (segment pairs, Window, the LDS window helpers, Row1 / row1_load: read that header first).
 //
 // Why.  Round 4 took a fifth of k_step4's vector instructions away and its launches took what they had taken: the four-step
@@ -32,9 +32,7 @@ namespace {
 // lost 12-23 % to that (profiles/r05_experiments.txt section 23).  (The counted HBM bytes do not show it -- 1.06 x compulsory before
 // and after, profiles/pmc_traffic.json --, the launch time does: 8192^2 1030 -> 894 us by rocprofv3.)  One box, 248 | 240 apart, k MLUPS: periodic 8192^2 334-350 | 375, pipe 8192^2
 // 351 | 369-376, cavity 3072^2 287-291 | 296-297, velocity inlet 4096^2 266-267 | 270-273; 4096^2 and below +-1 %
-// (profiles/r05_step5_align64_ab.txt): 3 % more strips, no partial sectors.
-constexpr int STEP5_SKIRT = 8;                          // cells a strip starts before / ends behind its stored cells (= one lane)
-constexpr int STEP5_VALID = STRIP_W - 2 * STEP5_SKIRT;  // 248 cells stored per strip and row
+// (profiles/r05_step5_align64_ab.txt): 3 % more strips, no partial sectors.  (STEP5_SKIRT, STEP5_VALID, step5_strips: plan_consts.h)
 
 struct March5State {
     Window w1, w2;                      // stage windows between steps 1/2 and 2/3 (registers)
@@ -240,9 +238,6 @@ __device__ __forceinline__ void march5(const StepArgs &a, const int x0, const in
     march5_iter<BC, MASK, MACRO, PF, DOWN, 4>(a, cx, 3, st, cur);
     for (int i = 4; i < cx.n_iter; ++i) march5_iter<BC, MASK, MACRO, PF, DOWN, 5>(a, cx, i, st, cur);
 }
-
-// strips a grid of nx columns is cut into
-constexpr int step5_strips(int nx) { return (nx + STEP5_VALID - 1) / STEP5_VALID; }
 
 // Launch geometry as k_step4: one workgroup = one segment pair of one strip (two waves), XCD-transposed order, shorter segments
 // for the two wall-column strips.

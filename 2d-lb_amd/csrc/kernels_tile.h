@@ -1,5 +1,5 @@
 // kernels_tile.h -- four time steps per pass for SMALL grids: 2-D tiles staged in LDS.
-// Included by lb_hip.cpp after kernels_fused.h.
+// Included after kernels_fused.h by tile.cpp (k_tile4, k_vel_band) and lb_hip.cpp (TileShape, for k1_tile4).
 //
 // Grids below ~1600^2 cells live in the Infinity Cache and are not bandwidth-bound: a single-step launch costs
 // its ~2 us of dependent-kernel boundary plus one global-memory round trip per step, and the marching kernels
@@ -15,8 +15,7 @@
 
 namespace {
 
-constexpr int TILE_T = 4;                   // time steps per pass = halo width
-
+// (TILE_T = 4 time steps per pass = halo width: plan_consts.h)
 // TW x TH = the tile; the region held in LDS is (TW + 8) x (TH + 8).  Two shapes, picked by the host: 32 x 16
 // (two cells per thread: 512 threads; one: 960) and, so that small grids still spread over the chip, 16 x 16.
 // CPT = cells per thread: few, so that the kernel stays near 45-60 VGPR and several workgroups share a CU
@@ -289,7 +288,7 @@ __global__ __launch_bounds__((TileShape<TW, TH, CPT>::THREADS), (CPT == 2 ? 8 : 
 
 // ---- the velocity-inlet family's wall-row bands, D time steps in one launch ---------------------------------------
 // A three-, four- or five-step marching pass of that family covers rows [D, ny-D); the 2D rows next to each wall, stacked, are a
-// velocity-inlet lattice of 4D rows of their own (lb_hip.cpp vel_band_pass: the north row's pull reaches "row ny-2" = band
+// velocity-inlet lattice of 4D rows of their own (launch.cpp vel_band_pass: the north row's pull reaches "row ny-2" = band
 // row 4D-2, the south row's "row 1" = band row 1; the seam in the middle spreads one row of garbage per step and reaches
 // exactly the rows that are not kept).  Round 2 copied them into a second handle, ran D single steps there and copied
 // the outer rows back: a dozen dependent launches.  Here one workgroup holds a column chunk of the band -- TW columns + D

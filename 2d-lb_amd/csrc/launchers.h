@@ -2,38 +2,16 @@
 //
 // Until round 5 liblbhip.so was ONE translation unit: 368 kernel instantiations compiled one after the other, six and a half
 // minutes on eight cores.  Now every kernel family is instantiated in a file of its own (step1.cpp, march23.cpp, march4.cpp,
-// march5.cpp, deep6.cpp, deep7.cpp, tile.cpp), which build.py compiles in parallel; lb_hip.cpp keeps the host side, the C ABI and the
-// small un-fused kernels.  A family's file exports one plain function -- below -- that picks the instantiation (boundary family,
+// march5.cpp, deep2.cpp, deep6.cpp, deep7.cpp, tile.cpp), which build.py compiles in parallel; the host side and the C ABI are cut by
+// concern (host.h: plan.cpp, launch.cpp, slab.cpp, transport.cpp, tune.cpp, lb_hip.cpp), the small un-fused kernels are emitted by the
+// one host unit that launches them.  A family's file exports one plain function -- below -- that picks the instantiation (boundary family,
 // obstacle mask, rho/u/v epilogue, ...) and launches it; arguments are the kernels' own (StepArgs, kernels_fused.h) plus the launch
 // geometry.  Every kernel stays a template in a header: a translation unit only pays for what it launches.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels_fused.h"
 
-// Bits of the kernel variant word (lb_set_variant, include/lb_hip.h; the automatic choice: effective_variant, lb_hip.cpp).  The values
-// are the public ABI's.
-enum VariantBits : int {
-    VAR_NT_STORES = 1 << 0,             // non-temporal stores
-    VAR_NT_LOADS = 1 << 1,              // non-temporal loads (k_step)
-    VAR_ROWS = 3 << 2,                  // rows per workgroup of k_step: 0 -> 4, VAR_ROWS_1 -> 1, VAR_ROWS_2 -> 2
-    VAR_ROWS_1 = 1 << 2,
-    VAR_ROWS_2 = 2 << 2,
-    VAR_XCD_ORDER = 1 << 4,             // XCD-aware tile order (k_step)
-    VAR_STEP2 = 1 << 5,                 // two time steps per pass
-    VAR_STEP3 = 1 << 6,                 // three
-    VAR_NO_CYCLE = 1 << 7,              // slabs exchange their halo after every launch (no halo cycle)
-    VAR_STEP4 = 1 << 8,                 // four
-    VAR_TILES = 1 << 9,                 // four through LDS tiles (k_tile4)
-    VAR_STEP4_NO_AHEAD = 1 << 10,       // A/B: k_step4 without its one-row-ahead gather
-    VAR_NO_PRIO_TURNS = 1 << 11,        // A/B: k_step4 / k_step5 without the priority turns of the two waves of a SIMD
-    VAR_STEP5 = 1 << 12,                // five (k_step5)
-    VAR_TILE_LAUNCH_ORDER = 1 << 13,    // A/B: k_tile4 takes its tiles in launch order
-    VAR_STEP6 = 1 << 14,                // six (k_deep<6>)
-    VAR_STEP7 = 1 << 15,                // with VAR_STEP6: seven (k_deep<7>)
-    VAR_DEEP2 = 1 << 16,                // with VAR_STEP6 | VAR_STEP7: the seven steps by k_deep2<7>
-};
-
-// geometry of a marching launch (k_step2 ... k_step5, k_deep; launch_step2 in lb_hip.cpp computes it)
+// geometry of a marching launch (k_step2 ... k_step5, k_deep; plan_march in plan.cpp computes it, launch_marching in launch.cpp fills it in)
 struct MarchLaunch {
     dim3 grid, block;
     hipStream_t stream;

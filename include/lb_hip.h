@@ -356,7 +356,7 @@ int lb_set_exchange_inline(lb_sim *s, int on);
  * stream that carries it (up to 256 exchanges between two queries; more are counted as dropped, not timed); lb_exchange_stats waits
  * for the exchanges recorded so far and returns their number, their total and longest duration in milliseconds -- pack / push, the
  * transfer, the wait for the neighbours' matching calls, unpack --, the depth of the halo cycle in use and the rows of one edge band
- * of its second launch (2 x depth + the extra rows that keep the band's waves busy as long as the interior's, lb_hip.cpp:
+ * of its second launch (2 x depth + the extra rows that keep the band's waves busy as long as the interior's, plan.cpp:
  * band_extra), then starts over.  The bands are split -- only their outer 2 x depth rows wait for the exchange, which runs on a stream
  * of its own beside the rest --, so an exchange delays the compute stream once it takes longer than about a whole launch; bench.py
  * --gpus N prints the figures per rank.  (The three streams of a slab handle must not share a hardware queue: a process that creates

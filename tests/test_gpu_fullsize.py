@@ -277,7 +277,7 @@ def test_full_size_families_default_and_four_step_kernel_equal_single_step_kerne
                                              ("velocity_inlet", 2304, 3000, True), ("pipe", 1024, 6000, False)])
 def test_wall_column_strips_with_shorter_segments_bitwise(lbhip, bc, nx, ny, masked):
     """In the wall families k_step4 and k_step5 give the first and the last strip (the wall columns) shorter segments than the
-    others (lb_hip.cpp launch_step2: `edge_seg_rows`); grids of many shapes -- few / many strips, short / tall, odd widths, with a
+    others (plan.cpp plan_march: `edge_seg_rows`); grids of many shapes -- few / many strips, short / tall, odd widths, with a
     mask, the velocity-inlet family's interior pass -- against the single-step kernel, bit for bit, 11 steps."""
     from LB_D2Q9.simulation import Simulation
     rng = np.random.default_rng(nx + ny)

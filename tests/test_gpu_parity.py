@@ -268,7 +268,7 @@ def test_run_is_split_into_the_cheapest_launches(lbhip):
 
 
 def test_launch_plan_follows_the_costs_autotune_measured(lbhip):
-    """lb_autotune leaves the handle the launch cost of every depth it timed (launch_costs in lb_hip.cpp); lb_plan_launches then
+    """lb_autotune leaves the handle the launch cost of every depth it timed (launch_costs in plan.cpp); lb_plan_launches then
     splits runs by THOSE costs: the plan still sums to n, uses no depth beyond the tuned one, and run(n) by that plan gives the
     single-step kernel's bits."""
     from LB_D2Q9.simulation import Simulation
@@ -559,7 +559,7 @@ def test_rccl_self_exchange_single_rank(lbhip):
 def test_slab_cycle_depth_set_by_the_caller_and_exchange_timing(lbhip, transport):
     """lb_set_slab_cycle (ABI 9), lb_set_exchange_inline (ABI 10): the halo cycle of lb_run on the depth the caller fixes -- what DistributedSlab.autotune does after
     the ranks have timed the candidates together -- gives the plain run's bits at every depth, over both transports (thick edge bands;
-    under RCCL split in two launches with the exchange on the communication stream: lb_hip.cpp, slab_cycle_first), with an obstacle
+    under RCCL split in two launches with the exchange on the communication stream: slab.cpp, slab_cycle_first), with an obstacle
     mask; lb_exchange_timing / lb_exchange_stats count the exchanges and report the cycle in use."""
     from LB_D2Q9.simulation import Simulation, comm_unique_id
     from LB_D2Q9.slabs import _SlabSet
@@ -925,7 +925,7 @@ QUICK_TUNE_STEPS = 361      # the quick tuning pass on grids above 768^2 (includ
 
 def test_quick_autotune_advances_at_most_max_steps(lbhip):
     """lb_autotune_quick(h, max_steps) advances at most max_steps steps -- also where the two seven-step kernels finish within 5 % of
-    each other, so that lb_autotune would time them once more over longer samples: 4096^2 periodic (lb_hip.cpp, autotune_whole_grid).
+    each other, so that lb_autotune would time them once more over longer samples: 4096^2 periodic (tune.cpp, autotune_whole_grid).
     A caller that passes exactly the pass's cost gets back at most that; the state is the single-step kernel's after that many steps.
     Then Simulation.run(4 x 361 + 7), the shortest run that tunes itself on such a grid, bit for bit 1451 single steps."""
     from LB_D2Q9.simulation import Simulation

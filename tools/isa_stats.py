@@ -29,6 +29,8 @@ TU = r"""
 #include "%(csrc)s/kernels_deep2.h"
 #include "%(csrc)s/kernels_tile.h"
 #include "%(csrc)s/kernels_phases.h"
+#include "%(csrc)s/kernels_check.h"
+#include "%(csrc)s/kernels_halo.h"
 void isa_stats_force(hipStream_t st) { void *p = (void *)(&%(kernel)s); hipLaunchKernel(p, dim3(1), dim3(1), nullptr, 0, st); }
 """
 
