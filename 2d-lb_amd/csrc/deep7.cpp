@@ -10,7 +10,7 @@ template <int BC, bool MASK, bool MACRO>
 struct LD {
     static void go(const MarchLaunch &g, const StepArgs &a)
     {
-        hipLaunchKernelGGL((k_deep<BC, MASK, MACRO, 7, deep_rw(7), deep_pfd(7)>), g.grid, g.block, 0, g.stream, a, g.strips, g.seg_rows,
+        hipLaunchKernelGGL((k_deep<BC, MASK, MACRO, 7, DEEP_RW, DEEP_PFD>), g.grid, g.block, 0, g.stream, a, g.strips, g.seg_rows,
                            g.nsegs, g.row_end);
     }
 };

@@ -31,10 +31,10 @@
 namespace {
 
 // (deep_skirt_lanes, deep_valid, deep_strips -- the skirt of a strip and what is left to store: plan_consts.h)
-// Where a wave's state lives, per depth (see the header comment): windows in registers, rows gathered ahead
-constexpr int deep_rw(int D) { return 1; }
+// Where a wave's state lives (see the header comment): k_deep is launched with one window in registers and one row gathered ahead at
+// either depth; k_deep2's waves (kernels_deep2.h) use RW = 1, 2 and PFD = 0 for their back waves
+constexpr int DEEP_RW = 1, DEEP_PFD = 1;
 constexpr int DEEP_WSLOTS = 8;          // LDS slots of a stage window
-constexpr int deep_pfd(int D) { return 1; }
 // Code footprint (two CUs share a 64 KB instruction cache; a lone wave has nobody to cover its fetch misses; 8192^2, k MLUPS,
 // profiles/r05_footprint.txt): the boundary rule out of line (boundary_rule_call): pipe 306 -> 383-393, cavity 319 -> 393-403; the
 // steady iterations in PAIRS (the two row buffers swap roles, the LDS ring slots become immediate offsets: -1.3 % instructions, twice
@@ -423,9 +423,7 @@ __device__ __forceinline__ void deep_stage(const StepArgs &a, const DeepCtx &cx,
                     deep_row_store(a, r, x4, t);
                     if (MACRO) {
                         const long long m = (long long)r * a.fpitch;
-                        store4<false>(lane_ptr(a.rho + m, x4), r4);
-                        store4<false>(lane_ptr(a.u + m, x4), u4);
-                        store4<false>(lane_ptr(a.v + m, x4), v4);
+                        store_moments(a, m, x4, r4, u4, v4);
                     }
                 }
             } else {
@@ -449,7 +447,9 @@ __device__ __forceinline__ void deep_stage(const StepArgs &a, const DeepCtx &cx,
 // One iteration: position i takes step 1, position i - 1 step 2, ..., position i - (D - 1) step D (stored).  NST = number of stages
 // that have a row: 1..D-1 in iterations 0..D-2 (code of their own, i a constant: the pipeline fills, the two waves of the pair hand
 // over), D in the loop.  PFD = 1: `cur` holds position i on entry and position i + 1 is gathered into `nxt` first; the caller swaps
-// the two from one iteration to the next.  PAR >= 0: the parity of i as a constant (the LDS ring slots become immediate offsets).
+// the two from one iteration to the next.  PFD = 0 is k_deep2's back waves (ROLE below), whose row is in `cur` already: a whole march
+// that loads its row at the point of use was never instantiated (commit 54ede03 has that arm and deep_march's loop for it).
+// PAR >= 0: the parity of i as a constant (the LDS ring slots become immediate offsets).
 // ROLE (k_deep2): a FRONT wave is a march of depth D whose last stage hands its row to the back wave instead of storing it; a BACK wave
 // is a march of depth D whose "step 1" is that row, already in `cur` (D, NST, i: the wave's own).  Neither has barriers of its own.
 template <int BC, bool MASK, bool MACRO, int D, int RW, int PFD, bool DOWN, int NST, int PAR = -1, int ROLE = DEEP_WHOLE>
@@ -480,8 +480,10 @@ __device__ __forceinline__ void deep_iter(const StepArgs &a, const DeepCtx &cx, 
         } else if (PFD && DEEP_MANUAL) {
             deep_row_take<BC, MASK, (NST < D ? 0 : (MACRO ? 12 : 9))>(cur);
             deep_row_issue<BC, MASK>(a, row_at(min(i + 1, cx.n_iter - 1)), x4, nxt);
-        } else if (PFD) deep_row_load<BC, MASK>(a, row_at(min(i + 1, cx.n_iter - 1)), x4, nxt);
-        else deep_row_load<BC, MASK>(a, row_at(i), x4, cur);
+        } else {
+            static_assert(PFD == 1 || ROLE == DEEP_BACK, "a march that gathers its rows gathers them one ahead");
+            deep_row_load<BC, MASK>(a, row_at(min(i + 1, cx.n_iter - 1)), x4, nxt);
+        }
     }
     f4a (&q1)[9] = cur.q;
     f4a r4, u4, v4;
@@ -499,13 +501,13 @@ __device__ __forceinline__ void deep_iter(const StepArgs &a, const DeepCtx &cx, 
     if (ROLE == DEEP_WHOLE && NST < D) __syncthreads();     // what was published in this iteration is consumed in the next
 }
 
-// the filling iterations 0..D-2, one after the other (NST = 1..D-1); PFD = 1: the two row buffers swap roles every iteration
+// the filling iterations 0..D-2, one after the other (NST = 1..D-1): the two row buffers swap roles every iteration
 template <int BC, bool MASK, bool MACRO, int D, int RW, int PFD, bool DOWN, int NST>
 __device__ __forceinline__ void deep_fill(const StepArgs &a, const DeepCtx &cx, DeepState<RW, D - 1 - RW> &st, Row1 &ra, Row1 &rb)
 {
     if constexpr (NST < D) {
-        if (PFD == 1 && (NST & 1) == 0) deep_iter<BC, MASK, MACRO, D, RW, PFD, DOWN, NST>(a, cx, NST - 1, st, rb, ra);
-        else deep_iter<BC, MASK, MACRO, D, RW, PFD, DOWN, NST>(a, cx, NST - 1, st, ra, PFD ? rb : ra);
+        if ((NST & 1) == 0) deep_iter<BC, MASK, MACRO, D, RW, PFD, DOWN, NST>(a, cx, NST - 1, st, rb, ra);
+        else deep_iter<BC, MASK, MACRO, D, RW, PFD, DOWN, NST>(a, cx, NST - 1, st, ra, rb);
         deep_fill<BC, MASK, MACRO, D, RW, PFD, DOWN, NST + 1>(a, cx, st, ra, rb);
     }
 }
@@ -518,31 +520,28 @@ __device__ __forceinline__ void deep_march(const StepArgs &a, const int x0, cons
 {
     DeepCtx cx;
     cx.lane = threadIdx.x;
-    const int xr = x0 + cx.lane * 4;                 // true column of my first cell: -8 .. ; may lie beyond either end of the box
-    // lanes beyond an end of the box: the periodic images as far as the skirt reaches (behind it: the last image lane's lines), or
-    // -- walls -- copies of the lane at that end (a wall column's rule rebuilds whatever it pulled from outside)
-    constexpr int SKL = deep_skirt_lanes(D);
-    if (BC == LB_BC_PERIODIC) cx.x4 = xr < 0 ? xr + a.nx : (xr >= a.nx ? (xr - a.nx < 4 * SKL ? xr - a.nx : 4 * (SKL - 1)) : xr);
-    else cx.x4 = min(max(xr, 0), (a.nx - 1) & ~3);
-    cx.store_lane = cx.lane >= SKL && cx.lane <= 63 - SKL && xr < a.nx;
+    const int xr = x0 + cx.lane * 4;
+    cx.x4 = skirt_column<BC>(a, xr, deep_skirt_lanes(D));
+    cx.store_lane = skirt_store_lane(a, cx.lane, xr, deep_skirt_lanes(D));
     cx.ym = ym; cx.n_iter = len + D - 1;
     cx.mine = mine; cx.other = other;
     DeepState<RW, D - 1 - RW> st = {};
     auto row_at = [&](int p) { return DOWN ? ym - 1 - p : ym + p; };
+    static_assert(PFD == 1, "a whole march gathers one row ahead");
     Row1 ra, rb;
-    if (PFD && DEEP_MANUAL) deep_row_issue<BC, MASK>(a, row_at(0), cx.x4, ra);
-    else if (PFD) deep_row_load<BC, MASK>(a, row_at(0), cx.x4, ra);
+    if (DEEP_MANUAL) deep_row_issue<BC, MASK>(a, row_at(0), cx.x4, ra);
+    else deep_row_load<BC, MASK>(a, row_at(0), cx.x4, ra);
     deep_fill<BC, MASK, MACRO, D, RW, PFD, DOWN, 1>(a, cx, st, ra, rb);
     // (the steady iterations wait with the count of a steady iteration's stores: the first one has none behind it)
-    if (PFD && DEEP_MANUAL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (PFD == 1 && !deep_pairs(MASK, BC)) {
+    if (DEEP_MANUAL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (!deep_pairs(MASK, BC)) {
         // one iteration per trip; the row gathered ahead moves into place (position D - 1 is in ra or rb by its parity)
         if ((D - 1) & 1) ra = rb;
         for (int i = D - 1; i < cx.n_iter; ++i) {
             deep_iter<BC, MASK, MACRO, D, RW, PFD, DOWN, D>(a, cx, i, st, ra, rb);
             ra = rb;
         }
-    } else if (PFD == 1) {
+    } else {
         // position i is in ra for even i, in rb for odd i; the steady iterations in pairs
         constexpr int P0 = (D - 1) & 1;
         int i = D - 1;
@@ -551,10 +550,8 @@ __device__ __forceinline__ void deep_march(const StepArgs &a, const int x0, cons
             deep_iter<BC, MASK, MACRO, D, RW, PFD, DOWN, D, 1 - P0>(a, cx, i + 1, st, P0 ? ra : rb, P0 ? rb : ra);
         }
         if (i < cx.n_iter) deep_iter<BC, MASK, MACRO, D, RW, PFD, DOWN, D, P0>(a, cx, i, st, P0 ? rb : ra, P0 ? ra : rb);
-    } else {
-        for (int i = D - 1; i < cx.n_iter; ++i) deep_iter<BC, MASK, MACRO, D, RW, PFD, DOWN, D>(a, cx, i, st, ra, ra);
     }
-    if (PFD && DEEP_MANUAL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the row gathered behind the last position)
+    if (DEEP_MANUAL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the row gathered behind the last position)
 }
 
 // Launch geometry as k_step5 / k_step6: one workgroup = one segment pair of one strip (two waves), XCD-transposed order, shorter

@@ -65,9 +65,7 @@ __device__ __forceinline__ void deep2_front(const StepArgs &a, const int x0, con
     DeepCtx cx;
     cx.lane = threadIdx.x;
     const int xr = x0 + cx.lane * 4;
-    constexpr int SKL = deep_skirt_lanes(D);
-    if (BC == LB_BC_PERIODIC) cx.x4 = xr < 0 ? xr + a.nx : (xr >= a.nx ? (xr - a.nx < 4 * SKL ? xr - a.nx : 4 * (SKL - 1)) : xr);
-    else cx.x4 = min(max(xr, 0), (a.nx - 1) & ~3);
+    cx.x4 = skirt_column<BC>(a, xr, deep_skirt_lanes(D));
     cx.store_lane = false;                              // (a front wave stores nothing)
     cx.ym = ym; cx.n_iter = len + D - 1;                // every position the BACK wave's last stage needs
     cx.mine = mine; cx.other = other; cx.ho = ho; cx.dma = dma;
@@ -129,10 +127,8 @@ __device__ __forceinline__ void deep2_back(const StepArgs &a, const int x0, cons
     DeepCtx cx;
     cx.lane = threadIdx.x;
     const int xr = x0 + cx.lane * 4;
-    constexpr int SKL = deep_skirt_lanes(D);
-    if (BC == LB_BC_PERIODIC) cx.x4 = xr < 0 ? xr + a.nx : (xr >= a.nx ? (xr - a.nx < 4 * SKL ? xr - a.nx : 4 * (SKL - 1)) : xr);
-    else cx.x4 = min(max(xr, 0), (a.nx - 1) & ~3);
-    cx.store_lane = cx.lane >= SKL && cx.lane <= 63 - SKL && xr < a.nx;
+    cx.x4 = skirt_column<BC>(a, xr, deep_skirt_lanes(D));
+    cx.store_lane = skirt_store_lane(a, cx.lane, xr, deep_skirt_lanes(D));
     cx.ym = ym; cx.n_iter = len + DB - 1;
     cx.mine = mine; cx.other = other; cx.ho = ho;
     DeepState<RW, DB - 1 - RW> st = {};

@@ -210,8 +210,8 @@ __device__ __forceinline__ void gather_row(const StepArgs &a, int x4, int yl, in
 // The nine 16-byte stores of a row of the marching kernels, non-temporal or plain by a RUN-TIME, wave-uniform flag (as a template
 // argument the choice doubled those kernels' instantiations: a minute and a half of the library's build).  The empty asm keeps
 // the two branches from being merged: merged, the stores lose the non-temporal hint (the compiler keeps only what both carry)
-// -- measured: 8192^2 277 k instead of 309 k MLUPS.
-template <bool NTS>
+// -- measured: 8192^2 277 k instead of 309 k MLUPS.  (The template flag NTS lived on beside the run-time one on store_row9, k_step2,
+// k_step3 and k_step4 with every launcher passing false; retired, commit 54ede03 has it.)
 __device__ __forceinline__ void store_row9(bool nts, float *d, long long S, int x4, const f4a (&t)[9])
 {
     // Addressing: ONE scalar base (the row) and a 32-bit per-lane offset that carries the plane as well -- (x + k S) * 4 bytes
@@ -220,7 +220,7 @@ __device__ __forceinline__ void store_row9(bool nts, float *d, long long S, int 
     // branch (instruction selection works block by block and then sees nine opaque pointers): 18 registers and 36 vector adds
     // per row.  The lane offset passes through an empty asm in either branch so that the sums are not shared either.
     const int kS = (int)S;
-    if (NTS || nts) {
+    if (nts) {
         asm volatile("" : "+v"(x4) : : "memory");       // (in front as well: common code is hoisted out of branches, too)
 #pragma unroll
         for (int k = 0; k < 9; ++k) store4<true>(lane_ptr(d, x4 + k * kS), t[k]);
@@ -230,6 +230,25 @@ __device__ __forceinline__ void store_row9(bool nts, float *d, long long S, int 
 #pragma unroll
         for (int k = 0; k < 9; ++k) store4<false>(lane_ptr(d, x4 + k * kS), t[k]);
     }
+}
+
+// rho, u, v of a lane's four cells, m = their row's offset in the fields (the epilogue of every fused kernel's last stage)
+__device__ __forceinline__ void store_moments(const StepArgs &a, long long m, int x4, f4a r4, f4a u4, f4a v4)
+{
+    store4<false>(lane_ptr(a.rho + m, x4), r4);
+    store4<false>(lane_ptr(a.u + m, x4), u4);
+    store4<false>(lane_ptr(a.v + m, x4), v4);
+}
+
+// cell j of a lane's four, out of / back into the nine gathered planes
+__device__ __forceinline__ Cell row_cell(const f4a (&q)[9], int j)
+{
+    return Cell{q[0][j], q[1][j], q[2][j], q[3][j], q[4][j], q[5][j], q[6][j], q[7][j], q[8][j]};
+}
+__device__ __forceinline__ void row_cell_put(f4a (&q)[9], int j, const Cell &c)
+{
+    q[0][j] = c.f0; q[1][j] = c.f1; q[2][j] = c.f2; q[3][j] = c.f3; q[4][j] = c.f4;
+    q[5][j] = c.f5; q[6][j] = c.f6; q[7][j] = c.f7; q[8][j] = c.f8;
 }
 
 // Boundary rule, obstacle swap, moments, equilibrium and relaxation of the 4 gathered cells, in place.
@@ -254,7 +273,7 @@ __device__ __forceinline__ void collide_row(const StepArgs &a, int x4, int yg, f
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (wall_row || (first && j == 0) || (last && j == jl)) {
-                    Cell c = {q[0][j], q[1][j], q[2][j], q[3][j], q[4][j], q[5][j], q[6][j], q[7][j], q[8][j]};
+                    Cell c = row_cell(q, j);
                     const bool w = first && j == 0, e = last && j == jl;
                     if constexpr (OOL && (BC == LB_BC_PIPE || BC == LB_BC_PIPE_I || BC == LB_BC_CAVITY)) {
                         const bool cav = (BC == LB_BC_CAVITY);
@@ -263,8 +282,7 @@ __device__ __forceinline__ void collide_row(const StepArgs &a, int x4, int yg, f
                     } else {
                         boundary_rule<BC>(a, c, w, e, south, north);
                     }
-                    q[0][j] = c.f0; q[1][j] = c.f1; q[2][j] = c.f2; q[3][j] = c.f3; q[4][j] = c.f4;
-                    q[5][j] = c.f5; q[6][j] = c.f6; q[7][j] = c.f7; q[8][j] = c.f8;
+                    row_cell_put(q, j, c);
                 }
             }
         }
@@ -280,7 +298,7 @@ __device__ __forceinline__ void collide_row(const StepArgs &a, int x4, int yg, f
         float rho[4], ux[4], uy[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            c[j] = Cell{q[0][j], q[1][j], q[2][j], q[3][j], q[4][j], q[5][j], q[6][j], q[7][j], q[8][j]};
+            c[j] = row_cell(q, j);
             if (MASK) bounce_cell(c[j], mk[j] != 0);
             moments_cell(c[j], rho[j], ux[j], uy[j]);
         }
@@ -299,20 +317,18 @@ __device__ __forceinline__ void collide_row(const StepArgs &a, int x4, int yg, f
         for (int j = 0; j < 4; ++j) {
             equilibrate_cell(c[j], a.omega, rho[j], ux[j], uy[j]);
             r4[j] = rho[j]; u4[j] = ux[j]; v4[j] = uy[j];
-            q[0][j] = c[j].f0; q[1][j] = c[j].f1; q[2][j] = c[j].f2; q[3][j] = c[j].f3; q[4][j] = c[j].f4;
-            q[5][j] = c[j].f5; q[6][j] = c[j].f6; q[7][j] = c[j].f7; q[8][j] = c[j].f8;
+            row_cell_put(q, j, c[j]);
         }
         return;
     }
     if (BC == LB_BC_PIPE_I) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            Cell c = {q[0][j], q[1][j], q[2][j], q[3][j], q[4][j], q[5][j], q[6][j], q[7][j], q[8][j]};
+            Cell c = row_cell(q, j);
             float rho, ux, uy;
             finish_cell<BC, MASK>(a, x4 + j, yg - a.y0, c, mk[j] != 0, rho, ux, uy);
             r4[j] = rho; u4[j] = ux; v4[j] = uy;
-            q[0][j] = c.f0; q[1][j] = c.f1; q[2][j] = c.f2; q[3][j] = c.f3; q[4][j] = c.f4;
-            q[5][j] = c.f5; q[6][j] = c.f6; q[7][j] = c.f7; q[8][j] = c.f8;
+            row_cell_put(q, j, c);
         }
         return;
     }
@@ -405,9 +421,7 @@ __device__ __forceinline__ void step_body(const StepArgs &a)
     for (int k = 0; k < 9; ++k) store4<NTS>(lane_ptr(d + k * S, x4), q[k]);
     if (MACRO) {
         const long long m0 = (long long)yl * a.fpitch;
-        store4<false>(lane_ptr(a.rho + m0, x4), r4);
-        store4<false>(lane_ptr(a.u + m0, x4), u4);
-        store4<false>(lane_ptr(a.v + m0, x4), v4);
+        store_moments(a, m0, x4, r4, u4, v4);
     }
 }
 
@@ -548,7 +562,7 @@ __device__ __forceinline__ void halo_cell_step1(const StepArgs &a, int hx, int r
 // Segment i of a launch covers output rows [row_begin + i*seg_stride, +seg_rows) clipped to row_end:
 // one contiguous range cut into equal shares (seg_stride == seg_rows), or the two edge bands of a slab
 // (seg_stride = their distance) that are computed first so their halo can travel early.
-template <int BC, bool MASK, bool MACRO, bool NTS>
+template <int BC, bool MASK, bool MACRO>
 __global__ __launch_bounds__(256, 2) void k_step2(const StepArgs a, int strips, int seg_rows, int nsegs, int row_end)
 {
     const int lane = threadIdx.x;                       // blockDim = (64, 4): four independent waves
@@ -630,12 +644,10 @@ __global__ __launch_bounds__(256, 2) void k_step2(const StepArgs a, int strips, 
 #endif
             if (store_lane) {
                 float *d = a.dst + o;
-                store_row9<NTS>(a.nts != 0, d, S, x4, t);
+                store_row9(a.nts != 0, d, S, x4, t);
                 if (MACRO) {
                     const long long m = (long long)y * a.fpitch;
-                    store4<false>(lane_ptr(a.rho + m, x4), r4);
-                    store4<false>(lane_ptr(a.u + m, x4), u4);
-                    store4<false>(lane_ptr(a.v + m, x4), v4);
+                    store_moments(a, m, x4, r4, u4, v4);
                 }
             }
         }
@@ -727,7 +739,7 @@ __device__ __forceinline__ uc4 mask_bits(unsigned hist, int age)
                (unsigned char)(b >> 24)};
 }
 
-template <int BC, bool MASK, bool MACRO, bool NTS>
+template <int BC, bool MASK, bool MACRO>
 __global__ __launch_bounds__(256, 2) void k_step3(const StepArgs a, int strips, int seg_rows, int nsegs, int row_end)
 {
     const int lane = threadIdx.x;                       // blockDim = (64, 4): four independent waves
@@ -838,12 +850,10 @@ __global__ __launch_bounds__(256, 2) void k_step3(const StepArgs a, int strips, 
             collide_row<BC, MASK>(a, x4, a.y0 + r3, t, mask_bits(mhist, 2), r4, u4, v4);
             if (store_lane) {
                 float *d = a.dst + o;
-                store_row9<NTS>(a.nts != 0, d, S, x4, t);
+                store_row9(a.nts != 0, d, S, x4, t);
                 if (MACRO) {
                     const long long m = (long long)r3 * a.fpitch;
-                    store4<false>(lane_ptr(a.rho + m, x4), r4);
-                    store4<false>(lane_ptr(a.u + m, x4), u4);
-                    store4<false>(lane_ptr(a.v + m, x4), v4);
+                    store_moments(a, m, x4, r4, u4, v4);
                 }
             }
         }

@@ -210,21 +210,7 @@ __device__ __forceinline__ void row1_load(const StepArgs &a, int r, int x4, bool
     }
 }
 
-// Halo lanes.  The three cells beyond each end of the strip are spread over six lanes -- lanes 0,1,2 own
-// the cells at distance 1,2,3 on the left, lanes 63,62,61 those on the right -- so that one scalar-cell
-// call per stage serves all of them at once (six sequential calls by two lanes made the kernel bound by
-// vector-ALU issue).  A halo cell takes the links moving toward the strip from the lane that owns the
-// cell farther out (`lane_out`) and the links moving away from it from the lane that owns the cell
-// closer in (`lane_in`; for distance 1 that is the strip's own edge cell, in the same lane), through
-// ds_bpermute, which does not occupy the vector ALU.
-//
-// One wave's march: strip [x0, x0 + 256), own rows = `len` rows starting at the pair's middle line `ym` and going up
-// (rows ym .. ym+len-1) or down (rows ym-1 .. ym-len).  Position p of the march = row ym + p / ym - 1 - p; iteration i
-// loads position i and runs step 1 on it, step 2 on position i-1, step 3 on i-2, step 4 on i-3 (stored): len + 3
-// iterations.  What the steps of position 0 pull from "position -1" is the other wave's position 0 (see the header).
-// (Touching the next row's 90 cache lines a row ahead with two one-lane-per-line loads, instead of the register prefetch
-//  PF below, costs more in the texture addresser than the wait it saves: 243 -> 162 k MLUPS at 8192^2,
-//  profiles/r02_experiments.txt.)
+// (halo lanes, positions and iterations of a wave's march: see march4 below)
 // Everything one wave's march carries from one iteration to the next (besides the two Row1 buffers of the one-row-ahead gather).
 struct March4State {
     Window w1;                                          // stage window between steps 1 and 2 (registers)
@@ -243,6 +229,20 @@ struct March4Ctx {
     HaloXchg *xchg;
 };
 
+// Two waves share a SIMD, and its arbiters serve the OLDER one first: measured per wave (tools/wave_timeline.py), the
+// wave in slot 0 of every SIMD finished its 134 rows after ~945 us, the one in slot 1 after ~1190 us, i.e. for the last
+// fifth of the launch every SIMD ran a single wave.  Priority outranks age, so the two take turns: both read the same
+// 100 MHz clock at the top of every fourth row and the wave whose slot parity matches bit 13 of it (82 us per turn, ten
+// rows or so) raises its priority -- complementary at (almost) all times without the waves knowing of each other.
+__device__ __forceinline__ void prio_turn(const StepArgs &a, int i, unsigned slot)
+{
+    if (a.prio_turns > 0 && (i & 3) == 0) {            // (every fourth row: reading the clock drains the wave's LDS queue)
+        const unsigned turn = (unsigned)(__builtin_amdgcn_s_memrealtime() >> a.prio_turns) & 1u;
+        if (turn == slot) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
+    }
+}
+
 // One iteration of the march (see march4 below): loads position i (or takes it from `cur`, gathered an iteration ago, and
 // gathers position i + 1 into `nxt`), step 1 on it, step 2 on position i - 1, step 3 on i - 2, step 4 on i - 3 (stored).
 //
@@ -252,7 +252,7 @@ struct March4Ctx {
 // (the generic form spends ~110 v_mov per row on those joins: the q2 / q3 arrays of a stage that may not run yet).  march4
 // runs the steady iterations in PAIRS with the two Row1 buffers swapping roles (PAR = i & 1 is then a constant: the LDS ring
 // slots are immediate offsets), so that "cur = nxt" and the windows' rotation are register names, not moves.
-template <int BC, bool MASK, bool MACRO, bool NTS, bool PF, bool DOWN, int NST>
+template <int BC, bool MASK, bool MACRO, bool PF, bool DOWN, int NST>
 __device__ __forceinline__ void march4_iter(const StepArgs &a, const March4Ctx &cx, const int i_, March4State &st, Row1 &cur,
                                             Row1 &nxt)
 {
@@ -268,16 +268,7 @@ __device__ __forceinline__ void march4_iter(const StepArgs &a, const March4Ctx &
     f4a(*W3)[64] = cx.W3;
     Window &w1 = st.w1;
 
-    // Two waves share a SIMD, and its arbiters serve the OLDER one first: measured per wave (tools/wave_timeline.py), the
-    // wave in slot 0 of every SIMD finished its 134 rows after ~945 us, the one in slot 1 after ~1190 us, i.e. for the last
-    // fifth of the launch every SIMD ran a single wave.  Priority outranks age, so the two take turns: both read the same
-    // 100 MHz clock at the top of every fourth row and the wave whose slot parity matches bit 13 of it (82 us per turn, ten
-    // rows or so) raises its priority -- complementary at (almost) all times without the waves knowing of each other.
-    if (a.prio_turns > 0 && (i & 3) == 0) {            // (every fourth row: reading the clock drains the wave's LDS queue)
-        const unsigned turn = (unsigned)(__builtin_amdgcn_s_memrealtime() >> a.prio_turns) & 1u;
-        if (turn == cx.slot) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-    }
+    prio_turn(a, i, cx.slot);
     // ---- what the other wave published for "position -1" in its previous iteration ---------------------------
     if (NST >= 2 && i >= 1 && i <= 3) {
         const float *hv = &cx.xchg->v[wy][i - 1][0][hslot];
@@ -394,27 +385,6 @@ __device__ __forceinline__ void march4_iter(const StepArgs &a, const March4Ctx &
         if (!(a.diag & 4))
 #endif
         collide_row<BC, MASK>(a, x4, a.y0 + r3, q3, mask_bits(st.mhist, 2), r4, u4, v4);
-#ifdef LB_DIAG
-        if (a.diag & 1048576) {
-            // timing only (wrong results): a FIFTH stage's worth of work -- a window load and push on W2 again, the gather with its
-            // six cross-lane moves, a halo-cell stage, a collide -- to price five steps per pass before building them
-            // (profiles/r04_experiments.txt section 9)
-            Window w2b;
-            lds_window_load(W2, lane, it, w2b);
-            f4a q3b[9];
-            stage_gather<DOWN>(w2b, q3, st.s2t, n3.tm, lane, q3b);
-            lds_window_push<DOWN>(W2, lane, it, q3);
-            if (halo3) {
-                Cell c;
-                Tri tw5 = {__shfl(st.s2t.d, lane_out), 0.f, __shfl(st.s2t.g, lane_out)};
-                halo_cell_next<BC, MASK, DOWN>(a, cx.hx, a.y0 + r3, left, false, st.s2c, n3.cm, tw5, n3.tm, n3.a0, n3.ap, n3.am, c);
-                n3 = halo_all<DOWN>(c, left);
-            }
-            collide_row<BC, MASK>(a, x4, a.y0 + r3, q3b, mask_bits(st.mhist, 2), r4, u4, v4);
-#pragma unroll
-            for (int k = 0; k < 9; ++k) q3[k] = q3b[k];
-        }
-#endif
         if (NST == 3) {                    // my position 0 after step 3 -> the other wave's window 3
             lds_publish<DOWN>(cx.P3, lane, 6, q3);
             if (halo1) cx.xchg->v[wy ^ 1][2][0][hslot] = n3.tm;
@@ -440,12 +410,10 @@ __device__ __forceinline__ void march4_iter(const StepArgs &a, const March4Ctx &
         if (cx.store_lane) {
             const long long o = (long long)r4_ * a.pitch;   // row start, uniform
             float *d = a.dst + o;
-            store_row9<NTS>(a.nts != 0, d, S, x4, t);
+            store_row9(a.nts != 0, d, S, x4, t);
             if (MACRO) {
                 const long long m = (long long)r4_ * a.fpitch;
-                store4<false>(lane_ptr(a.rho + m, x4), r4);
-                store4<false>(lane_ptr(a.u + m, x4), u4);
-                store4<false>(lane_ptr(a.v + m, x4), v4);
+                store_moments(a, m, x4, r4, u4, v4);
             }
         }
     } else if (i == 2) {
@@ -480,7 +448,7 @@ __device__ __forceinline__ void march4_iter(const StepArgs &a, const March4Ctx &
 // (Touching the next row's 90 cache lines a row ahead with two one-lane-per-line loads, instead of the register prefetch
 //  PF below, costs more in the texture addresser than the wait it saves: 243 -> 162 k MLUPS at 8192^2,
 //  profiles/r02_experiments.txt.)
-template <int BC, bool MASK, bool MACRO, bool NTS, bool PF, bool DOWN>
+template <int BC, bool MASK, bool MACRO, bool PF, bool DOWN>
 __device__ __forceinline__ void march4(const StepArgs &a, const int x0, const int ym, const int len, const int wy,
                                        f4a (*lds_win)[2][9][64], HaloXchg &xchg, const unsigned slot)
 {
@@ -512,27 +480,19 @@ __device__ __forceinline__ void march4(const StepArgs &a, const int x0, const in
     Row1 ra, rb;
     if (PF) row1_load<BC, MASK>(a, row_at(0), cx.x4, cx.halo1, cx.hx, ra);
     // the pipeline fills: iterations 0, 1, 2 run one, two, three stages (every launch gives a wave at least 4 rows: n_iter >= 7)
-    march4_iter<BC, MASK, MACRO, NTS, PF, DOWN, 1>(a, cx, 0, st, ra, PF ? rb : ra);
+    march4_iter<BC, MASK, MACRO, PF, DOWN, 1>(a, cx, 0, st, ra, PF ? rb : ra);
     if (PF) ra = rb;
-    march4_iter<BC, MASK, MACRO, NTS, PF, DOWN, 2>(a, cx, 1, st, ra, PF ? rb : ra);
+    march4_iter<BC, MASK, MACRO, PF, DOWN, 2>(a, cx, 1, st, ra, PF ? rb : ra);
     if (PF) ra = rb;
-    march4_iter<BC, MASK, MACRO, NTS, PF, DOWN, 3>(a, cx, 2, st, ra, PF ? rb : ra);
+    march4_iter<BC, MASK, MACRO, PF, DOWN, 3>(a, cx, 2, st, ra, PF ? rb : ra);
     if (PF) ra = rb;
     // The full pipeline.  (Round 4 also ran these iterations in PAIRS, the two row buffers swapping roles so that "this row =
     // the row gathered an iteration ago" is a register name instead of 60 v_mov per row: 927 instead of ~990 vector
     // instructions per wave and row, no scratch at 251-253 registers -- and 1-1.5 % SLOWER at 8192^2 on every box tried
     // (17 KB of loop body per direction instead of 9; profiles/r04_experiments.txt).  The kernel is not bound by vector-ALU
-    // issue any more; the pairs are not kept.  PAIRS = true restores them.)
-    constexpr bool PAIRS = false;
-    int i = 3;
-    if (PAIRS) {
-        for (; i + 1 < cx.n_iter; i += 2) {
-            march4_iter<BC, MASK, MACRO, NTS, PF, DOWN, 4>(a, cx, i, st, ra, rb);
-            march4_iter<BC, MASK, MACRO, NTS, PF, DOWN, 4>(a, cx, i + 1, st, rb, ra);
-        }
-    }
-    for (; i < cx.n_iter; ++i) {
-        march4_iter<BC, MASK, MACRO, NTS, PF, DOWN, 4>(a, cx, i, st, ra, PF ? rb : ra);
+    // issue any more; the pairs are not kept: commit 54ede03 has their loop.)
+    for (int i = 3; i < cx.n_iter; ++i) {
+        march4_iter<BC, MASK, MACRO, PF, DOWN, 4>(a, cx, i, st, ra, PF ? rb : ra);
         if (PF) ra = rb;
     }
 }
@@ -552,8 +512,10 @@ constexpr bool step4_prefetch(int bc, bool mask, bool macro)
 // halo cells and displaced loads take from its neighbour's strip (the read traffic beyond the compulsory bytes: +12.7 % at
 // 8192^2) would be lines the neighbour's waves fetch at about the same time on the same L2.  Bitwise equal, 74.9 KB of LDS per
 // workgroup, and no faster: 8192^2 314.7 / 316.3 / 314.3 k MLUPS against 318.7 / 316.2 / 319.1 k, 4096^2 287-292 k against
-// 285-299 k (one box, alternating: profiles/r04_experiments.txt).  The template parameter stays; nothing instantiates 2.
-template <int BC, bool MASK, bool MACRO, bool NTS, bool PF, int XW = 1>
+// 285-299 k (one box, alternating: profiles/r04_experiments.txt).  The template parameter stays; nothing instantiates 2 -- but wx
+// below is computed at run time (the compiler does not know that a workgroup has two waves): taking the axis out changes every
+// k_step4's prologue, so it waits for a change that is measured.
+template <int BC, bool MASK, bool MACRO, bool PF, int XW = 1>
 __global__ __launch_bounds__(64 * STEP4_WAVES * XW, 2) void k_step4(const StepArgs a, int strips, int seg_rows, int nsegs,
                                                                     int row_end)
 {
@@ -598,8 +560,8 @@ __global__ __launch_bounds__(64 * STEP4_WAVES * XW, 2) void k_step4(const StepAr
     if (ya >= row_end) return;                          // (both waves of the workgroup: the barriers below stay matched)
     const int yb = min(ya + rows, row_end);
     const int ym = ya + (yb - ya) / 2;                  // the pair's middle line: wave 0 marches down from it, wave 1 up
-    if (wy == 0) march4<BC, MASK, MACRO, NTS, PF, true>(a, sx * STRIP_W, ym, ym - ya, 0, lds_win, xchg, slot);
-    else march4<BC, MASK, MACRO, NTS, PF, false>(a, sx * STRIP_W, ym, yb - ym, 1, lds_win, xchg, slot);
+    if (wy == 0) march4<BC, MASK, MACRO, PF, true>(a, sx * STRIP_W, ym, ym - ya, 0, lds_win, xchg, slot);
+    else march4<BC, MASK, MACRO, PF, false>(a, sx * STRIP_W, ym, yb - ym, 1, lds_win, xchg, slot);
 #ifdef LB_DIAG
     if ((a.diag & 4096) && threadIdx.x == 0) {
         // per-wave timeline into the (otherwise unused) rho array: start, end (100 MHz ticks), XCC id, HW id, item

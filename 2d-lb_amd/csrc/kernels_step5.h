@@ -82,7 +82,9 @@ __device__ __forceinline__ void skirt_gather(const Window &w, const f4a (&q)[9],
 // One iteration: position i is loaded and takes step 1, position i-1 step 2 (window 1), i-2 step 3 (window 2), i-3 step 4 (LDS
 // window 3), i-4 step 5 (LDS window 4; stored).  NST = number of stages that have a row: 1..4 in iterations 0..3 (code of their
 // own, i a constant: the pipeline fills, the two waves of the pair hand over), 5 in the loop.
-// PF (not launched): `cur` holds position i on entry, gathered during the previous iteration, and is gathered anew -- position
+// PF (not launched -- and not free to take out: without its arms, compile-time false as they are, the prologue of k_step5's downward
+// march comes out one instruction shorter, so the axis waits for a change that is measured): `cur` holds position i on entry,
+// gathered during the previous iteration, and is gathered anew -- position
 // i + 1 -- as soon as step 2 has taken what it needs from it: the loads fly while steps 3, 4, 5 compute, in the registers the row
 // just consumed occupied.  Beside two register windows the compiler spills the row in flight wherever the gather sits (~21 scratch
 // accesses per row: 277-295 k instead of 327 k MLUPS at 8192^2), so PF also moves window 2's ring into LDS (its links 0,1,3 stay in
@@ -101,11 +103,7 @@ __device__ __forceinline__ void march5_iter(const StepArgs &a, const March5Ctx &
     f4a(*W4)[64] = cx.W4;
     Window &w1 = st.w1, &w2 = st.w2;
 
-    if (a.prio_turns > 0 && (i & 3) == 0) {            // the two waves of a SIMD take turns at the higher priority (march4_iter)
-        const unsigned turn = (unsigned)(__builtin_amdgcn_s_memrealtime() >> a.prio_turns) & 1u;
-        if (turn == cx.slot) __builtin_amdgcn_s_setprio(1);
-        else __builtin_amdgcn_s_setprio(0);
-    }
+    prio_turn(a, i, cx.slot);                       // the two waves of a SIMD take turns at the higher priority
     // ---- what the other wave published for "position -1" in its previous iteration ---------------------------
     // (steps 1 and 2 of its position 0 come through my still idle window 4 -- slots 6..8, then 3..5 -- into my register windows;
     //  steps 3 and 4 went straight into the ring slots of my LDS windows)
@@ -194,12 +192,10 @@ __device__ __forceinline__ void march5_iter(const StepArgs &a, const March5Ctx &
         if (cx.store_lane) {
             const long long o = (long long)r5 * a.pitch;    // row start, uniform
             float *d = a.dst + o;
-            store_row9<false>(a.nts != 0, d, S, x4, t);
+            store_row9(a.nts != 0, d, S, x4, t);
             if (MACRO) {
                 const long long m = (long long)r5 * a.fpitch;
-                store4<false>(lane_ptr(a.rho + m, x4), r4);
-                store4<false>(lane_ptr(a.u + m, x4), u4);
-                store4<false>(lane_ptr(a.v + m, x4), v4);
+                store_moments(a, m, x4, r4, u4, v4);
             }
         }
     } else if (NST == 4) {
@@ -209,7 +205,23 @@ __device__ __forceinline__ void march5_iter(const StepArgs &a, const March5Ctx &
     if (NST < 5) __syncthreads();                   // what was published in this iteration is consumed in the next
 }
 
-// One wave's march: columns [x0, x0 + 256) of which [x0 + 4, x0 + 252) are stored, `len` rows from the pair's middle line `ym`
+// The column a lane of an overlapping strip addresses, xr = the true column of its first cell (which may lie beyond either end of
+// the box), skl = lanes of skirt per side.  Lanes beyond an end of the box: the periodic image (nx % 4 == 0), or -- walls -- copies of
+// the lane at that end (their values are never within reach of a stored cell: the wall column's rule rebuilds what it pulled from them).
+// (periodic: only the image lanes as far as the skirt reaches are anybody's skirt; the lanes behind them -- the last strip of 8192
+//  columns stores 8 cells -- read what the last image lane reads, i.e. the same cache lines, instead of 240 more columns)
+template <int BC>
+__device__ __forceinline__ int skirt_column(const StepArgs &a, int xr, int skl)
+{
+    if (BC == LB_BC_PERIODIC) return xr < 0 ? xr + a.nx : (xr >= a.nx ? (xr - a.nx < 4 * skl ? xr - a.nx : 4 * (skl - 1)) : xr);
+    return min(max(xr, 0), (a.nx - 1) & ~3);
+}
+__device__ __forceinline__ bool skirt_store_lane(const StepArgs &a, int lane, int xr, int skl)
+{
+    return lane >= skl && lane <= 63 - skl && xr < a.nx;
+}
+
+// One wave's march: columns [x0, x0 + 256) of which all but the skirt lanes are stored, `len` rows from the pair's middle line `ym`
 // upward or downward; len + 4 iterations.
 template <int BC, bool MASK, bool MACRO, bool PF, bool DOWN>
 __device__ __forceinline__ void march5(const StepArgs &a, const int x0, const int ym, const int len, const int wy,
@@ -217,14 +229,9 @@ __device__ __forceinline__ void march5(const StepArgs &a, const int x0, const in
 {
     March5Ctx cx;
     cx.lane = threadIdx.x;
-    const int xr = x0 + cx.lane * 4;                 // true column of my first cell: -4 .. ; may lie beyond either end of the box
-    // lanes beyond an end of the box: the periodic image (nx % 4 == 0), or -- walls -- copies of the lane at that end (their
-    // values are never within reach of a stored cell: the wall column's rule rebuilds what it pulled from them)
-    // (periodic: only the first lane beyond the last column is anybody's skirt; the lanes behind it -- the last strip of 8192
-    //  columns stores 8 cells -- read what that lane reads, i.e. the same cache lines, instead of 240 more columns)
-    if (BC == LB_BC_PERIODIC) cx.x4 = xr < 0 ? xr + a.nx : (xr >= a.nx ? (xr - a.nx < 8 ? xr - a.nx : 4) : xr);
-    else cx.x4 = min(max(xr, 0), (a.nx - 1) & ~3);
-    cx.store_lane = cx.lane >= STEP5_SKIRT / 4 && cx.lane <= 63 - STEP5_SKIRT / 4 && xr < a.nx;
+    const int xr = x0 + cx.lane * 4;
+    cx.x4 = skirt_column<BC>(a, xr, STEP5_SKIRT / 4);
+    cx.store_lane = skirt_store_lane(a, cx.lane, xr, STEP5_SKIRT / 4);
     cx.ym = ym; cx.n_iter = len + 4; cx.wy = wy; cx.slot = slot;
     cx.W3 = mine; cx.W4 = mine + 9; cx.R2 = mine + 18;         // (slots: window 3, window 4, PF: the ring of window 2)
     cx.P3 = other; cx.P4 = other + 9; cx.Q2 = other + 18;

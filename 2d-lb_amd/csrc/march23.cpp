@@ -8,10 +8,10 @@ struct L23 {
     static void go(int depth, const MarchLaunch &g, const StepArgs &a)
     {
         if (depth == 3)
-            hipLaunchKernelGGL((k_step3<BC, MASK, MACRO, false>), g.grid, g.block, 0, g.stream, a, g.strips, g.seg_rows, g.nsegs,
+            hipLaunchKernelGGL((k_step3<BC, MASK, MACRO>), g.grid, g.block, 0, g.stream, a, g.strips, g.seg_rows, g.nsegs,
                                g.row_end);
         else
-            hipLaunchKernelGGL((k_step2<BC, MASK, MACRO, false>), g.grid, g.block, 0, g.stream, a, g.strips, g.seg_rows, g.nsegs,
+            hipLaunchKernelGGL((k_step2<BC, MASK, MACRO>), g.grid, g.block, 0, g.stream, a, g.strips, g.seg_rows, g.nsegs,
                                g.row_end);
     }
 };

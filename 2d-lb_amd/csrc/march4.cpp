@@ -10,10 +10,10 @@ struct L4 {
     {
         // the row-ahead gather where it fits in 256 registers without scratch (step4_prefetch), unless the caller switches it off
         if (step4_prefetch(BC, MASK, MACRO) && prefetch)
-            hipLaunchKernelGGL((k_step4<BC, MASK, MACRO, false, step4_prefetch(BC, MASK, MACRO)>), g.grid, g.block, 0, g.stream, a,
+            hipLaunchKernelGGL((k_step4<BC, MASK, MACRO, step4_prefetch(BC, MASK, MACRO)>), g.grid, g.block, 0, g.stream, a,
                                g.strips, g.seg_rows, g.nsegs, g.row_end);
         else
-            hipLaunchKernelGGL((k_step4<BC, MASK, MACRO, false, false>), g.grid, g.block, 0, g.stream, a, g.strips, g.seg_rows,
+            hipLaunchKernelGGL((k_step4<BC, MASK, MACRO, false>), g.grid, g.block, 0, g.stream, a, g.strips, g.seg_rows,
                                g.nsegs, g.row_end);
     }
 };

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Ablation timing of the fused kernels (diagnostic build, wrong results by design, timing only).
-LB_DIAG bits: 1 = skip step-1 collide, 2 = skip step-2 collide, 4 = no stores (k_step2) / skip step-3 collide
-(k_step3), 8 = all loads aligned, 512 = no boundary rule in the 4-cell path.
+LB_DIAG bits the kernel headers implement: 1 = skip step-1 collide, 2 = skip step-2 collide, 4 = no stores (k_step2) / skip
+step-3 collide (k_step3, k_step4), 8 = all loads aligned, 512 = no boundary rule in the 4-cell path, 1024 = no halo-cell stages
+(k_step4), 2048 = skip step-4 collide (k_step4), 4096 = per-wave timeline (tools/wave_timeline.py), 16384 = no periodic-wrap
+patch, 65536 = no XCD transposition (k_step4), 262144 = no halo-cell loads (k_step4), 1 << 22 = no stores (k_deep),
+1 << 23 = one gather only (k_deep), 1 << 24 = no barriers in k_deep2's steady state.
 Each configuration runs in its own process (the switches are read at lb_create)."""
 import os
 import subprocess
@@ -54,11 +57,10 @@ def main():
     for variant, name in configs:
         for diag, what in ((0, "full"), (1, "no step-1 collide"), (2, "no step-2 collide"), (3, "no collide at all"),
                            (4, "no stores"), (8, "aligned loads"), (11, "no collide, aligned loads"),
-                           (7, "loads only"), (16, "aligned 256-cell strips"), (19, "aligned strips, no collide"),
-                           (17, "aligned strips, no step-1 collide")) + \
+                           (7, "loads only")) + \
                 (((7, "no collide at all (3 steps)"), (0, "full again"))
                  if name == "k_step3" else ()):
-            if name == "k_step" and diag in (2, 3, 4, 7, 11, 16, 19, 17):
+            if name == "k_step" and diag in (2, 3, 4, 7, 11):
                 continue
             if name == "k_step3" and diag not in (0, 1, 7):
                 continue

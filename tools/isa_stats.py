@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static instruction mix of one kernel instantiation, per loop (hipcc --save-temps assembly).
 
-    tools/isa_stats.py "k_step4<LB_BC_PERIODIC, false, false, true, true>" [-D...] [--dump]
+    tools/isa_stats.py "k_step4<LB_BC_PERIODIC, false, false, true>" [-D...] [--dump]       (k_step4<BC, MASK, MACRO, PF>)
 
 Compiles a translation unit holding only that instantiation (seconds instead of the library's minutes), finds the
 innermost loops (backward branches) of every function in the assembly and prints, per loop: VALU instructions (packed,

@@ -107,10 +107,11 @@ def main():
         f = st.mean(pmc[(k, "FETCH_SIZE")])
         w = st.mean(pmc[(k, "WRITE_SIZE")])
         rd, wr = f * 1024 * fetch_corr, w * 1024 * write_corr
-        macro = k.split(",")[2].strip() == "true"      # k_step<BC, MASK, MACRO, ...> / k_step2<BC, MASK, MACRO, NTS> / k_tile4<BC, MASK, MACRO, ...>
-        masked = k.split(",")[1].strip() == "true"
-        # time steps per launch: k_tile4: 4; k_deep<BC, MASK, MACRO, D, RW, PFD>: D; k_stepN: N
-        spl = 4 if k.startswith("k_tile4") else (int(k.split(",")[3].strip(" >")) if k.startswith("k_deep") else (int(k[6]) if k[6:7].isdigit() else 1))
+        targs = [t.strip() for t in k.split("<", 1)[-1].split(">", 1)[0].split(",")]    # k_step<BC, MASK, MACRO, ...> / k_step2<BC, MASK, MACRO> / k_tile4<BC, MASK, MACRO, ...>
+        macro = targs[2] == "true"
+        masked = targs[1] == "true"
+        # time steps per launch: k_tile4: 4; k_deep<BC, MASK, MACRO, D, RW, PFD> / k_deep2<BC, MASK, MACRO, D>: D; k_stepN: N
+        spl = 4 if k.startswith("k_tile4") else (int(targs[3]) if k.startswith("k_deep") else (int(k[6]) if k[6:7].isdigit() else 1))
         alg = (73.0 if masked else 72.0) * side * side + (12.0 * side * side if macro else 0.0)      # compulsory bytes of one launch, whatever spl
         lines.append("| %s | %.4g | %.4g | %.4g | %.4g | %.4g | %.4g | %.3f |" % (k, f, w, rd, wr, rd + wr, alg, (rd + wr) / alg))
         key = ("%d/%d" % (side, spl)) if config == 4 else ("c%d/%d/%d" % (config, side, spl))
