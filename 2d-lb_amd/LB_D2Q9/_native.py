@@ -8,18 +8,18 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LB_LIB") or os.path.join(_HERE, "liblbhip.so")   # LB_LIB: diagnostic builds only
 
-LB_BC_PIPE, LB_BC_PERIODIC, LB_BC_CAVITY, LB_BC_VELOCITY_INLET = 0, 1, 2, 3
+LB_BC_PIPE, LB_BC_PERIODIC, LB_BC_CAVITY, LB_BC_VELOCITY_INLET, LB_BC_OPEN = 0, 1, 2, 3, 4
 LB_FLAG_HALO = 1
 LB_FLAG_PLANAR = 2
 LB_FLAG_EAGER_MACRO = 4
 LB_MASK_HALO_ROWS = 13
 LB_PEER_HANDLE_BYTES = 384
 LB_DEVICE_CPU = -1
-LB_SEM_OPENCL, LB_SEM_CYTHON, LB_SEM_OPENCL_D2Q9I = 0, 1, 2
+LB_SEM_OPENCL, LB_SEM_CYTHON, LB_SEM_OPENCL_D2Q9I, LB_SEM_DIFFUSION = 0, 1, 2, 3
 BC_NAMES = {"pipe": LB_BC_PIPE, "periodic": LB_BC_PERIODIC, "cavity": LB_BC_CAVITY,
-            "velocity_inlet": LB_BC_VELOCITY_INLET}
+            "velocity_inlet": LB_BC_VELOCITY_INLET, "open": LB_BC_OPEN}
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 # every symbol include/lb_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -33,6 +33,7 @@ EXPORTS = (
     "lb_autotune_quick", "lb_hot_kernel", "lb_get_corner_state", "lb_set_corner_state", "lb_check", "lb_set_debug_sync",
     "lb_peer_export", "lb_peer_connect", "lb_set_params_f64", "lb_set_slab_cycle", "lb_exchange_timing", "lb_exchange_stats",
     "lb_set_exchange_inline",
+    "lb_set_reaction", "lb_edge_floats", "lb_get_edge_state", "lb_set_edge_state", "lb_set_velocity_from",
 )
 
 
@@ -98,6 +99,12 @@ def lib():
                                         ct.POINTER(ct.c_int), ct.POINTER(ct.c_int)]
     if L.lb_abi_version() >= 10:
         L.lb_set_exchange_inline.argtypes = [h, I]
+    if L.lb_abi_version() >= 11:
+        L.lb_set_reaction.argtypes = [h, ct.c_float]
+        L.lb_edge_floats.argtypes = [h]
+        L.lb_get_edge_state.argtypes = [h, vp]
+        L.lb_set_edge_state.argtypes = [h, vp]
+        L.lb_set_velocity_from.argtypes = [h, h]
     L.lb_comm_init.argtypes = [h, vp, I, I]
     L.lb_timer_stop.argtypes = [h, fp]
     L.lb_layout.argtypes = [h, ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64)]

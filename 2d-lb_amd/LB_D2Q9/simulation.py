@@ -70,6 +70,10 @@ class Simulation(object):
         :param semantics: 'opencl' (D2Q9.cl, fused fast path), 'cython' (cython_dim.pyx: pipe family, whole grid,
                compatibility path; the two reference paths differ at walls and inlets) or 'd2q9i' (the reference's
                D2Q9i.cl fork of the OpenCL path: pipe family, whole grid, fused).
+               'diffusion': a SCALAR lattice (the reference's D2Q9_diffusion.cl / reaction_diffusion/diffusion.py): rho is a
+               concentration, u, v an imposed velocity field (set_fields, set_velocity_from) that no kernel writes, the
+               equilibrium is linear, set_reaction(G) adds Fisher growth; bc='periodic' or 'open' (the reference's box:
+               links entering from outside keep the values of the last set_f / init_pop, get_edge_state); whole grid.
         :param planar: device layout of the lattices: False = the nine planes of a row stored together (default),
                True = each plane contiguous (LB_FLAG_PLANAR); results are identical.  None: environment variable
                LB_LAYOUT=planar selects True (tuning aid).
@@ -99,7 +103,8 @@ class Simulation(object):
         self.eager_macro = bool(eager_macro)
         p.flags = ((_native.LB_FLAG_HALO if halo else 0) | (_native.LB_FLAG_PLANAR if self.planar else 0) |
                    (_native.LB_FLAG_EAGER_MACRO if self.eager_macro else 0))
-        sem = {"opencl": _native.LB_SEM_OPENCL, "cython": _native.LB_SEM_CYTHON, "d2q9i": _native.LB_SEM_OPENCL_D2Q9I}
+        sem = {"opencl": _native.LB_SEM_OPENCL, "cython": _native.LB_SEM_CYTHON, "d2q9i": _native.LB_SEM_OPENCL_D2Q9I,
+               "diffusion": _native.LB_SEM_DIFFUSION}
         if semantics not in sem:
             raise ValueError("semantics must be one of %s" % sorted(sem))
         p.semantics = sem[semantics]
@@ -117,6 +122,7 @@ class Simulation(object):
             check(self._lib.lb_set_params_f64(self._h, float(omega), float(inlet_rho), float(outlet_rho)))
         self._shape2 = (self.nx, self.local_ny)
         self._shape3 = (self.nx, self.local_ny, NUM_JUMPERS)
+        self.G = 0.                      # scalar lattices: growth rate of the Fisher term (set_reaction)
         self._mask_host = None
         self._mask_halo_host = None      # (south_rows, north_rows) as last given to set_obstacle_mask_halo
         if obstacle_mask is not None:
@@ -212,7 +218,7 @@ class Simulation(object):
         unchanged; the pass advances at most (n - 7) // 4 steps, a runner-up's longer comparison included) and keeps the
         fastest for this grid; shorter runs use the size heuristic (or call autotune())."""
         n = int(num_iterations)
-        if wait and n > 0:
+        if wait and n > 0 and self.semantics != "diffusion":      # (a scalar lattice's kernel is the planner's size rule: no tuning pass)
             # (the pass costs 361 steps, 889 on grids <= 768^2, some of them in configurations several times slower than
             #  the best: it only pays for itself in a run several times that long)
             used = self._lib.lb_autotune_quick(self._h, (n - 7) // 4)
@@ -303,6 +309,9 @@ class Simulation(object):
             d[k] = getattr(self, k)
         if self.bc_mode == _native.LB_BC_VELOCITY_INLET:
             d["corner_state"] = self.get_corner_state()
+        if self.semantics == "diffusion":
+            d["G"] = np.float32(self.G)
+            d["edge_state"] = self.get_edge_state()
         if self._mask_halo_host is not None:         # a slab: the neighbours' obstacle rows it was given
             empty = np.zeros((0, 0), np.int32)
             d["mask_halo_south"] = empty if self._mask_halo_host[0] is None else self._mask_halo_host[0]
@@ -336,7 +345,8 @@ class Simulation(object):
 
     def restore_arrays(self, d):
         self._check_compatible(d)
-        self.set_obstacle_mask(d["mask"] if d["mask"].size else None)
+        if self.semantics != "diffusion":                       # (a scalar lattice has no obstacles)
+            self.set_obstacle_mask(d["mask"] if d["mask"].size else None)
         if "mask_halo_south" in d:
             so, no = d["mask_halo_south"], d["mask_halo_north"]
             self.set_obstacle_mask_halo(so if so.size else None, no if no.size else None)
@@ -344,6 +354,40 @@ class Simulation(object):
         self.set_f(d["f"])
         if self.bc_mode == _native.LB_BC_VELOCITY_INLET:
             self.set_corner_state(d["corner_state"])           # (after set_f, which resets them to f's own corners)
+        if self.semantics == "diffusion":
+            self.set_reaction(float(d["G"]))
+            self.set_edge_state(d["edge_state"])               # (after set_f, likewise)
+
+    # -- scalar lattices (semantics='diffusion') -----------------------------------
+    def set_reaction(self, G):
+        """Growth rate of the Fisher term w_k G rho (1 - rho) added in the collision (D2Q9_diffusion.cl:95-124), lattice
+        units; 0 = none."""
+        check(self._lib.lb_set_reaction(self._h, float(np.float32(G))))
+        self.G = float(np.float32(G))
+
+    def set_velocity_from(self, flow):
+        """Take the imposed velocity from a flow Simulation of the same grid on the same device: its current u, v,
+        copied device to device behind the flow's enqueued work (lb_set_velocity_from)."""
+        check(self._lib.lb_set_velocity_from(self._h, flow._h))
+
+    def edge_floats(self):
+        n = self._lib.lb_edge_floats(self._h)
+        if n < 0:
+            check(n)
+        return n
+
+    def get_edge_state(self):
+        """bc='open': the links that enter from outside the box, frozen since the last set_f / init_pop: 6 (nx + ny)
+        floats in the order of include/lb_hip.h; empty in a periodic box."""
+        out = np.zeros(self.edge_floats(), np.float32)
+        check(self._lib.lb_get_edge_state(self._h, out.ctypes.data))
+        return out
+
+    def set_edge_state(self, values):
+        v = np.ascontiguousarray(values, np.float32)
+        if v.shape != (self.edge_floats(),):
+            raise ValueError("edge state = %d floats" % self.edge_floats())
+        check(self._lib.lb_set_edge_state(self._h, v.ctypes.data))
 
     def get_corner_state(self):
         """bc='velocity_inlet': the eight corner links no kernel of that rule set writes (include/lb_hip.h)."""

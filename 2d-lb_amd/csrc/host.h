@@ -22,6 +22,7 @@
 #include "cpu_backend.h"
 #include "plan.h"
 #include "launchers.h"          // StepArgs; the fused kernels are instantiated in their own translation units
+#include "scalar_launch.h"      // scalar lattices (LB_SEM_DIFFUSION): AdExtra, AdCheck, their launchers
 
 namespace {
 
@@ -39,6 +40,9 @@ struct lb_sim : PlanInputs {
     float *feq = nullptr;       // raw allocation, lazily created
     float *rho = nullptr, *u = nullptr, *v = nullptr;
     float *stage = nullptr;     // [H][pitch], lazily: one plane on its way between the host and interleaved rows (lattice_plane_*)
+    float *ad_edge = nullptr;   // scalar lattice, OPEN family: the edge state on the device (scalar_launch.h)
+    float ad_G = 0.f;           // scalar lattice: growth rate of the Fisher term (lb_set_reaction); 0 = plain relaxation
+    AdCheck *ad_part = nullptr; // scalar lattice: lb_check's records, allocated on first use
     float *vi_corner = nullptr; // VELOCITY_INLET: the eight corner links nothing ever writes (bc_vel_cell), device
     uint8_t *mask_raw = nullptr, *mask = nullptr;   // [H+2*MASK_GHOST][pitch] + guards; mask -> row 0
     bool feq_valid = false;     // feq buffer consistent with rho,u,v
@@ -47,6 +51,8 @@ struct lb_sim : PlanInputs {
     long long check_cap = 0;
     hipStream_t own_stream = nullptr, stream = nullptr, comm_stream = nullptr, edge_stream = nullptr;
     hipEvent_t ev_boundary = nullptr, ev_interior = nullptr, ev_halo = nullptr, ev_packed = nullptr, ev_edge = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
+    // (ev_interior also orders a scalar lattice and the flow handle it takes its velocity from, lb_set_velocity_from: both are whole-grid
+    //  handles there, whose runs never record it -- the slab schedules and lb_run_batch are its other users)
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
     float *halo_buf = nullptr;  // 4 x HALO_SEGS_DEEP (117) x nx floats: send north, send south, recv south, recv north (ensure_halo_buf)
@@ -106,6 +112,12 @@ int fail(int code, const char *fmt, ...);       // records the message lb_last_e
         if ((s) && (s)->cpu) return fail(LB_ERR_STATE, "%s is not available on the CPU backend", name);      \
     } while (0)
 
+// Scalar lattices (LB_SEM_DIFFUSION) are whole-grid handles without obstacles: what only slabs, masks or the flow kernels' tuning mean refuses.
+#define SCALAR_UNSUPPORTED(s, name)                                                                         \
+    do {                                                                                                    \
+        if ((s) && (s)->scalar()) return fail(LB_ERR_STATE, "%s is not available on a scalar lattice (LB_SEM_DIFFUSION)", name); \
+    } while (0)
+
 // ---- transport.cpp: RCCL, loaded lazily so that single-GPU use never touches librccl ---------------------------------------------
 struct Rccl {
     void *lib = nullptr;
@@ -146,6 +158,9 @@ int launch_marching(lb_sim *s, const MarchRows &r);
 void drop_graph(lb_sim *s);
 // n time steps on a whole-grid handle
 int run_whole_grid(lb_sim *s, int n_steps, bool final_macro = true);
+// n time steps on a scalar lattice; the last launch stores rho
+int run_scalar(lb_sim *s, int n_steps);
+inline AdExtra ad_extra(const lb_sim *s) { return AdExtra{s->ad_edge, s->ad_G}; }
 
 // ---- slab.cpp --------------------------------------------------------------------------------------------------------------------
 int ensure_halo_buf(lb_sim *s);         // the send / receive buffers of the halo exchange (also lb_check's scratch across ranks)

@@ -216,3 +216,22 @@ int run_whole_grid(lb_sim *s, int n_steps, bool final_macro)
     }
     return LB_OK;
 }
+
+// n time steps on a scalar lattice (kernels_scalar.h): k_ad_tile4 / k_ad_step launch by launch, as scalar_next_advance splits the run; the last
+// launch stores rho (with a growth term rho is not a moment of the populations a run leaves behind: never rebuilt on demand)
+int run_scalar(lb_sim *s, int n_steps)
+{
+    const AdExtra e = ad_extra(s);
+    int left = n_steps;
+    while (left > 0) {
+        const int adv = scalar_next_advance(s, left);
+        const StepArgs a = step_args(s, 0, 1, s->H);
+        if (adv == TILE_T) lbk_ad_tile4(s->p.bc_mode, s->ad_G != 0.f, left == adv, scalar_tile_shape(s), s->stream, a, e);
+        else lbk_ad_step(s->p.bc_mode, s->ad_G != 0.f, left == adv, s->stream, a, e);
+        HIP_TRY(hipGetLastError());
+        s->cur ^= 1;
+        left -= adv;
+    }
+    if (n_steps) { s->feq_valid = false; s->macro_valid = true; }
+    return LB_OK;
+}

@@ -221,6 +221,28 @@ int corners_patch(lb_sim *s, int which)
     return LB_OK;
 }
 
+// Scalar lattice, OPEN family: the edge state follows the populations whenever they are set as a whole (the reference's
+// f_streamed = f at that moment, diffusion.py:321-324) ...
+int edge_capture(lb_sim *s, int which)
+{
+    if (!s->ad_edge) return LB_OK;
+    lbk_ad_edge_capture(s->stream, step_args(s, 0, 1, s->H), s->origin(which), s->ad_edge);
+    HIP_TRY(hipGetLastError());
+    return LB_OK;
+}
+// ... and is written back into the lattice behind the un-fused streaming phase, whose second lattice holds, after a fused run,
+// something else than the reference's f_streamed (fused launches swap the lattices)
+int edge_patch(lb_sim *s, int which)
+{
+    if (!s->ad_edge) return LB_OK;
+    lbk_ad_edge_patch(s->stream, step_args(s, 0, 1, s->H), s->origin(which), s->ad_edge);
+    HIP_TRY(hipGetLastError());
+    return LB_OK;
+}
+
+// ABI order of the edge state (include/lb_hip.h: west, east, south, north; unpadded) <-> device order (scalar_launch.h)
+long long edge_host_floats(const lb_sim *s) { return s->ad_edge ? 6LL * (s->p.nx + s->p.ny) : 0; }
+
 // lb_run in Cython-path semantics
 int run_cython(lb_sim *s, int n_steps)
 {
@@ -296,7 +318,17 @@ int lb_create(const lb_params *p, lb_sim **out)
     if (p->nx < 2 || p->ny < 2) return fail(LB_ERR_ARG, "grid must be at least 2x2 (got %dx%d)", p->nx, p->ny);
     if (p->local_ny < 1 || p->y0 < 0 || p->y0 + p->local_ny > p->ny)
         return fail(LB_ERR_ARG, "slab [%d,%d) outside 0..%d", p->y0, p->y0 + p->local_ny, p->ny);
-    if (p->bc_mode < LB_BC_PIPE || p->bc_mode > LB_BC_VELOCITY_INLET) return fail(LB_ERR_ARG, "unknown bc_mode %d", p->bc_mode);
+    if (p->bc_mode < LB_BC_PIPE || p->bc_mode > LB_BC_OPEN) return fail(LB_ERR_ARG, "unknown bc_mode %d", p->bc_mode);
+    if (p->bc_mode == LB_BC_OPEN && p->semantics != LB_SEM_DIFFUSION)
+        return fail(LB_ERR_ARG, "LB_BC_OPEN exists for scalar lattices (LB_SEM_DIFFUSION) only");
+    if (p->semantics == LB_SEM_DIFFUSION) {
+        // scalar lattices (refused before any device is touched)
+        if (p->bc_mode != LB_BC_PERIODIC && p->bc_mode != LB_BC_OPEN)
+            return fail(LB_ERR_ARG, "a scalar lattice (LB_SEM_DIFFUSION) takes the families LB_BC_PERIODIC and LB_BC_OPEN only");
+        if (p->local_ny != p->ny || p->y0 != 0) return fail(LB_ERR_ARG, "a scalar lattice (LB_SEM_DIFFUSION) owns its whole grid: no slabs");
+        if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "a scalar lattice (LB_SEM_DIFFUSION) has no halo interface (LB_FLAG_HALO)");
+        if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "a scalar lattice (LB_SEM_DIFFUSION) runs on a GPU only (no CPU backend)");
+    }
     if (p->bc_mode == LB_BC_VELOCITY_INLET &&
         (p->local_ny != p->ny || (p->flags & LB_FLAG_HALO) || p->semantics != LB_SEM_OPENCL))
         return fail(LB_ERR_ARG, "the velocity-inlet family exists for whole-grid OpenCL-path handles only");
@@ -306,7 +338,7 @@ int lb_create(const lb_params *p, lb_sim **out)
     for (int r : p->reserved)
         if (r != 0) return fail(LB_ERR_ARG, "reserved fields must be zero");
     if (p->flags & ~(LB_FLAG_HALO | LB_FLAG_PLANAR | LB_FLAG_EAGER_MACRO)) return fail(LB_ERR_ARG, "unknown flags 0x%x", p->flags);
-    if (p->semantics != LB_SEM_OPENCL && p->semantics != LB_SEM_CYTHON && p->semantics != LB_SEM_OPENCL_D2Q9I)
+    if (p->semantics != LB_SEM_OPENCL && p->semantics != LB_SEM_CYTHON && p->semantics != LB_SEM_OPENCL_D2Q9I && p->semantics != LB_SEM_DIFFUSION)
         return fail(LB_ERR_ARG, "unknown semantics %d", p->semantics);
     if (p->semantics == LB_SEM_OPENCL_D2Q9I &&
         (p->bc_mode != LB_BC_PIPE || p->local_ny != p->ny || (p->flags & LB_FLAG_HALO)))
@@ -400,6 +432,11 @@ int lb_create(const lb_params *p, lb_sim **out)
     CREATE_TRY(hipMalloc(&s->rho, fld_bytes));
     CREATE_TRY(hipMalloc(&s->u, fld_bytes));
     CREATE_TRY(hipMalloc(&s->v, fld_bytes));
+    if (s->scalar() && p->bc_mode == LB_BC_OPEN) {
+        const size_t edge_bytes = sizeof(float) * (size_t)ad_edge_device_floats(s->pitch, p->ny);
+        CREATE_TRY(hipMalloc(&s->ad_edge, edge_bytes));
+        CREATE_TRY(hipMemsetAsync(s->ad_edge, 0, edge_bytes, s->stream));
+    }
     CREATE_TRY(hipMalloc(&s->vi_corner, 8 * sizeof(float)));
     CREATE_TRY(hipMemsetAsync(s->vi_corner, 0, 8 * sizeof(float), s->stream));
     CREATE_TRY(hipMalloc(&s->mask_raw, (size_t)s->pitch * (s->H + 2 * MASK_GHOST) + 2 * GUARD));
@@ -450,7 +487,8 @@ int lb_destroy(lb_sim *s)
         }
     if (s->peer_flags) (void)hipFree(s->peer_flags);
     if (s->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(s->comm);
-    for (float *p : {s->lat[0], s->lat[1], s->feq, s->rho, s->u, s->v, s->halo_buf, s->vi_corner, s->stage})
+    if (s->ad_part) (void)hipFree(s->ad_part);
+    for (float *p : {s->lat[0], s->lat[1], s->feq, s->rho, s->u, s->v, s->halo_buf, s->vi_corner, s->stage, s->ad_edge})
         if (p) (void)hipFree(p);
     if (s->mask_raw) (void)hipFree(s->mask_raw);
     if (s->check_part) (void)hipFree(s->check_part);
@@ -506,6 +544,7 @@ int lb_set_variant(lb_sim *s, int variant)
 int lb_set_slab_cycle(lb_sim *s, int depth)
 {
     if (s && s->cpu) return LB_OK;
+    SCALAR_UNSUPPORTED(s, "lb_set_slab_cycle");
     if (!s) return fail(LB_ERR_ARG, "null handle");
     // (8: the seven-step cycle with k_deep2<7> for its launches, 7: with k_deep<7>; 0: automatic depth, kernel by transport)
     if (depth != 0 && (depth < 3 || depth > MAX_DEPTH + 1))
@@ -518,6 +557,7 @@ int lb_set_slab_cycle(lb_sim *s, int depth)
 int lb_set_exchange_inline(lb_sim *s, int on)
 {
     if (s && s->cpu) return LB_OK;
+    SCALAR_UNSUPPORTED(s, "lb_set_exchange_inline");
     if (!s) return fail(LB_ERR_ARG, "null handle");
     s->xchg_inline = on != 0;
     return LB_OK;
@@ -526,6 +566,7 @@ int lb_set_exchange_inline(lb_sim *s, int on)
 int lb_exchange_timing(lb_sim *s, int enable)
 {
     CPU_UNSUPPORTED(s, "lb_exchange_timing");
+    SCALAR_UNSUPPORTED(s, "lb_exchange_timing");
     if (!s) return fail(LB_ERR_ARG, "null handle");
     DeviceGuard guard(s->p.device);
     if (enable && !s->xt_ev[0])
@@ -538,6 +579,7 @@ int lb_exchange_timing(lb_sim *s, int enable)
 int lb_exchange_stats(lb_sim *s, int64_t *n_exchanges, double *total_ms, double *max_ms, int *cycle_depth_out, int *band_rows)
 {
     CPU_UNSUPPORTED(s, "lb_exchange_stats");
+    SCALAR_UNSUPPORTED(s, "lb_exchange_stats");
     if (!s) return fail(LB_ERR_ARG, "null handle");
     DeviceGuard guard(s->p.device);
     double total = 0., mx = 0.;
@@ -636,6 +678,7 @@ int lb_set_f(lb_sim *s, const float *f)
     rc = copy_lattice(s, s->lat[s->cur ^ 1], s->lat[s->cur]);
     if (rc) return rc;
     if ((rc = corners_capture(s, s->cur))) return rc;
+    if ((rc = edge_capture(s, s->cur))) return rc;
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->ghost_depth = 0;
     return LB_OK;
@@ -663,6 +706,7 @@ int lb_get_f(lb_sim *s, float *f)
 int lb_get_corner_state(lb_sim *s, float *out8)
 {
     CPU_UNSUPPORTED(s, "lb_get_corner_state");
+    SCALAR_UNSUPPORTED(s, "lb_get_corner_state");
     if (!s || !out8) return fail(LB_ERR_ARG, "null argument");
     DeviceGuard guard(s->p.device);
     HIP_TRY(hipMemcpyAsync(out8, s->vi_corner, 8 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
@@ -673,6 +717,7 @@ int lb_get_corner_state(lb_sim *s, float *out8)
 int lb_set_corner_state(lb_sim *s, const float *in8)
 {
     CPU_UNSUPPORTED(s, "lb_set_corner_state");
+    SCALAR_UNSUPPORTED(s, "lb_set_corner_state");
     if (!s || !in8) return fail(LB_ERR_ARG, "null argument");
     DeviceGuard guard(s->p.device);
     HIP_TRY(hipMemcpyAsync(s->vi_corner, in8, 8 * sizeof(float), hipMemcpyHostToDevice, s->stream));
@@ -706,6 +751,7 @@ int lb_set_mask(lb_sim *s, const int32_t *mask)
         for (size_t c = 0; mask && c < s->cpu->plane(); ++c) s->cpu->mask[c] = mask[c] == 1;
         return LB_OK;
     }
+    SCALAR_UNSUPPORTED(s, "lb_set_mask");
     if (!s) return fail(LB_ERR_ARG, "null handle");
     DeviceGuard guard(s->p.device);
     if (!mask) {
@@ -741,6 +787,7 @@ int lb_set_mask(lb_sim *s, const int32_t *mask)
 int lb_set_mask_halo(lb_sim *s, const int32_t *south_rows, const int32_t *north_rows)
 {
     CPU_UNSUPPORTED(s, "lb_set_mask_halo");
+    SCALAR_UNSUPPORTED(s, "lb_set_mask_halo");
     if (!s) return fail(LB_ERR_ARG, "null handle");
     DeviceGuard guard(s->p.device);
     uint8_t *tmp = (uint8_t *)calloc((size_t)s->pitch * MASK_GHOST, 1);
@@ -773,6 +820,103 @@ int lb_set_mask_halo(lb_sim *s, const int32_t *south_rows, const int32_t *north_
     return LB_OK;
 }
 
+// ---- scalar lattices -----------------------------------------------------------------------
+#define NEED_SCALAR(s, name)                                                                                 \
+    do {                                                                                                     \
+        if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
+        if (!(s)->scalar()) return fail(LB_ERR_STATE, "%s is for scalar lattices (LB_SEM_DIFFUSION)", name); \
+    } while (0)
+
+int lb_set_reaction(lb_sim *s, float G)
+{
+    NEED_SCALAR(s, "lb_set_reaction");
+    if (!(fabsf(G) <= 3.0e38f)) return fail(LB_ERR_ARG, "the growth rate must be finite");
+    s->ad_G = G;
+    return LB_OK;
+}
+
+int lb_edge_floats(lb_sim *s)
+{
+    NEED_SCALAR(s, "lb_edge_floats");
+    return (int)edge_host_floats(s);
+}
+
+int lb_get_edge_state(lb_sim *s, float *out)
+{
+    NEED_SCALAR(s, "lb_get_edge_state");
+    if (!s->ad_edge) return LB_OK;                  // (PERIODIC: zero floats)
+    if (!out) return fail(LB_ERR_ARG, "null argument");
+    DeviceGuard guard(s->p.device);
+    const int nx = s->p.nx, ny = s->p.ny;
+    const size_t n = (size_t)ad_edge_device_floats(s->pitch, ny);
+    float *tmp = (float *)malloc(n * sizeof(float));
+    if (!tmp) return fail(LB_ERR_ARG, "out of host memory");
+    hipError_t e = hipMemcpyAsync(tmp, s->ad_edge, n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (e != hipSuccess) {
+        free(tmp);
+        return fail(LB_ERR_HIP, "edge state download: %s", hipGetErrorString(e));
+    }
+    memcpy(out, tmp + 6 * s->pitch, sizeof(float) * 6 * (size_t)ny);
+    float *rows = out + 6 * (size_t)ny;
+    for (int r = 0; r < 6; ++r) memcpy(rows + (size_t)r * nx, tmp + (size_t)r * s->pitch, sizeof(float) * (size_t)nx);
+    // the four corner links a column and a row share: the column's entry is the one that counts
+    rows[1 * (size_t)nx] = out[1 * (size_t)ny];                                 // south f5(0,0) = west f5[0]
+    rows[2 * (size_t)nx + nx - 1] = out[4 * (size_t)ny];                        // south f6(nx-1,0) = east f6[0]
+    rows[4 * (size_t)nx + nx - 1] = out[5 * (size_t)ny + ny - 1];               // north f7(nx-1,ny-1) = east f7[ny-1]
+    rows[5 * (size_t)nx] = out[2 * (size_t)ny + ny - 1];                        // north f8(0,ny-1) = west f8[ny-1]
+    free(tmp);
+    return LB_OK;
+}
+
+int lb_set_edge_state(lb_sim *s, const float *in)
+{
+    NEED_SCALAR(s, "lb_set_edge_state");
+    if (!s->ad_edge) return LB_OK;
+    if (!in) return fail(LB_ERR_ARG, "null argument");
+    DeviceGuard guard(s->p.device);
+    const int nx = s->p.nx, ny = s->p.ny;
+    const size_t n = (size_t)ad_edge_device_floats(s->pitch, ny);
+    float *tmp = (float *)calloc(n, sizeof(float));
+    if (!tmp) return fail(LB_ERR_ARG, "out of host memory");
+    memcpy(tmp + 6 * s->pitch, in, sizeof(float) * 6 * (size_t)ny);
+    const float *rows = in + 6 * (size_t)ny;
+    for (int r = 0; r < 6; ++r) memcpy(tmp + (size_t)r * s->pitch, rows + (size_t)r * nx, sizeof(float) * (size_t)nx);
+    hipError_t e = hipStreamSynchronize(s->stream);       // (kernels of an un-waited run may still be reading it)
+    if (e == hipSuccess) e = hipMemcpy(s->ad_edge, tmp, n * sizeof(float), hipMemcpyHostToDevice);
+    free(tmp);
+    if (e != hipSuccess) return fail(LB_ERR_HIP, "edge state upload: %s", hipGetErrorString(e));
+    return LB_OK;
+}
+
+int lb_set_velocity_from(lb_sim *s, lb_sim *flow)
+{
+    NEED_SCALAR(s, "lb_set_velocity_from");
+    if (!flow) return fail(LB_ERR_ARG, "null flow handle");
+    if (flow->cpu || flow->scalar() || flow->multi_slab())
+        return fail(LB_ERR_ARG, "lb_set_velocity_from takes a whole-grid GPU flow handle");
+    if (flow->p.nx != s->p.nx || flow->p.ny != s->p.ny || flow->p.device != s->p.device)
+        return fail(LB_ERR_ARG, "the flow handle must have the scalar lattice's grid (%d x %d) and device", s->p.nx, s->p.ny);
+    if (flow->stepping) return fail(LB_ERR_STATE, "lb_set_velocity_from inside a split step of the flow handle");
+    DeviceGuard guard(s->p.device);
+    int rc = ensure_macro(flow);                    // the flow's lazily rebuilt rho, u, v
+    if (rc) return rc;
+    // on the FLOW handle's stream, behind its work; this handle's kernels may still read u, v, and its later ones must see the new
+    HIP_TRY(hipEventRecord(s->ev_interior, s->stream));
+    HIP_TRY(hipStreamWaitEvent(flow->stream, s->ev_interior, 0));
+    // (rho, u, v are [H][pitch] whatever the layout of the lattices: LB_FLAG_PLANAR on either handle does not matter here)
+    const long long n4 = s->pitch * s->H / 4;       // (same pitch: same nx)
+    for (int i = 0; i < 2; ++i) {
+        hipLaunchKernelGGL(k_copy4<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, flow->stream,
+                           reinterpret_cast<const f4a *>(i ? flow->v : flow->u), reinterpret_cast<f4a *>(i ? s->v : s->u), n4);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(flow->ev_interior, flow->stream));
+    HIP_TRY(hipStreamWaitEvent(s->stream, flow->ev_interior, 0));
+    s->feq_valid = false;
+    return LB_OK;
+}
+
 // ---- un-fused phases ---------------------------------------------------------------------
 
 int lb_move(lb_sim *s)
@@ -801,6 +945,7 @@ int lb_move(lb_sim *s)
     // VELOCITY_INLET: the eight corner links no phase ever writes are kept apart (fused launches swap the lattices,
     // so "whatever f_streamed held" would not survive them): put them where the boundary phase reads them
     if (s->p.bc_mode == LB_BC_VELOCITY_INLET) return corners_patch(s, s->cur);
+    if (s->scalar()) return edge_patch(s, s->cur);       // (the OPEN family's edge links, likewise)
     return LB_OK;
 }
 
@@ -810,6 +955,7 @@ int lb_move_bcs(lb_sim *s)
     if (!s) return fail(LB_ERR_ARG, "null handle");
     int rc = need_single_slab(s, "lb_move_bcs");
     if (rc) return rc;
+    if (s->scalar()) return LB_OK;                  // (diffusion.py:326-331: `pass`)
     DeviceGuard guard(s->p.device);
     if ((rc = ensure_macro(s))) return rc;
     if (s->p.semantics == LB_SEM_CYTHON)
@@ -831,7 +977,9 @@ int lb_update_hydro(lb_sim *s)
     int rc = need_single_slab(s, "lb_update_hydro");
     if (rc) return rc;
     DeviceGuard guard(s->p.device);
-    if (s->p.semantics == LB_SEM_CYTHON)
+    if (s->scalar())
+        lbk_ad_hydro(s->stream, step_args(s, 0, 1, s->H));       // rho only: u, v are imposed
+    else if (s->p.semantics == LB_SEM_CYTHON)
         hipLaunchKernelGGL(k1_hydro, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
     else if (s->p.bc_mode == LB_BC_VELOCITY_INLET)
         hipLaunchKernelGGL(k_hydro_vel, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
@@ -857,7 +1005,9 @@ int lb_update_feq(lb_sim *s)
     if ((rc = ensure_macro(s))) return rc;
     PhaseArgs a = phase_args(s);
     a.ny = s->H;   // rho,u,v are local: valid for slabs too
-    if (s->p.semantics == LB_SEM_OPENCL_D2Q9I)
+    if (s->scalar())
+        lbk_ad_feq(s->stream, step_args(s, 0, 1, s->H), s->feq_origin());
+    else if (s->p.semantics == LB_SEM_OPENCL_D2Q9I)
         hipLaunchKernelGGL(k_feq_i, dim3((s->p.nx + 255) / 256, s->H, 1), dim3(256), 0, s->stream, a);
     else
         hipLaunchKernelGGL(k_feq, dim3((s->p.nx + 255) / 256, s->H, 1), dim3(256), 0, s->stream, a);
@@ -875,7 +1025,10 @@ int lb_collide_particles(lb_sim *s)
     if (!s->feq) return fail(LB_ERR_STATE, "lb_collide_particles before any lb_update_feq");
     DeviceGuard guard(s->p.device);
     if ((rc = ensure_macro(s))) return rc;
-    hipLaunchKernelGGL(k_collide, cells_grid(s, 9), dim3(256), 0, s->stream, phase_args(s));
+    if (s->scalar())
+        lbk_ad_collide(s->ad_G != 0.f, s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur), s->feq_origin(), s->ad_G);
+    else
+        hipLaunchKernelGGL(k_collide, cells_grid(s, 9), dim3(256), 0, s->stream, phase_args(s));
     HIP_TRY(hipGetLastError());
     return LB_OK;
 }
@@ -887,6 +1040,7 @@ int lb_zero_velocity_in_obstacle(lb_sim *s)
             if (s->cpu->mask[c]) { s->cpu->u[c] = 0.; s->cpu->v[c] = 0.; }
         return LB_OK;
     }
+    SCALAR_UNSUPPORTED(s, "lb_zero_velocity_in_obstacle");
     if (!s) return fail(LB_ERR_ARG, "null handle");
     if (!s->has_mask) return LB_OK;
     DeviceGuard guard(s->p.device);
@@ -913,6 +1067,7 @@ int lb_init_pop(lb_sim *s)
     for (int i = 0; i < 2; ++i)
         if ((rc = copy_lattice(s, s->lat[i], s->feq))) return rc;
     s->ghost_depth = 0;
+    if ((rc = edge_capture(s, s->cur))) return rc;
     return corners_capture(s, s->cur);
 }
 
@@ -928,6 +1083,7 @@ int lb_run(lb_sim *s, int n_steps)
     if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
     if (s->stepping) return fail(LB_ERR_STATE, "lb_run between lb_step_boundary and lb_step_finish");
     DeviceGuard guard(s->p.device);
+    if (s->scalar()) return run_scalar(s, n_steps);
     if (!s->tune_cache_checked) (void)tune_cache_apply(s);
     if (s->p.semantics == LB_SEM_CYTHON) return run_cython(s, n_steps);
     if (!s->multi_slab()) return run_whole_grid(s, n_steps);     // (never blocks the host: tuning is lb_autotune*'s job)
@@ -939,6 +1095,7 @@ int lb_run(lb_sim *s, int n_steps)
 int lb_run_batch(lb_sim **sims, int count, int n_steps)
 {
     for (int i = 0; sims && i < count; ++i) CPU_UNSUPPORTED(sims[i], "lb_run_batch");
+    for (int i = 0; sims && i < count; ++i) SCALAR_UNSUPPORTED(sims[i], "lb_run_batch");
     if (!sims || count < 1 || count > BATCH_MAX || n_steps < 0)
         return fail(LB_ERR_ARG, "lb_run_batch takes 1..%d handles and a non-negative step count", BATCH_MAX);
     for (int i = 0; i < count; ++i) {
@@ -1012,6 +1169,24 @@ int lb_check(lb_sim *s, int across_ranks, int64_t *n_nonfinite, float *max_mach,
     if (s->stepping) return fail(LB_ERR_STATE, "lb_check inside a split step");
     if (across_ranks && !s->comm) return fail(LB_ERR_STATE, "lb_check across ranks needs lb_comm_init");
     DeviceGuard guard(s->p.device);
+    if (s->scalar()) {
+        // the populations' sum and the imposed field (kernels_scalar.h, k_ad_check)
+        const StepArgs a = step_args(s, 0, 1, s->H);
+        const long long blocks = ad_check_blocks(a);
+        if (!s->ad_part) {
+            HIP_TRY(hipMalloc(&s->ad_part, sizeof(AdCheck) * (size_t)(blocks + 1)));
+            s->bytes += (int64_t)sizeof(AdCheck) * (blocks + 1);
+        }
+        lbk_ad_check(s->stream, a, s->ad_part);
+        HIP_TRY(hipGetLastError());
+        AdCheck h;
+        HIP_TRY(hipMemcpyAsync(&h, s->ad_part + blocks, sizeof(h), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        if (n_nonfinite) *n_nonfinite = (int64_t)h.nonfinite;
+        if (max_mach) *max_mach = sqrtf(3.f * h.max_usq);
+        if (sum_rho) *sum_rho = h.sum_rho;
+        return LB_OK;
+    }
     // the pass that rebuilds rho, u, v reduces the same three numbers: one pass serves both when the fields are due
     int rc = macro_check_pass(s, !s->macro_valid && lazy_macro(s));
     if (rc) return rc;

@@ -470,8 +470,47 @@ bool tune_entry_runs_here(const PlanInputs *s, int steps, int wpc)
 }
 
 // ---- behind the ABI's lb_plan_launches, lb_steps_per_launch, lb_hot_kernel --------------------------------------------------------
+// Scalar lattices.  An explicit variant decides: its tile bit (VAR_TILES) = k_ad_tile4 for every group of four steps, on any box
+// (the kernel wraps or clips its regions itself); without the bit, k_ad_step.  Automatic (-1): by size, the rule below.
+// The size rule (profiles/scalar_bench.txt: k_ad_step and the three tile shapes timed in alternation on one handle, both families, G = 0 and
+// 0.01): the best tile shape ran 2.5-3.0 x k_ad_step's rate at 256^2 (launch-bound: 18-21 k MLUPS against 52-56 k), 2.1-2.3 x at 512^2,
+// 2.0-2.5 x at 1024^2, 2.1-2.4 x at 2048^2, 2.2-2.6 x at 4096^2 and 2.3-2.75 x at 8192^2 (70 k against 162-192 k) -- faster in every case of
+// every size measured, so the tiles are taken over exactly that range; smaller and larger boxes were not measured and stay on k_ad_step.
+// The shape by size as for k_tile4 (tile_shape_of) is the sweep's best one at 256^2 (16 x 16), 512^2 (32 x 16, one cell per thread) and
+// from 2048^2 (two per thread); at 1024^2 it is the periodic family's best and 5 % behind the other 32 x 16 shape in the OPEN family.
+static const double SCALAR_TILE_MIN_CELLS = 256.0 * 256.0, SCALAR_TILE_MAX_CELLS = 8192.0 * 8192.0;
+bool scalar_use_tiles(const PlanInputs *s)
+{
+    if (s->variant >= 0) return (s->variant & VAR_TILES) != 0;
+    const double cells = (double)s->p.nx * s->H;
+    return cells >= SCALAR_TILE_MIN_CELLS && cells <= SCALAR_TILE_MAX_CELLS;
+}
+
+// With an explicit variant the bits that pick k_step's rows per workgroup (VAR_ROWS: meaningless here) pick the tile shape:
+// 0 = by size as for k_tile4, 1 / 2 / 3 = shape 0 / 1 / 2 (32 x 16 two cells per thread, 32 x 16 one, 16 x 16 one).
+int scalar_tile_shape(const PlanInputs *s)
+{
+    if (s->variant >= 0 && (s->variant & VAR_ROWS)) return ((s->variant & VAR_ROWS) >> 2) - 1;
+    return tile_shape_of(s);
+}
+
+int scalar_next_advance(const PlanInputs *s, int left)
+{
+    if (left <= 0) return 0;
+    return (left >= TILE_T && scalar_use_tiles(s)) ? TILE_T : 1;
+}
+
 int plan_launches(const PlanInputs *s, int n_steps, int *depths, int max_launches)
 {
+    if (s->scalar()) {
+        int n = 0;
+        for (int left = n_steps; left > 0; ++n) {
+            const int adv = scalar_next_advance(s, left);
+            if (depths && n < max_launches) depths[n] = adv;
+            left -= adv;
+        }
+        return n;
+    }
     const int allowed = whole_grid_depths(s);
     int n = 0;
     for (int left = n_steps; left > 0; ++n) {
@@ -484,6 +523,7 @@ int plan_launches(const PlanInputs *s, int n_steps, int *depths, int max_launche
 
 int steps_per_launch(const PlanInputs *s)
 {
+    if (s->scalar()) return scalar_use_tiles(s) ? TILE_T : 1;
     if (s->p.semantics == LB_SEM_CYTHON) return cython_tiles(s) ? TILE_T : 1;
     const int h = s->agreed_h();
     if (s->multi_slab() && cycle_depth(s, h)) return cycle_depth(s, h);
@@ -497,6 +537,13 @@ int steps_per_launch(const PlanInputs *s)
 void hot_kernel(const PlanInputs *s, char *buf, int buflen)
 {
     static const char *const bc_names[] = {"PIPE", "PERIODIC", "CAVITY", "VELOCITY_INLET", "PIPE, D2Q9i"};
+    if (s->scalar()) {
+        snprintf(buf, (size_t)buflen, "%s<%s>",
+                 scalar_use_tiles(s) ? "k_ad_tile4 (scalar lattice: four steps per launch in LDS tiles)"
+                                     : "k_ad_step (scalar lattice: one fused pull-stream + linear-equilibrium collide pass)",
+                 s->p.bc_mode == LB_BC_PERIODIC ? "PERIODIC" : "OPEN");
+        return;
+    }
     const char *kernel = "k_step";
     if (s->p.semantics == LB_SEM_CYTHON)
         kernel = cython_tiles(s) ? "k1_tile4 (Cython path, LDS tiles)" : "k1_fstep (Cython path)";

@@ -27,6 +27,7 @@ struct PlanInputs {
     int slab_flavour = -1;      // slabs, seven-step cycle: 0 k_deep<7>, 1 k_deep2<7> (lb_set_slab_cycle(8)), -1 automatic (k_deep2 under RCCL)
     int transport = SLAB_NO_TRANSPORT;   // slabs: lb_comm_init / lb_peer_connect
 
+    bool scalar() const { return p.semantics == LB_SEM_DIFFUSION; }      // a scalar lattice (kernels_scalar.h)
     bool multi_slab() const { return H != p.ny || (p.flags & LB_FLAG_HALO); }
     int agreed_h() const { return min_h > 0 ? min_h : H; }      // the height all ranks decide on
 };
@@ -79,5 +80,11 @@ int band_extra(const PlanInputs *s, int D, bool split = false);
 int steps_per_launch(const PlanInputs *s);
 int plan_launches(const PlanInputs *s, int n_steps, int *depths, int max_launches);
 void hot_kernel(const PlanInputs *s, char *buf, int buflen);
+// scalar lattices: whether k_ad_tile4 takes the groups of four steps of a run (forced by the variant's tile bit, else by size),
+// which of its three shapes, and the time steps of the next launch of a run with `left` steps to go: n = 4a + r as a tile
+// launches, then r single steps (k_ad_step)
+bool scalar_use_tiles(const PlanInputs *s);
+int scalar_tile_shape(const PlanInputs *s);
+int scalar_next_advance(const PlanInputs *s, int left);
 
 #pragma GCC visibility pop

@@ -1,0 +1,80 @@
+// scalar_cell.h -- device-side arithmetic of one cell of a SCALAR lattice (LB_SEM_DIFFUSION): the reference's
+// LB_D2Q9/D2Q9_diffusion.cl -- update_hydro_diffusion :41-68 (rho = sum f; u, v imposed), update_feq_diffusion :1-38 (the linear
+// equilibrium feq_k = w_k rho (1 + c_k.u / cs^2)), collide_particles :70-93 and collide_particles_fisher :95-124 (+ w_k G rho (1 - rho)).
+// Written once for a scalar cell (T = float) and for a pair of x-adjacent cells (T = f2a), in the style of d2q9_cell.h: the same
+// operations in the same order with explicit fma, so a cell gets the same bits whichever form, and whichever kernel, computes it.
+//
+// 1 / cs^2: the reference divides c_k.u by cs*cs of the float32 cs = fl(1 / sqrt(3)); here it is the constant 3, once (ad_relax_t and
+// ad_feq_t below): no division in the cell.  A numpy model with the constant 3 followed the reference's C to 1.0e-7 after 1000 steps.
+#pragma once
+#include "d2q9_cell.h"
+
+namespace {
+
+template <typename T>
+__device__ __forceinline__ T ad_rho_t(T f0, T f1, T f2, T f3, T f4, T f5, T f6, T f7, T f8)
+{
+    return f0 + f1 + f2 + f3 + f4 + f5 + f6 + f7 + f8;        // D2Q9_diffusion.cl:66, left to right
+}
+
+// omega feq_k for the pair of links +-c: r (1 +- 3 cu) as fma(+-3r, cu, r), r = fl(w) (omega rho)
+template <typename T>
+__device__ __forceinline__ void ad_feq_pair(T r, T r3, T cu, T &fp, T &fm)
+{
+    fp = lb_fma(r3, cu, r);
+    fm = lb_fma(-r3, cu, r);
+}
+
+// Equilibrium and relaxation (and, REACT, the growth term) of one cell / one pair, in place.  omega enters once, through the
+// density, as in equilibrate_t: every equilibrium below comes out as omega feq_k, the float32 weights multiply a run-time value.
+template <typename T, bool REACT>
+__device__ __forceinline__ void ad_relax_t(T &f0, T &f1, T &f2, T &f3, T &f4, T &f5, T &f6, T &f7, T &f8, float omega, float G,
+                                           T rho, T ux, T uy)
+{
+    const T keep = lb_splat<T>(1.f - omega);
+    const T rw = lb_splat<T>(omega) * rho;
+    const T r0 = (4.f / 9.f) * rw, r1 = (1.f / 9.f) * rw, r2 = (1.f / 36.f) * rw;
+    const T r13 = 3.f * r1, r23 = 3.f * r2;
+    T e1, e2, e3, e4, e5, e6, e7, e8;
+    ad_feq_pair<T>(r1, r13, ux, e1, e3);
+    ad_feq_pair<T>(r1, r13, uy, e2, e4);
+    ad_feq_pair<T>(r2, r23, ux + uy, e5, e7);
+    ad_feq_pair<T>(r2, r23, ux - uy, e8, e6);
+    f0 = lb_fma(f0, keep, r0);
+    f1 = lb_fma(f1, keep, e1);
+    f3 = lb_fma(f3, keep, e3);
+    f2 = lb_fma(f2, keep, e2);
+    f4 = lb_fma(f4, keep, e4);
+    f5 = lb_fma(f5, keep, e5);
+    f7 = lb_fma(f7, keep, e7);
+    f8 = lb_fma(f8, keep, e8);
+    f6 = lb_fma(f6, keep, e6);
+    if (REACT) {
+        // fl(w_k) (G rho (1 - rho)), added last (D2Q9_diffusion.cl:112, 121)
+        const T react = (lb_splat<T>(G) * rho) * (lb_splat<T>(1.f) - rho);
+        const T w0 = lb_splat<T>(4.f / 9.f), w1 = lb_splat<T>(1.f / 9.f), w2 = lb_splat<T>(1.f / 36.f);
+        f0 = lb_fma(w0, react, f0);
+        f1 = lb_fma(w1, react, f1);
+        f3 = lb_fma(w1, react, f3);
+        f2 = lb_fma(w1, react, f2);
+        f4 = lb_fma(w1, react, f4);
+        f5 = lb_fma(w2, react, f5);
+        f7 = lb_fma(w2, react, f7);
+        f8 = lb_fma(w2, react, f8);
+        f6 = lb_fma(w2, react, f6);
+    }
+}
+
+// feq_k itself (the un-fused update_feq_diffusion): ad_relax_t's equilibrium with omega = 1
+__device__ __forceinline__ void ad_feq_cell(float (&e)[9], float rho, float ux, float uy)
+{
+    const float r0 = (4.f / 9.f) * rho, r1 = (1.f / 9.f) * rho, r2 = (1.f / 36.f) * rho;
+    const float r13 = 3.f * r1, r23 = 3.f * r2;
+    e[0] = r0;
+    ad_feq_pair<float>(r1, r13, ux, e[1], e[3]);
+    ad_feq_pair<float>(r1, r13, uy, e[2], e[4]);
+    ad_feq_pair<float>(r2, r23, ux + uy, e[5], e[7]);
+    ad_feq_pair<float>(r2, r23, ux - uy, e[8], e[6]);
+}
+
+}  // namespace

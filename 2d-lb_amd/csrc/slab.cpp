@@ -435,6 +435,7 @@ extern "C" {
 int lb_step_boundary(lb_sim *s, int write_macro)
 {
     CPU_UNSUPPORTED(s, "lb_step_boundary");
+    SCALAR_UNSUPPORTED(s, "lb_step_boundary");
     if (!s) return fail(LB_ERR_ARG, "null handle");
     if (s->stepping) return fail(LB_ERR_STATE, "lb_step_boundary called twice");
     if (s->p.bc_mode == LB_BC_VELOCITY_INLET || s->p.semantics == LB_SEM_CYTHON)
@@ -450,6 +451,7 @@ int lb_step_boundary(lb_sim *s, int write_macro)
 int lb_step_interior(lb_sim *s, int write_macro)
 {
     CPU_UNSUPPORTED(s, "lb_step_interior");
+    SCALAR_UNSUPPORTED(s, "lb_step_interior");
     if (!s) return fail(LB_ERR_ARG, "null handle");
     if (!s->stepping) return fail(LB_ERR_STATE, "lb_step_interior before lb_step_boundary");
     DeviceGuard guard(s->p.device);
@@ -459,6 +461,7 @@ int lb_step_interior(lb_sim *s, int write_macro)
 int lb_step_finish(lb_sim *s)
 {
     CPU_UNSUPPORTED(s, "lb_step_finish");
+    SCALAR_UNSUPPORTED(s, "lb_step_finish");
     if (!s) return fail(LB_ERR_ARG, "null handle");
     if (!s->stepping) return fail(LB_ERR_STATE, "lb_step_finish before lb_step_boundary");
     s->cur ^= 1;
@@ -472,6 +475,7 @@ int lb_step_finish(lb_sim *s)
 int lb_halo_export(lb_sim *s, int side, void *buf)
 {
     CPU_UNSUPPORTED(s, "lb_halo_export");
+    SCALAR_UNSUPPORTED(s, "lb_halo_export");
     if (!s || !buf || side < 0 || side > 1) return fail(LB_ERR_ARG, "bad argument");
     DeviceGuard guard(s->p.device);
     const int which = s->stepping ? (s->cur ^ 1) : s->cur;
@@ -485,6 +489,7 @@ int lb_halo_export(lb_sim *s, int side, void *buf)
 int lb_halo_import(lb_sim *s, int side, const void *buf)
 {
     CPU_UNSUPPORTED(s, "lb_halo_import");
+    SCALAR_UNSUPPORTED(s, "lb_halo_import");
     if (!s || !buf || side < 0 || side > 1) return fail(LB_ERR_ARG, "bad argument");
     DeviceGuard guard(s->p.device);
     const int which = s->stepping ? (s->cur ^ 1) : s->cur;
@@ -498,6 +503,7 @@ int lb_halo_import(lb_sim *s, int side, const void *buf)
 int lb_halo_floats(lb_sim *s)
 {
     CPU_UNSUPPORTED(s, "lb_halo_floats");
+    SCALAR_UNSUPPORTED(s, "lb_halo_floats");
     if (!s) return fail(LB_ERR_ARG, "null handle");
     return HALO_SEGS * s->p.nx;
 }
@@ -533,6 +539,7 @@ int lb_set_debug_sync(int bits)
 int lb_run_group(lb_sim **sims, int count, int n_steps)
 {
     for (int i = 0; sims && i < count; ++i) CPU_UNSUPPORTED(sims[i], "lb_run_group");
+    for (int i = 0; sims && i < count; ++i) SCALAR_UNSUPPORTED(sims[i], "lb_run_group");
     if (!sims || count < 1 || n_steps < 0) return fail(LB_ERR_ARG, "bad argument");
     for (int i = 0; i < count; ++i) {
         if (!sims[i]) return fail(LB_ERR_ARG, "null handle in group");

@@ -55,6 +55,7 @@ int lb_comm_unique_id(void *unique_id_128)
 int lb_comm_init(lb_sim *s, const void *unique_id_128, int rank, int nranks)
 {
     CPU_UNSUPPORTED(s, "lb_comm_init");
+    SCALAR_UNSUPPORTED(s, "lb_comm_init");
     if (!s || !unique_id_128 || nranks < 1 || rank < 0 || rank >= nranks) return fail(LB_ERR_ARG, "bad argument");
     int rc = rccl_load();
     if (rc) return rc;
@@ -105,6 +106,7 @@ constexpr uint32_t PEER_MAGIC = 0x4c425052u;    // "LBPR"
 int lb_peer_export(lb_sim *s, void *handle_out)
 {
     CPU_UNSUPPORTED(s, "lb_peer_export");
+    SCALAR_UNSUPPORTED(s, "lb_peer_export");
     if (!s || !handle_out) return fail(LB_ERR_ARG, "null argument");
     if (!s->multi_slab()) return fail(LB_ERR_STATE, "lb_peer_export needs a slab handle (LB_FLAG_HALO)");
     DeviceGuard guard(s->p.device);
@@ -153,6 +155,7 @@ int lb_peer_export(lb_sim *s, void *handle_out)
 int lb_peer_connect(lb_sim *s, int rank, int nranks, const void *south_handle, const void *north_handle, int min_h)
 {
     CPU_UNSUPPORTED(s, "lb_peer_connect");
+    SCALAR_UNSUPPORTED(s, "lb_peer_connect");
     if (!s || nranks < 1 || rank < 0 || rank >= nranks || min_h < 1) return fail(LB_ERR_ARG, "bad argument");
     if (!s->peer_flags) return fail(LB_ERR_STATE, "lb_peer_connect before lb_peer_export");
     if (s->peer_connected() || s->comm) return fail(LB_ERR_STATE, "this handle already has a halo transport");

@@ -253,6 +253,7 @@ extern "C" {
 int lb_autotune(lb_sim *s)
 {
     if (s && s->cpu) return 0;                     // (one code path on the host: nothing to choose between)
+    SCALAR_UNSUPPORTED(s, "lb_autotune");
     if (!s) return fail(LB_ERR_ARG, "null handle");
     if (s->stepping) return fail(LB_ERR_STATE, "lb_autotune inside a split step");
     if (!autotune_applies(s)) return 0;                // nothing to choose between
@@ -269,6 +270,7 @@ int lb_autotune(lb_sim *s)
 int lb_autotune_quick(lb_sim *s, int max_steps)
 {
     if (s && s->cpu) return 0;
+    SCALAR_UNSUPPORTED(s, "lb_autotune_quick");
     if (!s) return fail(LB_ERR_ARG, "null handle");
     if (s->stepping) return fail(LB_ERR_STATE, "lb_autotune_quick inside a split step");
     if (!s->tune_cache_checked && tune_cache_apply(s)) return 0;       // (LB_TUNE_CACHE: an earlier handle of this shape was tuned)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define LB_ABI_VERSION 10
+#define LB_ABI_VERSION 11
 
 typedef enum {
     LB_OK = 0,
@@ -49,12 +49,15 @@ typedef enum {
     LB_BC_PIPE = 0,       /* pressure inlet x=0 / outlet x=nx-1, no-slip y=0,ny-1 */
     LB_BC_PERIODIC = 1,   /* periodic in x and y                               */
     LB_BC_CAVITY = 2,     /* four no-slip walls, north wall moving with lid_u  */
-    LB_BC_VELOCITY_INLET = 3  /* D2Q9.cl:263-374: imposed speed inlet_u at x=0 / outlet_u at x=nx-1, north and
+    LB_BC_VELOCITY_INLET = 3, /* D2Q9.cl:263-374: imposed speed inlet_u at x=0 / outlet_u at x=nx-1, north and
                              south rows copy their missing links from the opposite wall row.  Dead code in
                              the reference's `dimensionless` package (only OLD/opencl.py:281-327 launches
                              it).  Whole-grid handles; lb_run fuses it (up to four time steps per launch; from
                              three on the wall-row bands are advanced as a small lattice of their own), the phase
                              entry points run it un-fused. */
+    LB_BC_OPEN = 4        /* scalar lattices (LB_SEM_DIFFUSION) only: the box of the reference's Diffusion classes, whose move_bcs
+                             is `pass` (reaction_diffusion/diffusion.py): a link that would enter from outside the box keeps the
+                             value it had when the populations were last set -- the handle's edge state (lb_get_edge_state). */
 } lb_bc_mode;
 
 /* Which of the reference's two (numerically different) paths the handle reproduces.
@@ -67,11 +70,25 @@ typedef enum {
 typedef enum {
     LB_SEM_OPENCL = 0,
     LB_SEM_CYTHON = 1,
-    LB_SEM_OPENCL_D2Q9I = 2   /* LB_D2Q9/D2Q9i.cl driven as dimensionless/opencl_dim_D2Q9i.py does: the "incompressible"
+    LB_SEM_OPENCL_D2Q9I = 2,  /* LB_D2Q9/D2Q9i.cl driven as dimensionless/opencl_dim_D2Q9i.py does: the "incompressible"
                                  fork of the OpenCL path -- momentum in place of velocity (D2Q9i.cl:90-94), inner =
                                  rho + 3 cu + 4.5 cu^2 - 1.5 usq (:58), re-derived inlet / outlet (:194-205), u, v
                                  re-zeroed in the obstacle every step.  PIPE family, whole-grid handles; fused like the
                                  OpenCL path.  Restated as the fork has it: it is unstable (tests/golden/o2_d2q9i_53x27). */
+    LB_SEM_DIFFUSION = 3      /* a SCALAR lattice: LB_D2Q9/D2Q9_diffusion.cl driven as reaction_diffusion/diffusion.py does -- a
+                                 concentration rho carried by D2Q9 populations with the linear equilibrium feq_k = w_k rho (1 + 3 c_k.u),
+                                 an IMPOSED velocity field u, v (lb_set_macro, lb_set_velocity_from; no kernel writes it) and an optional
+                                 Fisher growth term w_k G rho (1 - rho) (lb_set_reaction).  Families LB_BC_PERIODIC (build-defined)
+                                 and LB_BC_OPEN (the reference's box); whole-grid GPU handles.  lb_run fuses the reference's five
+                                 launches per step into one (k_ad_step: 72 B of populations + 8 B of u, v per cell and step) or,
+                                 bitwise equal, four steps into one launch through LDS tiles (k_ad_tile4): n = 4a + r steps run
+                                 as a tile launches, then r single steps.  lb_set_variant: 0 = k_ad_step only; bit 9 = the
+                                 tiles, on any box, with bits 2-3 = 0 the tile shape by size, 1 / 2 / 3 = 32 x 16 cells two per
+                                 thread / 32 x 16 one / 16 x 16; -1 (default) = the tiles on boxes of 256^2 ... 8192^2 cells,
+                                 where they measured 2.0-3.0 x k_ad_step's rate (8192^2: 162-192 k against 69-71 k MLUPS, the
+                                 latter 0.89-0.91 of the copy rate on the same handle: profiles/scalar_bench.txt).  A run
+                                 always stores rho in its last launch -- with G != 0 rho is not a moment of what a run leaves
+                                 behind.  omega, nx, ny are the only other lb_params fields it reads. */
 } lb_semantics;
 
 typedef struct {
@@ -159,6 +176,26 @@ int lb_set_mask(lb_sim *s, const int32_t *mask); /* [H][nx], 1 = solid (opencl_d
  * needs them next to f (lb_set_f resets them). */
 int lb_get_corner_state(lb_sim *s, float *out8);
 int lb_set_corner_state(lb_sim *s, const float *in8);
+
+/* ---- scalar lattices (LB_SEM_DIFFUSION; LB_ERR_STATE on every other handle) ------------------------------------------
+ * lb_set_reaction: G of collide_particles_fisher (D2Q9_diffusion.cl:95-124), in lattice units; 0 (the default) = plain
+ * collide_particles.
+ * Edge state (LB_BC_OPEN; zero floats in the PERIODIC family): the links that enter a cell from outside the box.  The
+ * reference's push `move` never writes them and copy_buffer restores them from f_streamed, so they hold, whenever a step
+ * reads them, the values they had at the last lb_set_f / lb_init_pop -- which capture them; a checkpoint needs them beside f.
+ * lb_edge_floats() = 6 (nx + ny) floats, in this order:
+ *   west column x = 0:     f1[ny], f5[ny], f8[ny]      east column x = nx-1:  f3[ny], f6[ny], f7[ny]
+ *   south row y = 0:       f2[nx], f5[nx], f6[nx]      north row y = ny-1:    f4[nx], f7[nx], f8[nx]
+ * Four corner links appear twice (f5(0,0), f8(0,ny-1), f6(nx-1,0), f7(nx-1,ny-1)): the column's entry is the one the
+ * kernels read, lb_get_edge_state returns the same value in both places.
+ * lb_set_velocity_from: u, v of `flow` (any GPU flow handle of the same nx x ny that owns its whole grid, on the same
+ * device) become the scalar handle's imposed velocity, device to device, after the flow handle's lazily rebuilt fields
+ * were brought up to date; ordered behind the flow handle's enqueued work, never waits on the host. */
+int lb_set_reaction(lb_sim *s, float G);
+int lb_edge_floats(lb_sim *s);
+int lb_get_edge_state(lb_sim *s, float *out);
+int lb_set_edge_state(lb_sim *s, const float *in);
+int lb_set_velocity_from(lb_sim *s, lb_sim *flow);
 
 /* ---- the reference's per-phase methods, one kernel each (slow, un-fused;
  *      API and test parity).  Single-slab handles only. ------------------- */
