@@ -20,36 +20,14 @@ Differences a caller can see: ``self.f``, ``self.rho`` ... are ``DeviceField`` o
 """
 import numpy as np
 
-from ..masks import disc_pixels
+from .._dropin import NUM_JUMPERS, DeviceField, PipeDropIn, cs, cs2, cs22, cssq, lattice_arrays, w0, w1, w2  # noqa: F401
 from ..simulation import Simulation
 
 # ---- D2Q9 constants (names/values of cython_dim.pyx:16-29) -----------------------------------------
-NUM_JUMPERS = 9
-w = np.array([4. / 9.] + 4 * [1. / 9.] + 4 * [1. / 36.])
-cx = np.array([0, 1, 0, -1, 0, 1, -1, -1, 1])
-cy = np.array([0, 0, 1, 0, -1, 1, 1, -1, -1])
-cs = 1 / np.sqrt(3)
-cs2 = cs ** 2
-cs22 = 2 * cs2
-cssq = 2.0 / 9.0
-w0, w1, w2 = 4. / 9., 1. / 9., 1. / 36.
+w, cx, cy = lattice_arrays()
 
 
-class DeviceField(object):
-    """Read access to engine state under the reference's attribute names."""
-
-    def __init__(self, owner, key):
-        self._owner, self._key = owner, key
-
-    def get(self):
-        return self._owner.get_fields()[self._key]
-
-    def __array__(self, dtype=None, copy=None):
-        a = self.get()
-        return a if dtype is None else a.astype(dtype)
-
-
-class Pipe_Flow(object):
+class Pipe_Flow(PipeDropIn):
     """Pressure-driven pipe flow, CPU-class semantics, on the GPU."""
 
     def __init__(self, diameter=None, rho=None, viscosity=None, pressure_grad=1., pipe_length=None,
@@ -89,10 +67,6 @@ class Pipe_Flow(object):
         self.update_feq()
         self.init_pop()
 
-    def _say(self, *args):
-        if self.verbose:
-            print(*args)
-
     def _boundary_densities(self):
         """delta rho = nx (dt^2/dx)/cs^2 (T^2/(rho L)) gradP (cython_dim.pyx:138-144)."""
         nondim_deltaP = (self.T ** 2 / (self.phys_rho * self.L)) * self.phys_pressure_grad
@@ -102,34 +76,23 @@ class Pipe_Flow(object):
     def _obstacle(self):
         return None
 
+    def _read_field(self, key):
+        return self.get_fields()[key]
+
     # ---- hooks with the reference's names ---------------------------------------------------------
     def set_characteristic_length_time(self):
         """L = diameter, T = 8 rho nu / (|gradP| L) (cython_dim.pyx:107-115)."""
         self.L = self.phys_diameter
         self.T = (8 * self.phys_rho * self.phys_visc) / (np.abs(self.phys_pressure_grad) * self.L)
 
-    def initialize_grid_dims(self):
-        self.lx = int(np.ceil((self.phys_pipe_length / self.L) * self.N))
-        self.ly = self.N
-        self.nx, self.ny = self.lx + 1, self.ly + 1
-
     def init_hydro(self):
         """Density ramp, fluid at rest, velocity zero in the obstacle (cython_dim.pyx:129-157, 451-457)."""
-        self.inlet_rho, self.outlet_rho = self._boundary_densities()
-        self._say('inlet rho:', self.inlet_rho)
-        self._say('outlet rho:', self.outlet_rho)
+        rho_host, zero = self._density_ramp('C')
         if self._sim is None:
             self._sim = Simulation(self.nx, self.ny, self.omega, bc='pipe', inlet_rho=self.inlet_rho,
                                    outlet_rho=self.outlet_rho, device=self.device, semantics='cython')
         self._sim.set_obstacle_mask(self._obstacle())
-        i = np.arange(self.nx, dtype=np.float64)[:, None]
-        ramp = self.inlet_rho - i * (self.inlet_rho - self.outlet_rho) / float(self.nx)
-        rho_host = np.broadcast_to(ramp, (self.nx, self.ny)).astype(np.float32)
-        zero = np.zeros((self.nx, self.ny), np.float32)
         self._sim.set_fields(rho_host, zero, zero)
-
-    def update_feq(self):
-        self._sim.update_feq()
 
     def init_pop(self, amplitude=.001):
         """f = feq (1 + amplitude N(0,1)), one draw per CELL shared by the nine links (cython_dim.pyx:191-202)."""
@@ -137,25 +100,6 @@ class Pipe_Flow(object):
         if amplitude:
             perturb = (1. + amplitude * np.random.randn(self.nx, self.ny))[:, :, None]
         self._sim.init_pop(perturb)
-
-    def move_bcs(self):
-        self._sim.move_bcs()
-
-    def move(self):
-        self._sim.move()
-
-    def update_hydro(self):
-        self._sim.update_hydro()
-
-    def collide_particles(self):
-        self._sim.collide_particles()
-
-    def run(self, num_iterations):
-        """move_bcs, move, update_hydro, update_feq, collide_particles per iteration (cython_dim.pyx:346-359)."""
-        self._sim.run(num_iterations)
-
-    def step(self):
-        self._sim.run(1)
 
     # ---- state in / out ----------------------------------------------------------------------------
     def set_f(self, f):
@@ -174,18 +118,6 @@ class Pipe_Flow(object):
                 'rho': np.ascontiguousarray(g['rho']),
                 'u': np.ascontiguousarray(g['u'], dtype=np.float64),
                 'v': np.ascontiguousarray(g['v'], dtype=np.float64)}
-
-    def get_nondim_fields(self):
-        fields = self.get_fields()
-        fields['u'] *= self.delta_x / self.delta_t
-        fields['v'] *= self.delta_x / self.delta_t
-        return fields
-
-    def get_physical_fields(self):
-        fields = self.get_nondim_fields()
-        fields['u'] *= (self.L / self.T)
-        fields['v'] *= (self.L / self.T)
-        return fields
 
 
 class Pipe_Flow_Cylinder(Pipe_Flow):
@@ -206,13 +138,7 @@ class Pipe_Flow_Cylinder(Pipe_Flow):
         self.T = (8 * self.phys_rho * self.phys_visc * self.L) / (np.abs(self.phys_pressure_grad) * self.phys_diameter ** 2)
 
     def initialize_grid_dims(self):
-        self.lx = int(np.ceil((self.phys_pipe_length / self.L) * self.N))
-        self.ly = int(np.ceil((self.phys_diameter / self.L) * self.N))
-        self.nx, self.ny = self.lx + 1, self.ly + 1
-        self.obstacle_mask = np.zeros((self.nx, self.ny), dtype=bool, order='F')
-        xs, ys = disc_pixels(self.N * self.phys_cylinder_center[0] / self.L,
-                             self.N * self.phys_cylinder_center[1] / self.L, self.N, (self.nx, self.ny))
-        self.obstacle_mask[xs, ys] = True
+        self.obstacle_mask = self._cylinder_grid_dims(bool)
 
     def _obstacle(self):
         return self.obstacle_mask

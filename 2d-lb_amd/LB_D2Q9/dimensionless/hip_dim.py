@@ -18,39 +18,15 @@ Differences a caller can see:
 import numpy as np
 
 from .. import _native
-from ..masks import disc_pixels
+from .._dropin import (NUM_JUMPERS, DeviceField, PipeDropIn, cs, cs2, cs22, cssq, get_divisible_global,  # noqa: F401
+                       lattice_arrays, two_cs4, w0, w1, w2)
 from ..simulation import Simulation
 
 # ---- D2Q9 lattice constants (same names/values as opencl_dim.py:22-36) ----------------------
-NUM_JUMPERS = 9
-w = np.array([4. / 9.] + 4 * [1. / 9.] + 4 * [1. / 36.], order='F', dtype=np.float32)
-cx = np.array([0, 1, 0, -1, 0, 1, -1, -1, 1], order='F', dtype=np.int32)
-cy = np.array([0, 0, 1, 0, -1, 1, 1, -1, -1], order='F', dtype=np.int32)
-cs = 1. / np.sqrt(3)
-cs2 = cs ** 2
-cs22 = 2 * cs2
-cssq = 2.0 / 9.0
-two_cs4 = 2 * cs ** 4
-w0, w1, w2 = 4. / 9., 1. / 9., 1. / 36.
+w, cx, cy = lattice_arrays(np.float32, np.int32)
 
 
-def get_divisible_global(global_size, local_size):
-    """Smallest multiple of local_size that covers global_size, per dimension
-    (kept for callers that print or reuse it; opencl_dim.py:39-56)."""
-    return tuple(-(-g // l) * l for g, l in zip(global_size, local_size))
-
-
-class DeviceField(object):
-    """Stand-in for the reference's ``cl.Buffer`` attributes: a named view of engine state."""
-
-    def __init__(self, owner, key):
-        self._owner, self._key = owner, key
-
-    def get(self):
-        return self._owner._sim.get_fields((self._key,))[self._key]
-
-
-class Pipe_Flow(object):
+class Pipe_Flow(PipeDropIn):
     """Pressure-driven flow between two plates on the D2Q9 lattice (the reference's verification case)."""
 
     def __init__(self, diameter=None, rho=None, viscosity=None, pressure_grad=None, pipe_length=None,
@@ -120,10 +96,6 @@ class Pipe_Flow(object):
         self._say('omega', self.omega)
         assert self.omega < 2.
 
-    def _say(self, *args):
-        if self.verbose:
-            print(*args)
-
     def _boundary_densities(self):
         """rho_out = 1, rho_in = 1 + |nx (dt^2/dx) / cs^2| (opencl_dim.py:266-273)."""
         delta_rho = self.nx * (self.delta_t ** 2 / self.delta_x) * (1. / cs2) * 1.
@@ -134,12 +106,6 @@ class Pipe_Flow(object):
         """L = pipe diameter, T = sqrt(L / (|grad P| / rho)) (opencl_dim.py:180-189)."""
         self.L = self.phys_diameter
         self.T = np.sqrt(self.phys_diameter / (np.abs(self.phys_pressure_grad) / self.phys_rho))
-
-    def initialize_grid_dims(self):
-        """lx = ceil(pipe_length / L * N), ly = N; one boundary node more in each direction (:191-201)."""
-        self.lx = int(np.ceil((self.phys_pipe_length / self.L) * self.N))
-        self.ly = self.N
-        self.nx, self.ny = self.lx + 1, self.ly + 1
 
     # The reference-named classes keep the reference's observable fields: rho, u, v are what update_hydro stored in the last
     # step (the moments of the PRE-collision populations, opencl_dim.py:384-385), written by the last launch of every run().
@@ -166,43 +132,14 @@ class Pipe_Flow(object):
 
     def init_hydro(self):
         """Linear density ramp from inlet to outlet, fluid at rest (:258-293)."""
-        self.inlet_rho, self.outlet_rho = self._boundary_densities()
-        self._say('inlet rho:', self.inlet_rho)
-        self._say('outlet rho:', self.outlet_rho)
-        i = np.arange(self.nx, dtype=np.float64)[:, None]
-        ramp = self.inlet_rho - i * (self.inlet_rho - self.outlet_rho) / float(self.nx)
-        rho_host = np.asfortranarray(np.broadcast_to(ramp, (self.nx, self.ny)).astype(np.float32))
-        zero = np.zeros((self.nx, self.ny), np.float32, order='F')
+        rho_host, zero = self._density_ramp('F')
         self._sim.set_fields(rho_host, zero, zero)
-
-    def update_feq(self):
-        self._sim.update_feq()
 
     def init_pop(self, amplitude=.001):
         """f = f_streamed = feq (1 + amplitude N(0,1)) per population, drawn from numpy's global RNG
         like the reference (:308-327); amplitude=0 gives the unperturbed equilibrium."""
         perturb = (1. + amplitude * np.random.randn(self.nx, self.ny, NUM_JUMPERS)) if amplitude else None
         self._sim.init_pop(perturb)
-
-    def move_bcs(self):
-        self._sim.move_bcs()
-
-    def move(self):
-        self._sim.move()
-
-    def update_hydro(self):
-        self._sim.update_hydro()
-
-    def collide_particles(self):
-        self._sim.collide_particles()
-
-    def run(self, num_iterations):
-        """num_iterations time steps: move, move_bcs, update_hydro, update_feq, collide_particles
-        (:372-387), fused into one HIP launch per step."""
-        self._sim.run(num_iterations)
-
-    def step(self):
-        self._sim.run(1)
 
     def check(self, **kw):
         """Device-side health check (Simulation.check): non-finite cells, max Mach number, total mass."""
@@ -214,22 +151,6 @@ class Pipe_Flow(object):
 
     def load_checkpoint(self, path):
         self._sim.load_checkpoint(path)
-
-    # ---- read-back (:390-438) -------------------------------------------------------------------
-    def get_fields(self):
-        return self._sim.get_fields()
-
-    def get_nondim_fields(self):
-        fields = self.get_fields()
-        fields['u'] *= self.delta_x / self.delta_t
-        fields['v'] *= self.delta_x / self.delta_t
-        return fields
-
-    def get_physical_fields(self):
-        fields = self.get_nondim_fields()
-        fields['u'] *= (self.L / self.T)
-        fields['v'] *= (self.L / self.T)
-        return fields
 
 
 class Pipe_Flow_Cylinder(Pipe_Flow):
@@ -252,13 +173,7 @@ class Pipe_Flow_Cylinder(Pipe_Flow):
 
     def initialize_grid_dims(self):
         """Grid from pipe length and diameter in units of the radius; disc of N cells radius (:458-475)."""
-        self.lx = int(np.ceil((self.phys_pipe_length / self.L) * self.N))
-        self.ly = int(np.ceil((self.phys_diameter / self.L) * self.N))
-        self.nx, self.ny = self.lx + 1, self.ly + 1
-        self.obstacle_mask_host = np.zeros((self.nx, self.ny), dtype=np.int32, order='F')
-        xs, ys = disc_pixels(self.N * self.phys_cylinder_center[0] / self.L,
-                             self.N * self.phys_cylinder_center[1] / self.L, self.N, (self.nx, self.ny))
-        self.obstacle_mask_host[xs, ys] = 1
+        self.obstacle_mask_host = self._cylinder_grid_dims(np.int32)
 
     def init_hydro(self):
         """As the base class, then upload the mask and zero u, v inside it (:495-508)."""

@@ -15,19 +15,10 @@ offered: it launches a kernel the reference's .cl file does not contain.
 """
 import numpy as np
 
+from .._dropin import NUM_JUMPERS, DeviceField, DropIn, cs, get_divisible_global, lattice_arrays  # noqa: F401
 from ..simulation import Simulation
 
-NUM_JUMPERS = 9
-w = np.array([4. / 9.] + [1. / 9.] * 4 + [1. / 36.] * 4, order='F', dtype=np.float32)
-cx = np.array([0, 1, 0, -1, 0, 1, -1, -1, 1], order='F', dtype=np.int32)
-cy = np.array([0, 0, 1, 0, -1, 1, 1, -1, -1], order='F', dtype=np.int32)
-cs = 1. / np.sqrt(3)
-
-
-def get_divisible_global(global_size, local_size):
-    """Smallest global size >= global_size that local_size divides, per dimension (kept for the attributes the
-    reference's classes show; the HIP launches do not use it)."""
-    return tuple(g if g % l == 0 else g + l - g % l for g, l in zip(global_size, local_size))
+w, cx, cy = lattice_arrays(np.float32, np.int32)
 
 
 # ---- parameter arithmetic: no handle, no GPU -----------------------------------------------------------------------
@@ -100,20 +91,11 @@ def gaussian_blob(nx, ny, N):
     return x_center, y_center, X_dim, Y_dim, rho
 
 
-class _Field(object):
-    """What the reference's ``sim.rho`` / ``sim.u`` buffers are used for outside the classes: ``.get()`` a host copy."""
-
-    def __init__(self, sim, name):
-        self._sim, self._name = sim, name
-
-    def get(self):
-        return self._sim.get_fields((self._name,))[self._name]
-
-
-class Diffusion(object):
+class Diffusion(DropIn):
     """A Gaussian blob of concentration diffusing in a box (the reference's verification case)."""
 
     _bc = "open"       # the reference's box: move_bcs does nothing
+    _sim = property(lambda self: self.sim)      # the engine under the name the shared methods use
 
     def __init__(self, Lx=1.0, Ly=1.0, D=1.0, z=0.1, time_prefactor=1., N=50,
                  two_d_local_size=(32, 32), three_d_local_size=(32, 32, 1), use_interop=False, device=0):
@@ -145,8 +127,8 @@ class Diffusion(object):
 
         self.sim = Simulation(self.nx, self.ny, self.omega, bc=self._bc, semantics="diffusion", device=device)
         self.sim.set_reaction(getattr(self, "G", None) or 0.)
-        self.rho, self.u, self.v = _Field(self.sim, "rho"), _Field(self.sim, "u"), _Field(self.sim, "v")
-        self.f, self.feq = _Field(self.sim, "f"), _Field(self.sim, "feq")
+        self.rho, self.u, self.v = DeviceField(self, "rho"), DeviceField(self, "u"), DeviceField(self, "v")
+        self.f, self.feq = DeviceField(self, "f"), DeviceField(self, "feq")
 
         self.x_center = self.y_center = self.X_dim = self.Y_dim = None
         self.init_hydro()
@@ -177,45 +159,9 @@ class Diffusion(object):
         u, v = self._imposed_velocity()
         self.sim.set_fields(rho, u, v)
 
-    def update_feq(self):
-        self.sim.update_feq()
-
     def init_pop(self, perturb=None):
         """f = f_streamed = feq * perturb; None = exactly feq.  (The reference multiplies by 1 + 0.001 randn, unseeded.)"""
         self.sim.init_pop(perturb)
-
-    def move_bcs(self):
-        self.sim.move_bcs()         # nothing, as in the reference
-
-    def move(self):
-        self.sim.move()
-
-    def update_hydro(self):
-        self.sim.update_hydro()
-
-    def collide_particles(self):
-        self.sim.collide_particles()
-
-    def run(self, num_iterations):
-        self.sim.run(num_iterations)
-
-    def step(self):
-        self.sim.run(1)
-
-    def get_fields(self):
-        return self.sim.get_fields()
-
-    def get_nondim_fields(self):
-        fields = self.get_fields()
-        fields['u'] *= self.delta_x / self.delta_t
-        fields['v'] *= self.delta_x / self.delta_t
-        return fields
-
-    def get_physical_fields(self):
-        fields = self.get_nondim_fields()
-        fields['u'] *= (self.L / self.T)
-        fields['v'] *= (self.L / self.T)
-        return fields
 
 
 class Advection_Diffusion(Diffusion):

@@ -7,7 +7,8 @@
 //   tune.cpp       lb_autotune* and what they found, remembered (LB_TUNE_CACHE)
 //   lb_hip.cpp     create / destroy / setters, state transfer, the un-fused phases, lb_run, lb_run_batch, lb_check, timers
 // Small kernels are emitted by the one unit that includes their header: kernels_phases.h + kernels_check.h by lb_hip.cpp,
-// kernels_halo.h by slab.cpp.
+// kernels_halo.h by slab.cpp, kernels_scalar.h by scalar.cpp (its health check's first pass only: check_reduce.h is shared, the folding
+// pass is lb_hip.cpp's).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -22,7 +23,7 @@
 #include "cpu_backend.h"
 #include "plan.h"
 #include "launchers.h"          // StepArgs; the fused kernels are instantiated in their own translation units
-#include "scalar_launch.h"      // scalar lattices (LB_SEM_DIFFUSION): AdExtra, AdCheck, their launchers
+#include "scalar_launch.h"      // scalar lattices (LB_SEM_DIFFUSION): AdExtra, CheckPartial, their launchers
 
 namespace {
 
@@ -42,13 +43,12 @@ struct lb_sim : PlanInputs {
     float *stage = nullptr;     // [H][pitch], lazily: one plane on its way between the host and interleaved rows (lattice_plane_*)
     float *ad_edge = nullptr;   // scalar lattice, OPEN family: the edge state on the device (scalar_launch.h)
     float ad_G = 0.f;           // scalar lattice: growth rate of the Fisher term (lb_set_reaction); 0 = plain relaxation
-    AdCheck *ad_part = nullptr; // scalar lattice: lb_check's records, allocated on first use
     float *vi_corner = nullptr; // VELOCITY_INLET: the eight corner links nothing ever writes (bc_vel_cell), device
     uint8_t *mask_raw = nullptr, *mask = nullptr;   // [H+2*MASK_GHOST][pitch] + guards; mask -> row 0
     bool feq_valid = false;     // feq buffer consistent with rho,u,v
     bool macro_valid = true;    // rho,u,v hold the last step's fields (false: to be rebuilt from the populations, ensure_macro)
-    void *check_part = nullptr; // CheckPartial records (kernels_check.h, typed in lb_hip.cpp): one per workgroup of k_macro_check + the folded result behind them
-    long long check_cap = 0;
+    CheckPartial *check_part = nullptr;     // lb_check's records (check_reduce.h): one per workgroup of the first pass + the folded result behind them
+    long long check_cap = 0;                // ... and how many it holds
     hipStream_t own_stream = nullptr, stream = nullptr, comm_stream = nullptr, edge_stream = nullptr;
     hipEvent_t ev_boundary = nullptr, ev_interior = nullptr, ev_halo = nullptr, ev_packed = nullptr, ev_edge = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
     // (ev_interior also orders a scalar lattice and the flow handle it takes its velocity from, lb_set_velocity_from: both are whole-grid

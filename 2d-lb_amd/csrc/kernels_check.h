@@ -1,7 +1,8 @@
 // kernels_check.h -- rho, u, v rebuilt from the populations on demand and the device-side health check (k_macro_check, k_check_final,
-// k_check_spread).  Included by lb_hip.cpp only: its plain kernels must be emitted by exactly one translation unit.
+// k_check_spread; the reduction itself: check_reduce.h).  Included by lb_hip.cpp only: its plain kernels must be emitted by exactly one translation unit.
 #pragma once
 #include "d2q9_cell.h"
+#include "check_reduce.h"
 
 namespace {
 
@@ -11,32 +12,14 @@ namespace {
 // rounding).  lb_run therefore does not store them in the plain families; this kernel rebuilds them the first time
 // somebody asks (lb_get_macro, lb_update_feq, ...).  The same pass reduces what the reference's forks print or warn
 // about while they run -- max |u| against the speed of sound (porous_media/single_component.py:221-225), the sums of
-// check_fields() (:753-766) -- plus a count of non-finite cells: per workgroup a partial (wave reduction through
-// cross-lane moves, then four waves through LDS), and k_check_final folds the partials in a fixed order, so the
-// result does not depend on the order in which workgroups retire.
-struct CheckPartial {
-    double sum_rho;                 // over the finite cells
-    unsigned long long nonfinite;   // cells whose rho, u or v is not finite
-    float max_usq;                  // max u^2 + v^2 (lattice units)
-    int pad;
-};
-
-__device__ __forceinline__ void check_reduce_wave(double &s, unsigned long long &n, float &m)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        s += __shfl_xor(s, d);
-        n += __shfl_xor(n, d);
-        m = fmaxf(m, __shfl_xor(m, d));
-    }
-}
+// check_fields() (:753-766) -- plus a count of non-finite cells: per workgroup a partial, and k_check_final folds the
+// partials (its own or k_ad_check's, kernels_scalar.h) in a fixed order: the record and the reduction are check_reduce.h's.
 
 // grid = (ceil(fpitch / 1024), H), 256 threads, 4 cells per lane; origin = plane 0, row 0 of the current lattice
 template <bool STORE>
 __global__ __launch_bounds__(256) void k_macro_check(const float *origin, long long plane, int pitch, int fpitch, int nx,
                                                      float *rho, float *u, float *v, CheckPartial *part)
 {
-    __shared__ CheckPartial sh[4];
     const int x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y;
     double s = 0.0;
     unsigned long long n = 0;
@@ -66,35 +49,19 @@ __global__ __launch_bounds__(256) void k_macro_check(const float *origin, long l
             *reinterpret_cast<f4a *>(v + o) = v4;
         }
     }
-    check_reduce_wave(s, n, m);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[wave] = CheckPartial{s, n, m, 0};
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        CheckPartial t = sh[0];
-        for (int i = 1; i < 4; ++i) { t.sum_rho += sh[i].sum_rho; t.nonfinite += sh[i].nonfinite; t.max_usq = fmaxf(t.max_usq, sh[i].max_usq); }
-        part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = t;
-    }
+    check_reduce_block<4>(s, n, m, part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x));
 }
 
 // one workgroup of 1024 threads: thread t folds partials t, t + 1024, ... in that order, then a fixed tree
 __global__ __launch_bounds__(1024) void k_check_final(const CheckPartial *part, long long count, CheckPartial *out)
 {
-    __shared__ CheckPartial sh[16];
     double s = 0.0;
     unsigned long long n = 0;
     float m = 0.f;
     for (long long i = threadIdx.x; i < count; i += 1024) {
         s += part[i].sum_rho; n += part[i].nonfinite; m = fmaxf(m, part[i].max_usq);
     }
-    check_reduce_wave(s, n, m);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = CheckPartial{s, n, m, 0};
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        CheckPartial t = sh[0];
-        for (int i = 1; i < 16; ++i) { t.sum_rho += sh[i].sum_rho; t.nonfinite += sh[i].nonfinite; t.max_usq = fmaxf(t.max_usq, sh[i].max_usq); }
-        *out = t;
-    }
+    check_reduce_block<16>(s, n, m, out);
 }
 
 // the folded record laid out for two all-reduces: {sum_rho, count} as doubles, max u^2 as a float

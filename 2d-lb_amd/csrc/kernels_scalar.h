@@ -12,7 +12,7 @@
 //                               keep the reference's un-fused order -- feq stored, then f (1 - omega) + omega feq -- and so round
 //                               differently from the fused cell, where omega enters through rho: held to it by the contract's
 //                               tolerance, not bitwise
-//   k_ad_edge_capture / k_ad_edge_patch, k_ad_check / k_ad_check_final
+//   k_ad_edge_capture / k_ad_edge_patch, k_ad_check (the health check's first pass: check_reduce.h)
 // The OPEN family (the reference's box, whose move_bcs does nothing): a link that would enter from outside keeps the value it had
 // when the populations were last set -- the handle's edge state, scalar_launch.h.  The gather reads whatever lies beside the box
 // (row padding, ghost rows: inside the allocation, never used) and ad_edge_gather puts the edge state in its place.
@@ -284,20 +284,9 @@ __global__ void k_ad_edge_patch(const StepArgs a, float *f, const float *edge)
 }
 
 // ---- health check: non-finite cells, sum of rho = sum of the populations, max |u|^2 of the imposed field ------------------------------
-__device__ __forceinline__ void ad_reduce_wave(double &s, unsigned long long &n, float &m)
+// grid = (ceil(nx / 256), ny), 256 threads, one partial per workgroup (check_reduce.h); k_check_final (kernels_check.h) folds them
+__global__ __launch_bounds__(256) void k_ad_check(const StepArgs a, CheckPartial *part)
 {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        s += __shfl_xor(s, d);
-        n += __shfl_xor(n, d);
-        m = fmaxf(m, __shfl_xor(m, d));
-    }
-}
-
-// grid = (ceil(nx / 256), ny), 256 threads, one partial per workgroup; k_ad_check_final folds them in a fixed order
-__global__ __launch_bounds__(256) void k_ad_check(const StepArgs a, AdCheck *part)
-{
-    __shared__ AdCheck sh[4];
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     double s = 0.0;
     unsigned long long n = 0;
@@ -310,33 +299,7 @@ __global__ __launch_bounds__(256) void k_ad_check(const StepArgs a, AdCheck *par
         if (fabsf(rho) <= 3.0e38f && fabsf(usq) <= 3.0e38f) { s = (double)rho; m = usq; }     // (false for NaN)
         else n = 1;
     }
-    ad_reduce_wave(s, n, m);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = AdCheck{s, n, m, 0};
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        AdCheck t = sh[0];
-        for (int i = 1; i < 4; ++i) { t.sum_rho += sh[i].sum_rho; t.nonfinite += sh[i].nonfinite; t.max_usq = fmaxf(t.max_usq, sh[i].max_usq); }
-        part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = t;
-    }
-}
-
-__global__ __launch_bounds__(1024) void k_ad_check_final(const AdCheck *part, long long count, AdCheck *out)
-{
-    __shared__ AdCheck sh[16];
-    double s = 0.0;
-    unsigned long long n = 0;
-    float m = 0.f;
-    for (long long i = threadIdx.x; i < count; i += 1024) {
-        s += part[i].sum_rho; n += part[i].nonfinite; m = fmaxf(m, part[i].max_usq);
-    }
-    ad_reduce_wave(s, n, m);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = AdCheck{s, n, m, 0};
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        AdCheck t = sh[0];
-        for (int i = 1; i < 16; ++i) { t.sum_rho += sh[i].sum_rho; t.nonfinite += sh[i].nonfinite; t.max_usq = fmaxf(t.max_usq, sh[i].max_usq); }
-        *out = t;
-    }
+    check_reduce_block<4>(s, n, m, part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x));
 }
 
 }  // namespace

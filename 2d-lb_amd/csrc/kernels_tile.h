@@ -1,5 +1,5 @@
 // kernels_tile.h -- four time steps per pass for SMALL grids: 2-D tiles staged in LDS.
-// Included after kernels_fused.h by tile.cpp (k_tile4, k_vel_band) and lb_hip.cpp (TileShape, for k1_tile4).
+// Included after kernels_fused.h by tile.cpp (k_tile4, k_vel_band) and lb_hip.cpp (TileLaunch, for k1_tile4); scalar.cpp takes the tile plan for k_ad_tile4.
 //
 // Grids below ~1600^2 cells live in the Infinity Cache and are not bandwidth-bound: a single-step launch costs
 // its ~2 us of dependent-kernel boundary plus one global-memory round trip per step, and the marching kernels
@@ -37,6 +37,27 @@ __device__ __forceinline__ int xcd_band_tile(int b, int n_tiles)
 {
     const int share = (n_tiles + 7) >> 3;
     return (b & 7) * share + (b >> 3);
+}
+
+// Host side: the launch of a tile kernel over an nx x h box -- one workgroup per tile, the grid rounded up to eight equal shares
+// (xcd_band_tile); tiles_x and n_tiles are the kernel's last two arguments.
+template <int TW_, int TH_, int CPT_>
+struct TileLaunch {
+    static constexpr int TW = TW_, TH = TH_, CPT = CPT_;
+    int tiles_x, n_tiles;
+    dim3 grid, block;
+    TileLaunch(int nx, int h)
+        : tiles_x((nx + TW - 1) / TW), n_tiles(tiles_x * ((h + TH - 1) / TH)), grid((n_tiles + 7) / 8 * 8), block(TileShape<TW, TH, CPT>::THREADS) {}
+};
+
+// The shapes the planner picks from (plan.cpp) -- 0: 32 x 16 tiles, two cells per thread; 1: 32 x 16, one; 2: 16 x 16, one --:
+// launch(TileLaunch<TW, TH, CPT>) is called with the chosen one's geometry
+template <class Launch>
+void with_tile_shape(int shape, int nx, int h, Launch launch)
+{
+    if (shape == 0) launch(TileLaunch<32, 16, 2>(nx, h));
+    else if (shape == 1) launch(TileLaunch<32, 16, 1>(nx, h));
+    else launch(TileLaunch<16, 16, 1>(nx, h));
 }
 
 // Which region cell a thread STEPS, as opposed to loads (the region goes into LDS in linear order, rows coalesced).  With two

@@ -34,7 +34,7 @@
 #include <initializer_list>
 #include <stdarg.h>
 
-#include "kernels_tile.h"       // TileShape, for k1_tile4
+#include "kernels_tile.h"       // TileLaunch, for k1_tile4
 #include "kernels_phases.h"
 #include "kernels_check.h"
 
@@ -84,23 +84,26 @@ int need_single_slab(const lb_sim *s, const char *what)
     return LB_OK;
 }
 
-// One pass over the current populations (k_macro_check): store = rebuild rho, u, v from them; the per-workgroup partials of
-// the health check are folded into check_part[blocks] on the way (lb_check reads that one record).
-int macro_check_pass(lb_sim *s, bool store)
+// The health check's two passes on the handle's stream.  The first is the handle's kind's -- flow: k_macro_check over the current
+// populations (store = rebuild rho, u, v from them on the way); scalar lattice: k_ad_check over the populations' sum and the imposed
+// field -- and leaves one record per workgroup; k_check_final folds them into check_part[check_cap - 1], the record lb_check reads.
+int check_pass(lb_sim *s, bool store)
 {
+    const StepArgs ad = step_args(s, 0, 1, s->H);       // (the scalar pass's arguments)
     const dim3 grid((unsigned)((s->pitch / 4 + 255) / 256), (unsigned)s->H);
-    const long long blocks = (long long)grid.x * grid.y;
-    CheckPartial *part = static_cast<CheckPartial *>(s->check_part);
+    const long long blocks = s->scalar() ? ad_check_blocks(ad) : (long long)grid.x * grid.y;
     if (s->check_cap < blocks + 1) {
         if (s->check_part) HIP_TRY(hipFree(s->check_part));
         s->check_part = nullptr;
         s->check_cap = 0;
         HIP_TRY(hipMalloc(&s->check_part, sizeof(CheckPartial) * (size_t)(blocks + 1)));
-        part = static_cast<CheckPartial *>(s->check_part);
         s->check_cap = blocks + 1;
         s->bytes += (int64_t)sizeof(CheckPartial) * (blocks + 1);
     }
-    if (store)
+    CheckPartial *part = s->check_part;
+    if (s->scalar())
+        lbk_ad_check(s->stream, ad, part);
+    else if (store)
         hipLaunchKernelGGL(k_macro_check<true>, grid, dim3(256), 0, s->stream, (const float *)s->origin(s->cur), s->plane,
                            (int)s->rowp, (int)s->pitch, s->p.nx, s->rho, s->u, s->v, part);
     else
@@ -125,7 +128,7 @@ int ensure_macro(lb_sim *s)
         return LB_OK;
     }
     // (a run on a slab ends with both of its other streams joined into s->stream: lb_run's tail)
-    int rc = macro_check_pass(s, true);
+    int rc = check_pass(s, true);
     if (rc) return rc;
     s->macro_valid = true;
     return LB_OK;
@@ -191,54 +194,32 @@ int lattice_plane_d2h(lb_sim *s, float *host, const float *origin, int k)
     return LB_OK;
 }
 
-// VELOCITY_INLET: where the eight never-written corner links live in a lattice (bc_vel_cell's order): {link, x, y}
-struct CornerLink { int k, x, y; };
-void corner_links(const lb_sim *s, CornerLink (&c)[8])
+// Links no kernel ever writes keep the value they had when the populations were last set as a whole (the reference's f_streamed = f
+// at that moment: opencl_dim.py:323-327, diffusion.py:321-324): the eight corner links of the VELOCITY_INLET family (vi_corner), the
+// edge state of a scalar lattice's OPEN family (ad_edge, scalar_launch.h); no other handle has any.  They are kept apart because
+// fused launches swap the lattices, so "whatever f_streamed held" would not survive them.  !patch: copied out of lattice `which`;
+// patch: written back into it.
+int frozen_links(lb_sim *s, int which, bool patch)
 {
-    const int X = s->p.nx - 1, Y = s->p.ny - 1;
-    const CornerLink t[8] = {{1, 0, 0}, {8, 0, 0}, {1, 0, Y}, {5, 0, Y}, {3, X, 0}, {7, X, 0}, {3, X, Y}, {6, X, Y}};
-    for (int i = 0; i < 8; ++i) c[i] = t[i];
-}
-// ... copied out of lattice `which` whenever the populations are set as a whole (the reference's f_streamed = f at
-// that moment, opencl_dim.py:323-327), and written back into it before the un-fused boundary phase reads them
-int corners_capture(lb_sim *s, int which)
-{
-    if (s->p.bc_mode != LB_BC_VELOCITY_INLET) return LB_OK;
-    CornerLink c[8];
-    corner_links(s, c);
-    for (int i = 0; i < 8; ++i)
-        HIP_TRY(hipMemcpyAsync(s->vi_corner + i, s->origin(which) + c[i].k * s->plane + (long long)c[i].y * s->rowp + c[i].x,
-                               sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+    if (s->p.bc_mode == LB_BC_VELOCITY_INLET) {
+        const int X = s->p.nx - 1, Y = s->p.ny - 1;
+        const struct { int k, x, y; } c[8] = {{1, 0, 0}, {8, 0, 0}, {1, 0, Y}, {5, 0, Y}, {3, X, 0}, {7, X, 0}, {3, X, Y}, {6, X, Y}};   // (bc_vel_cell's order)
+        for (int i = 0; i < 8; ++i) {
+            float *in_lat = s->origin(which) + c[i].k * s->plane + (long long)c[i].y * s->rowp + c[i].x, *kept = s->vi_corner + i;
+            HIP_TRY(hipMemcpyAsync(patch ? in_lat : kept, patch ? kept : in_lat, sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+        }
+    } else if (s->ad_edge) {
+        const StepArgs a = step_args(s, 0, 1, s->H);
+        if (patch) lbk_ad_edge_patch(s->stream, a, s->origin(which), s->ad_edge);
+        else lbk_ad_edge_capture(s->stream, a, s->origin(which), s->ad_edge);
+        HIP_TRY(hipGetLastError());
+    }
     return LB_OK;
 }
-int corners_patch(lb_sim *s, int which)
-{
-    CornerLink c[8];
-    corner_links(s, c);
-    for (int i = 0; i < 8; ++i)
-        HIP_TRY(hipMemcpyAsync(s->origin(which) + c[i].k * s->plane + (long long)c[i].y * s->rowp + c[i].x, s->vi_corner + i,
-                               sizeof(float), hipMemcpyDeviceToDevice, s->stream));
-    return LB_OK;
-}
-
-// Scalar lattice, OPEN family: the edge state follows the populations whenever they are set as a whole (the reference's
-// f_streamed = f at that moment, diffusion.py:321-324) ...
-int edge_capture(lb_sim *s, int which)
-{
-    if (!s->ad_edge) return LB_OK;
-    lbk_ad_edge_capture(s->stream, step_args(s, 0, 1, s->H), s->origin(which), s->ad_edge);
-    HIP_TRY(hipGetLastError());
-    return LB_OK;
-}
-// ... and is written back into the lattice behind the un-fused streaming phase, whose second lattice holds, after a fused run,
-// something else than the reference's f_streamed (fused launches swap the lattices)
-int edge_patch(lb_sim *s, int which)
-{
-    if (!s->ad_edge) return LB_OK;
-    lbk_ad_edge_patch(s->stream, step_args(s, 0, 1, s->H), s->origin(which), s->ad_edge);
-    HIP_TRY(hipGetLastError());
-    return LB_OK;
-}
+// ... whenever the populations are set as a whole (lb_set_f, lb_init_pop)
+int frozen_capture(lb_sim *s, int which) { return frozen_links(s, which, false); }
+// ... behind the un-fused streaming phase (lb_move), where the boundary phase reads them
+int frozen_patch(lb_sim *s, int which) { return frozen_links(s, which, true); }
 
 // ABI order of the edge state (include/lb_hip.h: west, east, south, north; unpadded) <-> device order (scalar_launch.h)
 long long edge_host_floats(const lb_sim *s) { return s->ad_edge ? 6LL * (s->p.nx + s->p.ny) : 0; }
@@ -266,13 +247,12 @@ int run_cython(lb_sim *s, int n_steps)
     while (left > 0) {
         const PhaseArgs a = phase_args(s);
         if (tiles && left % TILE_T == 0) {
-            const int tiles_x = (s->p.nx + 31) / 32, tiles_y = (s->H + 15) / 16, n_tiles = tiles_x * tiles_y;
-            const dim3 tg((n_tiles + 7) / 8 * 8), tb(TileShape<32, 16, 2>::THREADS);    // (eight equal shares: xcd_band_tile)
+            const TileLaunch<32, 16, 2> t(s->p.nx, s->H);
             const bool lastp = (left == TILE_T);
 #define LB_LAUNCH1T(MASK)                                                                                                  \
             do {                                                                                                       \
-                if (lastp) hipLaunchKernelGGL((k1_tile4<MASK, true, false>), tg, tb, 0, s->stream, a, tiles_x, n_tiles); \
-                else hipLaunchKernelGGL((k1_tile4<MASK, false, true>), tg, tb, 0, s->stream, a, tiles_x, n_tiles);       \
+                if (lastp) hipLaunchKernelGGL((k1_tile4<MASK, true, false>), t.grid, t.block, 0, s->stream, a, t.tiles_x, t.n_tiles); \
+                else hipLaunchKernelGGL((k1_tile4<MASK, false, true>), t.grid, t.block, 0, s->stream, a, t.tiles_x, t.n_tiles);       \
             } while (0)
             if (s->has_mask) LB_LAUNCH1T(true); else LB_LAUNCH1T(false);
 #undef LB_LAUNCH1T
@@ -487,7 +467,6 @@ int lb_destroy(lb_sim *s)
         }
     if (s->peer_flags) (void)hipFree(s->peer_flags);
     if (s->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(s->comm);
-    if (s->ad_part) (void)hipFree(s->ad_part);
     for (float *p : {s->lat[0], s->lat[1], s->feq, s->rho, s->u, s->v, s->halo_buf, s->vi_corner, s->stage, s->ad_edge})
         if (p) (void)hipFree(p);
     if (s->mask_raw) (void)hipFree(s->mask_raw);
@@ -677,8 +656,7 @@ int lb_set_f(lb_sim *s, const float *f)
     // f_streamed = f (opencl_dim.py:323-327)
     rc = copy_lattice(s, s->lat[s->cur ^ 1], s->lat[s->cur]);
     if (rc) return rc;
-    if ((rc = corners_capture(s, s->cur))) return rc;
-    if ((rc = edge_capture(s, s->cur))) return rc;
+    if ((rc = frozen_capture(s, s->cur))) return rc;
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->ghost_depth = 0;
     return LB_OK;
@@ -942,11 +920,7 @@ int lb_move(lb_sim *s)
         int rc = copy_lattice(s, s->lat[s->cur], s->lat[s->cur ^ 1]);
         if (rc) return rc;
     }
-    // VELOCITY_INLET: the eight corner links no phase ever writes are kept apart (fused launches swap the lattices,
-    // so "whatever f_streamed held" would not survive them): put them where the boundary phase reads them
-    if (s->p.bc_mode == LB_BC_VELOCITY_INLET) return corners_patch(s, s->cur);
-    if (s->scalar()) return edge_patch(s, s->cur);       // (the OPEN family's edge links, likewise)
-    return LB_OK;
+    return frozen_patch(s, s->cur);
 }
 
 int lb_move_bcs(lb_sim *s)
@@ -1067,8 +1041,7 @@ int lb_init_pop(lb_sim *s)
     for (int i = 0; i < 2; ++i)
         if ((rc = copy_lattice(s, s->lat[i], s->feq))) return rc;
     s->ghost_depth = 0;
-    if ((rc = edge_capture(s, s->cur))) return rc;
-    return corners_capture(s, s->cur);
+    return frozen_capture(s, s->cur);
 }
 
 // ---- fused stepping (lb_step_*, lb_halo_*, lb_run_group: slab.cpp) --------------------------
@@ -1169,29 +1142,12 @@ int lb_check(lb_sim *s, int across_ranks, int64_t *n_nonfinite, float *max_mach,
     if (s->stepping) return fail(LB_ERR_STATE, "lb_check inside a split step");
     if (across_ranks && !s->comm) return fail(LB_ERR_STATE, "lb_check across ranks needs lb_comm_init");
     DeviceGuard guard(s->p.device);
-    if (s->scalar()) {
-        // the populations' sum and the imposed field (kernels_scalar.h, k_ad_check)
-        const StepArgs a = step_args(s, 0, 1, s->H);
-        const long long blocks = ad_check_blocks(a);
-        if (!s->ad_part) {
-            HIP_TRY(hipMalloc(&s->ad_part, sizeof(AdCheck) * (size_t)(blocks + 1)));
-            s->bytes += (int64_t)sizeof(AdCheck) * (blocks + 1);
-        }
-        lbk_ad_check(s->stream, a, s->ad_part);
-        HIP_TRY(hipGetLastError());
-        AdCheck h;
-        HIP_TRY(hipMemcpyAsync(&h, s->ad_part + blocks, sizeof(h), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        if (n_nonfinite) *n_nonfinite = (int64_t)h.nonfinite;
-        if (max_mach) *max_mach = sqrtf(3.f * h.max_usq);
-        if (sum_rho) *sum_rho = h.sum_rho;
-        return LB_OK;
-    }
-    // the pass that rebuilds rho, u, v reduces the same three numbers: one pass serves both when the fields are due
-    int rc = macro_check_pass(s, !s->macro_valid && lazy_macro(s));
+    // the pass that rebuilds rho, u, v reduces the same three numbers: one pass serves both when the fields are due (never on a
+    // scalar lattice, whose rho is stored by its runs and whose u, v are imposed: macro_valid stays true there)
+    int rc = check_pass(s, !s->macro_valid && lazy_macro(s));
     if (rc) return rc;
     s->macro_valid = true;
-    CheckPartial *res = static_cast<CheckPartial *>(s->check_part) + (s->check_cap - 1);
+    CheckPartial *res = s->check_part + (s->check_cap - 1);
     CheckPartial h;
     if (across_ranks) {
         // sum_rho and the count travel as two doubles (exact up to 2^53 cells), the maximum on its own

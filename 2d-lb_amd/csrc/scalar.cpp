@@ -17,20 +17,13 @@ void ad_step_go(bool react, bool store_rho, dim3 grid, dim3 block, hipStream_t s
     }
 }
 
-template <int BC, bool REACT, bool RHO, int TW, int TH, int CPT>
-void ad_tile_shape(hipStream_t st, const StepArgs &a, const AdExtra &e)
-{
-    const int tiles_x = (a.nx + TW - 1) / TW, tiles_y = (a.ny + TH - 1) / TH, n_tiles = tiles_x * tiles_y;
-    const dim3 grid((n_tiles + 7) / 8 * 8), block(TileShape<TW, TH, CPT>::THREADS);     // (eight equal shares: xcd_band_tile)
-    hipLaunchKernelGGL((k_ad_tile4<BC, REACT, RHO, TW, TH, CPT>), grid, block, 0, st, a, e, tiles_x, n_tiles);
-}
-
 template <int BC, bool REACT, bool RHO>
 void ad_tile_go(int shape, hipStream_t st, const StepArgs &a, const AdExtra &e)
 {
-    if (shape == 0) ad_tile_shape<BC, REACT, RHO, 32, 16, 2>(st, a, e);
-    else if (shape == 1) ad_tile_shape<BC, REACT, RHO, 32, 16, 1>(st, a, e);
-    else ad_tile_shape<BC, REACT, RHO, 16, 16, 1>(st, a, e);
+    with_tile_shape(shape, a.nx, a.ny, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_ad_tile4<BC, REACT, RHO, T::TW, T::TH, T::CPT>), t.grid, t.block, 0, st, a, e, t.tiles_x, t.n_tiles);
+    });
 }
 
 template <int BC>
@@ -84,9 +77,7 @@ void lbk_ad_edge_patch(hipStream_t st, const StepArgs &a, float *f, const float 
 
 long long ad_check_blocks(const StepArgs &a) { return (long long)((a.nx + 255) / 256) * a.ny; }
 
-void lbk_ad_check(hipStream_t st, const StepArgs &a, AdCheck *rec)
+void lbk_ad_check(hipStream_t st, const StepArgs &a, CheckPartial *part)
 {
-    const long long blocks = ad_check_blocks(a);
-    hipLaunchKernelGGL(k_ad_check, cells_grid(a), dim3(256), 0, st, a, rec);
-    hipLaunchKernelGGL(k_ad_check_final, dim3(1), dim3(1024), 0, st, (const AdCheck *)rec, blocks, rec + blocks);
+    hipLaunchKernelGGL(k_ad_check, cells_grid(a), dim3(256), 0, st, a, part);
 }

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels_fused.h"
+#include "check_reduce.h"       // CheckPartial
 
 // Edge state of the OPEN family on the device, floats: six rows of fpitch -- south f2, f5, f6, north f4, f7, f8 -- then six columns of
 // ny -- west f1, f5, f8, east f3, f6, f7.  (The ABI's order, include/lb_hip.h, is the host's: columns first, rows unpadded.)
@@ -12,14 +13,6 @@ struct AdExtra {
     float G;            // growth rate of the Fisher term; used by the REACT instantiations only
 };
 inline long long ad_edge_device_floats(long long fpitch, int ny) { return 6 * fpitch + 6LL * ny; }
-
-// the health check's record (one per workgroup of the first pass, folded by the second into rec[count])
-struct AdCheck {
-    double sum_rho;                 // sum of the populations over the finite cells
-    unsigned long long nonfinite;   // cells whose density or imposed velocity is not finite
-    float max_usq;                  // max u^2 + v^2 of the imposed field
-    int pad;
-};
 
 // bc: LB_BC_PERIODIC or LB_BC_OPEN.  k_ad_step over the whole grid; store_rho: the launch also stores rho.
 void lbk_ad_step(int bc, bool react, bool store_rho, hipStream_t st, const StepArgs &a, const AdExtra &e);
@@ -32,6 +25,7 @@ void lbk_ad_collide(bool react, hipStream_t st, const StepArgs &a, float *f, con
 // OPEN: the edge state copied out of / written back into the lattice at `f`
 void lbk_ad_edge_capture(hipStream_t st, const StepArgs &a, const float *f, float *edge);
 void lbk_ad_edge_patch(hipStream_t st, const StepArgs &a, float *f, const float *edge);
-// health check over the lattice at a.src and the fields a.u, a.v: rec must hold ad_check_blocks(a) + 1 records; the result is the last
+// the health check's first pass over the lattice at a.src and the fields a.u, a.v: one record per workgroup, ad_check_blocks(a) of
+// them, into part (k_check_final, lb_hip.cpp, folds them)
 long long ad_check_blocks(const StepArgs &a);
-void lbk_ad_check(hipStream_t st, const StepArgs &a, AdCheck *rec);
+void lbk_ad_check(hipStream_t st, const StepArgs &a, CheckPartial *part);

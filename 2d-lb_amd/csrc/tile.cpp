@@ -5,21 +5,14 @@
 
 namespace {
 
-template <int BC, bool MASK, bool MACRO, int TW, int TH, int CPT>
-void tile_shape(int nx, int h, hipStream_t st, const StepArgs &a)
-{
-    const int tiles_x = (nx + TW - 1) / TW, tiles_y = (h + TH - 1) / TH, n_tiles = tiles_x * tiles_y;
-    const dim3 grid((n_tiles + 7) / 8 * 8), block(TileShape<TW, TH, CPT>::THREADS);     // (eight equal shares: xcd_band_tile)
-    hipLaunchKernelGGL((k_tile4<BC, MASK, MACRO, TW, TH, CPT>), grid, block, 0, st, a, tiles_x, n_tiles);
-}
-
 template <int BC, bool MASK, bool MACRO>
 struct LT {
     static void go(int shape, int nx, int h, hipStream_t st, const StepArgs &a)
     {
-        if (shape == 0) tile_shape<BC, MASK, MACRO, 32, 16, 2>(nx, h, st, a);
-        else if (shape == 1) tile_shape<BC, MASK, MACRO, 32, 16, 1>(nx, h, st, a);
-        else tile_shape<BC, MASK, MACRO, 16, 16, 1>(nx, h, st, a);
+        with_tile_shape(shape, nx, h, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((k_tile4<BC, MASK, MACRO, T::TW, T::TH, T::CPT>), t.grid, t.block, 0, st, a, t.tiles_x, t.n_tiles);
+        });
     }
 };
 
