@@ -294,6 +294,64 @@ def gen_o2(L):
     save("o2_cyl_61x31", **out)
 
 
+def edge_pattern(nx, ny):
+    """Solid cells ON the box's own boundary (tests/test_gpu_edge_obstacles.py lays the same pattern on every shape it runs): the
+    four corners, two isolated cells on each edge and one beside a corner, a block standing on the south wall, one hanging from
+    the north wall, one on the inlet column and one on the outlet column, five interior cells."""
+    m = np.zeros((nx, ny), bool)
+    m[0, 0] = m[0, -1] = m[-1, 0] = m[-1, -1] = True
+    m[[nx // 8, nx // 3 + 1, 1], 0] = True
+    m[[nx // 6, (4 * nx) // 5], -1] = True
+    m[0, [ny // 6, (3 * ny) // 4]] = True
+    m[-1, [ny // 4, (5 * ny) // 6]] = True
+    m[nx // 2:nx // 2 + max(1, nx // 8), :max(1, ny // 6)] = True
+    m[(2 * nx) // 3:(2 * nx) // 3 + max(1, nx // 10), ny - max(1, ny // 8):] = True
+    m[:max(1, nx // 20), ny // 3:ny // 3 + max(1, ny // 5)] = True
+    m[nx - max(1, nx // 20):, ny // 2:ny // 2 + max(1, ny // 6)] = True
+    for fx, fy in ((.25, .5), (.27, .5), (.33, .3), (.8, .25), (.85, .7)):
+        m[int(fx * nx), int(fy * ny)] = True
+    return m
+
+
+def gen_o2_edge_mask(L):
+    """Obstacle cells on the walls, the inlet, the outlet and the corners: `move_bcs` on every edge cell, then
+    `bounceback_in_obstacle` (opencl_dim.py:510-518).  One call of every kernel on f0 as in o2_kernels_37x19 (plus the two
+    boundary kernels in the host's order), then the run of o2_cyl_61x31."""
+    nx, ny, omega, rin, rout = 61, 31, 1.7, 1.003, 1.0
+    rng = np.random.default_rng(41)
+    mask = edge_pattern(nx, ny)
+    s = RefOpenCL(L, nx, ny, omega, rin, rout, mask)
+    s.rho[...] = ramp(nx, ny, rin, rout)
+    s.zero_vel()
+    s.update_feq()
+    f0 = np.asfortranarray((s.feq * (1. + 0.01 * rng.standard_normal((nx, ny, 9)))).astype(np.float32))
+    out = {"nx": nx, "ny": ny, "omega": omega, "inlet_rho": rin, "outlet_rho": rout, "mask": mask, "f0": f0}
+    s.f[...] = f0
+    L.k_move_bcs(P(s.f), P(s.u), s.rin, s.rout, nx, ny)
+    out["after_bcs_f"] = s.f.copy(order="F")
+    L.k_bounceback(P(s.mask), P(s.f), nx, ny)
+    out["after_bcs_bounce_f"] = s.f.copy(order="F")          # the two in the host's order
+    s.f[...] = f0
+    L.k_bounceback(P(s.mask), P(s.f), nx, ny)
+    out["after_bounce_f"] = s.f.copy(order="F")
+    s.f[...] = f0
+    s.update_hydro()
+    out["hydro_rho"], out["hydro_u"], out["hydro_v"] = s.rho.copy(order="F"), s.u.copy(order="F"), s.v.copy(order="F")
+    s.update_feq()
+    out["feq"] = s.feq.copy(order="F")
+    s.collide()
+    out["after_collide_f"] = s.f.copy(order="F")
+    s.zero_vel()
+    out["zeroed_u"], out["zeroed_v"] = s.u.copy(order="F"), s.v.copy(order="F")
+    s.f[...] = f0; s.fs[...] = f0
+    done = 0
+    for n in (1, 100, 500):
+        s.run(n - done); done = n
+        out.update(flat("s%d" % n, s.snap()))
+    assert all(np.isfinite(v).all() for k, v in out.items() if k.startswith("s"))
+    save("o2_edge_mask_61x31", **out)
+
+
 def gen_o2_velocity_inlet(L):
     """The two velocity-inlet kernels of D2Q9.cl (:263-374), driven in the order of
     OLD/opencl.py:281-327 (Pipe_Flow_PeriodicBC_VelocityInlet: rho=1, u=u_w, v=0 at start)."""
@@ -450,6 +508,32 @@ def gen_o1(m):
          columns=np.array(["N", "radius", "L", "T", "Re", "omega", "inlet_rho", "nx", "ny"]))
 
 
+def gen_o1_edge_cyl(m):
+    """The cylinder of o1_cyl_61x41 (radius = 4 cells) moved onto the box's boundary: centred 3.2 cells above the south wall, so
+    that five of its cells lie on the wall row, and (second fixture) 3.2 cells from the inlet column.  3.2 > radius - 1: the
+    disc reaches row / column 0 and no further -- scikit-image's `circle` does not clip, and a negative index would put cells on
+    the opposite edge."""
+    kw = dict(diameter=1., rho=1., viscosity=2., pressure_grad=-10., pipe_length=1.5, N=4, time_prefactor=0.02)
+    for name, center, seed in (("o1_edge_cyl_61x41", [.4, .08], 51), ("o1_edge_cyl_inlet_61x41", [.08, .5], 52)):
+        s = m.Pipe_Flow_Cylinder(cylinder_center=center, cylinder_radius=.1, **kw)
+        mask = np.array(s.obstacle_mask)
+        assert np.array_equal(mask, disc(s.nx, s.ny, 4 * center[0] / .1, 4 * center[1] / .1, 4.))
+        assert mask[:, 0].sum() == 5 if name == "o1_edge_cyl_61x41" else mask[0, :].sum() == 5
+        rng = np.random.default_rng(seed)
+        perturb = o1_seed_state(s, rng)
+        out = {"kw_names": np.array(list(kw.keys())), "kw_vals": np.array(list(kw.values()), float),
+               "cylinder_center": np.array(center), "cylinder_radius": .1,
+               "nx": s.nx, "ny": s.ny, "omega": s.omega, "inlet_rho": s.inlet_rho, "outlet_rho": s.outlet_rho,
+               "T": s.T, "Re": s.Re, "mask": mask, "perturb": perturb,
+               "f0": s.f.copy(), "rho0": s.rho.copy()}
+        done = 0
+        for n in (1, 50, 300):
+            s.run(n - done); done = n
+            out.update(flat("s%d" % n, o1_snap(s)))
+        assert all(np.isfinite(v).all() for k, v in out.items() if k.startswith("s"))
+        save(name, **out)
+
+
 def gen_o1_config1(m):
     """BASELINE config 1 at full size through the imported reference: 256 x 256 Poiseuille start-up flow,
     `Pipe_Flow.run` (cython_dim.pyx:346-359), 1000 steps from f = feq (the perturbation of init_pop replaced by
@@ -542,6 +626,7 @@ def main():
     L = build_o2(tmp)
     if "--only-velocity-inlet" not in sys.argv and "--only-d2q9i" not in sys.argv:
         gen_o2(L)
+        gen_o2_edge_mask(L)
     if "--only-d2q9i" not in sys.argv:
         gen_o2_velocity_inlet(L)
     if "--only-velocity-inlet" in sys.argv:
@@ -552,6 +637,7 @@ def main():
     gen_move_periodic(tmp)
     m = build_o1(tmp)
     gen_o1(m)
+    gen_o1_edge_cyl(m)
     gen_o1_config1(m)
 
 

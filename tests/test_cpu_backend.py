@@ -67,6 +67,26 @@ def test_cpu_backend_cylinder_bit_exact(lbhip):
         assert np.all(g["u"][d["mask"]] == 0)
 
 
+@pytest.mark.parametrize("name,edge", [("o1_edge_cyl_61x41", "south"), ("o1_edge_cyl_inlet_61x41", "inlet")])
+def test_cpu_backend_cylinder_on_the_boundary_bit_exact(lbhip, name, edge):
+    """The same cylinder with five of its cells on the south wall row / on the inlet column: the boundary rule and the
+    bounce-back on one cell (c1_bcs_cell takes `solid` inside the rule)."""
+    from LB_D2Q9.dimensionless import cython_dim as lb
+    d = golden(name)
+    sim = lb.Pipe_Flow_Cylinder(cylinder_center=list(d["cylinder_center"]), cylinder_radius=float(d["cylinder_radius"]),
+                                device=-1, verbose=False, **kwargs_of(d))
+    assert np.array_equal(np.asarray(sim.obstacle_mask, bool), d["mask"])
+    assert int((d["mask"][:, 0] if edge == "south" else d["mask"][0, :]).sum()) == 5
+    sim.set_f(d["f0"])
+    done = 0
+    for n in (1, 50, 300):
+        sim.run(n - done)
+        done = n
+        g = sim.get_fields()
+        same_fields(g, d, "s%d_" % n)
+        assert np.all(g["u"][d["mask"]] == 0) and np.all(g["v"][d["mask"]] == 0)
+
+
 def test_config1_256_poiseuille_on_the_cpu_backend_without_a_gpu(lbhip):
     """BASELINE.json configs[0] -- 256 x 256 Poiseuille pipe flow on the CPU path, no GPU -- through the product: 1000 steps from
     f = feq against the imported reference's own run of that case (rows / columns / means stored in o1_config1_256; rho bit for

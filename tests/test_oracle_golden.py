@@ -50,7 +50,49 @@ def test_o2_each_kernel_bit_exact(oracle):
     assert exact(s.u.T, d["zeroed_u"]) and exact(s.v.T, d["zeroed_v"])
 
 
-@pytest.mark.parametrize("name", ["o2_pipe_N10", "o2_pipe_noise_49x25", "o2_cyl_61x31"])
+def test_o2_each_kernel_bit_exact_on_boundary_obstacles(oracle):
+    """The same single calls on o2_edge_mask_61x31, whose solid cells lie on the walls, the inlet, the outlet and the four
+    corners: there `move_bcs` and `bounceback_in_obstacle` write the same cell, in that order (opencl_dim.py:510-518)."""
+    O = oracle
+    d = golden("o2_edge_mask_61x31")
+    nx, ny = int(d["nx"]), int(d["ny"])
+    m = d["mask"]
+    from test_gpu_edge_obstacles import edge_pattern           # the GPU tests' copy of the generator's pattern: kept the same
+    assert np.array_equal(edge_pattern(nx, ny), m)
+    assert m[0, 0] and m[0, -1] and m[-1, 0] and m[-1, -1]
+    assert m[1:-1, 0].any() and m[1:-1, -1].any() and m[0, 1:-1].any() and m[-1, 1:-1].any() and m[1:-1, 1:-1].any()
+
+    def fresh():
+        s = O.O2Sim(nx, ny, float(d["omega"]), O.BC_PIPE, float(d["inlet_rho"]), float(d["outlet_rho"]), mask=m)
+        s.set_f(d["f0"])
+        return s
+
+    L = O.lib()
+    s = fresh()
+    L.o2_bc_pipe(O._f(s.f), np.float32(s.inlet_rho), np.float32(s.outlet_rho), nx, ny)
+    assert exact(s.f.transpose(2, 1, 0), d["after_bcs_f"])
+    L.o2_bounceback(s.mask.ctypes.data_as(O._ip), O._f(s.f), nx, ny)
+    assert exact(s.f.transpose(2, 1, 0), d["after_bcs_bounce_f"])
+    s = fresh()
+    s.move_bcs()                                               # the phase = the two of them
+    assert exact(s.f.transpose(2, 1, 0), d["after_bcs_bounce_f"])
+    assert not exact(d["after_bcs_bounce_f"][m], d["after_bounce_f"][m])      # (the rule is visible under the swap)
+    s = fresh()
+    L.o2_bounceback(s.mask.ctypes.data_as(O._ip), O._f(s.f), nx, ny)
+    assert exact(s.f.transpose(2, 1, 0), d["after_bounce_f"])
+    s = fresh()
+    s.update_hydro()
+    assert exact(s.rho.T, d["hydro_rho"]) and exact(s.u.T, d["hydro_u"]) and exact(s.v.T, d["hydro_v"])
+    s.update_feq()
+    assert exact(s.feq.transpose(2, 1, 0), d["feq"])
+    s.collide_particles()
+    assert exact(s.f.transpose(2, 1, 0), d["after_collide_f"])
+    s.zero_velocity_in_obstacle()
+    assert exact(s.u.T, d["zeroed_u"]) and exact(s.v.T, d["zeroed_v"])
+    assert np.all(s.u.T[m] == 0) and np.all(s.v.T[m] == 0)
+
+
+@pytest.mark.parametrize("name", ["o2_pipe_N10", "o2_pipe_noise_49x25", "o2_cyl_61x31", "o2_edge_mask_61x31"])
 def test_o2_runs_bit_exact(oracle, name):
     O = oracle
     d = golden(name)
@@ -143,6 +185,26 @@ def test_o1_cylinder_bit_exact(oracle):
         for k in ("f", "feq", "rho", "u", "v"):
             assert exact(g[k], d["s%d_%s" % (n, k)]), (n, k)
         assert np.all(g["u"][d["mask"]] == 0)
+
+
+@pytest.mark.parametrize("name,edge", [("o1_edge_cyl_61x41", "south"), ("o1_edge_cyl_inlet_61x41", "inlet")])
+def test_o1_cylinder_on_the_boundary_bit_exact(oracle, name, edge):
+    """The cylinder of o1_cyl_61x41 moved until five of its cells lie on the south wall row / on the inlet column."""
+    d = golden(name)
+    s = oracle.O1Sim.pipe_flow(cylinder_center=list(d["cylinder_center"]), cylinder_radius=float(d["cylinder_radius"]),
+                               perturb=d["perturb"], **kwargs_of(d))
+    assert exact(s.mask.astype(bool), d["mask"])
+    assert int((d["mask"][:, 0] if edge == "south" else d["mask"][0, :]).sum()) == 5
+    assert s.omega == float(d["omega"]) and s.inlet_rho == float(d["inlet_rho"])
+    assert exact(s.f, d["f0"])
+    done = 0
+    for n in (1, 50, 300):
+        s.run(n - done)
+        done = n
+        g = s.get_fields()
+        for k in ("f", "feq", "rho", "u", "v"):
+            assert exact(g[k], d["s%d_%s" % (n, k)]), (n, k)
+        assert np.all(g["u"][d["mask"]] == 0) and np.all(g["v"][d["mask"]] == 0)
 
 
 def test_o1_numpy1_mode_stays_within_one_ulp_per_step(oracle):
