@@ -490,6 +490,8 @@ class Simulation(object):
         return nbytes.value * iters / (ms.value * 1e-3) / 1e9, nbytes.value
 
     def set_variant(self, variant):
+        """Which fused kernel runs (lb_set_variant): an int, variants.AUTO (-1, the default) or a word made of the names in
+        LB_D2Q9/variants.py, e.g. variants.K_STEP5 or variants.marching(3) | variants.NO_CYCLE.  Results never depend on it."""
         check(self._lib.lb_set_variant(self._h, int(variant)))
 
     def set_slab_cycle(self, depth):

@@ -138,6 +138,7 @@ class LocalSlabRing(_SlabSet):
         self._ghosts_valid = False      # lb_run_group refreshes the ghosts itself
 
     def set_variant(self, variant):
+        """The same word on every slab (an int; the names: LB_D2Q9/variants.py)."""
         for s in self.slabs:
             s.set_variant(variant)
 

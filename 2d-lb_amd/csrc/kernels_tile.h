@@ -100,7 +100,7 @@ __global__ __launch_bounds__((TileShape<TW, TH, CPT>::THREADS), (CPT == 2 ? 8 : 
     __shared__ float lds[9][TILE_CELLS];
     __shared__ unsigned char lmask[TILE_CELLS];
     const int tid = threadIdx.x;
-    const int tile = a.tile_launch_order ? (int)blockIdx.x : xcd_band_tile(blockIdx.x, n_tiles);   // (A/B switch: variant bit 13)
+    const int tile = a.tile_launch_order ? (int)blockIdx.x : xcd_band_tile(blockIdx.x, n_tiles);   // (A/B switch: LB_VAR_TILE_LAUNCH_ORDER)
     if (tile >= n_tiles) return;
     const int tx = tile % tiles_x, ty = tile / tiles_x;
     const int gx0 = tx * TW - TILE_T, gy0 = ty * TH - TILE_T;         // global coordinates of region cell (0,0)

@@ -20,7 +20,7 @@ StepArgs step_args(const lb_sim *s, int row_begin, int row_step, int row_count)
     a.ghost_n = (s->multi_slab() && (periodic || s->p.y0 + s->H < s->p.ny)) ? 1 : 0;
     a.seg_stride = 0;
     a.edge_seg_rows = 0;
-    a.tile_launch_order = (s->variant >= 0 && (s->variant & VAR_TILE_LAUNCH_ORDER)) ? 1 : 0;    // (A/B switch: explicit variants only)
+    a.tile_launch_order = (s->variant >= 0 && (s->variant & LB_VAR_TILE_LAUNCH_ORDER)) ? 1 : 0;    // (A/B switch: explicit variants only)
     a.diag = s->diag;
     a.prio_turns = 0;      // (set by launch_marching from the variant)
     a.nts = 0;
@@ -36,8 +36,8 @@ int launch_step(lb_sim *s, int row_begin, int row_step, int row_count, bool macr
     macro = macro && !lazy_macro(s);       // (no fused kernel stores rho, u, v on a handle that rebuilds them on demand)
     const StepArgs a = step_args(s, row_begin, row_step, row_count);
     const int variant = effective_variant(s);
-    const int rpb_sel = variant & VAR_ROWS;
-    const int rows_per_block = rpb_sel == VAR_ROWS_1 ? 1 : (rpb_sel == VAR_ROWS_2 ? 2 : 4);
+    const int rpb_sel = variant & LB_VAR_ROWS;
+    const int rows_per_block = rpb_sel == LB_VAR_ROWS_1 ? 1 : (rpb_sel == LB_VAR_ROWS_2 ? 2 : 4);
     const int waves_x = 4 / rows_per_block;          // waves side by side in x
     dim3 block(64 * waves_x, rows_per_block);
     const int lanes_x = (int)(s->pitch / 4);
@@ -49,7 +49,7 @@ int launch_step(lb_sim *s, int row_begin, int row_step, int row_count, bool macr
 
 // A marching launch of `depth` time steps per pass (k_step2 ... k_step5, k_deep), by the translation unit that instantiates that depth.
 // k_step4 gathers one row ahead where that fits in 256 registers without scratch (step4_prefetch, kernels_step4.h: every
-// instantiation without an obstacle mask but the D2Q9i fork's); VAR_STEP4_NO_AHEAD switches it off (A/B runs).
+// instantiation without an obstacle mask but the D2Q9i fork's); LB_VAR_STEP4_NO_AHEAD switches it off (A/B runs).
 static bool launch_march(const lb_sim *s, hipStream_t st, const StepArgs &a, const MarchPlan &m, int row_end, bool macro, int depth)
 {
     const int waves = (depth >= 4) ? STEP4_WAVES : 4;      // waves per workgroup: k_step4 ... k_step6: the two directions of ONE item
@@ -61,12 +61,12 @@ static bool launch_march(const lb_sim *s, hipStream_t st, const StepArgs &a, con
     g.strips = m.strips; g.seg_rows = m.seg_rows; g.nsegs = m.segs; g.row_end = row_end;
     const int bc = kernel_bc(s);
     // (false: the unit has no instantiation for this boundary family -- k_deep / k_deep2 and the velocity-inlet family)
-    // k_deep2: four waves per workgroup -- asked for (VAR_DEEP2) or found faster by lb_autotune (seven steps at "eight waves per CU")
+    // k_deep2: four waves per workgroup -- asked for (LB_VAR_DEEP2) or found faster by lb_autotune (seven steps at "eight waves per CU")
     if (depth == 7 && deep2_chosen(s)) return lbk_launch_deep2_7(bc, s->has_mask, macro, g, a);
     if (depth == 7) return lbk_launch_deep7(bc, s->has_mask, macro, g, a);
     if (depth == 6) return lbk_launch_deep6(bc, s->has_mask, macro, g, a);
     if (depth == 5) lbk_launch_march5(bc, s->has_mask, macro, g, a);
-    else if (depth == 4) lbk_launch_march4(bc, s->has_mask, macro, !(effective_variant(s) & VAR_STEP4_NO_AHEAD), g, a);
+    else if (depth == 4) lbk_launch_march4(bc, s->has_mask, macro, !(effective_variant(s) & LB_VAR_STEP4_NO_AHEAD), g, a);
     else lbk_launch_march23(depth, bc, s->has_mask, macro, g, a);
     return true;
 }
@@ -80,9 +80,9 @@ int launch_marching(lb_sim *s, const MarchRows &r)
     const MarchPlan m = plan_march(s, r.row_end - r.row_begin, r.depth, r.bands, r.reserve);
     a.seg_stride = m.seg_stride;
     a.edge_seg_rows = m.edge_seg_rows;
-    // k_step4: the two waves of a SIMD take turns at the higher issue priority (see the kernel), in turns of 2^13 ticks of the 100 MHz clock; VAR_NO_PRIO_TURNS = off
-    a.prio_turns = (variant & VAR_NO_PRIO_TURNS) ? 0 : 13;
-    a.nts = (variant & VAR_NT_STORES) ? 1 : 0;     // (the marching kernels take it at run time)
+    // k_step4: the two waves of a SIMD take turns at the higher issue priority (see the kernel), in turns of 2^13 ticks of the 100 MHz clock; LB_VAR_NO_PRIO_TURNS = off
+    a.prio_turns = (variant & LB_VAR_NO_PRIO_TURNS) ? 0 : 13;
+    a.nts = (variant & LB_VAR_NT_STORES) ? 1 : 0;     // (the marching kernels take it at run time)
     if (!launch_march(s, r.stream, a, m, r.row_end, macro, r.depth))
         return fail(LB_ERR_STATE, "no %d-step kernel for this boundary family (the caller's schedule must not ask for one)", r.depth);
     HIP_TRY(hipGetLastError());

@@ -238,7 +238,7 @@ int run_cython(lb_sim *s, int n_steps)
     }
     // n = 4a + rem: the remainder first, step by step (k1_fstep: four cells per lane, 16-byte accesses, at the streaming
     // ceiling of a pass that moves 72 B per cell), then a launches of four steps each through LDS tiles (k1_tile4);
-    // grids too small for tiles, or LB_VARIANT / lb_set_variant without VAR_TILES with an explicit variant: single steps only
+    // grids too small for tiles, or LB_VARIANT / lb_set_variant without LB_VAR_TILES with an explicit variant: single steps only
     const dim3 blk(64, 4), grd((unsigned)((s->pitch / 4 + 63) / 64), (unsigned)((s->H + 3) / 4));
     // (rounds 4-5 also had a five-step marching form, k1_step5: bitwise right, slower than the tiles at the reference's sizes --
     //  3751 x 1251 with the cylinder 136 against 174 k MLUPS --, diagnostic build only in round 5, removed in round 6)

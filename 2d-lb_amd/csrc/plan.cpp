@@ -19,7 +19,7 @@ bool lazy_macro(const PlanInputs *s)
            (s->p.bc_mode == LB_BC_PIPE || s->p.bc_mode == LB_BC_PERIODIC || s->p.bc_mode == LB_BC_CAVITY);
 }
 
-// variant < 0 = automatic, from one-GPU sweeps (tools/sweep.py, tools/rect_probe.py;
+// The variant word in use: lb_variant_bits (LB_VAR_*, include/lb_hip.h).  variant < 0 = automatic, from one-GPU sweeps (tools/sweep.py, tools/rect_probe.py;
 // profiles/r01_sweep_variants.txt):
 //   >= 1024^2 / 1280^2 cells on this GPU : temporal blocking -- three / four time steps per pass (marching
 //                                          kernels; nx >= 512 and enough rows, else they do not apply)
@@ -41,17 +41,17 @@ int effective_variant(const PlanInputs *s)
     //  170 MB (periodic 1536^2) 306 | 298, 302 MB (2048^2) 369 | 363, pipe 2048^2 291 | 295; 338 MB -- the reference's 3751 x 1251 case --
     //  274-285 | 292-293 (two rounds, both depths), 415 MB: periodic 2400^2 385 | 388, pipe 337 against 308, cavity + mask 298 against 276:
     //  the threshold is 320 MB now)
-    int v = pair_bytes >= 3.2e8 ? ((s->p.flags & LB_FLAG_PLANAR) ? VAR_NT_STORES | VAR_ROWS_2 : VAR_NT_STORES) : VAR_XCD_ORDER;
+    int v = pair_bytes >= 3.2e8 ? ((s->p.flags & LB_FLAG_PLANAR) ? LB_VAR_NT_STORES | LB_VAR_ROWS_2 : LB_VAR_NT_STORES) : LB_VAR_XCD_ORDER;
     // from 1024^2 cells: three steps per pass (110 k MLUPS at 1024^2 against 87 k single-step); from 1280^2:
     // four (125 k at 1280^2, 158 k at 1536^2, 170 k at 2048^2, 220 k from 3072^2), whole grids and slabs alike,
     // in every boundary family, with and without obstacles (profiles/r01_sweep_variants.txt,
     // profiles/r01_slab_proxy_1gpu.txt).  Smaller grids: single step, replayed through a hipGraph.
-    if (cells >= 1024.0 * 1024.0) v = (v & ~VAR_XCD_ORDER) | VAR_STEP2 | VAR_STEP3;
-    if (cells >= 1280.0 * 1280.0) v |= VAR_STEP4;
+    if (cells >= 1024.0 * 1024.0) v = (v & ~LB_VAR_XCD_ORDER) | LB_VAR_STEP2 | LB_VAR_STEP3;
+    if (cells >= 1280.0 * 1280.0) v |= LB_VAR_STEP4;
     // ... and five wherever four are (k_step5, overlapping strips: periodic 2048^2 298 against 250 k MLUPS, 4096^2 315 against 289 k,
     // 8192^2 327-346 against 306-319 k; pipe 8192^2 346 against 309 k: profiles/r04_experiments.txt section 10), in every family,
     // whole grids and slabs (cycle_depth) alike
-    if (cells >= 1280.0 * 1280.0) v |= VAR_STEP5;
+    if (cells >= 1280.0 * 1280.0) v |= LB_VAR_STEP5;
     // ... and six / seven (k_deep, round 5: ONE wave per SIMD with the next row's gather in flight; kernels_deep.h) on the large whole
     // grids.  k MLUPS, k_step5 / k_deep<6> / k_deep<7>, one box (profiles/r05_size_sweep.txt): periodic 2048^2 281 / 283 / 279,
     // 2560^2 282 / 290 / 302, 4096^2 314 / 345 / 358, 8192^2 342 / 411 / 432 (other boxes: 346 / 436 / 459); pipe 3072^2 280 / 252 / 255,
@@ -89,17 +89,17 @@ int effective_variant(const PlanInputs *s)
                                           : (whole_grid ? 1700.0 : 3800.0);
     // (not the velocity-inlet family: its wall-row bands stop at five steps and k_deep has no instantiation for it)
     if (cells >= deep_side * deep_side && s->p.bc_mode != LB_BC_VELOCITY_INLET) {
-        v |= VAR_STEP6 | VAR_STEP7;     // (slabs: inside the twelve- / fourteen-step halo cycle, cycle_depth)
-        if (whole_grid && !s->multi_slab() && !periodic_box && cells < 2900.0 * 2900.0) v |= VAR_DEEP2;
+        v |= LB_VAR_STEP6 | LB_VAR_STEP7;     // (slabs: inside the twelve- / fourteen-step halo cycle, cycle_depth)
+        if (whole_grid && !s->multi_slab() && !periodic_box && cells < 2900.0 * 2900.0) v |= LB_VAR_DEEP2;
     }
     // Periodic whole grids without a mask, tiles | k_step5 | k_deep<6> | k_deep<7>, k MLUPS, 1680-step runs (profiles/r06q_periodic_small_sweep.txt):
     // 1024^2 214 | 186 | 205 | 195, 1152^2 220 | 227 | 246 | 239, 1280^2 234 | 256 | 263 | 258, 1408^2 242 | 266 | 291 | 287, 1536^2 245 | 291 | 310 | 308,
     // 1792^2 254 | 319 | 364 | 359, 2048^2 210 | 293 | 340 | 364: six steps per pass from 1100^2 cells, seven from 1900^2 (use_tile_kernel:
     // the tiles below 1100^2).
     if (periodic_box && whole_grid && !s->multi_slab() && !s->has_mask) {
-        v &= ~(VAR_STEP6 | VAR_STEP7);
-        if (cells >= 1100.0 * 1100.0) v |= VAR_STEP4 | VAR_STEP5 | VAR_STEP6;
-        if (cells >= 1900.0 * 1900.0) v |= VAR_STEP7;
+        v &= ~(LB_VAR_STEP6 | LB_VAR_STEP7);
+        if (cells >= 1100.0 * 1100.0) v |= LB_VAR_STEP4 | LB_VAR_STEP5 | LB_VAR_STEP6;
+        if (cells >= 1900.0 * 1900.0) v |= LB_VAR_STEP7;
     }
     return v;
 }
@@ -108,7 +108,7 @@ int effective_variant(const PlanInputs *s)
 bool deep2_chosen(const PlanInputs *s)
 {
     if (s->multi_slab() && s->slab_flavour >= 0) return s->slab_flavour == 1;      // lb_set_slab_cycle(7) / (8): the caller's word
-    if (s->variant >= 0) return (s->variant & VAR_DEEP2) != 0;
+    if (s->variant >= 0) return (s->variant & LB_VAR_DEEP2) != 0;
     // Slabs without the caller's word (above: the ranks' collective tuner): by transport.  Beside k_deep<7> (2 x 80 KB of
     // LDS per CU, lone waves) RCCL's send / receive kernel waits for places and slows what it shares SIMDs with; k_deep2<7>'s launches
     // (2 x 72 KB, waves in pairs per SIMD) do not run longer for it, though it still takes most of a launch beside them: one slab of 4 | 2 of an 8192^2 lattice over RCCL 381-392 | 402-450 k MLUPS by k_deep, 443-444 | 466 k by
@@ -116,7 +116,7 @@ bool deep2_chosen(const PlanInputs *s)
     // (profiles/r06s_slab_proxy_deep2.txt).  Every rank of a run shares the transport, so the ranks agree.
     if (s->multi_slab()) return s->transport == SLAB_RCCL;
     if (s->tuned_steps) return s->tuned_steps == 7 && s->tuned_wpc == 8;       // lb_autotune's word
-    return (effective_variant(s) & VAR_DEEP2) != 0;                                // the size table's
+    return (effective_variant(s) & LB_VAR_DEEP2) != 0;                                // the size table's
 }
 
 // The marching kernels address the nine planes of a row through ONE scalar base and a 32-bit byte offset per lane that carries the
@@ -331,7 +331,7 @@ int depth_mask(bool two, bool three, bool four, bool five, bool six, bool seven)
 int slab_step_depths(const PlanInputs *s, int h)
 {
     const int v = effective_variant(s);
-    return depth_mask((v & VAR_STEP2) && step2_applicable(s, h), (v & VAR_STEP3) && step3_applicable(s, h));
+    return depth_mask((v & LB_VAR_STEP2) && step2_applicable(s, h), (v & LB_VAR_STEP3) && step3_applicable(s, h));
 }
 
 // The halo cycle of a slab (slab.cpp): two D-step launches per halo exchange, ghost zone 2D rows deep.
@@ -340,18 +340,18 @@ int slab_step_depths(const PlanInputs *s, int h)
 int cycle_depth(const PlanInputs *s, int h)
 {
     const int v = effective_variant(s);
-    if (!(v & VAR_STEP3) || (v & VAR_NO_CYCLE) || !step3_applicable(s, h) || h < 32) return 0;
+    if (!(v & LB_VAR_STEP3) || (v & LB_VAR_NO_CYCLE) || !step3_applicable(s, h) || h < 32) return 0;
     // (lb_set_slab_cycle: the caller's choice -- the ranks of a run time the candidates together and agree, bench.py / slabs.py --
     //  wherever that depth can run; elsewhere the automatic one)
     if (s->forced_cycle >= 3 && s->forced_cycle <= MAX_DEPTH && h >= 16 * s->forced_cycle &&
         !(s->forced_cycle >= 6 && s->p.bc_mode == LB_BC_VELOCITY_INLET))
         return s->forced_cycle;
     // (k_deep on slabs, round 5: the fourteen- / twelve-step cycle, ghost zone as deep)
-    if ((v & VAR_STEP7) && (v & VAR_STEP6) && (v & VAR_STEP5) && (v & VAR_STEP4) && h >= 112) return 7;
-    if ((v & VAR_STEP6) && (v & VAR_STEP5) && (v & VAR_STEP4) && h >= 96) return 6;
+    if ((v & LB_VAR_STEP7) && (v & LB_VAR_STEP6) && (v & LB_VAR_STEP5) && (v & LB_VAR_STEP4) && h >= 112) return 7;
+    if ((v & LB_VAR_STEP6) && (v & LB_VAR_STEP5) && (v & LB_VAR_STEP4) && h >= 96) return 6;
     // (k_step5 on slabs: the ten-step cycle, ghost zone ten rows deep)
-    if ((v & VAR_STEP5) && (v & VAR_STEP4) && h >= 80) return 5;
-    return ((v & VAR_STEP4) && h >= 64) ? 4 : 3;
+    if ((v & LB_VAR_STEP5) && (v & LB_VAR_STEP4) && h >= 80) return 5;
+    return ((v & LB_VAR_STEP4) && h >= 64) ? 4 : 3;
 }
 
 // Thick edge bands (round 6).  The rows an edge band MUST cover are the 2D next to a slab edge (the halo is cut from them, D ghost rows
@@ -407,14 +407,14 @@ int band_extra(const PlanInputs *s, int D, bool split)
 
 // Which fused depths a whole-grid handle may use: the variant bits (explicit or from the size heuristic), or --
 // once lb_autotune has timed this grid -- everything applicable up to the depth it found fastest.
-// Four steps per pass through LDS tiles (k_tile4) instead of the marching kernels: asked for (VAR_TILES),
+// Four steps per pass through LDS tiles (k_tile4) instead of the marching kernels: asked for (LB_VAR_TILES),
 // found fastest by lb_autotune, or -- automatic -- on whole grids below ~1400^2 cells and on grids the marching
 // kernels do not serve (27 k MLUPS at 256^2, 82 k at 512^2, 120 k at 1024^2, 138 k at 1280^2, against 19 / 57 /
 // 113 / 129 k; from 1536^2 the marching kernel wins, 163 against 153 k: profiles/r01_sweep_variants.txt).
 bool use_tile_kernel(const PlanInputs *s)
 {
     if (!tile_applicable(s)) return false;
-    if (s->variant >= 0) return (s->variant & VAR_TILES) != 0;
+    if (s->variant >= 0) return (s->variant & LB_VAR_TILES) != 0;
     if (s->tuned_steps) return s->tuned_wpc < 0;
     // (walled boxes likewise: pipe 24 / 74 / 112 / 123 k at 256^2 / 512^2 / 1024^2 / 1280^2 against 16.5 / 55 / 95 / 113 k;
     //  marching from 1536^2: 136 against 130 k)
@@ -443,13 +443,13 @@ int whole_grid_depths(const PlanInputs *s)
                           step4_applicable(s) && s->tuned_steps >= 4, step5_applicable(s) && s->tuned_steps >= 5,
                           deep_applicable(s) && s->tuned_steps >= 6, deep_applicable(s) && s->tuned_steps >= 7);
     const int v = effective_variant(s);
-    return depth_mask((v & VAR_STEP2) && step2_applicable(s), (v & VAR_STEP3) && step3_applicable(s), (v & VAR_STEP4) && step4_applicable(s),
-                      (v & VAR_STEP5) && step5_applicable(s), (v & VAR_STEP6) && deep_applicable(s), (v & VAR_STEP7) && deep_applicable(s));
+    return depth_mask((v & LB_VAR_STEP2) && step2_applicable(s), (v & LB_VAR_STEP3) && step3_applicable(s), (v & LB_VAR_STEP4) && step4_applicable(s),
+                      (v & LB_VAR_STEP5) && step5_applicable(s), (v & LB_VAR_STEP6) && deep_applicable(s), (v & LB_VAR_STEP7) && deep_applicable(s));
 }
 
 // the Cython path runs four steps per launch through LDS tiles (k1_tile4) unless the grid is too small for them or an
-// explicit variant without VAR_TILES asks for single steps (k1_fstep)
-bool cython_tiles(const PlanInputs *s) { return s->p.nx >= 64 && s->H >= 64 && (s->variant < 0 || (s->variant & VAR_TILES)); }
+// explicit variant without LB_VAR_TILES asks for single steps (k1_fstep)
+bool cython_tiles(const PlanInputs *s) { return s->p.nx >= 64 && s->H >= 64 && (s->variant < 0 || (s->variant & LB_VAR_TILES)); }
 
 bool autotune_applies(const PlanInputs *s)
 {
@@ -470,7 +470,7 @@ bool tune_entry_runs_here(const PlanInputs *s, int steps, int wpc)
 }
 
 // ---- behind the ABI's lb_plan_launches, lb_steps_per_launch, lb_hot_kernel --------------------------------------------------------
-// Scalar lattices.  An explicit variant decides: its tile bit (VAR_TILES) = k_ad_tile4 for every group of four steps, on any box
+// Scalar lattices.  An explicit variant decides: its tile bit (LB_VAR_TILES) = k_ad_tile4 for every group of four steps, on any box
 // (the kernel wraps or clips its regions itself); without the bit, k_ad_step.  Automatic (-1): by size, the rule below.
 // The size rule (profiles/scalar_bench.txt: k_ad_step and the three tile shapes timed in alternation on one handle, both families, G = 0 and
 // 0.01): the best tile shape ran 2.5-3.0 x k_ad_step's rate at 256^2 (launch-bound: 18-21 k MLUPS against 52-56 k), 2.1-2.3 x at 512^2,
@@ -481,16 +481,16 @@ bool tune_entry_runs_here(const PlanInputs *s, int steps, int wpc)
 static const double SCALAR_TILE_MIN_CELLS = 256.0 * 256.0, SCALAR_TILE_MAX_CELLS = 8192.0 * 8192.0;
 bool scalar_use_tiles(const PlanInputs *s)
 {
-    if (s->variant >= 0) return (s->variant & VAR_TILES) != 0;
+    if (s->variant >= 0) return (s->variant & LB_VAR_TILES) != 0;
     const double cells = (double)s->p.nx * s->H;
     return cells >= SCALAR_TILE_MIN_CELLS && cells <= SCALAR_TILE_MAX_CELLS;
 }
 
-// With an explicit variant the bits that pick k_step's rows per workgroup (VAR_ROWS: meaningless here) pick the tile shape:
+// With an explicit variant the bits that pick k_step's rows per workgroup (LB_VAR_ROWS: meaningless here) pick the tile shape:
 // 0 = by size as for k_tile4, 1 / 2 / 3 = shape 0 / 1 / 2 (32 x 16 two cells per thread, 32 x 16 one, 16 x 16 one).
 int scalar_tile_shape(const PlanInputs *s)
 {
-    if (s->variant >= 0 && (s->variant & VAR_ROWS)) return ((s->variant & VAR_ROWS) >> 2) - 1;
+    if (s->variant >= 0 && (s->variant & LB_VAR_ROWS)) return ((s->variant & LB_VAR_ROWS) >> 2) - 1;
     return tile_shape_of(s);
 }
 

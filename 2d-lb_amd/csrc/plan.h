@@ -19,7 +19,7 @@ struct PlanInputs {
     bool has_mask = false;
     int cu_count = 256;
     int min_h = 0;              // smallest slab height over the ranks (every rank must pick the same schedule)
-    int variant = -1;           // < 0: automatic (effective_variant)
+    int variant = -1;           // < 0: automatic (effective_variant), else an OR of LB_VAR_* (lb_variant_bits)
     int tuned_steps = 0;        // 0: not tuned; else the fused kernel depth (1..7) chosen by lb_autotune
     int tuned_wpc = 0;          // and its waves per CU for the marching kernels (-1: the LDS tiles)
     float depth_cost[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // ms per launch of the d-step kernel as lb_autotune timed it (0: not timed): launch_costs
@@ -80,7 +80,7 @@ int band_extra(const PlanInputs *s, int D, bool split = false);
 int steps_per_launch(const PlanInputs *s);
 int plan_launches(const PlanInputs *s, int n_steps, int *depths, int max_launches);
 void hot_kernel(const PlanInputs *s, char *buf, int buflen);
-// scalar lattices: whether k_ad_tile4 takes the groups of four steps of a run (forced by the variant's tile bit, else by size),
+// scalar lattices: whether k_ad_tile4 takes the groups of four steps of a run (forced by the variant's LB_VAR_TILES, else by size),
 // which of its three shapes, and the time steps of the next launch of a run with `left` steps to go: n = 4a + r as a tile
 // launches, then r single steps (k_ad_step)
 bool scalar_use_tiles(const PlanInputs *s);

@@ -1,30 +1,11 @@
-// plan_consts.h -- the few numbers the kernels and the launch planner (plan.h) must agree on, and the bits of the variant word.
+// plan_consts.h -- the few numbers the kernels and the launch planner (plan.h) must agree on; the bits of the variant word are the
+// public header's (lb_variant_bits).
 // Plain C++: the kernel headers include it for their own use, plan.cpp includes nothing of HIP.  One definition each; why a number
 // has its value is told beside the kernel that uses it.
 #pragma once
 
-// Bits of the kernel variant word (lb_set_variant, include/lb_hip.h; the automatic choice: effective_variant, plan.cpp).  The values
-// are the public ABI's.
-enum VariantBits : int {
-    VAR_NT_STORES = 1 << 0,             // non-temporal stores
-    VAR_NT_LOADS = 1 << 1,              // non-temporal loads (k_step)
-    VAR_ROWS = 3 << 2,                  // rows per workgroup of k_step: 0 -> 4, VAR_ROWS_1 -> 1, VAR_ROWS_2 -> 2
-    VAR_ROWS_1 = 1 << 2,
-    VAR_ROWS_2 = 2 << 2,
-    VAR_XCD_ORDER = 1 << 4,             // XCD-aware tile order (k_step)
-    VAR_STEP2 = 1 << 5,                 // two time steps per pass
-    VAR_STEP3 = 1 << 6,                 // three
-    VAR_NO_CYCLE = 1 << 7,              // slabs exchange their halo after every launch (no halo cycle)
-    VAR_STEP4 = 1 << 8,                 // four
-    VAR_TILES = 1 << 9,                 // four through LDS tiles (k_tile4)
-    VAR_STEP4_NO_AHEAD = 1 << 10,       // A/B: k_step4 without its one-row-ahead gather
-    VAR_NO_PRIO_TURNS = 1 << 11,        // A/B: k_step4 / k_step5 without the priority turns of the two waves of a SIMD
-    VAR_STEP5 = 1 << 12,                // five (k_step5)
-    VAR_TILE_LAUNCH_ORDER = 1 << 13,    // A/B: k_tile4 takes its tiles in launch order
-    VAR_STEP6 = 1 << 14,                // six (k_deep<6>)
-    VAR_STEP7 = 1 << 15,                // with VAR_STEP6: seven (k_deep<7>)
-    VAR_DEEP2 = 1 << 16,                // with VAR_STEP6 | VAR_STEP7: the seven steps by k_deep2<7>
-};
+// LB_VAR_* (the automatic choice: effective_variant, plan.cpp)
+#include "../../include/lb_hip.h"
 
 namespace {
 

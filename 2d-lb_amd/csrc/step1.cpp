@@ -8,14 +8,14 @@ struct L1 {
     static void go(int variant, dim3 grid, dim3 block, hipStream_t st, const StepArgs &a)
     {
 #define LB_LAUNCH(NTL, NTS, XCD) hipLaunchKernelGGL((k_step<BC, MASK, MACRO, NTL, NTS, XCD>), grid, block, 0, st, a)
-        switch (variant & (VAR_NT_LOADS | VAR_NT_STORES | VAR_XCD_ORDER)) {
+        switch (variant & (LB_VAR_NT_LOADS | LB_VAR_NT_STORES | LB_VAR_XCD_ORDER)) {
         case 0: LB_LAUNCH(false, false, false); break;
-        case VAR_NT_STORES: LB_LAUNCH(false, true, false); break;
-        case VAR_NT_LOADS: LB_LAUNCH(true, false, false); break;
-        case VAR_NT_LOADS | VAR_NT_STORES: LB_LAUNCH(true, true, false); break;
-        case VAR_XCD_ORDER: LB_LAUNCH(false, false, true); break;
-        case VAR_XCD_ORDER | VAR_NT_STORES: LB_LAUNCH(false, true, true); break;
-        case VAR_XCD_ORDER | VAR_NT_LOADS: LB_LAUNCH(true, false, true); break;
+        case LB_VAR_NT_STORES: LB_LAUNCH(false, true, false); break;
+        case LB_VAR_NT_LOADS: LB_LAUNCH(true, false, false); break;
+        case LB_VAR_NT_LOADS | LB_VAR_NT_STORES: LB_LAUNCH(true, true, false); break;
+        case LB_VAR_XCD_ORDER: LB_LAUNCH(false, false, true); break;
+        case LB_VAR_XCD_ORDER | LB_VAR_NT_STORES: LB_LAUNCH(false, true, true); break;
+        case LB_VAR_XCD_ORDER | LB_VAR_NT_LOADS: LB_LAUNCH(true, false, true); break;
         default: LB_LAUNCH(true, true, true); break;
         }
 #undef LB_LAUNCH

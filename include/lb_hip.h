@@ -355,26 +355,48 @@ int lb_autotune_quick(lb_sim *s, int max_steps);
  * fused kernel's access shape: corrects rocprofv3 FETCH_SIZE on gfx950 and gives the device's
  * own streaming ceiling. */
 int lb_copy_calibration(lb_sim *s, int nontemporal, int64_t *bytes_moved);
-/* Kernel variant selector for tuning experiments: -1 = automatic (default); otherwise bit 0
- * non-temporal stores, bit 1 non-temporal loads, bits 2-3 rows per workgroup (0: 4, 1: 1, 2: 2),
- * bit 4 XCD-aware tile order, bit 5 two time steps per pass where applicable (nx >= 512), bit 6 three
- * time steps per pass, bit 7 slabs exchange their halo after every launch instead of every two (no
- * halo cycle), bit 8 four time steps per pass (nx >= 512; whole-grid handles of >= 128 rows, slabs of >= 64), bit 9
- * four time steps per pass through 32 x 16 LDS tiles (whole-grid handles of >= 64 x 64 cells; for small grids), bit 10
- * k_step4 without its one-row-ahead gather, bit 11 k_step4 / k_step5 without the priority turns of the two waves of a SIMD,
- * bit 12 five time steps per pass on overlapping strips (k_step5: whole-grid handles where bit 8 applies and slabs of >= 80
- * rows -- the ten-step halo cycle; what the automatic choice takes from 1200^2 periodic / 1850^2 walled cells of a whole
- * grid, 1280^2 cells of a slab or of the velocity-inlet family), bit 14 six and bit 15 (with bit 14) seven time steps per pass
- * (k_deep, one wave per SIMD: whole-grid handles and slabs of >= 96 / 112 rows -- the twelve- / fourteen-step halo cycle --, not
- * the velocity-inlet family; automatic from 1100^2 (six steps; seven from 1900^2) periodic (1250^2 with obstacle-mask cells; slabs: 2400^2) / 1700^2 walled (slabs: 3800^2) cells), bit 16
- * (with bits 14, 15) the seven-step launches by k_deep2 -- two waves per strip and direction, two waves per SIMD (round 6; automatic on walled whole grids of 1700^2 ... 2900^2 cells, one of lb_autotune's candidates), bit 13
- * the LDS-tile kernel takes its tiles in launch order instead of one band of tile rows per XCD (bits 10, 11, 13: A/B
- * switches of things on by default).  Results never depend on it (bitwise); the ranks of one run must use the same value.
- * The library's own names for these bits: VariantBits in 2d-lb_amd/csrc/launchers.h. */
+/* Bits of the kernel variant word of lb_set_variant (below).  A marching kernel of k steps per pass is taken only with every
+ * shallower one: the word for k_step5 is LB_VAR_STEP2 | LB_VAR_STEP3 | LB_VAR_STEP4 | LB_VAR_STEP5.  The values are part of the ABI
+ * (LB_D2Q9/variants.py carries the same names for Python). */
+typedef enum {
+    LB_VAR_NT_STORES = 1 << 0,          /* non-temporal stores */
+    LB_VAR_NT_LOADS = 1 << 1,           /* non-temporal loads (k_step) */
+    LB_VAR_ROWS = 3 << 2,               /* field: rows per workgroup of k_step: 0 -> 4, LB_VAR_ROWS_1 -> 1, LB_VAR_ROWS_2 -> 2 */
+    LB_VAR_ROWS_1 = 1 << 2,
+    LB_VAR_ROWS_2 = 2 << 2,
+    LB_VAR_XCD_ORDER = 1 << 4,          /* XCD-aware tile order (k_step) */
+    LB_VAR_STEP2 = 1 << 5,              /* two time steps per pass where applicable (nx >= 512) */
+    LB_VAR_STEP3 = 1 << 6,              /* three time steps per pass */
+    LB_VAR_NO_CYCLE = 1 << 7,           /* slabs exchange their halo after every launch instead of every two (no halo cycle) */
+    LB_VAR_STEP4 = 1 << 8,              /* four time steps per pass (nx >= 512; whole-grid handles of >= 128 rows, slabs of >= 64) */
+    LB_VAR_TILES = 1 << 9,              /* four time steps per pass through 32 x 16 LDS tiles (k_tile4: whole-grid handles of
+                                         * >= 64 x 64 cells; for small grids) */
+    LB_VAR_STEP4_NO_AHEAD = 1 << 10,    /* A/B switch of a thing on by default: k_step4 without its one-row-ahead gather */
+    LB_VAR_NO_PRIO_TURNS = 1 << 11,     /* A/B switch of a thing on by default: k_step4 / k_step5 without the priority turns of
+                                         * the two waves of a SIMD */
+    LB_VAR_STEP5 = 1 << 12,             /* five time steps per pass on overlapping strips (k_step5: whole-grid handles where
+                                         * LB_VAR_STEP4 applies and slabs of >= 80 rows -- the ten-step halo cycle; what the
+                                         * automatic choice takes from 1200^2 periodic / 1850^2 walled cells of a whole grid,
+                                         * 1280^2 cells of a slab or of the velocity-inlet family) */
+    LB_VAR_TILE_LAUNCH_ORDER = 1 << 13, /* A/B switch of a thing on by default: k_tile4 takes its tiles in launch order instead
+                                         * of one band of tile rows per XCD */
+    LB_VAR_STEP6 = 1 << 14,             /* six time steps per pass (k_deep<6>, one wave per SIMD: whole-grid handles and slabs of
+                                         * >= 96 rows -- the twelve-step halo cycle --, not the velocity-inlet family; automatic
+                                         * from 1100^2 periodic (1250^2 with obstacle-mask cells; slabs: 2400^2) / 1700^2 walled
+                                         * (slabs: 3800^2) cells) */
+    LB_VAR_STEP7 = 1 << 15,             /* with LB_VAR_STEP6: seven time steps per pass (k_deep<7>: as k_deep<6>, slabs of >= 112
+                                         * rows -- the fourteen-step halo cycle; automatic where six are, in a periodic whole grid
+                                         * without a mask from 1900^2 cells) */
+    LB_VAR_DEEP2 = 1 << 16              /* with LB_VAR_STEP6 | LB_VAR_STEP7: the seven-step launches by k_deep2 -- two waves per
+                                         * strip and direction, two waves per SIMD (round 6; automatic on walled whole grids of
+                                         * 1700^2 ... 2900^2 cells, one of lb_autotune's candidates) */
+} lb_variant_bits;
+/* Kernel variant selector for tuning experiments: -1 = automatic (default); otherwise an OR of lb_variant_bits.  Results never
+ * depend on it (bitwise); the ranks of one run must use the same value. */
 int lb_set_variant(lb_sim *s, int variant);
 /* Slab handles (round 6; new work, the reference is single-device: opencl_dim.py:229-240).  Depth of the fused kernel the halo cycle
  * of lb_run runs on (the cycle is 2 x depth time steps between two exchanges): 0 = automatic (the size thresholds of
- * lb_set_variant's bits 12, 14, 15), 3 ... 7 = that depth wherever the smallest slab of the run has >= 16 x depth rows, 8 = seven
+ * LB_VAR_STEP5, LB_VAR_STEP6, LB_VAR_STEP7), 3 ... 7 = that depth wherever the smallest slab of the run has >= 16 x depth rows, 8 = seven
  * steps per launch by k_deep2<7> (two waves per strip and direction, in pairs per SIMD) instead of k_deep<7> (lone waves: RCCL's
  * send / receive kernel slows the launches it runs beside by 5-30 %; k_deep2's do not run longer for it).  With 0 the
  * seven-step cycle runs on k_deep2 under the RCCL transport and on k_deep otherwise.  Results never depend on it (bitwise); EVERY

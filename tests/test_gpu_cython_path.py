@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import golden
+from LB_D2Q9.variants import K_STEP
 from test_oracle_golden import kwargs_of
 
 pytestmark = pytest.mark.gpu
@@ -124,9 +125,9 @@ def test_cython_path_fused_run_equals_phase_calls(lbhip):
         for k in ("f", "rho", "u", "v", "feq"):
             assert np.array_equal(ga[k], gb[k]), (cls.__name__, kw["N"], k)
         assert np.all(np.isfinite(ga["f"]))
-        # single steps only (explicit variant without the tile bit): the same bits again
+        # single steps only (explicit variant without TILES): the same bits again
         c = cls(**kw)
-        c._sim.set_variant(0)
+        c._sim.set_variant(K_STEP)
         c.set_f(f0)
         c.set_fields(g0["rho"], g0["u"], g0["v"])
         c.run(23)

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 from conftest import golden
+from kernel_variants import assert_forced_kernel, same_bits
+from LB_D2Q9.variants import AUTO, K_DEEP2, K_DEEP6, K_DEEP7, K_STEP, K_STEP2, K_STEP3, K_STEP4, K_STEP5, K_TILE4, TILES, marching
 from test_gpu_parity import TOL1, TOLN, assert_fields_close, maxdiff, _random_state
 
 pytestmark = pytest.mark.gpu
@@ -44,7 +46,7 @@ def test_d2q9i_phases_vs_executed_fork(lbhip):
     assert maxdiff(sim.get_fields(("feq",))["feq"], d["feq1"]) <= 2.5e-7
 
 
-@pytest.mark.parametrize("variant", [-1, 0])
+@pytest.mark.parametrize("variant", [AUTO, K_STEP])
 def test_d2q9i_fused_run_vs_executed_fork_over_its_stable_window(lbhip, variant):
     d = golden("o2_d2q9i_53x27")
     sim = _sim(d)
@@ -83,19 +85,18 @@ def test_d2q9i_every_fused_kernel_bitwise_and_vs_oracle(lbhip, oracle, nx, ny, m
         mask[0, :] = mask[-1, :] = False
         mask[:, 0] = mask[:, -1] = False
     outs = []
-    variants = (0, 33, 97, 353, 864, 353 | 4096, 353 | 4096 | 16384, 353 | 4096 | 16384 | 32768, 353 | 4096 | 16384 | 32768 | 65536) if nx >= 512 else (0, -1, 512)
+    variants = (K_STEP, K_STEP2, K_STEP3, K_STEP4, marching(4, nt_stores=False) | TILES, K_STEP5, K_DEEP6, K_DEEP7, K_DEEP2) if nx >= 512 else (K_STEP, AUTO, K_TILE4)
     for variant in variants:
         s = Simulation(nx, ny, 1.0, bc="pipe", inlet_rho=1.0002, obstacle_mask=mask, semantics="d2q9i")
         s.set_variant(variant)
         if nx >= 512:
-            assert s.steps_per_launch() == {0: 1, 33: 2, 97: 3, 353: 4, 864: 4, 4449: 5, 20833: 6, 53601: 7, 119137: 7}[variant]
+            assert_forced_kernel(s, variant)
         assert "D2Q9i" in s.hot_kernel()
         s.set_f(f0)
         s.run(5); s.run(3)
         outs.append(s.get_fields(("f", "rho", "u", "v")))
     for variant, o in zip(variants[1:], outs[1:]):
-        for k in o:
-            assert np.array_equal(outs[0][k], o[k]), (variant, k)
+        same_bits(o, outs[0], variant)
     ref = oracle.O2Sim(nx, ny, 1.0, oracle.BC_PIPE, 1.0002, 1., mask=mask, d2q9i=True)
     ref.set_f(f0)
     ref.run(8)

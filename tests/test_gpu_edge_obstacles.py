@@ -24,6 +24,9 @@ import numpy as np
 import pytest
 
 from conftest import golden
+from kernel_variants import assert_forced_kernel, same_bits
+from LB_D2Q9.variants import (AUTO, K_DEEP2, K_DEEP6, K_DEEP7, K_STEP, K_STEP2, K_STEP3, K_STEP4, K_STEP5, K_TILE4, NO_CYCLE, NT_STORES,
+                              ROWS_2, TILE_LAUNCH_ORDER, TILES, marching)
 from test_gpu_parity import TOL1, TOLN, _random_state, assert_fields_close, contract_tol
 
 pytestmark = pytest.mark.gpu
@@ -31,9 +34,7 @@ pytestmark = pytest.mark.gpu
 FIELDS = ("f", "rho", "u", "v")
 # single step / two-step / + NT stores / three- / four-step / LDS tiles / five-step / k_deep<6> / k_deep<7> / k_deep2<7>:
 # the list of test_two_step_kernel_equals_single_step_kernel
-VARIANTS = (0, 32, 33, 97, 97 | 256, 512, 97 | 256 | 4096, 97 | 256 | 4096 | 16384, 97 | 256 | 4096 | 16384 | 32768,
-            97 | 256 | 4096 | 16384 | 32768 | 65536)
-STEPS_PER_LAUNCH = {0: 1, 32: 2, 33: 2, 97: 3, 353: 4, 512: 4, 864: 4, 4449: 5, 20833: 6, 53601: 7, 119137: 7}
+VARIANTS = (K_STEP, marching(2, nt_stores=False), K_STEP2, K_STEP3, K_STEP4, K_TILE4, K_STEP5, K_DEEP6, K_DEEP7, K_DEEP2)
 # lid_u <= 0.06, noise <= 2 %: the range the oracle was checked in.  The velocity-inlet rule imposes its speed on solid inlet cells
 # too (the reference's moments override comes after the swap), and the executed reference itself is unstable under that: at the 0.03
 # the other tests impose, rho is 0.33 ... 18.9 after 38 steps at 67 x 29 and negative before step 50, at 130 x 130 negative by step
@@ -133,11 +134,6 @@ def engine(bc, nx, ny, omega, mask, f0, variant, uv=None, planar=False, **extra)
     return s
 
 
-def same_bits(got, want, what):
-    for k in FIELDS:
-        assert np.array_equal(got[k], want[k]), (what, k, int((got[k] != want[k]).sum()), "cells differ")
-
-
 def bounced(f, mask):
     """bounceback_in_obstacle on the host: opposite links exchanged on solid cells."""
     f, m = f.copy(), mask.astype(bool)
@@ -178,7 +174,7 @@ def test_unfused_phases_match_reference_kernels_on_boundary_obstacles(lbhip):
     assert np.all(g["u"][m] == 0) and np.all(g["v"][m] == 0)
 
 
-@pytest.mark.parametrize("variant", [0, -1])
+@pytest.mark.parametrize("variant", [K_STEP, AUTO])
 def test_fused_run_matches_reference_on_boundary_obstacles(lbhip, variant):
     d = golden("o2_edge_mask_61x31")
     sim = _fixture_sim(d)
@@ -201,7 +197,7 @@ def test_bc_families_with_boundary_obstacles_vs_oracle(lbhip, oracle, bc, nx, ny
     mask = edge_mask(rng, nx, ny, bc)
     state = rng.bit_generator.state
     sim, ref = make_pair(oracle, bc, nx, ny, 1.3, mask, f0, rng)
-    sim.set_variant(0)
+    sim.set_variant(K_STEP)
     sim.run(1); ref.run(1)
     print("%s %d x %d, 1 step:" % (bc, nx, ny))
     assert_fields_close(sim.get_fields(), ref.get_fields(), TOL1)
@@ -213,7 +209,7 @@ def test_bc_families_with_boundary_obstacles_vs_oracle(lbhip, oracle, bc, nx, ny
     a, _ = make_pair(None, bc, nx, ny, 1.3, mask, f0, rng)
     rng.bit_generator.state = state
     b, _ = make_pair(None, bc, nx, ny, 1.3, mask, f0, rng)
-    a.set_variant(0)
+    a.set_variant(K_STEP)
     for _ in range(5):
         a.run(1)
         b.move(); b.move_bcs(); b.update_hydro(); b.update_feq(); b.collide_particles()
@@ -238,14 +234,7 @@ def test_every_fused_kernel_with_boundary_obstacles(lbhip, oracle, bc, nx, ny):
         for variant in VARIANTS:
             s = engine(bc, nx, ny, 1.6, mask, f0, variant, planar=planar)
             assert s.layout()["planar"] == planar
-            assert s.steps_per_launch() == STEPS_PER_LAUNCH[variant], variant
-            name = s.hot_kernel()
-            if variant & 16384:
-                assert ("k_deep2<7>" if variant & 65536 else "k_deep<%d>" % s.steps_per_launch()) in name, (variant, name)
-            elif variant == 512:
-                assert "k_tile4" in name, name
-            elif variant:
-                assert "k_step%d" % s.steps_per_launch() in name, (variant, name)
+            assert_forced_kernel(s, variant)
             s.run(7)                      # 7 = 1+2+2+2 = 1+3+3 = 3+4 = 2+5 = 1+6 = 7
             s.run(4)
             got = s.get_fields(FIELDS)
@@ -277,10 +266,10 @@ def test_velocity_inlet_fused_kernels_with_boundary_obstacles(lbhip, oracle, nx,
     o.set_f(f0)
     want = None
     for planar in (False, True):
-        for variant in (0, 33, 97, 353, 353 | 4096, -1):
+        for variant in (K_STEP, K_STEP2, K_STEP3, K_STEP4, K_STEP5, AUTO):
             s = engine(bc, nx, ny, 1.25, mask, f0, variant, uv=(u0, v0), planar=planar)
             if variant > 0:
-                assert s.steps_per_launch() == STEPS_PER_LAUNCH[variant] and "k_step%d" % s.steps_per_launch() in s.hot_kernel(), variant
+                assert_forced_kernel(s, variant, max_depth=5)
             s.run(1)
             if want is None:
                 o.run(1)
@@ -309,16 +298,16 @@ def test_tile_kernel_with_boundary_obstacles(lbhip, oracle, bc, nx, ny, solid_wa
     f0 = _random_state(rng, nx, ny)
     mask = edge_mask(rng, nx, ny, bc, solid_wall_rows)
     out = []
-    for variant in (0, 512, 512 | 8192):
+    for variant in (K_STEP, K_TILE4, K_TILE4 | TILE_LAUNCH_ORDER):
         s = engine(bc, nx, ny, 1.45, mask, f0, variant)
         if variant:
-            assert s.steps_per_launch() == 4 and "k_tile4" in s.hot_kernel(), s.hot_kernel()
+            assert_forced_kernel(s, variant)
         s.run(9)                      # 9 = 1 + 4 + 4
         s.run(8)
         out.append(s.get_fields(FIELDS))
         s.close()
-    same_bits(out[1], out[0], (bc, nx, ny, 512))
-    same_bits(out[2], out[0], (bc, nx, ny, 512 | 8192))
+    same_bits(out[1], out[0], (bc, nx, ny, K_TILE4))
+    same_bits(out[2], out[0], (bc, nx, ny, K_TILE4 | TILE_LAUNCH_ORDER))
     code = {"pipe": oracle.BC_PIPE, "cavity": oracle.BC_CAVITY}[bc]
     o = oracle.O2Sim(nx, ny, 1.45, code, KW["inlet_rho"], 1., KW["lid_u"], 1., mask=mask)
     o.set_f(f0)
@@ -338,14 +327,9 @@ def test_wall_column_strips_with_boundary_obstacles_bitwise(lbhip, bc, nx, ny):
     assert mask[:, 0].all() and mask[:, -1].all() and mask[0, ::3].all() and mask[-1, ::3].all()
     f0 = _random_state(rng, nx, ny, 0.01)
     want = None
-    for variant in (9, 353, 353 | 4096, 353 | 4096 | 16384, 353 | 4096 | 16384 | 32768, 353 | 4096 | 16384 | 32768 | 65536):
+    for variant in (NT_STORES | ROWS_2, K_STEP4, K_STEP5, K_DEEP6, K_DEEP7, K_DEEP2):
         s = engine(bc, nx, ny, 1.5, mask, f0, variant, inlet_rho=1.0005, lid_u=0.05)
-        spl = s.steps_per_launch()
-        assert spl == (1 if variant == 9 else 4 if variant == 353 else 7 if variant & 32768 else 6 if variant & 16384 else 5)
-        if variant & 16384:
-            assert ("k_deep2<7>" if variant & 65536 else "k_deep<%d>" % spl) in s.hot_kernel(), s.hot_kernel()
-        elif variant != 9:
-            assert "k_step%d" % spl in s.hot_kernel(), s.hot_kernel()
+        assert_forced_kernel(s, variant)
         s.run(14)
         s.run(3)
         got = s.get_fields(FIELDS)
@@ -369,13 +353,13 @@ def test_d2q9i_every_fused_kernel_with_boundary_obstacles(lbhip, oracle, nx, ny)
     f0 = _random_state(rng, nx, ny, amp=0.001)
     mask = edge_mask(rng, nx, ny, "pipe")
     outs = []
-    variants = (0, 33, 97, 353, 864, 353 | 4096, 353 | 4096 | 16384, 353 | 4096 | 16384 | 32768,
-                353 | 4096 | 16384 | 32768 | 65536) if nx >= 512 else (0, -1, 512)
+    variants = (K_STEP, K_STEP2, K_STEP3, K_STEP4, marching(4, nt_stores=False) | TILES, K_STEP5, K_DEEP6, K_DEEP7,
+                K_DEEP2) if nx >= 512 else (K_STEP, AUTO, K_TILE4)
     for variant in variants:
         s = Simulation(nx, ny, 1.0, bc="pipe", inlet_rho=1.0002, obstacle_mask=mask, semantics="d2q9i")
         s.set_variant(variant)
         if nx >= 512:
-            assert s.steps_per_launch() == STEPS_PER_LAUNCH[variant], variant
+            assert_forced_kernel(s, variant)
         assert "D2Q9i" in s.hot_kernel()
         s.set_f(f0)
         s.run(5); s.run(3)
@@ -448,13 +432,12 @@ def test_cython_path_fused_run_equals_phase_calls_with_wall_overlapping_cylinder
         assert np.array_equal(ga[k], gb[k]), (center, k)
     assert np.all(np.isfinite(ga["f"])) and np.all(ga["u"][m] == 0) and np.all(ga["v"][m] == 0)
     c = lb.Pipe_Flow_Cylinder(**kw)
-    c._sim.set_variant(0)
+    c._sim.set_variant(K_STEP)
     c.set_f(f0)
     c.set_fields(g0["rho"], g0["u"], g0["v"])
     c.run(23)
     gc = c.get_fields()
-    for k in FIELDS:
-        assert np.array_equal(ga[k], gc[k]), (center, "single steps", k)
+    same_bits(ga, gc, (center, "single steps"))
 
 
 # ---- the drop-in class -----------------------------------------------------------------------------------------------
@@ -490,10 +473,10 @@ def test_in_library_slab_schedule_with_boundary_obstacles_bitwise(lbhip, bc, nsl
     f0 = _random_state(rng, nx, ny)
     mask = edge_mask(rng, nx, ny, bc)
     kw = dict(inlet_rho=1.006, lid_u=0.05)
-    one = engine(bc, nx, ny, 1.55, mask, f0, 0, **kw)
+    one = engine(bc, nx, ny, 1.55, mask, f0, K_STEP, **kw)
     one.run(31)
     want = one.get_fields(FIELDS)
-    for variant in (97 | 256 | 4096 | 16384 | 32768, 97 | 256 | 4096 | 16384, 97 | 256 | 4096, 97 | 256, 97, 97 | 128, 33, 1):
+    for variant in (K_DEEP7, K_DEEP6, K_STEP5, K_STEP4, K_STEP3, marching(3) | NO_CYCLE, K_STEP2, NT_STORES):
         ring = LocalSlabRing(nx, ny, 1.55, nslabs, bc=bc, obstacle_mask=mask, **kw)
         ring.set_variant(variant)
         ring.set_f(f0)
@@ -513,10 +496,10 @@ def test_slab_schedule_inside_lb_run_with_boundary_obstacles_single_rank(lbhip, 
     f0 = _random_state(rng, nx, ny)
     mask = edge_mask(rng, nx, ny, bc)
     kw = dict(inlet_rho=1.004, lid_u=0.05)
-    one = engine(bc, nx, ny, 1.4, mask, f0, 0, **kw)
+    one = engine(bc, nx, ny, 1.4, mask, f0, K_STEP, **kw)
     one.run(20 + 7 + 4 + 9)
     want = one.get_fields(FIELDS)
-    for variant in (97 | 256 | 4096 | 16384 | 32768 | 65536, 97 | 256 | 4096 | 16384 | 32768, 97 | 256 | 4096 | 16384, 97 | 256, 97, 33):
+    for variant in (K_DEEP2, K_DEEP7, K_DEEP6, K_STEP4, K_STEP3, K_STEP2):
         s = Simulation(nx, ny, 1.4, bc=bc, obstacle_mask=mask, halo=True, **kw)
         s.set_variant(variant)
         s.comm_init(comm_unique_id(), 0, 1)
@@ -542,7 +525,7 @@ def test_random_configuration_with_boundary_obstacles(lbhip, oracle, seed):
     mask = edge_mask(rng, nx, ny, bc, solid_wall_rows=bool(seed & 2))
     kw = dict(inlet_rho=1.0 + float(rng.uniform(0, 0.01)), lid_u=float(rng.uniform(0, 0.06)))
     f0 = _random_state(rng, nx, ny)
-    base = engine(bc, nx, ny, omega, mask, f0, 0, **kw)
+    base = engine(bc, nx, ny, omega, mask, f0, K_STEP, **kw)
     base.run(steps)
     want = base.get_fields(FIELDS)
     for i, variant in enumerate(rng.choice(RANDOM_VARIANTS, size=4, replace=False)):

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from kernel_variants import assert_forced_kernel
+from LB_D2Q9.variants import AUTO, K_DEEP2, K_DEEP6, K_DEEP7, K_STEP2, K_STEP3, K_STEP4, K_STEP5, NT_STORES, ROWS_2, STEP5
 from test_gpu_parity import TOL1, assert_fields_close, contract_tol, maxdiff
 
 pytestmark = pytest.mark.gpu
@@ -46,13 +48,14 @@ def test_config2_lid_driven_cavity_1024_vs_oracle(lbhip, oracle):
     assert g["u"][n // 2, -1] > 0.05          # the lid drags the top row along
 
 
-@pytest.mark.parametrize("variant,steps", [(9, 2), (33, 2), (97, 3), (353, 4), (353, 8), (4449, 5), (4449, 10), (20833, 6), (20833, 12),
-                                           (-1, 4), (-1, 7), (-1, 14), (119137, 7), (119137, 14), ("tuned", 7)])
+@pytest.mark.parametrize("variant,steps", [(NT_STORES | ROWS_2, 2), (K_STEP2, 2), (K_STEP3, 3), (K_STEP4, 4), (K_STEP4, 8), (K_STEP5, 5),
+                                           (K_STEP5, 10), (K_DEEP6, 6), (K_DEEP6, 12), (AUTO, 4), (AUTO, 7), (AUTO, 14), (K_DEEP2, 7),
+                                           (K_DEEP2, 14), ("tuned", 7)])
 def test_config3_kelvin_helmholtz_4096_vs_oracle(lbhip, oracle, variant, steps):
     """4096x4096 periodic double shear layer against the oracle: single-, two-, three-, four- and five-step kernels
-    (353 = k_step4, 4449 = k_step5, 20833 = k_deep<6> forced, -1 = the automatic choice, which is k_deep<7> at this size: the kernel
+    (K_STEP4, K_STEP5, K_DEEP6 forced, AUTO = the automatic choice, which is k_deep<7> at this size: the kernel
     bench.py times; 4 steps of it = its remainder launch, k_step4), one and two launches of the four- ... seven-step kernel; k_deep2<7>
-    forced (119137) and whatever autotune() picks (the bench's sequence: tune, then the initial state again)."""
+    forced (K_DEEP2) and whatever autotune() picks (the bench's sequence: tune, then the initial state again)."""
     from LB_D2Q9.simulation import Simulation
     import bench
     n = 4096
@@ -67,16 +70,16 @@ def test_config3_kelvin_helmholtz_4096_vs_oracle(lbhip, oracle, variant, steps):
         assert sim.plan_launches(steps) == [7] and ("k_deep<7>" in tuned or "k_deep2<7>" in tuned), tuned
     else:
         sim.set_variant(variant)
-    if variant in (353, 4449, 20833, -1, 119137):
-        assert sim.steps_per_launch() == {353: 4, 4449: 5, 20833: 6, -1: 7, 119137: 7}[variant]
-    if variant in (-1, 119137):
-        assert ("k_deep2<7>" if variant == 119137 else "k_deep<7>") in sim.hot_kernel()
-    if variant == 119137:
+    if variant == AUTO:
+        assert sim.steps_per_launch() == 7 and "k_deep<7>" in sim.hot_kernel()
+    elif variant in (K_STEP4, K_STEP5, K_DEEP6, K_DEEP2):
+        assert_forced_kernel(sim, variant)
+    if variant == K_DEEP2:
         assert sim.plan_launches(steps) == [7] * (steps // 7)
     sim.set_f(f0)
     ref = oracle.O2Sim(n, n, 1.8, oracle.BC_PERIODIC)
     ref.set_f(f0)
-    sim.run(steps); ref.run(steps, openmp=variant in (119137, "tuned"))
+    sim.run(steps); ref.run(steps, openmp=variant in (K_DEEP2, "tuned"))
     # the contract's bound for this many steps (contract_tol: n x the single-step bounds of SURVEY 8c, not fitted to a kernel);
     # measured at 4096^2, round 5's arithmetic (= round 4's): 4 steps f 3.3e-7 rho 1.01e-6; 8 steps f 6.9e-7 rho 1.25e-6
     tol = contract_tol(steps)
@@ -111,7 +114,7 @@ def test_config4_shear_layer_8192_default_kernel_vs_oracle(lbhip, oracle):
     """8192x8192, the bench workload, the bench's initial state, the kernels the bench times (k_deep<7> or k_deep2<7> on segment pairs:
     one launch = 7 steps, two launches = 14) DIRECTLY against the oracle at the size the metric is quoted on -- the same-size field
     comparison the reference's own check makes (testing/Bryan/opencl_check_03.ipynb:593, 778).  Three handles against one oracle run:
-    (a) the static default, k_deep<7>; (b) k_deep2<7> forced (variant 119137); (c) the bench's own sequence -- autotune(), the initial
+    (a) the static default, k_deep<7>; (b) k_deep2<7> forced (K_DEEP2); (c) the bench's own sequence -- autotune(), the initial
     state again, run -- whichever of the two the tuner picks, which must also be the bits of (a) or (b).  The oracle runs its -fopenmp
     build (same bits as the serial one: tests/test_oracle_golden.py).  Bounds: the contract's, n x the single-step ones (contract_tol);
     the measured margins are printed."""
@@ -120,7 +123,7 @@ def test_config4_shear_layer_8192_default_kernel_vs_oracle(lbhip, oracle):
     n = 8192
     fields = bench.shear_layer(n, n, 0, n)
     sims = {}
-    for name, variant in (("default", -1), ("k_deep2<7>", 119137), ("tuned", -1)):
+    for name, variant in (("default", AUTO), ("k_deep2<7>", K_DEEP2), ("tuned", AUTO)):
         sim = Simulation(n, n, 1.7, bc="periodic")
         sim.set_variant(variant)
         sim.init_equilibrium(*fields)                              # f = feq, built on the device, as bench.py does
@@ -175,17 +178,20 @@ def test_config4_shear_layer_8192_default_kernel_vs_oracle(lbhip, oracle):
 
 def test_config4_shear_layer_8192_default_and_four_step_kernel_equal_single_step_kernel_bitwise(lbhip):
     """8192x8192, the bench workload: the default kernel (k_deep<7>: 4 + 4 steps, then the driver's 5 + 10 x 20 steps = 6 + 7 + 7
-    each), the six-step kernel (20833: k_deep<6>), the five-step kernel (variant 4449: the velocity-inlet family's) and the four-step kernel (353) against
-    the single-step kernel (variant 9) on the populations themselves, bit for bit.  The single-step kernel is the one the
+    each), the six-step kernel (K_DEEP6: k_deep<6>), the five-step kernel (K_STEP5: the velocity-inlet family's) and the four-step kernel (K_STEP4) against
+    the single-step kernel (NT_STORES | ROWS_2) on the populations themselves, bit for bit.  The single-step kernel is the one the
     oracle comparisons at <= 4096^2 pin; this carries them to the size the metric is quoted on."""
     from LB_D2Q9.simulation import Simulation
     import bench
     n = 8192
     ref = None
-    for variant in (9, -1, 20833, 4449, 353, 119137):
+    for variant in (NT_STORES | ROWS_2, AUTO, K_DEEP6, K_STEP5, K_STEP4, K_DEEP2):
         sim = Simulation(n, n, 1.7, bc="periodic")
         sim.set_variant(variant)
-        assert sim.steps_per_launch() == {9: 1, -1: 7, 20833: 6, 4449: 5, 353: 4, 119137: 7}[variant]
+        if variant == AUTO:
+            assert sim.steps_per_launch() == 7
+        else:
+            assert_forced_kernel(sim, variant)
         sim.init_equilibrium(*bench.shear_layer(n, n, 0, n))
         f0 = sim.get_fields(("f",))["f"] if ref is None else None
         sim.run(8)
@@ -217,12 +223,15 @@ def test_planar_layout_8192_deep_kernels_equal_single_step_kernel_bitwise(lbhip)
     import bench
     n = 8192
     ref = None
-    for variant in (9, -1, 20833):
+    for variant in (NT_STORES | ROWS_2, AUTO, K_DEEP6):
         sim = Simulation(n, n, 1.7, bc="periodic", planar=True)
         lay = sim.layout()
         assert lay["planar"] and 8 * lay["plane_stride"] * 4 > 2 ** 31
         sim.set_variant(variant)
-        assert sim.steps_per_launch() == {9: 1, -1: 7, 20833: 6}[variant]
+        if variant == AUTO:
+            assert sim.steps_per_launch() == 7
+        else:
+            assert_forced_kernel(sim, variant)
         sim.init_equilibrium(*bench.shear_layer(n, n, 0, n))
         sim.run(14)
         f = sim.get_fields(("f",))["f"]
@@ -241,7 +250,7 @@ def test_planar_layout_8192_deep_kernels_equal_single_step_kernel_bitwise(lbhip)
 def test_full_size_families_default_and_four_step_kernel_equal_single_step_kernel_bitwise(lbhip, bc, masked):
     """8192 x 8192 in the other boundary families, with and without an obstacle mask (the instantiations of k_step5 and k_step4
     the periodic bench never runs: wall rules on the boundary cell, lanes beyond the box, mask history registers): default
-    kernel (k_deep<7> at this size: 4 + 4, 3 steps), six-, five- and four-step kernel and k_deep2<7> (119137: what the tuner may pick)
+    kernel (k_deep<7> at this size: 4 + 4, 3 steps), six-, five- and four-step kernel and k_deep2<7> (K_DEEP2: what the tuner may pick)
     against the single-step kernel, bit for bit."""
     from LB_D2Q9.simulation import Simulation
     import bench
@@ -253,12 +262,13 @@ def test_full_size_families_default_and_four_step_kernel_equal_single_step_kerne
             mask[0, :] = mask[-1, :] = False
             mask[:, 0] = mask[:, -1] = False
     want = None
-    for variant in (9, -1, 353, 4449, 20833, 119137):       # (each result against the single-step kernel's as it arrives)
+    for variant in (NT_STORES | ROWS_2, AUTO, K_STEP4, K_STEP5, K_DEEP6, K_DEEP2):       # (each result against the single-step kernel's as it arrives)
         sim = Simulation(n, n, 1.6, bc=bc, inlet_rho=1.0005, lid_u=0.05, obstacle_mask=mask)
         sim.set_variant(variant)
-        assert sim.steps_per_launch() == {9: 1, -1: 7, 353: 4, 4449: 5, 20833: 6, 119137: 7}[variant]
-        if variant in (-1, 119137):
-            assert ("k_deep2<7>" if variant == 119137 else "k_deep<7>") in sim.hot_kernel(), sim.hot_kernel()
+        if variant == AUTO:
+            assert sim.steps_per_launch() == 7 and "k_deep<7>" in sim.hot_kernel(), sim.hot_kernel()
+        else:
+            assert_forced_kernel(sim, variant)
         sim.init_equilibrium(*bench.shear_layer(n, n, 0, n))
         sim.run(14)
         sim.run(3)
@@ -290,11 +300,11 @@ def test_wall_column_strips_with_shorter_segments_bitwise(lbhip, bc, nx, ny, mas
     u = (0.02 + 1e-3 * rng.standard_normal((nx, ny))).astype(np.float32)
     v = (1e-3 * rng.standard_normal((nx, ny))).astype(np.float32)
     out = []
-    for variant in (353, 9, 353 | 4096, 353 | 4096 | 16384, 353 | 4096 | 16384 | 32768, 353 | 4096 | 16384 | 32768 | 65536):
+    for variant in (K_STEP4, NT_STORES | ROWS_2, K_STEP5, K_DEEP6, K_DEEP7, K_DEEP2):
         sim = Simulation(nx, ny, 1.5, bc=bc, inlet_rho=1.0005, lid_u=0.05, inlet_u=0.02, obstacle_mask=mask)
         sim.set_variant(variant)
-        if variant & 4096:
-            assert sim.steps_per_launch() == ((7 if variant & 32768 else 6) if (variant & 16384) and bc != "velocity_inlet" else 5)
+        if variant & STEP5:
+            assert_forced_kernel(sim, variant, max_depth=5 if bc == "velocity_inlet" else 7)
         sim.init_equilibrium(rho, u, v)
         sim.run(14)
         sim.run(3)
@@ -374,7 +384,7 @@ def test_config5_porous_obstacles_4096_vs_oracle(lbhip, oracle):
     ramp = oracle.density_ramp(n, n, rin, 1.)
     f0 = equilibrium(ramp.astype(np.float64), np.zeros((n, n)), np.zeros((n, n)))
     sims = {}
-    for name, variant in (("static", -1), ("k_deep2<7>", 119137), ("tuned", -1)):
+    for name, variant in (("static", AUTO), ("k_deep2<7>", K_DEEP2), ("tuned", AUTO)):
         sims[name] = s = Simulation(n, n, 1.0, bc="pipe", inlet_rho=rin, outlet_rho=1., obstacle_mask=mask)
         s.set_variant(variant)
         s.set_f(f0)

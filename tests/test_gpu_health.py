@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 
 from conftest import golden
+from kernel_variants import assert_forced_kernel, same_bits
+from LB_D2Q9.variants import AUTO, K_DEEP2, K_DEEP6, K_DEEP7, K_STEP, K_STEP4, K_TILE4
 from test_gpu_parity import _random_state, maxdiff
 
 pytestmark = pytest.mark.gpu
@@ -52,15 +54,15 @@ def test_deep_kernels_store_the_single_step_kernels_fields_when_eager(lbhip, bc,
             mask[0, :] = mask[-1, :] = False
             mask[:, 0] = mask[:, -1] = False
     want = None
-    deep6, deep7, deep2 = 97 | 256 | 4096 | 16384, 97 | 256 | 4096 | 16384 | 32768, 97 | 256 | 4096 | 16384 | 32768 | 65536
-    variants = (0, deep6, deep7, deep2) + ((-1,) if nx * ny >= 2048 * 2048 else ())
+    variants = (K_STEP, K_DEEP6, K_DEEP7, K_DEEP2) + ((AUTO,) if nx * ny >= 2048 * 2048 else ())
     for variant in variants:
         s = Simulation(nx, ny, 1.6, bc=bc, obstacle_mask=mask, eager_macro=True, inlet_rho=1.002, lid_u=0.04)
         s.set_variant(variant)
-        if variant:
-            kernel = {deep6: "k_deep<6>", deep7: "k_deep<7>", deep2: "k_deep2<7>",
-                      -1: "k_deep<7>" if bc == "periodic" else "k_deep2<7>"}[variant]
-            assert s.steps_per_launch() == (6 if variant == deep6 else 7) and kernel in s.hot_kernel(), (variant, s.hot_kernel())
+        if variant == AUTO:
+            kernel = "k_deep<7>" if bc == "periodic" else "k_deep2<7>"
+            assert s.steps_per_launch() == 7 and kernel in s.hot_kernel(), (variant, s.hot_kernel())
+        elif variant:
+            assert_forced_kernel(s, variant)
         s.set_f(f0)
         for n in (7, 14, 6, 13, 1):
             s.run(n)
@@ -69,12 +71,11 @@ def test_deep_kernels_store_the_single_step_kernels_fields_when_eager(lbhip, bc,
         if want is None:
             want = got
             continue
-        for k in want:
-            assert np.array_equal(want[k], got[k]), (variant, k)
+        same_bits(got, want, variant)
 
 
 @pytest.mark.parametrize("bc,kw", FAMILIES)
-@pytest.mark.parametrize("nx,ny,variant", [(67, 29, 0), (1030, 130, -1), (1024, 256, 353), (300, 200, 512)])
+@pytest.mark.parametrize("nx,ny,variant", [(67, 29, K_STEP), (1030, 130, AUTO), (1024, 256, K_STEP4), (300, 200, K_TILE4)])
 def test_fields_on_demand_equal_stored_fields_within_rounding(lbhip, bc, kw, nx, ny, variant):
     from LB_D2Q9.simulation import Simulation
     if bc == "periodic" and nx % 4 and variant > 0:

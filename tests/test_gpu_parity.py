@@ -13,6 +13,9 @@ import numpy as np
 import pytest
 
 from conftest import golden
+from kernel_variants import assert_forced_kernel, same_bits
+from LB_D2Q9.variants import (AUTO, K_DEEP2, K_DEEP6, K_DEEP7, K_STEP, K_STEP2, K_STEP3, K_STEP4, K_STEP5, K_TILE4, NO_CYCLE, NT_STORES,
+                              ROWS_2, TILE_LAUNCH_ORDER, marching)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -131,7 +134,7 @@ def test_fused_opencl_path_kernel_vs_imported_cython_reference_interior(lbhip):
     from LB_D2Q9.simulation import Simulation
     d = golden("o1_pipe_33x17")
     nx, ny = int(d["nx"]), int(d["ny"])
-    for variant in (-1, 0, 512):                       # automatic choice, single-step kernel, LDS-tile kernel (1 step = k_step)
+    for variant in (AUTO, K_STEP, K_TILE4):            # automatic choice, single-step kernel, LDS-tile kernel (1 step = k_step)
         sim = Simulation(nx, ny, float(d["omega"]), bc="pipe", inlet_rho=float(d["inlet_rho"]), outlet_rho=float(d["outlet_rho"]))
         sim.set_variant(variant)
         sim.set_f(np.asarray(d["pre_f"]).transpose(1, 2, 0))        # reference layout (9, nx, ny) -> (nx, ny, 9)
@@ -202,8 +205,8 @@ def test_periodic_mass_drift_tracks_reference(lbhip, oracle):
                                       ("cavity", 777, 201), ("pipe", 2048, 300)])
 @pytest.mark.parametrize("masked", [False, True])
 def test_two_step_kernel_equals_single_step_kernel(lbhip, oracle, bc, nx, ny, masked):
-    """variant bit 5 selects k_step2 (two time steps per pass, register window + lane shuffles), bits 6 / 8 / 12 the three-,
-    four- and five-step kernels, bit 9 the LDS tiles.  Same
+    """STEP2 selects k_step2 (two time steps per pass, register window + lane shuffles), STEP3 / STEP4 / STEP5 the three-,
+    four- and five-step kernels, TILES the LDS tiles.  Same
     per-cell arithmetic as k_step and the library is built with -ffp-contract=on, so the fields must
     be bitwise equal to the single-step kernel's, and match the oracle."""
     from LB_D2Q9.simulation import Simulation
@@ -219,24 +222,19 @@ def test_two_step_kernel_equals_single_step_kernel(lbhip, oracle, bc, nx, ny, ma
     # single step / two-step / + NT stores / three-step (+ two-step remainder) / four-step (+ remainders) /
     # four steps through LDS tiles (+ single-step remainders) / five-step on overlapping strips (+ remainders) /
     # k_deep<6> / k_deep<7> / k_deep2<7>
-    variants = (0, 32, 33, 97, 97 | 256, 512, 97 | 256 | 4096, 97 | 256 | 4096 | 16384, 97 | 256 | 4096 | 16384 | 32768,
-                97 | 256 | 4096 | 16384 | 32768 | 65536)
+    variants = (K_STEP, marching(2, nt_stores=False), K_STEP2, K_STEP3, K_STEP4, K_TILE4, K_STEP5, K_DEEP6, K_DEEP7, K_DEEP2)
     for variant in variants:
         s = Simulation(nx, ny, 1.6, bc=bc, obstacle_mask=mask, **kw)
         s.set_variant(variant)
-        assert s.steps_per_launch() == {0: 1, 32: 2, 33: 2, 97: 3, 353: 4, 512: 4, 4449: 5, 20833: 6, 53601: 7, 119137: 7}[variant]
-        if variant & 16384:
-            assert ("k_deep2<7>" if variant & 65536 else "k_deep<%d>" % s.steps_per_launch()) in s.hot_kernel(), variant
+        assert_forced_kernel(s, variant)
         s.set_f(f0)
         s.run(7)                      # 7 = 1+2+2+2 (two-step) = 1+3+3 (three-step) = 3+4 (four-step) = 2+5 (five-step) = 1+6 = 7
         s.run(4)                      # 4 = 2+2 = 1+3 = 4
         sims.append(s.get_fields(("f", "rho", "u", "v")))
-    for k in ("f", "rho", "u", "v"):
-        assert np.array_equal(sims[1][k], sims[2][k]), k          # NT stores never change results
+    same_bits(sims[2], sims[1], "NT_STORES")                     # NT stores never change results
     # -ffp-contract=on: same rounding in every kernel -- every variant above, bit for bit the single-step kernel's
     for variant, o in zip(variants[1:], sims[1:]):
-        for k in ("f", "rho", "u", "v"):
-            assert np.array_equal(sims[0][k], o[k]), (variant, k)
+        same_bits(o, sims[0], variant)
     code = {"pipe": oracle.BC_PIPE, "periodic": oracle.BC_PERIODIC, "cavity": oracle.BC_CAVITY}[bc]
     o = oracle.O2Sim(nx, ny, 1.6, code, 1.004, 1., 0.06, 1., mask=mask)
     o.set_f(f0)
@@ -257,11 +255,11 @@ def test_run_is_split_into_the_cheapest_launches(lbhip):
     for n in (1, 2, 3, 11, 13, 29, 64, 65, 100, 131):
         p = s.plan_launches(n)
         assert sum(p) == n and all(1 <= d <= 7 for d in p) and (n > 64 or p == sorted(p)), (n, p)
-    s.set_variant(353 | 4096 | 16384)
+    s.set_variant(K_DEEP6)
     assert s.plan_launches(20) == [4, 4, 6, 6] and s.plan_launches(60) == [6] * 10 and s.plan_launches(23) == [5, 6, 6, 6]
-    s.set_variant(353 | 4096)
+    s.set_variant(K_STEP5)
     assert s.plan_launches(20) == [5] * 4 and s.plan_launches(23) == [4, 4, 5, 5, 5]
-    s.set_variant(9)
+    s.set_variant(NT_STORES | ROWS_2)
     assert s.plan_launches(4) == [1, 1, 1, 1]
     slab = Simulation(1024, 256, 1.5, bc="periodic", y0=0, local_ny=128)
     assert slab.plan_launches(8) is None
@@ -286,7 +284,7 @@ def test_launch_plan_follows_the_costs_autotune_measured(lbhip):
     a.run(20)
     a.run(13)
     b = Simulation(nx, ny, 1.6, bc="periodic")
-    b.set_variant(0)
+    b.set_variant(K_STEP)
     b.set_f(f0)
     b.run(used + 33)
     ga, gb = a.get_fields(("f",)), b.get_fields(("f",))
@@ -355,30 +353,28 @@ def test_five_and_six_step_kernel_strip_boundaries(lbhip, bc, nx):
         mask[0, :] = mask[-1, :] = False
         mask[:, 0] = mask[:, -1] = False
     out = []
-    variants = (0, 97 | 256 | 4096, 97 | 256 | 4096 | 16384, 97 | 256 | 4096 | 16384 | 32768, 97 | 256 | 4096 | 16384 | 32768 | 65536)
+    variants = (K_STEP, K_STEP5, K_DEEP6, K_DEEP7, K_DEEP2)
     for variant in variants:
         s = Simulation(nx, ny, 1.55, bc=bc, obstacle_mask=mask, inlet_rho=1.003, lid_u=0.05)
         s.set_variant(variant)
         if variant:
-            spl = 7 if variant & 32768 else (6 if variant & 16384 else 5)
-            assert s.steps_per_launch() == spl and ("k_step5" if spl == 5 else ("k_deep2<7>" if variant & 65536 else "k_deep<%d>" % spl)) in s.hot_kernel()
+            assert_forced_kernel(s, variant)
         s.set_f(f0)
         s.run(12)
         s.run(7)
         out.append(s.get_fields(("f", "rho", "u", "v")))
         s.close()
     for variant, o in zip(variants[1:], out[1:]):
-        for k in out[0]:
-            assert np.array_equal(out[0][k], o[k]), (variant, k)
+        same_bits(o, out[0], variant)
 
 
 @pytest.mark.parametrize("bc,nx,ny", [("pipe", 96, 64), ("periodic", 64, 96), ("cavity", 130, 70), ("periodic", 256, 256),
                                       ("pipe", 301, 101)])
 @pytest.mark.parametrize("masked", [False, True])
 def test_tile_kernel_equals_single_step_kernel_small_grids(lbhip, bc, nx, ny, masked):
-    """k_tile4 (variant bit 9): four time steps per pass inside 32 x 16 LDS tiles, for the small grids the
+    """k_tile4 (TILES): four time steps per pass inside 32 x 16 LDS tiles, for the small grids the
     marching kernels do not serve; tile edges that are not multiples of 32, periodic images, walls, masks; one band of
-    tile rows per XCD (default; tile counts that do not divide by eight) and tiles in launch order (variant bit 13)."""
+    tile rows per XCD (default; tile counts that do not divide by eight) and tiles in launch order (TILE_LAUNCH_ORDER)."""
     from LB_D2Q9.simulation import Simulation
     rng = np.random.default_rng(7 * nx + ny)
     f0 = _random_state(rng, nx, ny)
@@ -390,7 +386,7 @@ def test_tile_kernel_equals_single_step_kernel_small_grids(lbhip, bc, nx, ny, ma
             mask[:, 0] = mask[:, -1] = False
     kw = dict(inlet_rho=1.004, lid_u=0.06)
     out = []
-    for variant in (0, 512, 512 | 8192):
+    for variant in (K_STEP, K_TILE4, K_TILE4 | TILE_LAUNCH_ORDER):
         s = Simulation(nx, ny, 1.45, bc=bc, obstacle_mask=mask, **kw)
         s.set_variant(variant)
         s.set_f(f0)
@@ -398,9 +394,8 @@ def test_tile_kernel_equals_single_step_kernel_small_grids(lbhip, bc, nx, ny, ma
         s.run(8)
         out.append(s.get_fields(("f", "rho", "u", "v")))
         s.close()
-    for k in ("f", "rho", "u", "v"):
-        assert np.array_equal(out[0][k], out[1][k]), k
-        assert np.array_equal(out[0][k], out[2][k]), k
+    same_bits(out[1], out[0], K_TILE4)
+    same_bits(out[2], out[0], K_TILE4 | TILE_LAUNCH_ORDER)
 
 
 # ---- row slabs ---------------------------------------------------------------------------------------
@@ -446,13 +441,13 @@ def test_in_library_slab_schedule_with_two_step_kernel_bitwise(lbhip, bc, nslabs
         mask[:, 0] = mask[:, -1] = False
     kw = dict(inlet_rho=1.006, lid_u=0.05)
     one = Simulation(nx, ny, 1.55, bc=bc, obstacle_mask=mask, **kw)
-    one.set_variant(0)
+    one.set_variant(K_STEP)
     one.set_f(f0)
     # fourteen- / twelve-step cycles of k_deep (slabs of >= 112 / 96 rows; else what fits) / ten-step (k_step5) / eight-step
     # cycles (slabs of >= 64 rows, else six-step) / six-step cycles / three-step launches without the cycle / two-step /
     # single-step kernels on slabs
     first = True
-    for variant in (97 | 256 | 4096 | 16384 | 32768, 97 | 256 | 4096 | 16384, 97 | 256 | 4096, 97 | 256, 97, 97 | 128, 33, 1):
+    for variant in (K_DEEP7, K_DEEP6, K_STEP5, K_STEP4, K_STEP3, marching(3) | NO_CYCLE, K_STEP2, NT_STORES):
         ring = LocalSlabRing(nx, ny, 1.55, nslabs, bc=bc, obstacle_mask=mask, **kw)
         ring.set_variant(variant)
         ring.set_f(f0)
@@ -462,9 +457,7 @@ def test_in_library_slab_schedule_with_two_step_kernel_bitwise(lbhip, bc, nslabs
         if first:
             one.run(31)
             first = False
-        a, b = one.get_fields(("f", "rho", "u", "v")), ring.get_fields(("f", "rho", "u", "v"))
-        for k in a:
-            assert np.array_equal(a[k], b[k]), (variant, k)
+        same_bits(ring.get_fields(("f", "rho", "u", "v")), one.get_fields(("f", "rho", "u", "v")), variant)
 
 
 def test_rccl_self_ring_cycles_with_mask(lbhip):
@@ -476,10 +469,10 @@ def test_rccl_self_ring_cycles_with_mask(lbhip):
     f0 = _random_state(rng, nx, ny)
     mask = rng.random((nx, ny)) < 0.02
     one = Simulation(nx, ny, 1.3, bc="periodic", obstacle_mask=mask)
-    one.set_variant(0)
+    one.set_variant(K_STEP)
     one.set_f(f0)
     one.run(61 + 29 + 4 + 5 + 16 + 7)
-    for variant in (97 | 256 | 4096 | 16384 | 32768, 97 | 256 | 4096 | 16384, 97 | 256, 97, 97 | 128):      # fourteen-, twelve-, eight-step cycle, six-step cycle, no cycle
+    for variant in (K_DEEP7, K_DEEP6, K_STEP4, K_STEP3, marching(3) | NO_CYCLE):      # fourteen-, twelve-, eight-step cycle, six-step cycle, no cycle
         two = Simulation(nx, ny, 1.3, bc="periodic", obstacle_mask=mask, halo=True)
         two.set_variant(variant)
         two.comm_init(comm_unique_id(), 0, 1)
@@ -495,9 +488,7 @@ def test_rccl_self_ring_cycles_with_mask(lbhip):
         two.run(5)                                #   (it reads 2D deep: must exchange first -- was wrong until tools/ring_stress.py)
         two.run(16)                               # full cycles only: leaves 2D-deep ghosts
         two.run(7)                                # eight-step cycle: first half, not last, from 8-deep ghosts
-        a, b = one.get_fields(("f", "rho", "u", "v")), two.get_fields(("f", "rho", "u", "v"))
-        for k in a:
-            assert np.array_equal(a[k], b[k]), (variant, k)
+        same_bits(two.get_fields(("f", "rho", "u", "v")), one.get_fields(("f", "rho", "u", "v")), variant)
         two.close()
 
 
@@ -515,20 +506,18 @@ def test_slab_schedule_inside_lb_run_wall_families_single_rank(lbhip, bc):
     mask[:, 0] = mask[:, -1] = False
     kw = dict(inlet_rho=1.004, lid_u=0.05)
     one = Simulation(nx, ny, 1.4, bc=bc, obstacle_mask=mask, **kw)
-    one.set_variant(0)
+    one.set_variant(K_STEP)
     one.set_f(f0)
     one.run(20 + 7 + 4 + 9)
     want = one.get_fields(("f", "rho", "u", "v"))
-    for variant in (97 | 256 | 4096 | 16384 | 32768 | 65536, 97 | 256 | 4096 | 16384 | 32768, 97 | 256 | 4096 | 16384, 97 | 256, 97, 33):
+    for variant in (K_DEEP2, K_DEEP7, K_DEEP6, K_STEP4, K_STEP3, K_STEP2):
         s = Simulation(nx, ny, 1.4, bc=bc, obstacle_mask=mask, halo=True, **kw)
         s.set_variant(variant)
         s.comm_init(comm_unique_id(), 0, 1)
         s.set_f(f0)
         for n in (20, 7, 4, 9):
             s.run(n)
-        got = s.get_fields(("f", "rho", "u", "v"))
-        for k in want:
-            assert np.array_equal(got[k], want[k]), (variant, k)
+        same_bits(s.get_fields(("f", "rho", "u", "v")), want, variant)
         s.close()
 
 
@@ -568,7 +557,7 @@ def test_slab_cycle_depth_set_by_the_caller_and_exchange_timing(lbhip, transport
     f0 = _random_state(rng, nx, ny)
     mask = rng.random((nx, ny)) < 0.02
     one = Simulation(nx, ny, 1.5, bc="periodic", obstacle_mask=mask)
-    one.set_variant(0)
+    one.set_variant(K_STEP)
     one.set_f(f0)
     one.run(3 * 28 + 9)
     want = one.get_fields(("f",))["f"]
@@ -578,7 +567,7 @@ def test_slab_cycle_depth_set_by_the_caller_and_exchange_timing(lbhip, transport
     for depth, inline in ((7, False), (7, True), (8, False), (8, True), (6, False), (6, True), (5, True), (5, False), (4, False), (3, False)):
         s = Simulation(nx, ny, 1.5, bc="periodic", obstacle_mask=mask, halo=True)
         s.set_obstacle_mask_halo(*_SlabSet._mask_halo_rows(mask, 0, ny, ny, True))
-        s.set_variant(97 | 256 | 4096 | 16384 | 32768)        # every marching kernel allowed; the cycle's depth (and k_deep / k_deep2) is the caller's
+        s.set_variant(K_DEEP7)        # every marching kernel allowed; the cycle's depth (and k_deep / k_deep2) is the caller's
         if transport == "rccl":
             s.comm_init(comm_unique_id(), 0, 1)
         else:
@@ -630,7 +619,7 @@ def test_checkpoint_restart_is_bitwise(lbhip, tmp_path):
     mask[0, :] = mask[-1, :] = False
     mask[:, 0] = mask[:, -1] = False
     a = Simulation(nx, ny, 1.45, bc="pipe", inlet_rho=1.003, obstacle_mask=mask)
-    a.set_variant(33)
+    a.set_variant(K_STEP2)
     a.set_f(_random_state(rng, nx, ny))
     a.run(9)
     path = str(tmp_path / "state.npz")
@@ -734,7 +723,7 @@ def test_pipe_flow_cylinder_published_case_vs_oracle(lbhip, oracle):
     sim = lb.Pipe_Flow_Cylinder(verbose=False, **cyl, **kw)
     np.random.seed(1234)
     single = lb.Pipe_Flow_Cylinder(verbose=False, **cyl, **kw)
-    single._sim.set_variant(0)
+    single._sim.set_variant(K_STEP)
     np.random.seed(1234)
     perturb = 1. + .001 * np.random.randn(sim.nx, sim.ny, 9)
     ref = oracle.O2Sim.pipe_flow(perturb=perturb, **cyl, **kw)
@@ -754,9 +743,7 @@ def test_pipe_flow_cylinder_published_case_vs_oracle(lbhip, oracle):
     got = sim.get_fields()
     print("published case, %d steps:" % steps)
     assert_fields_close(got, ref.get_fields(), contract_tol(steps))
-    want = single.get_fields()
-    for k in ("f", "rho", "u", "v"):
-        assert np.array_equal(got[k], want[k]), k
+    same_bits(got, single.get_fields(), "K_STEP")
 
 
 @pytest.mark.parametrize("bc", ["pipe", "periodic", "cavity"])
@@ -848,16 +835,14 @@ def test_velocity_inlet_fused_kernels_vs_oracle_and_unfused(lbhip, oracle, nx, n
     o.set_macro(np.ones((nx, ny)), u0, v0)
     o.set_f(f0)
     outs = {}
-    variants = [("single", 0), ("two", 33), ("auto", -1)]
+    variants = [("single", K_STEP), ("two", K_STEP2), ("auto", AUTO)]
     if nx >= 512 and ny >= 128:
-        variants += [("three", 97), ("four", 353), ("five", 353 | 4096)]
+        variants += [("three", K_STEP3), ("four", K_STEP4), ("five", K_STEP5)]
     for name, variant in variants:
         s = Simulation(nx, ny, omega, bc="velocity_inlet", inlet_u=uw, outlet_u=ue, obstacle_mask=mask)
         s.set_variant(variant)
-        if variant == 33 and nx >= 512 and ny >= 64:
-            assert s.steps_per_launch() == 2 and "k_step2" in s.hot_kernel()
-        if variant in (97, 353, 353 | 4096):
-            assert s.steps_per_launch() == {97: 3, 353: 4, 4449: 5}[variant]
+        if (variant == K_STEP2 and nx >= 512 and ny >= 64) or variant in (K_STEP3, K_STEP4, K_STEP5):
+            assert_forced_kernel(s, variant, max_depth=5)
         s.set_fields(np.ones((nx, ny)), u0, v0)
         s.set_f(f0)
         s.run(1)
@@ -871,8 +856,7 @@ def test_velocity_inlet_fused_kernels_vs_oracle_and_unfused(lbhip, oracle, nx, n
     o.run(11)
     assert_fields_close(outs["single"], o.get_fields(), dict(f=2e-6, rho=2e-6, u=2e-6, v=2e-6))
     for name in outs:
-        for k in ("f", "rho", "u", "v"):
-            assert np.array_equal(outs["single"][k], outs[name][k]), (name, k)
+        same_bits(outs[name], outs["single"], name)
     # the un-fused phase sequence (opencl_dim.py:380-387 order), also after fused steps have swapped the lattices
     u = Simulation(nx, ny, omega, bc="velocity_inlet", inlet_u=uw, outlet_u=ue, obstacle_mask=mask)
     u.set_fields(np.ones((nx, ny)), u0, v0)
@@ -896,7 +880,7 @@ def test_autotune_is_transparent(lbhip, oracle):
     mask[0, :] = mask[-1, :] = False
     mask[:, 0] = mask[:, -1] = False
     ref = Simulation(nx, ny, 1.3, bc="pipe", inlet_rho=1.002, obstacle_mask=mask)
-    ref.set_variant(0)
+    ref.set_variant(K_STEP)
     ref.set_f(f0)
     a = Simulation(nx, ny, 1.3, bc="pipe", inlet_rho=1.002, obstacle_mask=mask)
     a.set_f(f0)
@@ -915,7 +899,7 @@ def test_autotune_is_transparent(lbhip, oracle):
     b.run(2900)                                   # long blocking first run (a small grid: >= 4 x 721 + 7 steps): tunes itself on the way
     assert b.steps_per_launch() in (1, 2, 3, 4)
     ref2 = Simulation(nx, ny, 1.3, bc="pipe", inlet_rho=1.002, obstacle_mask=mask)
-    ref2.set_variant(0); ref2.set_f(f0); ref2.run(2900)
+    ref2.set_variant(K_STEP); ref2.set_f(f0); ref2.run(2900)
     for k in ("f", "rho", "u", "v"):
         assert np.array_equal(b.get_fields((k,))[k], ref2.get_fields((k,))[k]), k
 
@@ -932,7 +916,7 @@ def test_quick_autotune_advances_at_most_max_steps(lbhip):
     n = 4096
     f0 = _random_state(np.random.default_rng(361), n, n)
     ref = Simulation(n, n, 1.7, bc="periodic")
-    ref.set_variant(0)
+    ref.set_variant(K_STEP)
     ref.set_f(f0)
     a = Simulation(n, n, 1.7, bc="periodic")
     a.set_f(f0)

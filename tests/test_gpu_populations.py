@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import golden
+from LB_D2Q9.variants import K_STEP
 from test_gpu_parity import TOLN, assert_fields_close, _random_state
 
 pytestmark = pytest.mark.gpu
@@ -62,7 +63,7 @@ def test_population_set_streaming_and_batched_step(lbhip, oracle, nx, ny, masked
     g = pops.get_fields()
     for i, om in enumerate(omegas):
         one = Simulation(nx, ny, om, bc="periodic", obstacle_mask=mask)
-        one.set_variant(0)
+        one.set_variant(K_STEP)
         one.set_f(f0[:, :, i, :])
         one.run(11)
         h = one.get_fields(("f", "rho", "u", "v"))

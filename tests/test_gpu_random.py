@@ -6,13 +6,17 @@ import os
 import numpy as np
 import pytest
 
+from kernel_variants import same_bits
+from LB_D2Q9.variants import (AUTO, K_DEEP2, K_DEEP6, K_DEEP7, K_STEP, K_STEP2, K_STEP3, K_STEP4, K_STEP5, K_TILE4, NO_CYCLE, NT_STORES,
+                              ROWS_2, XCD_ORDER, marching)
 from test_gpu_parity import assert_fields_close, _random_state
 
 pytestmark = pytest.mark.gpu
 
 # NT / tile shapes / XCD order / two-, three-, four-step marching kernels / LDS-tile kernel / the automatic choice
-VARIANTS = (1, 9, 16, 24, 33, 41, 97, 105, 97 | 256, 105 | 256, 97 | 256 | 4096, 105 | 256 | 4096, 97 | 256 | 4096 | 16384, 105 | 256 | 4096 | 16384, 97 | 256 | 4096 | 16384 | 32768, 105 | 256 | 4096 | 16384 | 32768,
-            97 | 256 | 4096 | 16384 | 32768 | 65536, 105 | 256 | 4096 | 16384 | 32768 | 65536, 512, 512 | 1, -1)
+VARIANTS = (NT_STORES, NT_STORES | ROWS_2, XCD_ORDER, XCD_ORDER | ROWS_2, K_STEP2, marching(2) | ROWS_2, K_STEP3, marching(3) | ROWS_2,
+            K_STEP4, marching(4) | ROWS_2, K_STEP5, marching(5) | ROWS_2, K_DEEP6, marching(6) | ROWS_2, K_DEEP7, marching(7) | ROWS_2,
+            K_DEEP2, marching(7, deep2=True) | ROWS_2, K_TILE4, K_TILE4 | NT_STORES, AUTO)
 WIDTHS = (2, 3, 5, 63, 64, 65, 255, 256, 257, 511, 512, 513, 600, 768, 1021, 1024, 1028, 1280)
 
 
@@ -36,7 +40,7 @@ def test_random_configuration(lbhip, oracle, seed):
     kw = dict(inlet_rho=1.0 + float(rng.uniform(0, 0.01)), lid_u=float(rng.uniform(0, 0.08)))
     f0 = _random_state(rng, nx, ny)
     base = Simulation(nx, ny, omega, bc=bc, obstacle_mask=mask, **kw)
-    base.set_variant(0)
+    base.set_variant(K_STEP)
     base.set_f(f0)
     base.run(steps)
     want = base.get_fields(("f", "rho", "u", "v"))
@@ -46,9 +50,7 @@ def test_random_configuration(lbhip, oracle, seed):
         s.set_variant(int(variant))
         s.set_f(f0)
         s.run(steps)
-        got = s.get_fields(("f", "rho", "u", "v"))
-        for k in want:
-            assert np.array_equal(got[k], want[k]), (bc, nx, ny, steps, int(variant), bool(i & 1), k)
+        same_bits(s.get_fields(("f", "rho", "u", "v")), want, (bc, nx, ny, steps, int(variant), bool(i & 1)))
         s.close()
     code = {"pipe": oracle.BC_PIPE, "periodic": oracle.BC_PERIODIC, "cavity": oracle.BC_CAVITY}[bc]
     o = oracle.O2Sim(nx, ny, omega, code, kw["inlet_rho"], 1., kw["lid_u"], 1., mask=mask)
@@ -81,9 +83,9 @@ def _random_slab_partition_case(seed):
     nx = int(rng.choice((512, 516, 768, 1000, 1024, 1284)))
     nslabs = int(rng.integers(2, 6))
     ny = int(rng.integers(nslabs * 7, 700))                  # slab heights from 7 rows (no fused kernel) to 350
-    variant = int(rng.choice((-1, 97 | 256 | 4096, 97 | 256, 97, 97 | 128, 33, 1)))
+    variant = int(rng.choice((AUTO, K_STEP5, K_STEP4, K_STEP3, marching(3) | NO_CYCLE, K_STEP2, NT_STORES)))
     if seed % 4 == 3:                                # (the twelve- / fourteen-step cycle: k_deep<6>, k_deep<7>, k_deep2<7> -- from 96 / 112 rows)
-        variant = (97 | 256 | 4096 | 16384, 97 | 256 | 4096 | 16384 | 32768, 97 | 256 | 4096 | 16384 | 32768 | 65536)[(seed // 4) % 3]
+        variant = (K_DEEP6, K_DEEP7, K_DEEP2)[(seed // 4) % 3]
     mask = None
     if rng.integers(0, 2):
         mask = rng.random((nx, ny)) < 0.03
@@ -93,7 +95,7 @@ def _random_slab_partition_case(seed):
     kw = dict(inlet_rho=1.005, lid_u=0.05)
     f0 = _random_state(rng, nx, ny)
     one = Simulation(nx, ny, 1.5, bc=bc, obstacle_mask=mask, **kw)
-    one.set_variant(0)
+    one.set_variant(K_STEP)
     one.set_f(f0)
     ring = LocalSlabRing(nx, ny, 1.5, nslabs, bc=bc, obstacle_mask=mask, **kw)
     ring.set_variant(variant)
@@ -103,9 +105,7 @@ def _random_slab_partition_case(seed):
         ring.run_in_library(int(n))
         total += int(n)
     one.run(total)
-    a, b = one.get_fields(("f", "rho", "u", "v")), ring.get_fields(("f", "rho", "u", "v"))
-    for k in a:
-        assert np.array_equal(a[k], b[k]), (bc, nx, ny, nslabs, variant, total, k)
+    same_bits(ring.get_fields(("f", "rho", "u", "v")), one.get_fields(("f", "rho", "u", "v")), (bc, nx, ny, nslabs, variant, total))
 
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("LB_RANDOM_RING_SEEDS", "16"))))
@@ -118,13 +118,13 @@ def test_random_self_ring(lbhip, seed):
     rng = np.random.default_rng(9000 + (71 if seed == 0 else seed))      # 9071: the case that found the ghost-depth bug
     nx = int(rng.choice((512, 516, 768, 1000, 1024, 1284, 2048)))
     ny = int(rng.integers(8, 700))
-    variant = int(rng.choice((-1, 97 | 256 | 4096, 97 | 256, 97, 97 | 128, 33, 1)))
+    variant = int(rng.choice((AUTO, K_STEP5, K_STEP4, K_STEP3, marching(3) | NO_CYCLE, K_STEP2, NT_STORES)))
     mask = None
     if rng.integers(0, 2):
         mask = rng.random((nx, ny)) < 0.03
     f0 = _random_state(rng, nx, ny)
     one = Simulation(nx, ny, 1.5, bc="periodic", obstacle_mask=mask)
-    one.set_variant(0)
+    one.set_variant(K_STEP)
     one.set_f(f0)
     ring = Simulation(nx, ny, 1.5, bc="periodic", obstacle_mask=mask, halo=True)
     ring.comm_init(comm_unique_id(), 0, 1)
@@ -135,9 +135,7 @@ def test_random_self_ring(lbhip, seed):
     for n in runs:
         ring.run(n)
     one.run(sum(runs))
-    a, b = one.get_fields(("f", "rho", "u", "v")), ring.get_fields(("f", "rho", "u", "v"))
-    for k in a:
-        assert np.array_equal(a[k], b[k]), (nx, ny, variant, runs, k)
+    same_bits(ring.get_fields(("f", "rho", "u", "v")), one.get_fields(("f", "rho", "u", "v")), (nx, ny, variant, runs))
     one.close()
     ring.close()
 

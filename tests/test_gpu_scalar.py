@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import golden
+from LB_D2Q9.variants import AUTO, K_STEP, TILES
 from scalar_model import ScalarModel, W, contract_tol
 
 pytestmark = pytest.mark.gpu
@@ -137,7 +138,6 @@ def test_step_kernel_follows_model_full_size(lbhip, bc, n):
 
 
 # ---- k_ad_tile4 bitwise against k_ad_step ----------------------------------------------------------------------------------------
-VAR_TILES = 1 << 9
 # widths that are and are not multiples of 4, 32 and 64; heights that are not multiples of 16; boxes smaller than one tile
 TILE_BOXES = [(64, 48), (128, 50), (96, 33), (160, 17), (37, 23), (130, 50), (63, 17), (255, 33), (258, 70), (20, 10), (9, 5), (5, 3),
               (4, 2)]
@@ -153,14 +153,14 @@ def assert_same_bits(a, b, what):
 @pytest.mark.parametrize("G", [0., 0.01])
 @pytest.mark.parametrize("shape", [0, 1, 2, 3])       # 0: by size; 1, 2, 3: 32 x 16 two cells per thread, 32 x 16 one, 16 x 16
 def test_tile_kernel_equals_step_kernel_bitwise(lbhip, bc, G, shape):
-    """lb_set_variant(0) forces k_ad_step, the tile bit k_ad_tile4 for every group of four steps (bits 2-3: the shape).  Runs of
+    """K_STEP forces k_ad_step, TILES k_ad_tile4 for every group of four steps (the ROWS field: the shape).  Runs of
     1 ... 13 steps one after the other (1, 1 + 1, ..., 4 + 4 + 4 + 1), each compared bit for bit, on every box."""
     for nx, ny in TILE_BOXES:
         c = random_case(nx, ny, seed=nx * 100 + ny)
         c.update(omega=np.float32(1.35), G=np.float32(G))
         a, b = sim_of(c, bc), sim_of(c, bc)
-        a.set_variant(0)
-        b.set_variant(VAR_TILES | (shape << 2))
+        a.set_variant(K_STEP)
+        b.set_variant(TILES | (shape << 2))         # (shape 1, 2: TILES | ROWS_1, TILES | ROWS_2)
         assert a.plan_launches(13) == [1] * 13 and b.plan_launches(13) == [4, 4, 4, 1] and b.plan_launches(3) == [1, 1, 1]
         assert a.hot_kernel().startswith("k_ad_step") and b.hot_kernel().startswith("k_ad_tile4")
         assert a.steps_per_launch() == 1 and b.steps_per_launch() == 4
@@ -176,8 +176,8 @@ def test_tile_kernel_equals_step_kernel_bitwise_long_run(lbhip, bc, G):
         c = random_case(nx, ny, seed=nx + ny)
         c.update(omega=np.float32(1.7), G=np.float32(G))
         a, b = sim_of(c, bc), sim_of(c, bc)
-        a.set_variant(0)
-        b.set_variant(VAR_TILES | (shape << 2))
+        a.set_variant(K_STEP)
+        b.set_variant(TILES | (shape << 2))         # (shape 1, 2: TILES | ROWS_1, TILES | ROWS_2)
         a.run(403); b.run(403)
         assert_same_bits(a, b, "%s %dx%d G=%g shape %d, 403 steps" % (bc, nx, ny, G, shape))
 
@@ -185,24 +185,24 @@ def test_tile_kernel_equals_step_kernel_bitwise_long_run(lbhip, bc, G):
 def test_tile_kernel_follows_model_and_fixture(lbhip):
     d = golden("ad_fisher_37x23")
     s = sim_of(d)
-    s.set_variant(VAR_TILES)
+    s.set_variant(TILES)
     s.run(200)
     assert_close(s.get_fields(), dict(f=d["f_200"], rho=d["rho_200"], feq=d["feq_200"]), 200, what="ad_fisher tiles")
     for bc in ("periodic", "open"):
         t, m, _ = pair(256, 256, 1.6, 0.01, bc, seed=77)
-        t.set_variant(VAR_TILES)
+        t.set_variant(TILES)
         t.run(40); m.run(40)
         assert_close(t.get_fields(), m.get_fields(), 40, what="%s 256^2 tiles" % bc)
 
 
 def test_automatic_choice_follows_the_size_rule(lbhip):
-    """variant -1: the planner's size rule (plan.cpp, from profiles/scalar_bench.txt): k_ad_tile4 on boxes of 256^2 ... 8192^2 cells,
+    """AUTO: the planner's size rule (plan.cpp, from profiles/scalar_bench.txt): k_ad_tile4 on boxes of 256^2 ... 8192^2 cells,
     k_ad_step below -- and whichever it picks, the bits are k_ad_step's."""
     for n, want in ((96, [1] * 9), (700, [4, 4, 1])):
         c = random_case(n, n, seed=n)
         c.update(omega=np.float32(1.2), G=np.float32(0.))
         a, b = sim_of(c, "open"), sim_of(c, "open")
-        a.set_variant(0)
+        a.set_variant(K_STEP)
         plan = b.plan_launches(9)
         assert plan == want and (b.steps_per_launch() == 4) == (plan[0] == 4)
         assert b.hot_kernel().startswith("k_ad_tile4" if plan[0] == 4 else "k_ad_step")
@@ -298,10 +298,10 @@ def test_set_velocity_from_equals_download_and_set_fields(lbhip, eager):
 # ---- what a scalar handle answers ----------------------------------------------------------------------------------------------
 def test_introspection_and_refusals_on_a_scalar_handle(lbhip):
     s, m, c = pair(96, 40, 1.2, 0.01, "open", seed=7)
-    s.set_variant(0)
+    s.set_variant(K_STEP)
     assert s.plan_launches(6) == [1] * 6 and s.steps_per_launch() == 1
     assert s.hot_kernel().startswith("k_ad_step") and s.hot_kernel().endswith("<OPEN>")
-    s.set_variant(-1)
+    s.set_variant(AUTO)
     chk = s.check()
     assert chk["n_nonfinite"] == 0
     assert chk["sum_rho"] == pytest.approx(float(c["f0"].astype(np.float64).sum()), rel=1e-6)
@@ -313,7 +313,7 @@ def test_introspection_and_refusals_on_a_scalar_handle(lbhip):
     s.set_f(c["f0"])
     lay = s.layout()
     assert lay["pitch"] == 128
-    s.set_variant(0); s.run(3); s.set_variant(VAR_TILES); s.run(6); s.set_variant(-1); s.run(2)
+    s.set_variant(K_STEP); s.run(3); s.set_variant(TILES); s.run(6); s.set_variant(AUTO); s.run(2)
     m.run(11)
     assert_close(s.get_fields(), m.get_fields(), 11, what="variants")
     gbs, nbytes = s.copy_calibration(iters=2)

@@ -166,6 +166,27 @@ def test_mask_halo_rows_of_a_slab_match_the_header():
     assert north[:3].any() == rows(range(ny - 3, ny)).any() and not north[3:].any()
 
 
+def test_variant_names_in_python_match_the_header():
+    """The kernel variant word has one list of names: lb_variant_bits in include/lb_hip.h; LB_D2Q9/variants.py carries the same
+    names without the LB_VAR_ prefix and the same values, neither list has a name the other lacks, and the words the public
+    values have always given stay what they were."""
+    import re
+    from LB_D2Q9 import variants as V
+    hdr = open(os.path.join(os.path.dirname(__file__), "..", "include", "lb_hip.h")).read()
+    header = {name: int(a) << int(b) for name, a, b in re.findall(r"\bLB_VAR_(\w+) = (\d+) << (\d+)", hdr)}
+    assert len(header) == 18 and len(re.findall(r"\bLB_VAR_\w+ =", hdr)) == 18      # (every enumerator is written in that form)
+    module = {name: value for name, value in vars(V).items()
+              if name.isupper() and not name.startswith(("_", "K_")) and name != "AUTO" and isinstance(value, int)}
+    assert module == header
+    assert V.AUTO == -1
+    assert [V.marching(d) for d in range(2, 8)] == [33, 97, 353, 4449, 20833, 53601]
+    assert V.marching(7, deep2=True) == 119137 and V.marching(2, nt_stores=False) == 32
+    assert (V.K_STEP, V.K_STEP2, V.K_STEP3, V.K_STEP4, V.K_STEP5) == (0, 33, 97, 353, 4449)
+    assert (V.K_DEEP6, V.K_DEEP7, V.K_DEEP2, V.K_TILE4) == (20833, 53601, 119137, 512)
+    assert (V.NT_STORES | V.ROWS_2, V.marching(3) | V.NO_CYCLE, V.K_TILE4 | V.TILE_LAUNCH_ORDER, V.marching(4, nt_stores=False) | V.TILES) == (9, 225, 8704, 864)
+    assert V.describe(119137) == "STEP2..7 | NT_STORES | DEEP2" and V.describe(-1) == "AUTO" and V.describe(0) == "K_STEP"
+
+
 # ---- headless frame dumper (reference: field_visualizer.py:146-161) -------------------------------------------
 class _FakeSim(object):
     """run()/get_fields() provider without a GPU: a rigid rotation whose angle grows with the step count."""

@@ -5,7 +5,7 @@
 
 Rank r drives GPU r; the slabs exchange halos over RCCL inside lb_run.  Every rank also runs the UNDIVIDED grid
 on its own GPU with the single-step kernel and compares its rows of the slab run with it bit for bit (no gather).
-Cases: the automatic kernel choice (variant -1) on slabs of 2048 x 1024 cells -- the deepest halo cycle that fits, on
+Cases: the automatic kernel choice (variants.AUTO) on slabs of 2048 x 1024 cells -- the deepest halo cycle that fits, on
 k_step5 that bench.py --gpus N runs -- and every explicit schedule (ten-step, eight-step, six-step cycle, three-step
 launches without the cycle, two-step, single-step) on small slabs; three boundary families, with an obstacle mask;
 step counts that are and are not multiples of the cycle.  Prints one line per case and exits non-zero on a mismatch.
@@ -30,11 +30,13 @@ def main():
     rank, world = dist.get_rank(), dist.get_world_size()
     from LB_D2Q9.simulation import Simulation
     from LB_D2Q9.slabs import DistributedSlab
+    from LB_D2Q9.variants import (AUTO, K_DEEP6, K_DEEP7, K_STEP, K_STEP2, K_STEP3, K_STEP4, K_STEP5, NO_CYCLE, NT_STORES, describe,
+                                  marching)
     w = np.array([4. / 9.] + [1. / 9.] * 4 + [1. / 36.] * 4)
     bad = 0
-    cases = [(2048, 1024 * world, -1, (23, 10, 5))]                      # automatic: ten-step cycle on k_step5
+    cases = [(2048, 1024 * world, AUTO, (23, 10, 5))]                      # automatic: ten-step cycle on k_step5
     if not quick:
-        cases += [(1024, 128 * world, v, (20, 7, 4)) for v in (97 | 256 | 4096 | 16384 | 32768, 97 | 256 | 4096 | 16384, 97 | 256 | 4096, 97 | 256, 97, 97 | 128, 33, 1)]
+        cases += [(1024, 128 * world, v, (20, 7, 4)) for v in (K_DEEP7, K_DEEP6, K_STEP5, K_STEP4, K_STEP3, marching(3) | NO_CYCLE, K_STEP2, NT_STORES)]
     for nx, ny, variant, runs in cases:
         rng = np.random.default_rng(3)
         f0 = (w[None, None, :] * (1 + 0.02 * rng.standard_normal((nx, ny, 9)))).astype(np.float32)
@@ -53,7 +55,7 @@ def main():
                 slab.run(n)
             g = slab.get_local_fields(("f", "rho", "u", "v"))
             one = Simulation(nx, ny, 1.5, bc=bc, obstacle_mask=m, device=dev, **kw)
-            one.set_variant(0)
+            one.set_variant(K_STEP)
             one.set_f(f0)
             one.run(sum(runs))
             h = one.get_fields(("f", "rho", "u", "v"))
@@ -62,8 +64,8 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             bad += int(t[0])
             if rank == 0:
-                print("%d ranks, %dx%d, bc=%s, variant=%d (%d steps per launch), runs=%s: bitwise equal to the undivided "
-                      "run = %s" % (world, nx, ny, bc, variant, spl, list(runs), not int(t[0])), flush=True)
+                print("%d ranks, %dx%d, bc=%s, variant=%d (%s: %d steps per launch), runs=%s: bitwise equal to the undivided "
+                      "run = %s" % (world, nx, ny, bc, variant, describe(variant), spl, list(runs), not int(t[0])), flush=True)
             slab.engine.close()
             one.close()
     dist.barrier()

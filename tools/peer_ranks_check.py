@@ -31,13 +31,16 @@ def child():
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from LB_D2Q9.simulation import Simulation
     from LB_D2Q9.slabs import DistributedSlab
+    from LB_D2Q9.variants import (AUTO, K_DEEP2, K_DEEP6, K_DEEP7, K_STEP, K_STEP2, K_STEP3, K_STEP4, K_STEP5, NO_CYCLE, NT_STORES, describe,
+                                  marching)
     w = np.array([4. / 9.] + [1. / 9.] * 4 + [1. / 36.] * 4)
     bad = 0
-    cases = [(2048, 1024 * world, -1, (33, 14, 5), ("periodic",))] if not quick else []       # automatic: fourteen-step cycle on k_deep<7>
+    cases = [(2048, 1024 * world, AUTO, (33, 14, 5), ("periodic",))] if not quick else []       # automatic: fourteen-step cycle on k_deep<7>
     # explicit schedules on small slabs: ten-step cycle, eight-step cycle, six-step cycle, three-step launches without the cycle,
     # two-step, single-step
     cases += [(1024, 128 * world + 5, v, (20, 7, 4), ("periodic", "pipe", "cavity"))
-              for v in ((97 | 256 | 4096 | 16384 | 32768 | 65536, 97 | 256 | 4096 | 16384 | 32768, 97 | 256 | 4096 | 16384, 97 | 256 | 4096, 97 | 256, 97, 97 | 128, 33, 1) if not quick else (97 | 256 | 4096 | 16384 | 32768 | 65536, 97 | 256 | 4096 | 16384 | 32768, 97 | 256 | 4096, 97 | 256, 1))]
+              for v in ((K_DEEP2, K_DEEP7, K_DEEP6, K_STEP5, K_STEP4, K_STEP3, marching(3) | NO_CYCLE, K_STEP2, NT_STORES) if not quick
+                        else (K_DEEP2, K_DEEP7, K_STEP5, K_STEP4, NT_STORES))]
     for nx, ny, variant, runs, families in cases:
         rng = np.random.default_rng(3)
         f0 = (w[None, None, :] * (1 + 0.02 * rng.standard_normal((nx, ny, 9)))).astype(np.float32)
@@ -57,7 +60,7 @@ def child():
                 slab.run(n)                      # (waits: lb_sync reports a neighbour that never arrived)
             g = slab.get_local_fields(("f", "rho", "u", "v"))
             one = Simulation(nx, ny, 1.5, bc=bc, obstacle_mask=m, device=dev, **kw)
-            one.set_variant(0)
+            one.set_variant(K_STEP)
             one.set_f(f0)
             one.run(sum(runs))
             h = one.get_fields(("f", "rho", "u", "v"))
@@ -66,8 +69,8 @@ def child():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             bad += int(t[0])
             if rank == 0:
-                print("%d rank processes (peer transport), %dx%d, bc=%s, variant=%d (%d steps per launch), runs=%s: bitwise equal "
-                      "to the undivided run = %s" % (world, nx, ny, bc, variant, spl, list(runs), not int(t[0])), flush=True)
+                print("%d rank processes (peer transport), %dx%d, bc=%s, variant=%d (%s: %d steps per launch), runs=%s: bitwise equal "
+                      "to the undivided run = %s" % (world, nx, ny, bc, variant, describe(variant), spl, list(runs), not int(t[0])), flush=True)
             dist.barrier()                       # nobody unmaps a lattice a neighbour may still be storing into
             slab.engine.close()
             one.close()

@@ -14,13 +14,14 @@ sys.path[:0] = [os.path.join(ROOT, "2d-lb_amd"), ROOT, os.path.join(ROOT, "tests
 def main():
     seeds = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     from LB_D2Q9.simulation import Simulation, comm_unique_id
+    from LB_D2Q9.variants import AUTO, K_STEP, K_STEP2, K_STEP3, K_STEP4, K_STEP5, NO_CYCLE, NT_STORES, describe, marching
     from test_gpu_parity import _random_state
     bad = 0
     for seed in range(seeds):
         rng = np.random.default_rng(9000 + seed)
         nx = int(rng.choice((512, 516, 768, 1000, 1024, 1284, 2048)))
         ny = int(rng.integers(8, 700))
-        variant = int(rng.choice((-1, 97 | 256 | 4096, 97 | 256, 97, 97 | 128, 33, 1)))
+        variant = int(rng.choice((AUTO, K_STEP5, K_STEP4, K_STEP3, marching(3) | NO_CYCLE, K_STEP2, NT_STORES)))
         mask = None
         if rng.integers(0, 2):
             mask = rng.random((nx, ny)) < 0.03
@@ -33,7 +34,7 @@ def main():
             mask[0, :] = mask[-1, :] = False
             mask[:, 0] = mask[:, -1] = False
         one = Simulation(nx, ny, 1.5, bc=bc, obstacle_mask=mask, **kw)
-        one.set_variant(0)
+        one.set_variant(K_STEP)
         one.set_f(f0)
         ring = Simulation(nx, ny, 1.5, bc=bc, obstacle_mask=mask, halo=True, **kw)
         ring.comm_init(comm_unique_id(), 0, 1)
@@ -51,8 +52,8 @@ def main():
                 if d.ndim == 3:
                     d = d.any(axis=2)
                 rows = np.nonzero(d.any(axis=0))[0]
-                print("seed %d %s %dx%d variant %d runs %s mask %d: %s differs in %d cells, rows %d..%d" % (
-                    seed, bc, nx, ny, variant, runs, mask is not None, k, int(d.sum()), rows.min(), rows.max()), flush=True)
+                print("seed %d %s %dx%d variant %d (%s) runs %s mask %d: %s differs in %d cells, rows %d..%d" % (
+                    seed, bc, nx, ny, variant, describe(variant), runs, mask is not None, k, int(d.sum()), rows.min(), rows.max()), flush=True)
         one.close()
         ring.close()
     print("%d seeds, %d mismatching fields" % (seeds, bad))

@@ -24,6 +24,7 @@ def main():
     ap.add_argument("--variant", type=int, default=-1)
     a = ap.parse_args()
     from LB_D2Q9.simulation import Simulation
+    from LB_D2Q9.variants import describe
     from bench import shear_layer
     mask = None
     ny = a.ny or a.n
@@ -42,8 +43,8 @@ def main():
     sim.init_equilibrium(*shear_layer(a.n, ny, 0, ny))
     sim.run(a.steps)
     ms = min(sim.timed_run(a.steps) for _ in range(a.repeat))
-    print("%s %dx%d mask=%d variant=%d [%s]: %.1f MLUPS, %.1f us per step" % (
-        a.bc, a.n, ny, bool(a.mask or a.cyl or a.tiff), a.variant, sim.hot_kernel(), a.n * ny * a.steps / ms / 1e3, ms * 1e3 / a.steps))
+    print("%s %dx%d mask=%d variant=%d (%s) [%s]: %.1f MLUPS, %.1f us per step" % (
+        a.bc, a.n, ny, bool(a.mask or a.cyl or a.tiff), a.variant, describe(a.variant), sim.hot_kernel(), a.n * ny * a.steps / ms / 1e3, ms * 1e3 / a.steps))
 
 
 if __name__ == "__main__":

@@ -4,7 +4,7 @@
     python tools/scalar_bench.py [--sizes 512,1024,2048,4096,8192] [--steps 40] [--rounds 3] > profiles/scalar_bench.txt
 
 For every box size, both families (periodic, open) and G = 0 / G != 0: the engine's timers around lb_run(steps) with
-k_ad_step forced (variant 0) and with k_ad_tile4 forced in each of its three shapes (variant bit 9, shape in bits 2-3), taken
+k_ad_step forced (K_STEP) and with k_ad_tile4 forced in each of its three shapes (TILES, the shape in the ROWS field), taken
 `rounds` times IN ALTERNATION -- step, tile shape 0, 1, 2, copy, step, ... -- on the same handle, with lb_copy_calibration (a
 16-byte-per-lane copy of one lattice into the other: known bytes, the streaming ceiling in the kernel's own access shape);
 best of the rounds.  Printed per case: MLUPS of each, k_ad_step's compulsory traffic 80 B x updates / time (72 B of
@@ -21,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "2d-lb_amd"))
 
 from LB_D2Q9.simulation import Simulation      # noqa: E402
+from LB_D2Q9.variants import K_STEP, TILES     # noqa: E402
 
 W = np.array([4. / 9.] + [1. / 9.] * 4 + [1. / 36.] * 4, dtype=np.float32)
 
@@ -36,7 +37,7 @@ def case(n, bc, G, steps, rounds):
     f0[:] = 0.5 * W[None, None, :]
     s.set_f(f0)
     del f0
-    variants = [0] + [(1 << 9) | (k << 2) for k in (1, 2, 3)]      # k_ad_step; k_ad_tile4 shapes 0, 1, 2
+    variants = [K_STEP] + [TILES | (k << 2) for k in (1, 2, 3)]      # k_ad_step; k_ad_tile4 shapes 0, 1, 2
     for v in variants:                              # warm-up
         s.set_variant(v)
         s.run(steps)

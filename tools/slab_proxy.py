@@ -36,6 +36,7 @@ def main():
         dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
         dist.barrier()
     from LB_D2Q9.simulation import Simulation, comm_unique_id
+    from LB_D2Q9.variants import describe
     from bench import shear_layer
     for parts in [int(p) for p in args.parts.split(",")]:
         ny = args.nx // parts
@@ -76,9 +77,9 @@ def main():
                         st["cycle_depth"], st["band_rows"], 1e3 * st["total_ms"] / max(1, st["n"]), 1e3 * st["max_ms"])
                 sim.close()
             for mode in modes[1:]:
-                print("grid %5d x %5d (1/%d of %d^2) variant %3d: plain %9.1f MLUPS, slab path (%s) %9.1f MLUPS "
+                print("grid %5d x %5d (1/%d of %d^2) variant %3d (%s): plain %9.1f MLUPS, slab path (%s) %9.1f MLUPS "
                       "(%.1f us/step GPU, %.0f us/step host enqueue; %s) -> x%d = %9.1f"
-                      % (args.nx, ny, parts, args.nx, variant, res["plain"], mode[5:], res[mode],
+                      % (args.nx, ny, parts, args.nx, variant, describe(variant), res["plain"], mode[5:], res[mode],
                          args.nx * ny / res[mode], res[mode + "_host_us"], res[mode + "_xchg"], parts, parts * res[mode]), flush=True)
 
 

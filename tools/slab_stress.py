@@ -29,6 +29,7 @@ def main():
     nnoise = int(sys.argv[2]) if len(sys.argv) > 2 else 3
     from LB_D2Q9.simulation import Simulation
     from LB_D2Q9.slabs import LocalSlabRing, partition_rows
+    from LB_D2Q9.variants import AUTO, K_STEP, K_STEP2, K_STEP3, K_STEP4, NO_CYCLE, NT_STORES, describe, marching
     from test_gpu_parity import _random_state
     noise = [subprocess.Popen([sys.executable, "-c", NOISE]) for _ in range(nnoise)]
     bad = 0
@@ -39,7 +40,7 @@ def main():
             nx = int(rng.choice((512, 516, 768, 1000, 1024, 1284)))
             nslabs = int(rng.integers(2, 6))
             ny = int(rng.integers(nslabs * 7, 700))
-            variant = int(rng.choice((-1, 97 | 256, 97, 97 | 128, 33, 1)))
+            variant = int(rng.choice((AUTO, K_STEP4, K_STEP3, marching(3) | NO_CYCLE, K_STEP2, NT_STORES)))
             mask = None
             if rng.integers(0, 2):
                 mask = rng.random((nx, ny)) < 0.03
@@ -49,7 +50,7 @@ def main():
             kw = dict(inlet_rho=1.005, lid_u=0.05)
             f0 = _random_state(rng, nx, ny)
             one = Simulation(nx, ny, 1.5, bc=bc, obstacle_mask=mask, **kw)
-            one.set_variant(0)
+            one.set_variant(K_STEP)
             one.set_f(f0)
             ring = LocalSlabRing(nx, ny, 1.5, nslabs, bc=bc, obstacle_mask=mask, **kw)
             ring.set_variant(variant)
@@ -74,8 +75,8 @@ def main():
                             runs_of_rows[-1][1] = int(r)
                         else:
                             runs_of_rows.append([int(r), int(r)])
-                    print("seed %d %s %dx%d slabs %d variant %d runs %s mask %d: %s differs in %d cells, rows %s, cols %d..%d; "
-                          "partition %s" % (seed, bc, nx, ny, nslabs, variant, runs, mask is not None, k, int(d.sum()),
+                    print("seed %d %s %dx%d slabs %d variant %d (%s) runs %s mask %d: %s differs in %d cells, rows %s, cols %d..%d; "
+                          "partition %s" % (seed, bc, nx, ny, nslabs, variant, describe(variant), runs, mask is not None, k, int(d.sum()),
                                             runs_of_rows, cols.min(), cols.max(), parts), flush=True)
             one.close()
             for s in ring.slabs:

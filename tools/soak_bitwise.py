@@ -5,6 +5,7 @@ import os, sys, numpy as np
 ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
 sys.path[:0] = [os.path.join(ROOT, "2d-lb_amd"), ROOT]
 from LB_D2Q9.simulation import Simulation
+from LB_D2Q9.variants import AUTO, NT_STORES, ROWS_2, describe
 def case(bc, nx, ny, steps, masked, **kw):
     rng = np.random.default_rng(3)
     mask = None
@@ -15,7 +16,8 @@ def case(bc, nx, ny, steps, masked, **kw):
     u = (0.02 + 1e-3 * rng.standard_normal((nx, ny))).astype(np.float32)
     v = (1e-3 * rng.standard_normal((nx, ny))).astype(np.float32)
     out = []
-    for variant in (int(os.environ.get("LB_SOAK_VARIANT", "-1")), 9):       # (LB_SOAK_VARIANT=119137: k_deep2 for the seven-step launches)
+    variants = (int(os.environ.get("LB_SOAK_VARIANT", AUTO)), NT_STORES | ROWS_2)       # (LB_SOAK_VARIANT = variants.K_DEEP2: k_deep2 for the seven-step launches)
+    for variant in variants:
         s = Simulation(nx, ny, 1.2, bc=bc, obstacle_mask=mask, **kw)
         s.set_variant(variant)
         s.init_equilibrium(rho, u, v)
@@ -24,7 +26,7 @@ def case(bc, nx, ny, steps, masked, **kw):
         out.append(s.get_fields(("f", "rho", "u", "v")))
         s.close()
     ok = all(np.array_equal(out[0][k], out[1][k]) for k in out[0]) and np.all(np.isfinite(out[0]["f"]))
-    print(bc, nx, ny, steps, "mask" if masked else "", "bitwise equal" if ok else "MISMATCH", flush=True)
+    print(bc, nx, ny, steps, "mask" if masked else "", describe(variants[0]), "bitwise equal" if ok else "MISMATCH", flush=True)
 case("pipe", 4096, 4096, 403, True, inlet_rho=1.0005)
 case("velocity_inlet", 4096, 1000, 401, False, inlet_u=0.02)
 case("cavity", 3000, 3000, 402, False, lid_u=0.05)

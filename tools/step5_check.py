@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""k_step5 (variant bit 12) against the single-step kernel (bitwise) and against k_step4 (time).
+"""k_step5 (variants.K_STEP5) against the single-step kernel (bitwise) and against k_step4 (time).
 
     python tools/step5_check.py [--no-time] [--sizes 8192,4096]
 """
@@ -11,14 +11,15 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "2d-lb_amd"))
 from LB_D2Q9.simulation import Simulation  # noqa: E402
+from LB_D2Q9.variants import K_DEEP2, K_DEEP6, K_DEEP7, K_STEP, describe, marching      # noqa: E402
 
 W = np.array([4. / 9.] + [1. / 9.] * 4 + [1. / 36.] * 4)
-SIX = "--six" in sys.argv                       # k_deep<6> (variant bit 14) instead of k_step5 (bit 12)
-SEVEN = "--seven" in sys.argv                   # k_deep<7> (variant bit 15)
-DEEP2 = "--deep2" in sys.argv                   # k_deep2 (variant bit 16: the seven-step launches by two waves per strip and direction)
+SIX = "--six" in sys.argv                       # k_deep<6> (STEP6) instead of k_step5
+SEVEN = "--seven" in sys.argv                   # k_deep<7> (STEP7)
+DEEP2 = "--deep2" in sys.argv                   # k_deep2 (DEEP2: the seven-step launches by two waves per strip and direction)
 SEVEN = SEVEN or DEEP2
-DEEP = 97 | 256 | 4096 | (16384 if SIX or SEVEN else 0) | (32768 if SEVEN else 0) | (65536 if DEEP2 else 0)
 DEEP_SPL = 7 if SEVEN else (6 if SIX else 5)
+DEEP = marching(DEEP_SPL, deep2=DEEP2)
 
 
 def state(rng, nx, ny, amp=0.02):
@@ -38,7 +39,7 @@ def bitwise():
             mask[0, :] = mask[-1, :] = False
             mask[:, 0] = mask[:, -1] = False
         out = []
-        for variant in (0, DEEP):
+        for variant in (K_STEP, DEEP):
             kw = dict(inlet_rho=1.004, lid_u=0.06)
             if bc == "pipe_i":
                 s = Simulation(nx, ny, 1.6, bc="pipe", obstacle_mask=mask, semantics="d2q9i", **kw)
@@ -60,15 +61,14 @@ def bitwise():
                 d = np.abs(out[0][k].astype(np.float64) - out[1][k])
                 idx = np.argwhere(d > 0)
                 print("MISMATCH", bc, nx, ny, masked, k, "max", d.max(), "n", len(idx), "first", idx[:5].tolist())
-        print("checked", bc, nx, ny, "mask" if masked else "")
+        print("checked", bc, nx, ny, "mask" if masked else "", describe(DEEP))
     return bad
 
 
 def timing(sizes):
     for n in sizes:
         for bc in ("periodic", "pipe"):
-            for name, variant in (("k_deep<6>", 353 | 4096 | 16384), ("k_deep<7>", 353 | 4096 | 16384 | 32768), ("k_deep2<7>", 353 | 4096 | 16384 | 32768 | 65536),
-                                  ("k_deep<6>", 353 | 4096 | 16384), ("k_deep<7>", 353 | 4096 | 16384 | 32768), ("k_deep2<7>", 353 | 4096 | 16384 | 32768 | 65536)):
+            for name, variant in (("k_deep<6>", K_DEEP6), ("k_deep<7>", K_DEEP7), ("k_deep2<7>", K_DEEP2)) * 2:
                 s = Simulation(n, n, 1.7, bc=bc, inlet_rho=1.003)
                 s.set_variant(variant)
                 spl = s.steps_per_launch()
@@ -78,8 +78,8 @@ def timing(sizes):
                 best = 1e9
                 for _ in range(3):
                     best = min(best, s.timed_run(launches * spl))
-                print("%5d^2 %-8s %s steps/launch %d  %.1f k MLUPS  (%.3f ms per launch)" % (
-                    n, bc, name, spl, n * n * launches * spl / best / 1e6, best / launches), flush=True)
+                print("%5d^2 %-8s %s (%s) steps/launch %d  %.1f k MLUPS  (%.3f ms per launch)" % (
+                    n, bc, name, describe(variant), spl, n * n * launches * spl / best / 1e6, best / launches), flush=True)
                 s.close()
 
 

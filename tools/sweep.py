@@ -3,8 +3,7 @@
 
 Times the fused step for every (variant, grid) pair inside ONE process, interleaved over rounds
 (cdna_hip_programming.md section 5.4 rule 24), and prints MLUPS / GB/s / fraction of 8 TB/s.
-variant bits: 0 = non-temporal stores, 1 = non-temporal loads, 2-3 = rows per block (0:4, 1:1, 2:2),
-4 = XCD-aware tile order, 5 = two time steps per pass (k_step2).
+The variant words: LB_D2Q9/variants.py (the default: K_STEP, NT_STORES, NT_STORES | ROWS_2, STEP2, K_STEP2).
 """
 import argparse
 import os
@@ -26,6 +25,7 @@ def main():
     ap.add_argument("--mask", action="store_true")
     args = ap.parse_args()
     from LB_D2Q9.simulation import Simulation
+    from LB_D2Q9.variants import describe
     from bench import shear_layer
     for n in [int(s) for s in args.sizes.split(",")]:
         mask = None
@@ -47,8 +47,8 @@ def main():
             print("n=%5d float4 copy (nt=%d): %.1f GB/s (%.0f MB per launch)" % (n, nt, gbs, nb / 1e6), flush=True)
         for v in variants:
             best, med = max(res[v]), float(np.median(res[v]))
-            print("n=%5d bc=%s mask=%d variant=%2d  MLUPS best %9.1f median %9.1f  -> %7.1f GB/s  %.3f of 8 TB/s"
-                  % (n, args.bc, int(args.mask), v, best, med, med * 72e-3, med * 72e-3 / 8000.), flush=True)
+            print("n=%5d bc=%s mask=%d variant=%2d (%s)  MLUPS best %9.1f median %9.1f  -> %7.1f GB/s  %.3f of 8 TB/s"
+                  % (n, args.bc, int(args.mask), v, describe(v), best, med, med * 72e-3, med * 72e-3 / 8000.), flush=True)
         sim.close()
 
 

@@ -9,6 +9,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "2d-lb_amd"))
 from LB_D2Q9.simulation import Simulation  # noqa: E402
+from LB_D2Q9.variants import describe       # noqa: E402
 
 
 def main():
@@ -29,8 +30,8 @@ def main():
             s.run(2 * spl)
             s.sync()
             best = min(s.timed_run(launches * spl) for _ in range(3))
-            print("%s %-8s variant %5d steps/launch %d  %7.1f k MLUPS  %.4f ms per launch  %s" % (
-                size, bc, v, spl, nx * ny * launches * spl / best / 1e6, best / launches,
+            print("%s %-8s variant %5d (%s) steps/launch %d  %7.1f k MLUPS  %.4f ms per launch  %s" % (
+                size, bc, v, describe(v), spl, nx * ny * launches * spl / best / 1e6, best / launches,
                 " ".join("%s=%s" % (k, os.environ[k]) for k in sorted(os.environ) if k.startswith("LB_") and k != "LB_LIB")), flush=True)
             s.close()
 

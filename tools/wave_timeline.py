@@ -16,13 +16,15 @@ def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
     ny = int(os.environ.get("LB_TIMELINE_NY", n))
     from LB_D2Q9.simulation import Simulation
+    from LB_D2Q9.variants import DEEP2, marching
     from bench import shear_layer
     # (the records travel in the rho array: no launch stores rho, u, v on this handle, and LB_DIAG bit 12 keeps lb_get_macro
     #  from rebuilding them)
     sim = Simulation(n, ny, 1.7, bc=os.environ.get("LB_TIMELINE_BC", "periodic"), inlet_rho=1.0005)
     depth = int(os.environ.get("LB_TIMELINE_DEPTH", "4"))
     deep2 = os.environ.get("LB_TIMELINE_DEEP2") == "1"             # k_deep2<7>: four waves per item (front / back x down / up)
-    sim.set_variant({4: 353, 6: 353 | 4096 | 16384, 7: 353 | 4096 | 16384 | 32768}[depth] | (65536 if deep2 else 0))
+    assert depth in (4, 6, 7), depth
+    sim.set_variant(marching(depth) | (DEEP2 if deep2 else 0))
     sim.init_equilibrium(*shear_layer(n, ny, 0, ny))
     sim.run(2 * depth)
     sim.run(depth)                                # the launch whose timeline is read
