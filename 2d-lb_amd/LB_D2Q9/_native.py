@@ -8,16 +8,16 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LB_LIB") or os.path.join(_HERE, "liblbhip.so")   # LB_LIB: diagnostic builds only
 
-LB_BC_PIPE, LB_BC_PERIODIC, LB_BC_CAVITY, LB_BC_VELOCITY_INLET, LB_BC_OPEN = 0, 1, 2, 3, 4
+LB_BC_PIPE, LB_BC_PERIODIC, LB_BC_CAVITY, LB_BC_VELOCITY_INLET, LB_BC_OPEN, LB_BC_BOX = 0, 1, 2, 3, 4, 5
 LB_FLAG_HALO = 1
 LB_FLAG_PLANAR = 2
 LB_FLAG_EAGER_MACRO = 4
 LB_MASK_HALO_ROWS = 13
 LB_PEER_HANDLE_BYTES = 384
 LB_DEVICE_CPU = -1
-LB_SEM_OPENCL, LB_SEM_CYTHON, LB_SEM_OPENCL_D2Q9I, LB_SEM_DIFFUSION = 0, 1, 2, 3
+LB_SEM_OPENCL, LB_SEM_CYTHON, LB_SEM_OPENCL_D2Q9I, LB_SEM_DIFFUSION, LB_SEM_MULTIFIELD = 0, 1, 2, 3, 4
 BC_NAMES = {"pipe": LB_BC_PIPE, "periodic": LB_BC_PERIODIC, "cavity": LB_BC_CAVITY,
-            "velocity_inlet": LB_BC_VELOCITY_INLET, "open": LB_BC_OPEN}
+            "velocity_inlet": LB_BC_VELOCITY_INLET, "open": LB_BC_OPEN, "box": LB_BC_BOX}
 
 ABI_VERSION = 11
 
@@ -34,6 +34,7 @@ EXPORTS = (
     "lb_peer_export", "lb_peer_connect", "lb_set_params_f64", "lb_set_slab_cycle", "lb_exchange_timing", "lb_exchange_stats",
     "lb_set_exchange_inline",
     "lb_set_reaction", "lb_edge_floats", "lb_get_edge_state", "lb_set_edge_state", "lb_set_velocity_from",
+    "lb_run_coupled", "lb_collide_coupled",
 )
 
 
@@ -105,6 +106,9 @@ def lib():
         L.lb_get_edge_state.argtypes = [h, vp]
         L.lb_set_edge_state.argtypes = [h, vp]
         L.lb_set_velocity_from.argtypes = [h, h]
+    if hasattr(L, "lb_run_coupled"):                # (added within ABI 11: an older diagnostic build of that version lacks them)
+        L.lb_run_coupled.argtypes = [ct.POINTER(h), I, I]
+        L.lb_collide_coupled.argtypes = [ct.POINTER(h), I]
     L.lb_comm_init.argtypes = [h, vp, I, I]
     L.lb_timer_stop.argtypes = [h, fp]
     L.lb_layout.argtypes = [h, ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64)]

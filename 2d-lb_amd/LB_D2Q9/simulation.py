@@ -74,6 +74,10 @@ class Simulation(object):
                concentration, u, v an imposed velocity field (set_fields, set_velocity_from) that no kernel writes, the
                equilibrium is linear, set_reaction(G) adds Fisher growth; bc='periodic' or 'open' (the reference's box:
                links entering from outside keep the values of the last set_f / init_pop, get_edge_state); whole grid.
+               'multifield': one field of a set of COUPLED scalar lattices (the reference's D2Q9_multifield_fisher.cl): as
+               'diffusion', but the growth term is G rho (1 - sum of the set's rho) and bc is 'periodic' or 'box' (on-node
+               bounce-back on four walls; get_corner_state).  LB_D2Q9.coupled.Coupled_Scalars advances a set in lock step;
+               run() on one member is the set of one.
         :param planar: device layout of the lattices: False = the nine planes of a row stored together (default),
                True = each plane contiguous (LB_FLAG_PLANAR); results are identical.  None: environment variable
                LB_LAYOUT=planar selects True (tuning aid).
@@ -104,7 +108,7 @@ class Simulation(object):
         p.flags = ((_native.LB_FLAG_HALO if halo else 0) | (_native.LB_FLAG_PLANAR if self.planar else 0) |
                    (_native.LB_FLAG_EAGER_MACRO if self.eager_macro else 0))
         sem = {"opencl": _native.LB_SEM_OPENCL, "cython": _native.LB_SEM_CYTHON, "d2q9i": _native.LB_SEM_OPENCL_D2Q9I,
-               "diffusion": _native.LB_SEM_DIFFUSION}
+               "diffusion": _native.LB_SEM_DIFFUSION, "multifield": _native.LB_SEM_MULTIFIELD}
         if semantics not in sem:
             raise ValueError("semantics must be one of %s" % sorted(sem))
         p.semantics = sem[semantics]
@@ -218,7 +222,7 @@ class Simulation(object):
         unchanged; the pass advances at most (n - 7) // 4 steps, a runner-up's longer comparison included) and keeps the
         fastest for this grid; shorter runs use the size heuristic (or call autotune())."""
         n = int(num_iterations)
-        if wait and n > 0 and self.semantics != "diffusion":      # (a scalar lattice's kernel is the planner's size rule: no tuning pass)
+        if wait and n > 0 and self.semantics not in ("diffusion", "multifield"):      # (a scalar lattice's kernel is the planner's size rule: no tuning pass)
             # (the pass costs 361 steps, 889 on grids <= 768^2, some of them in configurations several times slower than
             #  the best: it only pays for itself in a run several times that long)
             used = self._lib.lb_autotune_quick(self._h, (n - 7) // 4)
@@ -312,6 +316,9 @@ class Simulation(object):
         if self.semantics == "diffusion":
             d["G"] = np.float32(self.G)
             d["edge_state"] = self.get_edge_state()
+        if self.semantics == "multifield":
+            d["G"] = np.float32(self.G)
+            d["corner_state"] = self.get_corner_state()
         if self._mask_halo_host is not None:         # a slab: the neighbours' obstacle rows it was given
             empty = np.zeros((0, 0), np.int32)
             d["mask_halo_south"] = empty if self._mask_halo_host[0] is None else self._mask_halo_host[0]
@@ -345,7 +352,7 @@ class Simulation(object):
 
     def restore_arrays(self, d):
         self._check_compatible(d)
-        if self.semantics != "diffusion":                       # (a scalar lattice has no obstacles)
+        if self.semantics not in ("diffusion", "multifield"):   # (a scalar lattice has no obstacles)
             self.set_obstacle_mask(d["mask"] if d["mask"].size else None)
         if "mask_halo_south" in d:
             so, no = d["mask_halo_south"], d["mask_halo_north"]
@@ -357,6 +364,9 @@ class Simulation(object):
         if self.semantics == "diffusion":
             self.set_reaction(float(d["G"]))
             self.set_edge_state(d["edge_state"])               # (after set_f, likewise)
+        if self.semantics == "multifield":
+            self.set_reaction(float(d["G"]))
+            self.set_corner_state(d["corner_state"])           # (after set_f, likewise)
 
     # -- scalar lattices (semantics='diffusion') -----------------------------------
     def set_reaction(self, G):
@@ -390,7 +400,8 @@ class Simulation(object):
         check(self._lib.lb_set_edge_state(self._h, v.ctypes.data))
 
     def get_corner_state(self):
-        """bc='velocity_inlet': the eight corner links no kernel of that rule set writes (include/lb_hip.h)."""
+        """bc='velocity_inlet', and bc='box' of a coupled scalar lattice: the eight corner links no kernel of that rule set
+        writes (include/lb_hip.h)."""
         out = np.zeros(8, np.float32)
         check(self._lib.lb_get_corner_state(self._h, out.ctypes.data))
         return out

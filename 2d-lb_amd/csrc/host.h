@@ -8,7 +8,7 @@
 //   lb_hip.cpp     create / destroy / setters, state transfer, the un-fused phases, lb_run, lb_run_batch, lb_check, timers
 // Small kernels are emitted by the one unit that includes their header: kernels_phases.h + kernels_check.h by lb_hip.cpp,
 // kernels_halo.h by slab.cpp, kernels_scalar.h by scalar.cpp (its health check's first pass only: check_reduce.h is shared, the folding
-// pass is lb_hip.cpp's).
+// pass is lb_hip.cpp's), kernels_multifield.h by multifield.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -24,6 +24,7 @@
 #include "plan.h"
 #include "launchers.h"          // StepArgs; the fused kernels are instantiated in their own translation units
 #include "scalar_launch.h"      // scalar lattices (LB_SEM_DIFFUSION): AdExtra, CheckPartial, their launchers
+#include "multifield_launch.h"  // coupled scalar lattices (LB_SEM_MULTIFIELD): MfArgs, their launchers
 
 namespace {
 
@@ -43,7 +44,7 @@ struct lb_sim : PlanInputs {
     float *stage = nullptr;     // [H][pitch], lazily: one plane on its way between the host and interleaved rows (lattice_plane_*)
     float *ad_edge = nullptr;   // scalar lattice, OPEN family: the edge state on the device (scalar_launch.h)
     float ad_G = 0.f;           // scalar lattice: growth rate of the Fisher term (lb_set_reaction); 0 = plain relaxation
-    float *vi_corner = nullptr; // VELOCITY_INLET: the eight corner links nothing ever writes (bc_vel_cell), device
+    float *vi_corner = nullptr; // VELOCITY_INLET: the eight corner links nothing ever writes (bc_vel_cell), device; LB_BC_BOX: likewise (mf_box_cell)
     uint8_t *mask_raw = nullptr, *mask = nullptr;   // [H+2*MASK_GHOST][pitch] + guards; mask -> row 0
     bool feq_valid = false;     // feq buffer consistent with rho,u,v
     bool macro_valid = true;    // rho,u,v hold the last step's fields (false: to be rebuilt from the populations, ensure_macro)
@@ -112,7 +113,7 @@ int fail(int code, const char *fmt, ...);       // records the message lb_last_e
         if ((s) && (s)->cpu) return fail(LB_ERR_STATE, "%s is not available on the CPU backend", name);      \
     } while (0)
 
-// Scalar lattices (LB_SEM_DIFFUSION) are whole-grid handles without obstacles: what only slabs, masks or the flow kernels' tuning mean refuses.
+// Scalar lattices (LB_SEM_DIFFUSION, and the fields of a coupled set: LB_SEM_MULTIFIELD) are whole-grid handles without obstacles: what only slabs, masks or the flow kernels' tuning mean refuses.
 #define SCALAR_UNSUPPORTED(s, name)                                                                         \
     do {                                                                                                    \
         if ((s) && (s)->scalar()) return fail(LB_ERR_STATE, "%s is not available on a scalar lattice (LB_SEM_DIFFUSION)", name); \

@@ -195,15 +195,18 @@ int lattice_plane_d2h(lb_sim *s, float *host, const float *origin, int k)
 }
 
 // Links no kernel ever writes keep the value they had when the populations were last set as a whole (the reference's f_streamed = f
-// at that moment: opencl_dim.py:323-327, diffusion.py:321-324): the eight corner links of the VELOCITY_INLET family (vi_corner), the
-// edge state of a scalar lattice's OPEN family (ad_edge, scalar_launch.h); no other handle has any.  They are kept apart because
+// at that moment: opencl_dim.py:323-327, diffusion.py:321-324): the eight corner links of the VELOCITY_INLET family and the eight of
+// a coupled scalar lattice's LB_BC_BOX (vi_corner), the edge state of a scalar lattice's OPEN family (ad_edge, scalar_launch.h); no other handle has any.  They are kept apart because
 // fused launches swap the lattices, so "whatever f_streamed held" would not survive them.  !patch: copied out of lattice `which`;
 // patch: written back into it.
 int frozen_links(lb_sim *s, int which, bool patch)
 {
-    if (s->p.bc_mode == LB_BC_VELOCITY_INLET) {
+    if (s->p.bc_mode == LB_BC_VELOCITY_INLET || s->p.bc_mode == LB_BC_BOX) {
         const int X = s->p.nx - 1, Y = s->p.ny - 1;
-        const struct { int k, x, y; } c[8] = {{1, 0, 0}, {8, 0, 0}, {1, 0, Y}, {5, 0, Y}, {3, X, 0}, {7, X, 0}, {3, X, Y}, {6, X, Y}};   // (bc_vel_cell's order)
+        struct Link { int k, x, y; };
+        const Link vel[8] = {{1, 0, 0}, {8, 0, 0}, {1, 0, Y}, {5, 0, Y}, {3, X, 0}, {7, X, 0}, {3, X, Y}, {6, X, Y}};   // (bc_vel_cell's order)
+        const Link box[8] = {{6, 0, 0}, {8, 0, 0}, {5, X, 0}, {7, X, 0}, {5, 0, Y}, {7, 0, Y}, {6, X, Y}, {8, X, Y}};   // (mf_box_cell's order)
+        const Link *c = s->p.bc_mode == LB_BC_BOX ? box : vel;
         for (int i = 0; i < 8; ++i) {
             float *in_lat = s->origin(which) + c[i].k * s->plane + (long long)c[i].y * s->rowp + c[i].x, *kept = s->vi_corner + i;
             HIP_TRY(hipMemcpyAsync(patch ? in_lat : kept, patch ? kept : in_lat, sizeof(float), hipMemcpyDeviceToDevice, s->stream));
@@ -298,9 +301,19 @@ int lb_create(const lb_params *p, lb_sim **out)
     if (p->nx < 2 || p->ny < 2) return fail(LB_ERR_ARG, "grid must be at least 2x2 (got %dx%d)", p->nx, p->ny);
     if (p->local_ny < 1 || p->y0 < 0 || p->y0 + p->local_ny > p->ny)
         return fail(LB_ERR_ARG, "slab [%d,%d) outside 0..%d", p->y0, p->y0 + p->local_ny, p->ny);
-    if (p->bc_mode < LB_BC_PIPE || p->bc_mode > LB_BC_OPEN) return fail(LB_ERR_ARG, "unknown bc_mode %d", p->bc_mode);
+    if (p->bc_mode < LB_BC_PIPE || p->bc_mode > LB_BC_BOX) return fail(LB_ERR_ARG, "unknown bc_mode %d", p->bc_mode);
     if (p->bc_mode == LB_BC_OPEN && p->semantics != LB_SEM_DIFFUSION)
         return fail(LB_ERR_ARG, "LB_BC_OPEN exists for scalar lattices (LB_SEM_DIFFUSION) only");
+    if (p->bc_mode == LB_BC_BOX && p->semantics != LB_SEM_MULTIFIELD)
+        return fail(LB_ERR_ARG, "bc_mode LB_BC_BOX exists for coupled scalar lattices (LB_SEM_MULTIFIELD) only");
+    if (p->semantics == LB_SEM_MULTIFIELD) {
+        // the fields of a coupled set: scalar lattices, refused likewise
+        if (p->bc_mode != LB_BC_PERIODIC && p->bc_mode != LB_BC_BOX)
+            return fail(LB_ERR_ARG, "a coupled scalar lattice (LB_SEM_MULTIFIELD) takes the families LB_BC_PERIODIC and LB_BC_BOX only");
+        if (p->local_ny != p->ny || p->y0 != 0) return fail(LB_ERR_ARG, "a coupled scalar lattice (LB_SEM_MULTIFIELD) owns its whole grid: no slabs");
+        if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "a coupled scalar lattice (LB_SEM_MULTIFIELD) has no halo interface (LB_FLAG_HALO)");
+        if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "a coupled scalar lattice (LB_SEM_MULTIFIELD) runs on a GPU only (no CPU backend)");
+    }
     if (p->semantics == LB_SEM_DIFFUSION) {
         // scalar lattices (refused before any device is touched)
         if (p->bc_mode != LB_BC_PERIODIC && p->bc_mode != LB_BC_OPEN)
@@ -318,7 +331,8 @@ int lb_create(const lb_params *p, lb_sim **out)
     for (int r : p->reserved)
         if (r != 0) return fail(LB_ERR_ARG, "reserved fields must be zero");
     if (p->flags & ~(LB_FLAG_HALO | LB_FLAG_PLANAR | LB_FLAG_EAGER_MACRO)) return fail(LB_ERR_ARG, "unknown flags 0x%x", p->flags);
-    if (p->semantics != LB_SEM_OPENCL && p->semantics != LB_SEM_CYTHON && p->semantics != LB_SEM_OPENCL_D2Q9I && p->semantics != LB_SEM_DIFFUSION)
+    if (p->semantics != LB_SEM_OPENCL && p->semantics != LB_SEM_CYTHON && p->semantics != LB_SEM_OPENCL_D2Q9I && p->semantics != LB_SEM_DIFFUSION &&
+        p->semantics != LB_SEM_MULTIFIELD)
         return fail(LB_ERR_ARG, "unknown semantics %d", p->semantics);
     if (p->semantics == LB_SEM_OPENCL_D2Q9I &&
         (p->bc_mode != LB_BC_PIPE || p->local_ny != p->ny || (p->flags & LB_FLAG_HALO)))
@@ -516,6 +530,8 @@ int lb_set_variant(lb_sim *s, int variant)
 {
     if (s && s->cpu) return LB_OK;                 // (one code path: nothing to select)
     if (!s) return fail(LB_ERR_ARG, "null handle");
+    if (s->multifield() && variant != -1 && variant != 0)
+        return fail(LB_ERR_ARG, "a coupled scalar lattice (LB_SEM_MULTIFIELD) takes the variants -1 and 0 only: k_mf_step, no tiles");
     s->variant = variant;
     return LB_OK;
 }
@@ -684,7 +700,7 @@ int lb_get_f(lb_sim *s, float *f)
 int lb_get_corner_state(lb_sim *s, float *out8)
 {
     CPU_UNSUPPORTED(s, "lb_get_corner_state");
-    SCALAR_UNSUPPORTED(s, "lb_get_corner_state");
+    if (s && !s->multifield()) SCALAR_UNSUPPORTED(s, "lb_get_corner_state");
     if (!s || !out8) return fail(LB_ERR_ARG, "null argument");
     DeviceGuard guard(s->p.device);
     HIP_TRY(hipMemcpyAsync(out8, s->vi_corner, 8 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
@@ -695,7 +711,7 @@ int lb_get_corner_state(lb_sim *s, float *out8)
 int lb_set_corner_state(lb_sim *s, const float *in8)
 {
     CPU_UNSUPPORTED(s, "lb_set_corner_state");
-    SCALAR_UNSUPPORTED(s, "lb_set_corner_state");
+    if (s && !s->multifield()) SCALAR_UNSUPPORTED(s, "lb_set_corner_state");
     if (!s || !in8) return fail(LB_ERR_ARG, "null argument");
     DeviceGuard guard(s->p.device);
     HIP_TRY(hipMemcpyAsync(s->vi_corner, in8, 8 * sizeof(float), hipMemcpyHostToDevice, s->stream));
@@ -929,8 +945,13 @@ int lb_move_bcs(lb_sim *s)
     if (!s) return fail(LB_ERR_ARG, "null handle");
     int rc = need_single_slab(s, "lb_move_bcs");
     if (rc) return rc;
-    if (s->scalar()) return LB_OK;                  // (diffusion.py:326-331: `pass`)
+    if (s->scalar() && s->p.bc_mode != LB_BC_BOX) return LB_OK;     // (diffusion.py:326-331: `pass`; the periodic families have none)
     DeviceGuard guard(s->p.device);
+    if (s->scalar()) {                              // D2Q9_multifield_fisher.cl's move_bcs: on-node bounce-back on four walls
+        lbk_mf_move_bcs(s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur));
+        HIP_TRY(hipGetLastError());
+        return LB_OK;
+    }
     if ((rc = ensure_macro(s))) return rc;
     if (s->p.semantics == LB_SEM_CYTHON)
         hipLaunchKernelGGL(k1_bcs, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
@@ -997,6 +1018,7 @@ int lb_collide_particles(lb_sim *s)
     int rc = need_single_slab(s, "lb_collide_particles");
     if (rc) return rc;
     if (!s->feq) return fail(LB_ERR_STATE, "lb_collide_particles before any lb_update_feq");
+    if (s->multifield()) return lb_collide_coupled(&s, 1);
     DeviceGuard guard(s->p.device);
     if ((rc = ensure_macro(s))) return rc;
     if (s->scalar())
@@ -1056,6 +1078,7 @@ int lb_run(lb_sim *s, int n_steps)
     if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
     if (s->stepping) return fail(LB_ERR_STATE, "lb_run between lb_step_boundary and lb_step_finish");
     DeviceGuard guard(s->p.device);
+    if (s->multifield()) return lb_run_coupled(&s, 1, n_steps);
     if (s->scalar()) return run_scalar(s, n_steps);
     if (!s->tune_cache_checked) (void)tune_cache_apply(s);
     if (s->p.semantics == LB_SEM_CYTHON) return run_cython(s, n_steps);
@@ -1111,6 +1134,89 @@ int lb_run_batch(lb_sim **sims, int count, int n_steps)
         sims[i]->macro_valid = !lazy;
     }
     return LB_OK;
+}
+
+// Coupled scalar lattices: the members of a set, checked alike for lb_run_coupled and lb_collide_coupled.
+static int coupled_members(lb_sim **f, int count, const char *what)
+{
+    if (!f || count < 1 || count > MF_MAX) return fail(LB_ERR_ARG, "%s takes 1..%d handles", what, MF_MAX);
+    for (int i = 0; i < count; ++i) {
+        lb_sim *s = f[i];
+        if (!s) return fail(LB_ERR_ARG, "null handle in the coupled set");
+        if (s->cpu || !s->multifield()) return fail(LB_ERR_ARG, "the members of a coupled set must be LB_SEM_MULTIFIELD handles");
+        if (s->p.nx != f[0]->p.nx || s->p.ny != f[0]->p.ny || s->p.bc_mode != f[0]->p.bc_mode || s->p.device != f[0]->p.device ||
+            (s->p.flags & LB_FLAG_PLANAR) != (f[0]->p.flags & LB_FLAG_PLANAR))
+            return fail(LB_ERR_ARG, "the members of a coupled set must share grid, boundary family, layout flag and device");
+        if (s->stepping) return fail(LB_ERR_STATE, "%s inside a split step", what);
+        for (int j = 0; j < i; ++j)
+            if (f[j] == s) return fail(LB_ERR_ARG, "a handle appears twice in the coupled set");
+    }
+    return LB_OK;
+}
+
+// everything of a coupled call is enqueued on the first member's stream, behind whatever the others still have in flight ...
+static int coupled_join(lb_sim **f, int count)
+{
+    for (int i = 1; i < count; ++i) {
+        HIP_TRY(hipEventRecord(f[i]->ev_interior, f[i]->stream));
+        HIP_TRY(hipStreamWaitEvent(f[0]->stream, f[i]->ev_interior, 0));
+    }
+    return LB_OK;
+}
+// ... and the other members' streams see the result
+static int coupled_release(lb_sim **f, int count)
+{
+    if (count < 2) return LB_OK;
+    HIP_TRY(hipEventRecord(f[0]->ev_interior, f[0]->stream));
+    for (int i = 1; i < count; ++i) HIP_TRY(hipStreamWaitEvent(f[i]->stream, f[0]->ev_interior, 0));
+    return LB_OK;
+}
+
+int lb_run_coupled(lb_sim **fields, int count, int n_steps)
+{
+    int rc = coupled_members(fields, count, "lb_run_coupled");
+    if (rc) return rc;
+    if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
+    if (n_steps == 0) return LB_OK;
+    lb_sim *s0 = fields[0];
+    DeviceGuard guard(s0->p.device);
+    if ((rc = coupled_join(fields, count))) return rc;
+    for (int it = 0; it < n_steps; ++it) {
+        MfArgs m = {};
+        for (int i = 0; i < count; ++i) {
+            m.a[i] = step_args(fields[i], 0, 1, fields[i]->H);
+            m.G[i] = fields[i]->ad_G;
+        }
+        lbk_mf_step(s0->p.bc_mode, count, it == n_steps - 1, s0->stream, m);      // the last launch stores every field's rho
+        HIP_TRY(hipGetLastError());
+        for (int i = 0; i < count; ++i) fields[i]->cur ^= 1;
+    }
+    for (int i = 0; i < count; ++i) {
+        fields[i]->feq_valid = false;
+        fields[i]->macro_valid = true;
+    }
+    return coupled_release(fields, count);
+}
+
+int lb_collide_coupled(lb_sim **fields, int count)
+{
+    int rc = coupled_members(fields, count, "lb_collide_coupled");
+    if (rc) return rc;
+    for (int i = 0; i < count; ++i)
+        if (!fields[i]->feq) return fail(LB_ERR_STATE, "lb_collide_coupled before lb_update_feq on every member");
+    lb_sim *s0 = fields[0];
+    DeviceGuard guard(s0->p.device);
+    if ((rc = coupled_join(fields, count))) return rc;
+    MfArgs m = {};
+    for (int i = 0; i < count; ++i) {
+        m.a[i] = step_args(fields[i], 0, 1, fields[i]->H);
+        m.a[i].dst = fields[i]->origin(fields[i]->cur);         // relaxed in place
+        m.G[i] = fields[i]->ad_G;
+        m.feq[i] = fields[i]->feq_origin();
+    }
+    lbk_mf_collide(count, s0->stream, m);
+    HIP_TRY(hipGetLastError());
+    return coupled_release(fields, count);
 }
 
 // ---- health check ------------------------------------------------------------------------

@@ -27,7 +27,8 @@ struct PlanInputs {
     int slab_flavour = -1;      // slabs, seven-step cycle: 0 k_deep<7>, 1 k_deep2<7> (lb_set_slab_cycle(8)), -1 automatic (k_deep2 under RCCL)
     int transport = SLAB_NO_TRANSPORT;   // slabs: lb_comm_init / lb_peer_connect
 
-    bool scalar() const { return p.semantics == LB_SEM_DIFFUSION; }      // a scalar lattice (kernels_scalar.h)
+    bool multifield() const { return p.semantics == LB_SEM_MULTIFIELD; } // one field of a coupled set of scalar lattices (kernels_multifield.h)
+    bool scalar() const { return p.semantics == LB_SEM_DIFFUSION || multifield(); }      // a scalar lattice (kernels_scalar.h), on its own or coupled
     bool multi_slab() const { return H != p.ny || (p.flags & LB_FLAG_HALO); }
     int agreed_h() const { return min_h > 0 ? min_h : H; }      // the height all ranks decide on
 };

@@ -25,6 +25,25 @@ __device__ __forceinline__ void ad_feq_pair(T r, T r3, T cu, T &fp, T &fm)
     fm = lb_fma(-r3, cu, r);
 }
 
+// The growth term of one cell / one pair, added last: fl(w_k) ((G rho) room), room = 1 - rho for a lattice on its own
+// (D2Q9_diffusion.cl:112, 121), 1 - (rho_0 + rho_1 + ...) for a field of a coupled set (D2Q9_multifield_fisher.cl:
+// collide_particles).  With one field the two are the same bits.
+template <typename T>
+__device__ __forceinline__ void ad_grow_t(T &f0, T &f1, T &f2, T &f3, T &f4, T &f5, T &f6, T &f7, T &f8, float G, T rho, T room)
+{
+    const T react = (lb_splat<T>(G) * rho) * room;
+    const T w0 = lb_splat<T>(4.f / 9.f), w1 = lb_splat<T>(1.f / 9.f), w2 = lb_splat<T>(1.f / 36.f);
+    f0 = lb_fma(w0, react, f0);
+    f1 = lb_fma(w1, react, f1);
+    f3 = lb_fma(w1, react, f3);
+    f2 = lb_fma(w1, react, f2);
+    f4 = lb_fma(w1, react, f4);
+    f5 = lb_fma(w2, react, f5);
+    f7 = lb_fma(w2, react, f7);
+    f8 = lb_fma(w2, react, f8);
+    f6 = lb_fma(w2, react, f6);
+}
+
 // Equilibrium and relaxation (and, REACT, the growth term) of one cell / one pair, in place.  omega enters once, through the
 // density, as in equilibrate_t: every equilibrium below comes out as omega feq_k, the float32 weights multiply a run-time value.
 template <typename T, bool REACT>
@@ -49,20 +68,7 @@ __device__ __forceinline__ void ad_relax_t(T &f0, T &f1, T &f2, T &f3, T &f4, T 
     f7 = lb_fma(f7, keep, e7);
     f8 = lb_fma(f8, keep, e8);
     f6 = lb_fma(f6, keep, e6);
-    if (REACT) {
-        // fl(w_k) (G rho (1 - rho)), added last (D2Q9_diffusion.cl:112, 121)
-        const T react = (lb_splat<T>(G) * rho) * (lb_splat<T>(1.f) - rho);
-        const T w0 = lb_splat<T>(4.f / 9.f), w1 = lb_splat<T>(1.f / 9.f), w2 = lb_splat<T>(1.f / 36.f);
-        f0 = lb_fma(w0, react, f0);
-        f1 = lb_fma(w1, react, f1);
-        f3 = lb_fma(w1, react, f3);
-        f2 = lb_fma(w1, react, f2);
-        f4 = lb_fma(w1, react, f4);
-        f5 = lb_fma(w2, react, f5);
-        f7 = lb_fma(w2, react, f7);
-        f8 = lb_fma(w2, react, f8);
-        f6 = lb_fma(w2, react, f6);
-    }
+    if (REACT) ad_grow_t<T>(f0, f1, f2, f3, f4, f5, f6, f7, f8, G, rho, lb_splat<T>(1.f) - rho);
 }
 
 // feq_k itself (the un-fused update_feq_diffusion): ad_relax_t's equilibrium with omega = 1

@@ -55,9 +55,13 @@ typedef enum {
                              it).  Whole-grid handles; lb_run fuses it (up to four time steps per launch; from
                              three on the wall-row bands are advanced as a small lattice of their own), the phase
                              entry points run it un-fused. */
-    LB_BC_OPEN = 4        /* scalar lattices (LB_SEM_DIFFUSION) only: the box of the reference's Diffusion classes, whose move_bcs
+    LB_BC_OPEN = 4,       /* scalar lattices (LB_SEM_DIFFUSION) only: the box of the reference's Diffusion classes, whose move_bcs
                              is `pass` (reaction_diffusion/diffusion.py): a link that would enter from outside the box keeps the
                              value it had when the populations were last set -- the handle's edge state (lb_get_edge_state). */
+    LB_BC_BOX = 5         /* coupled scalar lattices (LB_SEM_MULTIFIELD) only: the closed box of the reference's
+                             D2Q9_multifield_fisher.cl, whose move_bcs bounces every link that would enter from outside back on
+                             the node itself (f1 := f3 at x = 0, ...), on all four walls.  Two links per corner are neither
+                             streamed nor bounced: the handle's corner state (lb_get_corner_state). */
 } lb_bc_mode;
 
 /* Which of the reference's two (numerically different) paths the handle reproduces.
@@ -75,7 +79,7 @@ typedef enum {
                                  rho + 3 cu + 4.5 cu^2 - 1.5 usq (:58), re-derived inlet / outlet (:194-205), u, v
                                  re-zeroed in the obstacle every step.  PIPE family, whole-grid handles; fused like the
                                  OpenCL path.  Restated as the fork has it: it is unstable (tests/golden/o2_d2q9i_53x27). */
-    LB_SEM_DIFFUSION = 3      /* a SCALAR lattice: LB_D2Q9/D2Q9_diffusion.cl driven as reaction_diffusion/diffusion.py does -- a
+    LB_SEM_DIFFUSION = 3,     /* a SCALAR lattice: LB_D2Q9/D2Q9_diffusion.cl driven as reaction_diffusion/diffusion.py does -- a
                                  concentration rho carried by D2Q9 populations with the linear equilibrium feq_k = w_k rho (1 + 3 c_k.u),
                                  an IMPOSED velocity field u, v (lb_set_macro, lb_set_velocity_from; no kernel writes it) and an optional
                                  Fisher growth term w_k G rho (1 - rho) (lb_set_reaction).  Families LB_BC_PERIODIC (build-defined)
@@ -89,6 +93,14 @@ typedef enum {
                                  latter 0.89-0.91 of the copy rate on the same handle: profiles/scalar_bench.txt).  A run
                                  always stores rho in its last launch -- with G != 0 rho is not a moment of what a run leaves
                                  behind.  omega, nx, ny are the only other lb_params fields it reads. */
+    LB_SEM_MULTIFIELD = 4     /* ONE FIELD of a set of coupled scalar lattices: LB_D2Q9/D2Q9_multifield_fisher.cl driven as
+                                 advecting_range_expansion/deterministic_fisher_waves.py does.  A scalar lattice in every respect
+                                 above (whole-grid GPU handle, imposed u, v, lb_set_reaction = this field's G, rho always stored),
+                                 except that the growth term of field i is w_k G_i rho_i (1 - sum_j rho_j) over the fields
+                                 advanced together (lb_run_coupled; lb_run = the set of one), and that the families are
+                                 LB_BC_PERIODIC (build-defined) and LB_BC_BOX (the reference's closed box).  One fused launch
+                                 per time step for the whole set (k_mf_step: 72 B of populations per field + 8 B of u, v per
+                                 cell and step); lb_set_variant takes -1 and 0 only (no LDS tiles for coupled sets). */
 } lb_semantics;
 
 typedef struct {
@@ -173,7 +185,11 @@ int lb_set_mask(lb_sim *s, const int32_t *mask); /* [H][nx], 1 = solid (opencl_d
  * `move` drops what would enter from outside the box, D2Q9.cl:151-169, and the rules skip them): they keep the
  * values f had at the last lb_set_f / lb_init_pop -- in the reference inside its f_streamed buffer.  Order:
  * f1(0,0), f8(0,0), f1(0,ny-1), f5(0,ny-1), f3(nx-1,0), f7(nx-1,0), f3(nx-1,ny-1), f6(nx-1,ny-1).  A checkpoint
- * needs them next to f (lb_set_f resets them). */
+ * needs them next to f (lb_set_f resets them).
+ * LB_SEM_MULTIFIELD handles (LB_BC_BOX): likewise the eight corner links the push `move` of D2Q9_multifield_fisher.cl never
+ * writes and its move_bcs skips, in this order:
+ * f6(0,0), f8(0,0), f5(nx-1,0), f7(nx-1,0), f5(0,ny-1), f7(0,ny-1), f6(nx-1,ny-1), f8(nx-1,ny-1)
+ * (eight zeros that nothing reads in the PERIODIC family). */
 int lb_get_corner_state(lb_sim *s, float *out8);
 int lb_set_corner_state(lb_sim *s, const float *in8);
 
@@ -258,6 +274,20 @@ int lb_run_group(lb_sim **sims, int count, int n_steps);
  * handles of one geometry on one device, one per population, each with its own omega, advance n_steps in lock step
  * with ONE fused launch per time step for all of them.  Bitwise equal to lb_run on each handle. */
 int lb_run_batch(lb_sim **sims, int count, int n_steps);
+
+/* Coupled scalar lattices (the competing concentrations of the reference's advecting_range_expansion fork:
+ * deterministic_fisher_waves.py runs five launches and five host waits per step, each looping over the fields in every
+ * work-item).  `count` = 1 ... 4 LB_SEM_MULTIFIELD handles of one geometry, boundary family, layout flag and device, one per
+ * field, each with its own omega and G (lb_set_reaction), advance n_steps in lock step with ONE fused launch per time step:
+ * per cell rho_i = sum f of every field, rho_tot = rho_0 + rho_1 + ... in the order of `fields`, then field i relaxes towards
+ * its linear equilibrium and grows by w_k G_i rho_i (1 - rho_tot).  The imposed velocity read is that of fields[0] for
+ * every field (the fork has one u, v for all; Coupled_Scalars writes the same to every member).  The last launch stores every
+ * field's rho.  lb_run on such a handle is the set of one.
+ * lb_collide_coupled: the fork's un-fused collide_particles over the set -- every member's stored feq and rho, rho_tot summed
+ * over the members' stored rho in order; lb_collide_particles on one such handle is the set of one.  The other phase entry
+ * points work per handle (lb_move_bcs: the in-place bounce-back of LB_BC_BOX). */
+int lb_run_coupled(lb_sim **fields, int count, int n_steps);
+int lb_collide_coupled(lb_sim **fields, int count);
 
 /* RCCL point-to-point halo exchange over xGMI, one rank per GPU.  Rank r owns
  * slab r; neighbours are r-1 (south) and r+1 (north), wrapping for PERIODIC.
