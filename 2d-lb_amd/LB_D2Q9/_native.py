@@ -8,16 +8,16 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LB_LIB") or os.path.join(_HERE, "liblbhip.so")   # LB_LIB: diagnostic builds only
 
-LB_BC_PIPE, LB_BC_PERIODIC, LB_BC_CAVITY, LB_BC_VELOCITY_INLET, LB_BC_OPEN, LB_BC_BOX = 0, 1, 2, 3, 4, 5
+LB_BC_PIPE, LB_BC_PERIODIC, LB_BC_CAVITY, LB_BC_VELOCITY_INLET, LB_BC_OPEN, LB_BC_BOX, LB_BC_DIRICHLET = 0, 1, 2, 3, 4, 5, 6
 LB_FLAG_HALO = 1
 LB_FLAG_PLANAR = 2
 LB_FLAG_EAGER_MACRO = 4
 LB_MASK_HALO_ROWS = 13
 LB_PEER_HANDLE_BYTES = 384
 LB_DEVICE_CPU = -1
-LB_SEM_OPENCL, LB_SEM_CYTHON, LB_SEM_OPENCL_D2Q9I, LB_SEM_DIFFUSION, LB_SEM_MULTIFIELD = 0, 1, 2, 3, 4
+LB_SEM_OPENCL, LB_SEM_CYTHON, LB_SEM_OPENCL_D2Q9I, LB_SEM_DIFFUSION, LB_SEM_MULTIFIELD, LB_SEM_POISSON = 0, 1, 2, 3, 4, 5
 BC_NAMES = {"pipe": LB_BC_PIPE, "periodic": LB_BC_PERIODIC, "cavity": LB_BC_CAVITY,
-            "velocity_inlet": LB_BC_VELOCITY_INLET, "open": LB_BC_OPEN, "box": LB_BC_BOX}
+            "velocity_inlet": LB_BC_VELOCITY_INLET, "open": LB_BC_OPEN, "box": LB_BC_BOX, "dirichlet": LB_BC_DIRICHLET}
 
 ABI_VERSION = 11
 
@@ -35,6 +35,8 @@ EXPORTS = (
     "lb_set_exchange_inline",
     "lb_set_reaction", "lb_edge_floats", "lb_get_edge_state", "lb_set_edge_state", "lb_set_velocity_from",
     "lb_run_coupled", "lb_collide_coupled",
+    "lb_set_poisson", "lb_set_source", "lb_get_source", "lb_solve", "lb_solve_reset", "lb_get_solve_state", "lb_set_solve_state",
+    "lb_gradient",
 )
 
 
@@ -109,6 +111,16 @@ def lib():
     if hasattr(L, "lb_run_coupled"):                # (added within ABI 11: an older diagnostic build of that version lacks them)
         L.lb_run_coupled.argtypes = [ct.POINTER(h), I, I]
         L.lb_collide_coupled.argtypes = [ct.POINTER(h), I]
+    if hasattr(L, "lb_solve"):                      # (likewise: the LB Poisson solver)
+        ip = ct.POINTER(ct.c_int)
+        L.lb_set_poisson.argtypes = [h, ct.c_float, ct.c_float, ct.c_float]
+        L.lb_set_source.argtypes = [h, vp, I]
+        L.lb_get_source.argtypes = [h, vp]
+        L.lb_solve.argtypes = [h, I, ip, ip, fp]
+        L.lb_solve_reset.argtypes = [h]
+        L.lb_get_solve_state.argtypes = [h, ip, ip]
+        L.lb_set_solve_state.argtypes = [h, I, I]
+        L.lb_gradient.argtypes = [h, ct.c_float, vp, vp]
     L.lb_comm_init.argtypes = [h, vp, I, I]
     L.lb_timer_stop.argtypes = [h, fp]
     L.lb_layout.argtypes = [h, ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64)]

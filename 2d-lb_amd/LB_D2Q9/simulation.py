@@ -78,6 +78,9 @@ class Simulation(object):
                'diffusion', but the growth term is G rho (1 - sum of the set's rho) and bc is 'periodic' or 'box' (on-node
                bounce-back on four walls; get_corner_state).  LB_D2Q9.coupled.Coupled_Scalars advances a set in lock step;
                run() on one member is the set of one.
+               'poisson': the LB Poisson solver (the reference's D2Q9_poisson.cl / poisson/solver.py): bc='dirichlet' (a value
+               prescribed on the four walls, set_poisson), a source field (set_source), solve(max_iterations) with the
+               reference's stopping rule decided on the device, gradient(); whole grid.  run(n) = n iterations, no check.
         :param planar: device layout of the lattices: False = the nine planes of a row stored together (default),
                True = each plane contiguous (LB_FLAG_PLANAR); results are identical.  None: environment variable
                LB_LAYOUT=planar selects True (tuning aid).
@@ -108,7 +111,7 @@ class Simulation(object):
         p.flags = ((_native.LB_FLAG_HALO if halo else 0) | (_native.LB_FLAG_PLANAR if self.planar else 0) |
                    (_native.LB_FLAG_EAGER_MACRO if self.eager_macro else 0))
         sem = {"opencl": _native.LB_SEM_OPENCL, "cython": _native.LB_SEM_CYTHON, "d2q9i": _native.LB_SEM_OPENCL_D2Q9I,
-               "diffusion": _native.LB_SEM_DIFFUSION, "multifield": _native.LB_SEM_MULTIFIELD}
+               "diffusion": _native.LB_SEM_DIFFUSION, "multifield": _native.LB_SEM_MULTIFIELD, "poisson": _native.LB_SEM_POISSON}
         if semantics not in sem:
             raise ValueError("semantics must be one of %s" % sorted(sem))
         p.semantics = sem[semantics]
@@ -127,6 +130,7 @@ class Simulation(object):
         self._shape2 = (self.nx, self.local_ny)
         self._shape3 = (self.nx, self.local_ny, NUM_JUMPERS)
         self.G = 0.                      # scalar lattices: growth rate of the Fisher term (set_reaction)
+        self.rho_on_boundary, self.react_factor, self.tolerance = 0., 1., 1e-6      # the Poisson solver's (set_poisson)
         self._mask_host = None
         self._mask_halo_host = None      # (south_rows, north_rows) as last given to set_obstacle_mask_halo
         if obstacle_mask is not None:
@@ -222,7 +226,7 @@ class Simulation(object):
         unchanged; the pass advances at most (n - 7) // 4 steps, a runner-up's longer comparison included) and keeps the
         fastest for this grid; shorter runs use the size heuristic (or call autotune())."""
         n = int(num_iterations)
-        if wait and n > 0 and self.semantics not in ("diffusion", "multifield"):      # (a scalar lattice's kernel is the planner's size rule: no tuning pass)
+        if wait and n > 0 and self.semantics not in ("diffusion", "multifield", "poisson"):      # (a scalar lattice's kernel is the planner's size rule: no tuning pass)
             # (the pass costs 361 steps, 889 on grids <= 768^2, some of them in configurations several times slower than
             #  the best: it only pays for itself in a run several times that long)
             used = self._lib.lb_autotune_quick(self._h, (n - 7) // 4)
@@ -319,6 +323,11 @@ class Simulation(object):
         if self.semantics == "multifield":
             d["G"] = np.float32(self.G)
             d["corner_state"] = self.get_corner_state()
+        if self.semantics == "poisson":
+            d["corner_state"] = self.get_corner_state()
+            d["source"] = self.get_source()
+            d["poisson"] = np.array([self.rho_on_boundary, self.react_factor, self.tolerance], np.float32)
+            d["solve_state"] = np.array(self.solve_state(), np.int32)
         if self._mask_halo_host is not None:         # a slab: the neighbours' obstacle rows it was given
             empty = np.zeros((0, 0), np.int32)
             d["mask_halo_south"] = empty if self._mask_halo_host[0] is None else self._mask_halo_host[0]
@@ -352,7 +361,7 @@ class Simulation(object):
 
     def restore_arrays(self, d):
         self._check_compatible(d)
-        if self.semantics not in ("diffusion", "multifield"):   # (a scalar lattice has no obstacles)
+        if self.semantics not in ("diffusion", "multifield", "poisson"):   # (a scalar lattice has no obstacles)
             self.set_obstacle_mask(d["mask"] if d["mask"].size else None)
         if "mask_halo_south" in d:
             so, no = d["mask_halo_south"], d["mask_halo_north"]
@@ -367,6 +376,67 @@ class Simulation(object):
         if self.semantics == "multifield":
             self.set_reaction(float(d["G"]))
             self.set_corner_state(d["corner_state"])           # (after set_f, likewise)
+
+        if self.semantics == "poisson":
+            self.set_poisson(*[float(x) for x in d["poisson"]])
+            self.set_source(d["source"])
+            self.set_corner_state(d["corner_state"])           # (after set_f, likewise)
+            check(self._lib.lb_set_solve_state(self._h, int(d["solve_state"][0]), int(d["solve_state"][1])))
+
+    # -- the LB Poisson solver (semantics='poisson') --------------------------------
+    def set_poisson(self, rho_on_boundary=0., react_factor=1., tolerance=1e-6):
+        """The value prescribed on the four walls, the factor of the source term (the `delta_t * D` of the reference's
+        collide_particles: every cell adds w_k source react_factor) and the tolerance of solve()'s stopping rule."""
+        vals = [float(np.float32(x)) for x in (rho_on_boundary, react_factor, tolerance)]
+        check(self._lib.lb_set_poisson(self._h, *vals))
+        self.rho_on_boundary, self.react_factor, self.tolerance = vals
+
+    def set_source(self, source):
+        """The source field: an (nx, ny) array, or a float32 torch tensor of that shape already on this handle's device,
+        which is copied device to device (lb_set_source)."""
+        if hasattr(source, "data_ptr"):                         # a torch tensor
+            import torch
+            if tuple(source.shape) != self._shape2 or source.dtype != torch.float32 or not source.is_cuda:
+                raise ValueError("a device source must be a float32 tensor of shape %s on the GPU" % (self._shape2,))
+            dense = source.t().contiguous()                     # [ny][nx], x fastest: the ABI's layout
+            torch.cuda.current_stream(dense.device).synchronize()
+            check(self._lib.lb_set_source(self._h, dense.data_ptr(), 1))
+            return
+        s = _f_order(source, self._shape2)
+        check(self._lib.lb_set_source(self._h, s.ctypes.data, 0))
+
+    def get_source(self):
+        out = np.zeros(self._shape2, np.float32, order="F")
+        check(self._lib.lb_get_source(self._h, out.ctypes.data))
+        return out
+
+    def solve(self, max_iterations):
+        """Up to max_iterations iterations of the reference's run loop; stops after the first iteration n >= 2 (counted since
+        the last solve_reset) with mean |rho - rho_before| / mean rho_before < tolerance, decided on the device (lb_solve).
+        Returns (iterations made by this call, converged, the ratio of the last iteration checked)."""
+        n, c, r = ct.c_int(), ct.c_int(), ct.c_float()
+        check(self._lib.lb_solve(self._h, int(max_iterations), ct.byref(n), ct.byref(c), ct.byref(r)))
+        return n.value, bool(c.value), r.value
+
+    def solve_reset(self):
+        """The iteration counter back to 0 (what the reference's update_source does); rho and the populations stay."""
+        check(self._lib.lb_solve_reset(self._h))
+
+    def solve_state(self):
+        """(iterations since the last solve_reset, the device's stop word: 0 or the iteration a solve stopped at)"""
+        n, w = ct.c_int(), ct.c_int()
+        check(self._lib.lb_get_solve_state(self._h, ct.byref(n), ct.byref(w)))
+        return n.value, w.value
+
+    def gradient(self, dx=1.0):
+        """(d rho / dx, d rho / dy): central differences over 2 dx, 0 for a neighbour outside the box; (nx, ny) arrays, which
+        get_fields()['u'], ['v'] return as well from then on (lb_gradient; it also takes device pointers).  (The
+        reference's update_negative_gradient stores MINUS the y-difference as `u` and MINUS the x-difference as `v`: the
+        drop-in class LB_D2Q9.poisson.Poisson_Solver keeps those names, this method does not.)"""
+        ddx, ddy = np.zeros(self._shape2, np.float32, order="F"), np.zeros(self._shape2, np.float32, order="F")
+        inv = float(np.float32(1.) / (np.float32(2.) * np.float32(dx)))
+        check(self._lib.lb_gradient(self._h, inv, ddx.ctypes.data, ddy.ctypes.data))
+        return ddx, ddy
 
     # -- scalar lattices (semantics='diffusion') -----------------------------------
     def set_reaction(self, G):

@@ -8,7 +8,7 @@
 //   lb_hip.cpp     create / destroy / setters, state transfer, the un-fused phases, lb_run, lb_run_batch, lb_check, timers
 // Small kernels are emitted by the one unit that includes their header: kernels_phases.h + kernels_check.h by lb_hip.cpp,
 // kernels_halo.h by slab.cpp, kernels_scalar.h by scalar.cpp (its health check's first pass only: check_reduce.h is shared, the folding
-// pass is lb_hip.cpp's), kernels_multifield.h by multifield.cpp.
+// pass is lb_hip.cpp's), kernels_multifield.h by multifield.cpp, kernels_poisson.h by poisson.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -25,6 +25,7 @@
 #include "launchers.h"          // StepArgs; the fused kernels are instantiated in their own translation units
 #include "scalar_launch.h"      // scalar lattices (LB_SEM_DIFFUSION): AdExtra, CheckPartial, their launchers
 #include "multifield_launch.h"  // coupled scalar lattices (LB_SEM_MULTIFIELD): MfArgs, their launchers
+#include "poisson_launch.h"     // the LB Poisson solver (LB_SEM_POISSON): PsExtra, PsState, its launchers
 
 namespace {
 
@@ -44,7 +45,14 @@ struct lb_sim : PlanInputs {
     float *stage = nullptr;     // [H][pitch], lazily: one plane on its way between the host and interleaved rows (lattice_plane_*)
     float *ad_edge = nullptr;   // scalar lattice, OPEN family: the edge state on the device (scalar_launch.h)
     float ad_G = 0.f;           // scalar lattice: growth rate of the Fisher term (lb_set_reaction); 0 = plain relaxation
-    float *vi_corner = nullptr; // VELOCITY_INLET: the eight corner links nothing ever writes (bc_vel_cell), device; LB_BC_BOX: likewise (mf_box_cell)
+    float *vi_corner = nullptr; // VELOCITY_INLET: the eight corner links nothing ever writes (bc_vel_cell), device; LB_BC_BOX, LB_BC_DIRICHLET: likewise (mf_box_cell, ps_box_cell)
+    // the LB Poisson solver (LB_SEM_POISSON; poisson_launch.h)
+    float *ps_source = nullptr;         // [H][pitch]: the source, padding zero
+    float *ps_part = nullptr;           // two floats per workgroup of k_ps_step
+    PsState *ps_state = nullptr;        // the device's side of a solve: stop word, last ratio
+    float ps_rho_b = 0.f, ps_react = 1.f, ps_tol = 1.0e-6f;     // lb_set_poisson
+    int ps_iter = 0;                    // iterations since the last lb_solve_reset (solver.py's num_iterations)
+    int ps_batch = 0;                   // lb_solve's launches between two reads of the stop word; 0 = PS_BATCH (LB_DIAG on such a handle: diagnosis)
     uint8_t *mask_raw = nullptr, *mask = nullptr;   // [H+2*MASK_GHOST][pitch] + guards; mask -> row 0
     bool feq_valid = false;     // feq buffer consistent with rho,u,v
     bool macro_valid = true;    // rho,u,v hold the last step's fields (false: to be rebuilt from the populations, ensure_macro)
@@ -161,6 +169,13 @@ void drop_graph(lb_sim *s);
 int run_whole_grid(lb_sim *s, int n_steps, bool final_macro = true);
 // n time steps on a scalar lattice; the last launch stores rho
 int run_scalar(lb_sim *s, int n_steps);
+// n iterations of the Poisson solver with no check and no early out; the last launch stores rho
+int run_poisson(lb_sim *s, int n_steps);
+inline PsExtra ps_extra(const lb_sim *s)
+{
+    const float w0 = 4.f / 9.f;
+    return PsExtra{s->ps_source, s->ps_part, s->ps_state, (-1.f + w0) * s->ps_rho_b, s->ps_react, 0};
+}
 inline AdExtra ad_extra(const lb_sim *s) { return AdExtra{s->ad_edge, s->ad_G}; }
 
 // ---- slab.cpp --------------------------------------------------------------------------------------------------------------------

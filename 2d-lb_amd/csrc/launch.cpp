@@ -235,3 +235,19 @@ int run_scalar(lb_sim *s, int n_steps)
     if (n_steps) { s->feq_valid = false; s->macro_valid = true; }
     return LB_OK;
 }
+
+// n iterations of the LB Poisson solver (kernels_poisson.h) in lb_run's form: k_ps_step<false>, one launch each, no stop word, no sums;
+// the last launch stores rho, which is the next iteration's rho_before.  They count as iterations of the solve (solver.py:346).
+int run_poisson(lb_sim *s, int n_steps)
+{
+    PsExtra e = ps_extra(s);
+    for (int it = 0; it < n_steps; ++it) {
+        e.store_rho = it == n_steps - 1;
+        lbk_ps_step(false, s->stream, step_args(s, 0, 1, s->H), e);
+        HIP_TRY(hipGetLastError());
+        s->cur ^= 1;
+    }
+    s->ps_iter += n_steps;
+    if (n_steps) { s->feq_valid = false; s->macro_valid = true; }
+    return LB_OK;
+}

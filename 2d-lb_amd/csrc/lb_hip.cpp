@@ -201,12 +201,12 @@ int lattice_plane_d2h(lb_sim *s, float *host, const float *origin, int k)
 // patch: written back into it.
 int frozen_links(lb_sim *s, int which, bool patch)
 {
-    if (s->p.bc_mode == LB_BC_VELOCITY_INLET || s->p.bc_mode == LB_BC_BOX) {
+    if (s->p.bc_mode == LB_BC_VELOCITY_INLET || s->p.bc_mode == LB_BC_BOX || s->p.bc_mode == LB_BC_DIRICHLET) {
         const int X = s->p.nx - 1, Y = s->p.ny - 1;
         struct Link { int k, x, y; };
         const Link vel[8] = {{1, 0, 0}, {8, 0, 0}, {1, 0, Y}, {5, 0, Y}, {3, X, 0}, {7, X, 0}, {3, X, Y}, {6, X, Y}};   // (bc_vel_cell's order)
-        const Link box[8] = {{6, 0, 0}, {8, 0, 0}, {5, X, 0}, {7, X, 0}, {5, 0, Y}, {7, 0, Y}, {6, X, Y}, {8, X, Y}};   // (mf_box_cell's order)
-        const Link *c = s->p.bc_mode == LB_BC_BOX ? box : vel;
+        const Link box[8] = {{6, 0, 0}, {8, 0, 0}, {5, X, 0}, {7, X, 0}, {5, 0, Y}, {7, 0, Y}, {6, X, Y}, {8, X, Y}};   // (mf_box_cell's and ps_box_cell's order)
+        const Link *c = s->p.bc_mode == LB_BC_VELOCITY_INLET ? vel : box;
         for (int i = 0; i < 8; ++i) {
             float *in_lat = s->origin(which) + c[i].k * s->plane + (long long)c[i].y * s->rowp + c[i].x, *kept = s->vi_corner + i;
             HIP_TRY(hipMemcpyAsync(patch ? in_lat : kept, patch ? kept : in_lat, sizeof(float), hipMemcpyDeviceToDevice, s->stream));
@@ -301,7 +301,17 @@ int lb_create(const lb_params *p, lb_sim **out)
     if (p->nx < 2 || p->ny < 2) return fail(LB_ERR_ARG, "grid must be at least 2x2 (got %dx%d)", p->nx, p->ny);
     if (p->local_ny < 1 || p->y0 < 0 || p->y0 + p->local_ny > p->ny)
         return fail(LB_ERR_ARG, "slab [%d,%d) outside 0..%d", p->y0, p->y0 + p->local_ny, p->ny);
-    if (p->bc_mode < LB_BC_PIPE || p->bc_mode > LB_BC_BOX) return fail(LB_ERR_ARG, "unknown bc_mode %d", p->bc_mode);
+    if (p->bc_mode < LB_BC_PIPE || p->bc_mode > LB_BC_DIRICHLET) return fail(LB_ERR_ARG, "unknown bc_mode %d", p->bc_mode);
+    if (p->bc_mode == LB_BC_DIRICHLET && p->semantics != LB_SEM_POISSON)
+        return fail(LB_ERR_ARG, "LB_BC_DIRICHLET exists for the LB Poisson solver (LB_SEM_POISSON) only: unknown bc_mode %d for semantics %d", p->bc_mode, p->semantics);
+    if (p->semantics == LB_SEM_POISSON) {
+        // the LB Poisson solver: a scalar lattice, refused likewise (before any device is touched)
+        if (p->bc_mode != LB_BC_DIRICHLET)
+            return fail(LB_ERR_ARG, "the LB Poisson solver (LB_SEM_POISSON) takes the family LB_BC_DIRICHLET only: unknown semantics %d for bc_mode %d", p->semantics, p->bc_mode);
+        if (p->local_ny != p->ny || p->y0 != 0) return fail(LB_ERR_ARG, "the LB Poisson solver (LB_SEM_POISSON) owns its whole grid: no slabs");
+        if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "the LB Poisson solver (LB_SEM_POISSON) has no halo interface (LB_FLAG_HALO)");
+        if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "the LB Poisson solver (LB_SEM_POISSON) runs on a GPU only (no CPU backend)");
+    }
     if (p->bc_mode == LB_BC_OPEN && p->semantics != LB_SEM_DIFFUSION)
         return fail(LB_ERR_ARG, "LB_BC_OPEN exists for scalar lattices (LB_SEM_DIFFUSION) only");
     if (p->bc_mode == LB_BC_BOX && p->semantics != LB_SEM_MULTIFIELD)
@@ -332,7 +342,7 @@ int lb_create(const lb_params *p, lb_sim **out)
         if (r != 0) return fail(LB_ERR_ARG, "reserved fields must be zero");
     if (p->flags & ~(LB_FLAG_HALO | LB_FLAG_PLANAR | LB_FLAG_EAGER_MACRO)) return fail(LB_ERR_ARG, "unknown flags 0x%x", p->flags);
     if (p->semantics != LB_SEM_OPENCL && p->semantics != LB_SEM_CYTHON && p->semantics != LB_SEM_OPENCL_D2Q9I && p->semantics != LB_SEM_DIFFUSION &&
-        p->semantics != LB_SEM_MULTIFIELD)
+        p->semantics != LB_SEM_MULTIFIELD && p->semantics != LB_SEM_POISSON)
         return fail(LB_ERR_ARG, "unknown semantics %d", p->semantics);
     if (p->semantics == LB_SEM_OPENCL_D2Q9I &&
         (p->bc_mode != LB_BC_PIPE || p->local_ny != p->ny || (p->flags & LB_FLAG_HALO)))
@@ -431,6 +441,20 @@ int lb_create(const lb_params *p, lb_sim **out)
         CREATE_TRY(hipMalloc(&s->ad_edge, edge_bytes));
         CREATE_TRY(hipMemsetAsync(s->ad_edge, 0, edge_bytes, s->stream));
     }
+    if (s->poisson()) {
+        // (the diagnostic word of the flow kernels means nothing here: on this handle it is lb_solve's batch length)
+        s->ps_batch = s->diag > 0 ? s->diag : 0;
+        s->diag = 0;
+        const size_t part_bytes = 2 * sizeof(float) * (size_t)ps_step_blocks(step_args(s, 0, 1, s->H));
+        CREATE_TRY(hipMalloc(&s->ps_source, fld_bytes));
+        CREATE_TRY(hipMemsetAsync(s->ps_source, 0, fld_bytes, s->stream));
+        CREATE_TRY(hipMalloc(&s->ps_part, part_bytes));
+        CREATE_TRY(hipMemsetAsync(s->ps_part, 0, part_bytes, s->stream));
+        CREATE_TRY(hipMalloc(&s->ps_state, sizeof(PsState)));
+        const PsState fresh = {0, nanf(""), 0, 0};
+        CREATE_TRY(hipMemcpy(s->ps_state, &fresh, sizeof(fresh), hipMemcpyHostToDevice));
+        s->bytes += fld_bytes + part_bytes + sizeof(PsState);
+    }
     CREATE_TRY(hipMalloc(&s->vi_corner, 8 * sizeof(float)));
     CREATE_TRY(hipMemsetAsync(s->vi_corner, 0, 8 * sizeof(float), s->stream));
     CREATE_TRY(hipMalloc(&s->mask_raw, (size_t)s->pitch * (s->H + 2 * MASK_GHOST) + 2 * GUARD));
@@ -441,7 +465,7 @@ int lb_create(const lb_params *p, lb_sim **out)
     CREATE_TRY(hipMemsetAsync(s->mask_raw, 0, (size_t)s->pitch * (s->H + 2 * MASK_GHOST) + 2 * GUARD, s->stream));
     CREATE_TRY(hipStreamSynchronize(s->stream));
 #undef CREATE_TRY
-    s->bytes = 2 * lat_bytes + 3 * fld_bytes + (size_t)s->pitch * s->H;
+    s->bytes += 2 * lat_bytes + 3 * fld_bytes + (size_t)s->pitch * s->H;
     // A periodic box whose width is not a multiple of 4 cannot use the marching kernels (their lanes hold four consecutive
     // cells, and the wrap at x = nx must fall on a lane boundary): above the Infinity Cache that costs a factor of two or
     // more (LDS tiles / single steps instead of k_step5 / k_step6).  Say so once instead of being silently slow; LB_QUIET=1 mutes it.
@@ -481,10 +505,11 @@ int lb_destroy(lb_sim *s)
         }
     if (s->peer_flags) (void)hipFree(s->peer_flags);
     if (s->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(s->comm);
-    for (float *p : {s->lat[0], s->lat[1], s->feq, s->rho, s->u, s->v, s->halo_buf, s->vi_corner, s->stage, s->ad_edge})
+    for (float *p : {s->lat[0], s->lat[1], s->feq, s->rho, s->u, s->v, s->halo_buf, s->vi_corner, s->stage, s->ad_edge, s->ps_source, s->ps_part})
         if (p) (void)hipFree(p);
     if (s->mask_raw) (void)hipFree(s->mask_raw);
     if (s->check_part) (void)hipFree(s->check_part);
+    if (s->ps_state) (void)hipFree(s->ps_state);
     for (hipEvent_t e : {s->ev_boundary, s->ev_interior, s->ev_halo, s->ev_packed, s->ev_edge, s->ev_t0, s->ev_t1})
         if (e) (void)hipEventDestroy(e);
     if (s->own_stream) (void)hipStreamDestroy(s->own_stream);
@@ -532,6 +557,8 @@ int lb_set_variant(lb_sim *s, int variant)
     if (!s) return fail(LB_ERR_ARG, "null handle");
     if (s->multifield() && variant != -1 && variant != 0)
         return fail(LB_ERR_ARG, "a coupled scalar lattice (LB_SEM_MULTIFIELD) takes the variants -1 and 0 only: k_mf_step, no tiles");
+    if (s->poisson() && variant != -1 && variant != 0)
+        return fail(LB_ERR_STATE, "the LB Poisson solver (LB_SEM_POISSON) takes the variants -1 and 0 only: k_ps_step, no tiles");
     s->variant = variant;
     return LB_OK;
 }
@@ -700,7 +727,7 @@ int lb_get_f(lb_sim *s, float *f)
 int lb_get_corner_state(lb_sim *s, float *out8)
 {
     CPU_UNSUPPORTED(s, "lb_get_corner_state");
-    if (s && !s->multifield()) SCALAR_UNSUPPORTED(s, "lb_get_corner_state");
+    if (s && !s->multifield() && !s->poisson()) SCALAR_UNSUPPORTED(s, "lb_get_corner_state");
     if (!s || !out8) return fail(LB_ERR_ARG, "null argument");
     DeviceGuard guard(s->p.device);
     HIP_TRY(hipMemcpyAsync(out8, s->vi_corner, 8 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
@@ -711,7 +738,7 @@ int lb_get_corner_state(lb_sim *s, float *out8)
 int lb_set_corner_state(lb_sim *s, const float *in8)
 {
     CPU_UNSUPPORTED(s, "lb_set_corner_state");
-    if (s && !s->multifield()) SCALAR_UNSUPPORTED(s, "lb_set_corner_state");
+    if (s && !s->multifield() && !s->poisson()) SCALAR_UNSUPPORTED(s, "lb_set_corner_state");
     if (!s || !in8) return fail(LB_ERR_ARG, "null argument");
     DeviceGuard guard(s->p.device);
     HIP_TRY(hipMemcpyAsync(s->vi_corner, in8, 8 * sizeof(float), hipMemcpyHostToDevice, s->stream));
@@ -821,9 +848,16 @@ int lb_set_mask_halo(lb_sim *s, const int32_t *south_rows, const int32_t *north_
         if (!(s)->scalar()) return fail(LB_ERR_STATE, "%s is for scalar lattices (LB_SEM_DIFFUSION)", name); \
     } while (0)
 
+// ... whose velocity is imposed: the Poisson solver has none, and its source term is lb_set_source's
+#define NOT_POISSON(s, name)                                                                                 \
+    do {                                                                                                     \
+        if ((s)->poisson()) return fail(LB_ERR_STATE, "%s is not available on the LB Poisson solver (LB_SEM_POISSON)", name); \
+    } while (0)
+
 int lb_set_reaction(lb_sim *s, float G)
 {
     NEED_SCALAR(s, "lb_set_reaction");
+    NOT_POISSON(s, "lb_set_reaction");
     if (!(fabsf(G) <= 3.0e38f)) return fail(LB_ERR_ARG, "the growth rate must be finite");
     s->ad_G = G;
     return LB_OK;
@@ -886,6 +920,7 @@ int lb_set_edge_state(lb_sim *s, const float *in)
 int lb_set_velocity_from(lb_sim *s, lb_sim *flow)
 {
     NEED_SCALAR(s, "lb_set_velocity_from");
+    NOT_POISSON(s, "lb_set_velocity_from");
     if (!flow) return fail(LB_ERR_ARG, "null flow handle");
     if (flow->cpu || flow->scalar() || flow->multi_slab())
         return fail(LB_ERR_ARG, "lb_set_velocity_from takes a whole-grid GPU flow handle");
@@ -908,6 +943,141 @@ int lb_set_velocity_from(lb_sim *s, lb_sim *flow)
     HIP_TRY(hipEventRecord(flow->ev_interior, flow->stream));
     HIP_TRY(hipStreamWaitEvent(s->stream, flow->ev_interior, 0));
     s->feq_valid = false;
+    return LB_OK;
+}
+
+// ---- the LB Poisson solver ---------------------------------------------------------------------
+#define NEED_POISSON(s, name)                                                                                \
+    do {                                                                                                     \
+        if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
+        if (!(s)->poisson()) return fail(LB_ERR_STATE, "%s is for the LB Poisson solver (LB_SEM_POISSON)", name); \
+    } while (0)
+
+// lb_solve's launches between two reads of the stop word.  profiles/poisson_bench.txt: the read-back is one host round trip per batch,
+// the launches behind a stop inside a batch are empty early-outs.
+static const int PS_BATCH = 32;
+
+int lb_set_poisson(lb_sim *s, float rho_on_boundary, float react_factor, float tolerance)
+{
+    NEED_POISSON(s, "lb_set_poisson");
+    if (!(fabsf(rho_on_boundary) <= 3.0e38f) || !(fabsf(react_factor) <= 3.0e38f)) return fail(LB_ERR_ARG, "rho_on_boundary and react_factor must be finite");
+    if (!(tolerance >= 0.f)) return fail(LB_ERR_ARG, "the tolerance must be >= 0");
+    s->ps_rho_b = rho_on_boundary;
+    s->ps_react = react_factor;
+    s->ps_tol = tolerance;
+    return LB_OK;
+}
+
+int lb_set_source(lb_sim *s, const float *src, int on_device)
+{
+    NEED_POISSON(s, "lb_set_source");
+    if (!src) return fail(LB_ERR_ARG, "null argument");
+    DeviceGuard guard(s->p.device);
+    HIP_TRY(hipMemcpy2DAsync(s->ps_source, s->pitch * sizeof(float), src, s->p.nx * sizeof(float), s->p.nx * sizeof(float), s->H,
+                             on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return LB_OK;
+}
+
+int lb_get_source(lb_sim *s, float *src)
+{
+    NEED_POISSON(s, "lb_get_source");
+    if (!src) return fail(LB_ERR_ARG, "null argument");
+    DeviceGuard guard(s->p.device);
+    int rc = copy_plane_d2h(s, src, s->ps_source);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return LB_OK;
+}
+
+int lb_solve_reset(lb_sim *s)
+{
+    NEED_POISSON(s, "lb_solve_reset");
+    s->ps_iter = 0;
+    return LB_OK;
+}
+
+int lb_get_solve_state(lb_sim *s, int *iterations, int *stop_word)
+{
+    NEED_POISSON(s, "lb_get_solve_state");
+    DeviceGuard guard(s->p.device);
+    PsState h;
+    HIP_TRY(hipMemcpyAsync(&h, s->ps_state, sizeof(h), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (iterations) *iterations = s->ps_iter;
+    if (stop_word) *stop_word = h.stop;
+    return LB_OK;
+}
+
+int lb_set_solve_state(lb_sim *s, int iterations, int stop_word)
+{
+    NEED_POISSON(s, "lb_set_solve_state");
+    if (iterations < 0 || stop_word < 0 || stop_word > iterations) return fail(LB_ERR_ARG, "need 0 <= stop_word <= iterations");
+    DeviceGuard guard(s->p.device);
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(&s->ps_state->stop, &stop_word, sizeof(int), hipMemcpyHostToDevice));
+    s->ps_iter = iterations;
+    return LB_OK;
+}
+
+// solver.py:324-358 without its host waits: per iteration one k_ps_step<true> and -- from the second iteration since the last reset --
+// one k_ps_check, PS_BATCH iterations enqueued at a time; after each batch the stop word comes back (4 bytes).  A stop at iteration
+// n* leaves the launches behind it as empty early-outs, so the populations and rho are those after n* iterations; which lattice of the
+// pair holds them follows from n*.
+int lb_solve(lb_sim *s, int max_iterations, int *iterations_done, int *converged, float *last_ratio)
+{
+    NEED_POISSON(s, "lb_solve");
+    if (max_iterations < 0) return fail(LB_ERR_ARG, "negative iteration count");
+    DeviceGuard guard(s->p.device);
+    const int batch = s->ps_batch > 0 ? s->ps_batch : PS_BATCH, first = s->ps_iter, cur0 = s->cur;
+    const long long blocks = ps_step_blocks(step_args(s, 0, 1, s->H));
+    const PsExtra e = ps_extra(s);
+    HIP_TRY(hipMemsetAsync(&s->ps_state->stop, 0, sizeof(int), s->stream));     // (a call after a stop goes on, as the reference's run does)
+    int launched = 0, stop = 0;
+    while (launched < max_iterations && !stop) {
+        const int nb = std::min(batch, max_iterations - launched);
+        for (int i = 0; i < nb; ++i, ++launched) {
+            const int it = first + launched + 1;
+            lbk_ps_step(true, s->stream, step_args(s, 0, 1, s->H), e);
+            HIP_TRY(hipGetLastError());
+            s->cur ^= 1;
+            if (it >= 2) {
+                lbk_ps_check(s->stream, s->ps_part, blocks, s->ps_state, it, s->ps_tol);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(&stop, &s->ps_state->stop, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    const int done = stop ? stop - first : launched;
+    s->cur = cur0 ^ (done & 1);
+    s->ps_iter = first + done;
+    if (done) { s->feq_valid = false; s->macro_valid = true; }
+    if (last_ratio) {
+        HIP_TRY(hipMemcpyAsync(last_ratio, &s->ps_state->ratio, sizeof(float), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    if (iterations_done) *iterations_done = done;
+    if (converged) *converged = stop ? 1 : 0;
+    return LB_OK;
+}
+
+// One launch into the handle's u, v planes -- which no other kernel of this semantics writes: they hold the last gradient, lb_get_macro
+// returns it --, then one pitched copy each to wherever the caller's pointers lead.
+int lb_gradient(lb_sim *s, float inv_two_dx, float *ddx, float *ddy)
+{
+    NEED_POISSON(s, "lb_gradient");
+    if (!(fabsf(inv_two_dx) <= 3.0e38f)) return fail(LB_ERR_ARG, "inv_two_dx must be finite");
+    DeviceGuard guard(s->p.device);
+    lbk_ps_gradient(s->stream, step_args(s, 0, 1, s->H), inv_two_dx);
+    HIP_TRY(hipGetLastError());
+    float *out[2] = {ddx, ddy};
+    const float *from[2] = {s->u, s->v};
+    for (int i = 0; i < 2; ++i)
+        if (out[i])
+            HIP_TRY(hipMemcpy2DAsync(out[i], s->p.nx * sizeof(float), from[i], s->pitch * sizeof(float), s->p.nx * sizeof(float), s->H,
+                                     hipMemcpyDefault, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
     return LB_OK;
 }
 
@@ -945,8 +1115,13 @@ int lb_move_bcs(lb_sim *s)
     if (!s) return fail(LB_ERR_ARG, "null handle");
     int rc = need_single_slab(s, "lb_move_bcs");
     if (rc) return rc;
-    if (s->scalar() && s->p.bc_mode != LB_BC_BOX) return LB_OK;     // (diffusion.py:326-331: `pass`; the periodic families have none)
+    if (s->scalar() && s->p.bc_mode != LB_BC_BOX && !s->poisson()) return LB_OK;     // (diffusion.py:326-331: `pass`; the periodic families have none)
     DeviceGuard guard(s->p.device);
+    if (s->poisson()) {                             // D2Q9_poisson.cl's move_bcs: the prescribed value on four walls
+        lbk_ps_move_bcs(s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur), ps_extra(s).wall);
+        HIP_TRY(hipGetLastError());
+        return LB_OK;
+    }
     if (s->scalar()) {                              // D2Q9_multifield_fisher.cl's move_bcs: on-node bounce-back on four walls
         lbk_mf_move_bcs(s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur));
         HIP_TRY(hipGetLastError());
@@ -972,7 +1147,9 @@ int lb_update_hydro(lb_sim *s)
     int rc = need_single_slab(s, "lb_update_hydro");
     if (rc) return rc;
     DeviceGuard guard(s->p.device);
-    if (s->scalar())
+    if (s->poisson())
+        lbk_ps_hydro(s->stream, step_args(s, 0, 1, s->H));       // rho = (9/5)(f1 + ... + f8)
+    else if (s->scalar())
         lbk_ad_hydro(s->stream, step_args(s, 0, 1, s->H));       // rho only: u, v are imposed
     else if (s->p.semantics == LB_SEM_CYTHON)
         hipLaunchKernelGGL(k1_hydro, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
@@ -1000,7 +1177,9 @@ int lb_update_feq(lb_sim *s)
     if ((rc = ensure_macro(s))) return rc;
     PhaseArgs a = phase_args(s);
     a.ny = s->H;   // rho,u,v are local: valid for slabs too
-    if (s->scalar())
+    if (s->poisson())
+        lbk_ps_feq(s->stream, step_args(s, 0, 1, s->H), s->feq_origin());
+    else if (s->scalar())
         lbk_ad_feq(s->stream, step_args(s, 0, 1, s->H), s->feq_origin());
     else if (s->p.semantics == LB_SEM_OPENCL_D2Q9I)
         hipLaunchKernelGGL(k_feq_i, dim3((s->p.nx + 255) / 256, s->H, 1), dim3(256), 0, s->stream, a);
@@ -1021,7 +1200,9 @@ int lb_collide_particles(lb_sim *s)
     if (s->multifield()) return lb_collide_coupled(&s, 1);
     DeviceGuard guard(s->p.device);
     if ((rc = ensure_macro(s))) return rc;
-    if (s->scalar())
+    if (s->poisson())
+        lbk_ps_collide(s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur), s->feq_origin(), s->ps_source, s->ps_react);
+    else if (s->scalar())
         lbk_ad_collide(s->ad_G != 0.f, s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur), s->feq_origin(), s->ad_G);
     else
         hipLaunchKernelGGL(k_collide, cells_grid(s, 9), dim3(256), 0, s->stream, phase_args(s));
@@ -1079,6 +1260,7 @@ int lb_run(lb_sim *s, int n_steps)
     if (s->stepping) return fail(LB_ERR_STATE, "lb_run between lb_step_boundary and lb_step_finish");
     DeviceGuard guard(s->p.device);
     if (s->multifield()) return lb_run_coupled(&s, 1, n_steps);
+    if (s->poisson()) return run_poisson(s, n_steps);
     if (s->scalar()) return run_scalar(s, n_steps);
     if (!s->tune_cache_checked) (void)tune_cache_apply(s);
     if (s->p.semantics == LB_SEM_CYTHON) return run_cython(s, n_steps);
@@ -1246,6 +1428,7 @@ int lb_check(lb_sim *s, int across_ranks, int64_t *n_nonfinite, float *max_mach,
     }
     if (!s) return fail(LB_ERR_ARG, "null handle");
     if (s->stepping) return fail(LB_ERR_STATE, "lb_check inside a split step");
+    if (s->poisson()) return fail(LB_ERR_STATE, "lb_check is not available on the LB Poisson solver (LB_SEM_POISSON): lb_solve reports its residual");
     if (across_ranks && !s->comm) return fail(LB_ERR_STATE, "lb_check across ranks needs lb_comm_init");
     DeviceGuard guard(s->p.device);
     // the pass that rebuilds rho, u, v reduces the same three numbers: one pass serves both when the fields are due (never on a

@@ -481,7 +481,7 @@ bool tune_entry_runs_here(const PlanInputs *s, int steps, int wpc)
 static const double SCALAR_TILE_MIN_CELLS = 256.0 * 256.0, SCALAR_TILE_MAX_CELLS = 8192.0 * 8192.0;
 bool scalar_use_tiles(const PlanInputs *s)
 {
-    if (s->multifield()) return false;              // (no tiles for coupled sets: k_mf_step, one step per launch)
+    if (s->multifield() || s->poisson()) return false;      // (no tiles for coupled sets and the Poisson solver: k_mf_step / k_ps_step, one step per launch)
     if (s->variant >= 0) return (s->variant & LB_VAR_TILES) != 0;
     const double cells = (double)s->p.nx * s->H;
     return cells >= SCALAR_TILE_MIN_CELLS && cells <= SCALAR_TILE_MAX_CELLS;
@@ -538,6 +538,10 @@ int steps_per_launch(const PlanInputs *s)
 void hot_kernel(const PlanInputs *s, char *buf, int buflen)
 {
     static const char *const bc_names[] = {"PIPE", "PERIODIC", "CAVITY", "VELOCITY_INLET", "PIPE, D2Q9i"};
+    if (s->poisson()) {
+        snprintf(buf, (size_t)buflen, "k_ps_step (LB Poisson solver: one fused pull-stream + prescribed-value walls + relaxation pass that also leaves the convergence sums)<DIRICHLET>");
+        return;
+    }
     if (s->multifield()) {
         snprintf(buf, (size_t)buflen, "k_mf_step (coupled scalar lattices: one fused pull-stream + linear-equilibrium collide pass for all fields)<%s>",
                  s->p.bc_mode == LB_BC_PERIODIC ? "PERIODIC" : "BOX");

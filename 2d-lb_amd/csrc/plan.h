@@ -28,7 +28,8 @@ struct PlanInputs {
     int transport = SLAB_NO_TRANSPORT;   // slabs: lb_comm_init / lb_peer_connect
 
     bool multifield() const { return p.semantics == LB_SEM_MULTIFIELD; } // one field of a coupled set of scalar lattices (kernels_multifield.h)
-    bool scalar() const { return p.semantics == LB_SEM_DIFFUSION || multifield(); }      // a scalar lattice (kernels_scalar.h), on its own or coupled
+    bool poisson() const { return p.semantics == LB_SEM_POISSON; }       // the LB Poisson solver (kernels_poisson.h)
+    bool scalar() const { return p.semantics == LB_SEM_DIFFUSION || multifield() || poisson(); }  // a scalar lattice (kernels_scalar.h), on its own or coupled, or the Poisson solver's
     bool multi_slab() const { return H != p.ny || (p.flags & LB_FLAG_HALO); }
     int agreed_h() const { return min_h > 0 ? min_h : H; }      // the height all ranks decide on
 };

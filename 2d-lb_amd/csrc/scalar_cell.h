@@ -83,4 +83,34 @@ __device__ __forceinline__ void ad_feq_cell(float (&e)[9], float rho, float ux, 
     ad_feq_pair<float>(r2, r23, ux - uy, e[8], e[6]);
 }
 
+// ---- the Poisson relaxation (LB_SEM_POISSON): the reference's LB_D2Q9/D2Q9_poisson.cl -- update_hydro :34-63 (rho = (9/5)(f1 + ... + f8);
+// f0 is not read), update_feq :1-31 (feq_0 = (w0 - 1) rho, feq_k = w_k rho), collide_particles :65-97 (f_k (1 - omega) + omega feq_k +
+// w_k react).  Unlike the transport cell above, the fused step and the un-fused phases are held to each other BITWISE: both go through
+// these three functions, feq_k is a float32 of its own (stored by the phases, a register of the fused cell), and omega multiplies it.
+template <typename T>
+__device__ __forceinline__ T ps_rho_t(T f1, T f2, T f3, T f4, T f5, T f6, T f7, T f8)
+{
+    return (9.f / 5.f) * (f1 + f2 + f3 + f4 + f5 + f6 + f7 + f8);     // D2Q9_poisson.cl:59, left to right
+}
+
+template <typename T>
+__device__ __forceinline__ void ps_feq_t(T (&e)[9], T rho)
+{
+    const float w0 = 4.f / 9.f, w1 = 1.f / 9.f, w2 = 1.f / 36.f;
+    e[0] = (w0 - 1.f) * rho;
+    e[1] = w1 * rho; e[2] = w1 * rho; e[3] = w1 * rho; e[4] = w1 * rho;
+    e[5] = w2 * rho; e[6] = w2 * rho; e[7] = w2 * rho; e[8] = w2 * rho;
+}
+
+// f_k := fma(w_k, react, fma(f_k, 1 - omega, omega feq_k)), in place; react = source x (delta_t D), one float32 per cell
+template <typename T>
+__device__ __forceinline__ void ps_relax_t(T (&f)[9], const T (&e)[9], float omega, T react)
+{
+    const T keep = lb_splat<T>(1.f - omega), om = lb_splat<T>(omega);
+    const T w[9] = {lb_splat<T>(4.f / 9.f), lb_splat<T>(1.f / 9.f), lb_splat<T>(1.f / 9.f), lb_splat<T>(1.f / 9.f), lb_splat<T>(1.f / 9.f),
+                    lb_splat<T>(1.f / 36.f), lb_splat<T>(1.f / 36.f), lb_splat<T>(1.f / 36.f), lb_splat<T>(1.f / 36.f)};
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[k] = lb_fma(w[k], react, lb_fma(f[k], keep, om * e[k]));
+}
+
 }  // namespace

@@ -58,10 +58,15 @@ typedef enum {
     LB_BC_OPEN = 4,       /* scalar lattices (LB_SEM_DIFFUSION) only: the box of the reference's Diffusion classes, whose move_bcs
                              is `pass` (reaction_diffusion/diffusion.py): a link that would enter from outside the box keeps the
                              value it had when the populations were last set -- the handle's edge state (lb_get_edge_state). */
-    LB_BC_BOX = 5         /* coupled scalar lattices (LB_SEM_MULTIFIELD) only: the closed box of the reference's
+    LB_BC_BOX = 5,        /* coupled scalar lattices (LB_SEM_MULTIFIELD) only: the closed box of the reference's
                              D2Q9_multifield_fisher.cl, whose move_bcs bounces every link that would enter from outside back on
                              the node itself (f1 := f3 at x = 0, ...), on all four walls.  Two links per corner are neither
                              streamed nor bounced: the handle's corner state (lb_get_corner_state). */
+    LB_BC_DIRICHLET = 6   /* the LB Poisson solver (LB_SEM_POISSON) only: the box of the reference's D2Q9_poisson.cl, whose move_bcs
+                             prescribes a value on all four walls: on each wall and in each corner the three links pointing into the
+                             box become w_k R, R = -(sum of the cell's five other non-rest links + (w0 - 1) rho_on_boundary) /
+                             (sum of the three weights).  Two links per corner are neither streamed nor written, and the corner's
+                             rule reads them: the handle's corner state, LB_BC_BOX's eight links in the same order. */
 } lb_bc_mode;
 
 /* Which of the reference's two (numerically different) paths the handle reproduces.
@@ -93,7 +98,7 @@ typedef enum {
                                  latter 0.89-0.91 of the copy rate on the same handle: profiles/scalar_bench.txt).  A run
                                  always stores rho in its last launch -- with G != 0 rho is not a moment of what a run leaves
                                  behind.  omega, nx, ny are the only other lb_params fields it reads. */
-    LB_SEM_MULTIFIELD = 4     /* ONE FIELD of a set of coupled scalar lattices: LB_D2Q9/D2Q9_multifield_fisher.cl driven as
+    LB_SEM_MULTIFIELD = 4,    /* ONE FIELD of a set of coupled scalar lattices: LB_D2Q9/D2Q9_multifield_fisher.cl driven as
                                  advecting_range_expansion/deterministic_fisher_waves.py does.  A scalar lattice in every respect
                                  above (whole-grid GPU handle, imposed u, v, lb_set_reaction = this field's G, rho always stored),
                                  except that the growth term of field i is w_k G_i rho_i (1 - sum_j rho_j) over the fields
@@ -101,6 +106,16 @@ typedef enum {
                                  LB_BC_PERIODIC (build-defined) and LB_BC_BOX (the reference's closed box).  One fused launch
                                  per time step for the whole set (k_mf_step: 72 B of populations per field + 8 B of u, v per
                                  cell and step); lb_set_variant takes -1 and 0 only (no LDS tiles for coupled sets). */
+    LB_SEM_POISSON = 5        /* the LB POISSON SOLVER: LB_D2Q9/D2Q9_poisson.cl driven as poisson/solver.py does -- a D2Q9 relaxation
+                                 whose fixed point solves a Poisson problem in a box: rho = (9/5)(f1 + ... + f8), feq_0 = (w0 - 1) rho,
+                                 feq_k = w_k rho, f_k (1 - omega) + omega feq_k + w_k source react_factor, a prescribed value on the four
+                                 walls (LB_BC_DIRICHLET, the only family), and a run loop that stops when rho has stopped changing.
+                                 Whole-grid GPU handles without obstacles; omega, nx, ny are the only lb_params fields read
+                                 (lb_set_poisson has the rest).  One fused launch per iteration (k_ps_step: 88 B per cell) that
+                                 also leaves the two sums of the reference's convergence test, one small launch that folds them and
+                                 sets a device-side stop word (k_ps_check), no host wait but one 4-byte read-back per batch of
+                                 iterations: lb_solve, below.  u, v of such a handle are written by lb_gradient only.
+                                 lb_set_variant takes -1 and 0 only. */
 } lb_semantics;
 
 typedef struct {
@@ -212,6 +227,44 @@ int lb_edge_floats(lb_sim *s);
 int lb_get_edge_state(lb_sim *s, float *out);
 int lb_set_edge_state(lb_sim *s, const float *in);
 int lb_set_velocity_from(lb_sim *s, lb_sim *flow);
+
+/* ---- the LB Poisson solver (LB_SEM_POISSON; LB_ERR_STATE on every other handle) --------------------------------------
+ * A fresh handle is the reference's start: f = 0, rho = 0, source = 0, corner state = 0, iteration counter = 0.
+ * lb_set_poisson: rho_on_boundary, the value prescribed on the walls (default 0); react_factor, the `delta_t * D` of the
+ *   reference's collide_particles (default 1): every cell adds w_k source react_factor.  (The reference's class scales the
+ *   source by lb_D delta_t once more on the host, update_source: the caller's business, LB_D2Q9.poisson does it.)
+ *   tolerance, of lb_solve's stopping rule (default 1e-6).
+ * lb_set_source / lb_get_source: the source field, [ny][nx] floats.  on_device != 0: src is a device pointer to that dense
+ *   layout and the copy into the handle's padded plane never goes through the host (ordered on the handle's stream; the
+ *   caller has finished writing src).
+ * lb_solve: up to max_iterations iterations of solver.py's run loop.  After every iteration whose index n (counted since
+ *   the last lb_solve_reset; lb_run's iterations count as well) is >= 2 the device forms
+ *   ratio = mean |rho - rho_before| / mean rho_before (sums in a fixed order: reproducible) and, if ratio < tolerance --
+ *   false for the inf and NaN of a lattice that starts at zero --, sets its stop word to n.  Launches are enqueued in batches
+ *   with no host wait inside a batch; the launches of a batch behind the stop do nothing, so what the call leaves is exactly
+ *   the state after n iterations: the reference's.  *iterations_done = iterations made by this call, *converged = 1 if it
+ *   stopped by the rule, *last_ratio = the ratio of the last iteration checked (NaN: none yet).  Any may be NULL.  Waits for
+ *   the handle's work.  The counter persists between calls (solver.py's num_iterations); a call after a stop goes on.
+ * lb_solve_reset: the counter back to 0 (what update_source does); rho and the populations stay.
+ * lb_get_solve_state / lb_set_solve_state: the counter and the stop word (0, or the iteration a solve stopped at), for
+ *   checkpoints.
+ * lb_gradient: central differences of rho over 2 dx, inv_two_dx = 1 / (2 dx), 0 for a neighbour outside the box:
+ *   ddx[y nx + x] = (rho(x+1, y) - rho(x-1, y)) inv_two_dx, ddy likewise in y.  One launch writes them into the handle's u and
+ *   v fields (lb_get_macro returns them from then on: nothing else ever writes u, v of such a handle), then each is copied
+ *   to nx ny floats at ddx / ddy: device pointers, or host pointers (hipMemcpyDefault), or NULL for no copy.  Waits for the
+ *   handle's work.  (The reference's update_negative_gradient stores MINUS the y-difference in `u` and MINUS the x-difference
+ *   in `v`; LB_D2Q9.poisson.Poisson_Solver keeps that.)
+ * On such a handle lb_run(n) = n fused iterations with no check and no early out (the last stores rho), lb_move ...
+ * lb_collide_particles, lb_init_pop are the reference's phases, lb_get_corner_state / lb_set_corner_state work as on
+ * LB_BC_BOX; lb_set_reaction, lb_set_velocity_from, lb_check, lb_autotune* and every slab / mask call: LB_ERR_STATE. */
+int lb_set_poisson(lb_sim *s, float rho_on_boundary, float react_factor, float tolerance);
+int lb_set_source(lb_sim *s, const float *src, int on_device);
+int lb_get_source(lb_sim *s, float *src);
+int lb_solve(lb_sim *s, int max_iterations, int *iterations_done, int *converged, float *last_ratio);
+int lb_solve_reset(lb_sim *s);
+int lb_get_solve_state(lb_sim *s, int *iterations, int *stop_word);
+int lb_set_solve_state(lb_sim *s, int iterations, int stop_word);
+int lb_gradient(lb_sim *s, float inv_two_dx, float *ddx, float *ddy);
 
 /* ---- the reference's per-phase methods, one kernel each (slow, un-fused;
  *      API and test parity).  Single-slab handles only. ------------------- */
