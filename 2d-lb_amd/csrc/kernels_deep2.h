@@ -23,6 +23,9 @@
 // + 1 LDS window (8 KB); the hand-over slot 10 KB per direction: 72 KB per workgroup, two workgroups = eight waves per CU; 256 vector
 // registers per wave, no accumulation register.
 //
+// Issue priority.  Every back wave raises its priority once, at entry (deep2_set_prio below): without it the older of a CU's two
+// workgroups is served first on every SIMD and the younger runs a third of the launch alone.
+//
 // The launch moves the same 72 B per cell; same cell functions, same operations in the same order: bitwise equal to k_step.
 #pragma once
 
@@ -40,6 +43,26 @@ constexpr int DEEP2_WAVES = 4;
 // 8192^2 launch where k_deep<7> takes 0.89).  What the waves hand each other goes through LDS: an LDS instruction that has completed
 // (lgkmcnt) is visible to the workgroup.
 __device__ __forceinline__ void deep2_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// Static issue priority by role.  The hardware gives a SIMD's vector issue to the higher priority, then to the OLDER wave: at equal
+// priority the workgroup a CU was given first wins on all four SIMDs, runs as if alone and ends at two thirds of the launch, and the
+// second runs the last third with one wave per SIMD (profiles/r06y_wave_timeline_deep2.txt).  One role raises its priority -- once,
+// at entry, never inside the march.  What then meets on a SIMD is measured (per-wave records, profiles/deep2_priority_ab.txt): on a CU
+// with two workgroups two SIMDs hold a front wave of one and a back wave of the other, one holds two front waves and one two back
+// waves.  So with one role raised each workgroup wins ONE SIMD by priority, and on the two SIMDs that hold two of a kind age decides
+// as before: the older workgroup wins three SIMDs of four, not all four.  Which role is measured too (8192^2 periodic): with the
+// FRONT waves raised the two workgroups still end 30 % of the launch apart; with the BACK waves raised they advance alike and end 1 %
+// apart, and the product's launch is the shortest of the three.
+// mode (StepArgs::deep2_prio): 0 none, 1 front waves, 2 back waves; the diagnostic build overrides it by LB_DIAG bits 25-26
+// (0 = as launched, 1 / 2 / 3 = mode 0 / 1 / 2) so that one library runs the A/B.
+__device__ __forceinline__ void deep2_set_prio(const StepArgs &a, const int role_mode)
+{
+    int mode = a.deep2_prio;
+#ifdef LB_DIAG
+    if ((a.diag >> 25) & 3) mode = ((a.diag >> 25) & 3) - 1;
+#endif
+    if (mode == role_mode) __builtin_amdgcn_s_setprio(1);
+}
 
 // ---- the front wave: stages 1..F of positions 0 .. len + D - 2, one per trip from trip 0 ---------------------------------------
 template <int BC, bool MASK, int F, int RW, bool DOWN, int NST>
@@ -62,6 +85,7 @@ template <int BC, bool MASK, int D, int F, int RW, bool DOWN>
 __device__ __forceinline__ void deep2_front(const StepArgs &a, const int x0, const int ym, const int len, const int trips, f4a (*mine)[64],
                                             f4a (*other)[64], f4a (*ho)[64], f4a (*dma)[64])
 {
+    deep2_set_prio(a, 1);
     DeepCtx cx;
     cx.lane = threadIdx.x;
     const int xr = x0 + cx.lane * 4;
@@ -124,6 +148,7 @@ __device__ __forceinline__ void deep2_back(const StepArgs &a, const int x0, cons
                                            f4a (*other)[64], f4a (*ho)[64])
 {
     constexpr int DB = D - F + 1;                       // the back wave's own depth: "step 1" = the row handed over
+    deep2_set_prio(a, 2);
     DeepCtx cx;
     cx.lane = threadIdx.x;
     const int xr = x0 + cx.lane * 4;
@@ -168,9 +193,11 @@ __global__ __launch_bounds__(64 * DEEP2_WAVES, 2) void k_deep2(const StepArgs a,
     __shared__ f4a lds_front[2][LF][64];
     __shared__ f4a lds_back[2][LBK][64];
     __shared__ f4a lds_ho[2][DEEP_HO_SLOTS][64];
-    // 0 front-down, 1 front-up, 2 back-down, 3 back-up.  A workgroup's wave w lands on SIMD w, and the two workgroups of a CU are (in
-    // launch order) 256 apart: every other 256 workgroups take the roles two waves on, so that a SIMD holds a front wave (four stages
-    // and the gather) AND a back wave (three stages and the stores), not two of a kind.
+    // 0 front-down, 1 front-up, 2 back-down, 3 back-up.  The two workgroups of a CU are (in launch order) 256 apart: every other 256
+    // workgroups take the roles two waves on, meant to give every SIMD a front wave (four stages and the gather) AND a back wave (three
+    // stages and the stores).  It does on half of the shared SIMDs: per-wave records (tools/wave_timeline.py,
+    // profiles/deep2_priority_ab.txt) have a front and a back wave on two SIMDs of a CU, two front waves on one and two back waves on
+    // one -- as if the second workgroup's wave w landed on SIMD w + 1, not on SIMD w like the first's.
     const int wy = (__builtin_amdgcn_readfirstlane(threadIdx.y) + ((blockIdx.x >> 8) & 1) * 2) & 3;
     const int item = xcd_item(blockIdx.x, gridDim.x);
 #ifdef LB_DIAG

@@ -26,6 +26,7 @@ struct StepArgs {
     int edge_seg_rows;     // k_step4: > 0: the first and the last strip march segments of this many rows (see the kernel)
     int diag;              // ablation switches, read only by the LB_DIAG build (tools/ablate.py)
     int prio_turns;        // k_step4: the two waves of a SIMD alternate their issue priority (bit of the 100 MHz clock)
+    int deep2_prio;        // k_deep2: static issue priority by role, set once at entry: 0 none, 1 the front waves raised, 2 the back waves
     int nts;               // marching kernels: non-temporal stores (a run-time flag there: halves their instantiations and takes a
                            // minute off the library's build)
     int tile_launch_order; // k_tile4: 1 = tile = blockIdx (A/B switch; default: one band of tile rows per XCD)

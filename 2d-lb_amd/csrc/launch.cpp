@@ -23,6 +23,7 @@ StepArgs step_args(const lb_sim *s, int row_begin, int row_step, int row_count)
     a.tile_launch_order = (s->variant >= 0 && (s->variant & LB_VAR_TILE_LAUNCH_ORDER)) ? 1 : 0;    // (A/B switch: explicit variants only)
     a.diag = s->diag;
     a.prio_turns = 0;      // (set by launch_marching from the variant)
+    a.deep2_prio = 0;      // (set by launch_marching)
     a.nts = 0;
     a.omega = s->p.omega; a.rho_in = s->p.inlet_rho; a.rho_out = s->p.outlet_rho;
     a.lid_u = s->p.lid_u; a.rho0 = s->p.rho0;
@@ -71,6 +72,11 @@ static bool launch_march(const lb_sim *s, hipStream_t st, const StepArgs &a, con
     return true;
 }
 
+// k_deep2: which role of a workgroup raises its issue priority at entry (kernels_deep2.h: deep2_set_prio): 0 none, 1 the front
+// waves, 2 the back waves.  The back waves: the one mode in which a CU's two workgroups end together and the launch is shorter
+// (profiles/deep2_priority_ab.txt); the diagnostic build overrides it per run (LB_DIAG bits 25-26).
+constexpr int DEEP2_PRIO = 2;
+
 int launch_marching(lb_sim *s, const MarchRows &r)
 {
     if (r.row_end <= r.row_begin) return LB_OK;
@@ -82,6 +88,7 @@ int launch_marching(lb_sim *s, const MarchRows &r)
     a.edge_seg_rows = m.edge_seg_rows;
     // k_step4: the two waves of a SIMD take turns at the higher issue priority (see the kernel), in turns of 2^13 ticks of the 100 MHz clock; LB_VAR_NO_PRIO_TURNS = off
     a.prio_turns = (variant & LB_VAR_NO_PRIO_TURNS) ? 0 : 13;
+    a.deep2_prio = DEEP2_PRIO;
     a.nts = (variant & LB_VAR_NT_STORES) ? 1 : 0;     // (the marching kernels take it at run time)
     if (!launch_march(s, r.stream, a, m, r.row_end, macro, r.depth))
         return fail(LB_ERR_STATE, "no %d-step kernel for this boundary family (the caller's schedule must not ask for one)", r.depth);

@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Per-wave timeline of one k_step4 / k_deep launch (diagnostic build, LB_DIAG bit 12): when each wave started and ended, on which
-XCD / CU / SIMD.  Usage (GPU box): [LB_TIMELINE_BC=pipe] [LB_TIMELINE_DEPTH=6|7] python tools/wave_timeline.py [n]"""
+XCD / CU / SIMD.  Usage (GPU box): [LB_TIMELINE_BC=pipe] [LB_TIMELINE_DEPTH=6|7] python tools/wave_timeline.py [n]
+
+k_deep2<7> (four waves per item): LB_TIMELINE_DEEP2=1 LB_TIMELINE_DEPTH=7; the report adds, per CU with two workgroups, when each ended,
+and what shares a SIMD.  Its issue-priority mode (csrc/kernels_deep2.h: deep2_set_prio; 0 none, 1 front waves, 2 back waves) is chosen
+per run by LB_DIAG bits 25-26 of the diagnostic build: LB_DIAG = 4096 | ((mode + 1) << 25), i.e. 33558528 / 67112960 / 100667392 for
+modes 0 / 1 / 2; plain 4096 runs the mode the library launches with.  (profiles/deep2_priority_ab.txt)"""
 import os
 import sys
 
@@ -115,6 +120,28 @@ def deep2_report(u, strips, segs, n, ny):
     for c in sorted(set(counts.tolist())):
         ends = np.array([max(v) for v in per_cu.values() if len(v) == c])
         print("  CUs with %d waves: last wave ends median %.1f max %.1f us" % (c, np.median(ends), ends.max()))
+    # the two workgroups of a CU (a workgroup = the four waves of an item; its end = its last wave's): which ends first, and how far apart
+    wg = rec[:, 6] >> 2
+    per_cu_wg = {}
+    for k, g, e in zip(key.tolist(), wg.tolist(), end.tolist()):
+        d = per_cu_wg.setdefault(k, {})
+        d[g] = max(d.get(g, 0.0), e)
+    two = np.array([sorted(d.values()) for d in per_cu_wg.values() if len(d) == 2])
+    if len(two):
+        gap = two[:, 1] - two[:, 0]
+        print("CUs with two workgroups: %d; first to end: median %.1f us, second: median %.1f us; gap median %.1f p10 %.1f p90 %.1f us = "
+              "%.1f %% of the launch (median)" % (len(two), np.median(two[:, 0]), np.median(two[:, 1]), np.median(gap),
+                                                 np.percentile(gap, 10), np.percentile(gap, 90), 100 * np.median(gap) / end.max()))
+        # does the workgroup launched first (the lower item on the CU) end first?  (a stable sign is what a static bias would need)
+        first_low = np.array([min(d, key=d.get) == min(d) for d in per_cu_wg.values() if len(d) == 2])
+        print("  the workgroup with the lower item number ends first on %d of %d such CUs" % (int(first_low.sum()), len(first_low)))
+    # what shares a SIMD: a front wave and a back wave (the role rotation of k_deep2), or two of a kind
+    per_simd = {}
+    for k, sd, r in zip(key.tolist(), simd.tolist(), role.tolist()):
+        per_simd.setdefault((k, sd), []).append(r >> 1)
+    pairs = [sorted(v) for v in per_simd.values() if len(v) == 2]
+    print("SIMDs holding two waves: %d; a front and a back wave on %d, two front waves on %d, two back waves on %d" % (
+        len(pairs), pairs.count([0, 1]), pairs.count([0, 0]), pairs.count([1, 1])))
     hist, edges = np.histogram(end, bins=12)
     print("wave ends, histogram:", " ".join("%.0f-%.0f:%d" % (edges[i], edges[i + 1], hist[i]) for i in range(len(hist))))
     hist, edges = np.histogram(start, bins=8)
