@@ -9,6 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LB_LIB") or os.path.join(_HERE, "liblbhip.so")   # LB_LIB: diagnostic builds only
 
 LB_BC_PIPE, LB_BC_PERIODIC, LB_BC_CAVITY, LB_BC_VELOCITY_INLET, LB_BC_OPEN, LB_BC_BOX, LB_BC_DIRICHLET = 0, 1, 2, 3, 4, 5, 6
+LB_BC_ZERO_GRADIENT = 7
 LB_FLAG_HALO = 1
 LB_FLAG_PLANAR = 2
 LB_FLAG_EAGER_MACRO = 4
@@ -16,8 +17,10 @@ LB_MASK_HALO_ROWS = 13
 LB_PEER_HANDLE_BYTES = 384
 LB_DEVICE_CPU = -1
 LB_SEM_OPENCL, LB_SEM_CYTHON, LB_SEM_OPENCL_D2Q9I, LB_SEM_DIFFUSION, LB_SEM_MULTIFIELD, LB_SEM_POISSON = 0, 1, 2, 3, 4, 5
+LB_SEM_POROUS = 7        # (6 is not assigned: include/lb_hip.h)
 BC_NAMES = {"pipe": LB_BC_PIPE, "periodic": LB_BC_PERIODIC, "cavity": LB_BC_CAVITY,
-            "velocity_inlet": LB_BC_VELOCITY_INLET, "open": LB_BC_OPEN, "box": LB_BC_BOX, "dirichlet": LB_BC_DIRICHLET}
+            "velocity_inlet": LB_BC_VELOCITY_INLET, "open": LB_BC_OPEN, "box": LB_BC_BOX, "dirichlet": LB_BC_DIRICHLET,
+            "zero_gradient": LB_BC_ZERO_GRADIENT}
 
 ABI_VERSION = 11
 
@@ -37,6 +40,8 @@ EXPORTS = (
     "lb_run_coupled", "lb_collide_coupled",
     "lb_set_poisson", "lb_set_source", "lb_get_source", "lb_solve", "lb_solve_reset", "lb_get_solve_state", "lb_set_solve_state",
     "lb_gradient",
+    "lb_set_porous", "lb_set_body_force", "lb_set_force_field", "lb_get_force", "lb_set_force", "lb_set_bary_velocity",
+    "lb_get_bary_velocity", "lb_update_forces", "lb_update_bary_velocity",
 )
 
 
@@ -121,6 +126,14 @@ def lib():
         L.lb_get_solve_state.argtypes = [h, ip, ip]
         L.lb_set_solve_state.argtypes = [h, I, I]
         L.lb_gradient.argtypes = [h, ct.c_float, vp, vp]
+    if hasattr(L, "lb_set_porous"):                 # (likewise: forced flow in a porous medium; bound by presence, not by version)
+        L.lb_set_porous.argtypes = [h, ct.c_float, ct.c_float, ct.c_float, ct.c_float]
+        L.lb_set_body_force.argtypes = [h, ct.c_float, ct.c_float]
+        L.lb_set_force_field.argtypes = [h, vp, vp, I]
+        for name in ("lb_get_force", "lb_set_force", "lb_set_bary_velocity", "lb_get_bary_velocity"):
+            getattr(L, name).argtypes = [h, vp, vp]
+        L.lb_update_forces.argtypes = [h]
+        L.lb_update_bary_velocity.argtypes = [h]
     L.lb_comm_init.argtypes = [h, vp, I, I]
     L.lb_timer_stop.argtypes = [h, fp]
     L.lb_layout.argtypes = [h, ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64)]

@@ -81,6 +81,10 @@ class Simulation(object):
                'poisson': the LB Poisson solver (the reference's D2Q9_poisson.cl / poisson/solver.py): bc='dirichlet' (a value
                prescribed on the four walls, set_poisson), a source field (set_source), solve(max_iterations) with the
                reference's stopping rule decided on the device, gradient(); whole grid.  run(n) = n iterations, no check.
+               'porous': forced flow in a porous medium (the reference's porous_media/single_component.cl / .py with one
+               fluid): a Guo-forced BGK fluid with porosity, linear and quadratic drag (set_porous) and body forces
+               (set_body_force, set_force_field); bc='periodic' or 'zero_gradient'; whole grid, no obstacles.  float32 like
+               every lattice here (the reference's fork is float64).  get_fields adds 'u_bary', 'v_bary', 'Gx', 'Gy'.
         :param planar: device layout of the lattices: False = the nine planes of a row stored together (default),
                True = each plane contiguous (LB_FLAG_PLANAR); results are identical.  None: environment variable
                LB_LAYOUT=planar selects True (tuning aid).
@@ -111,7 +115,8 @@ class Simulation(object):
         p.flags = ((_native.LB_FLAG_HALO if halo else 0) | (_native.LB_FLAG_PLANAR if self.planar else 0) |
                    (_native.LB_FLAG_EAGER_MACRO if self.eager_macro else 0))
         sem = {"opencl": _native.LB_SEM_OPENCL, "cython": _native.LB_SEM_CYTHON, "d2q9i": _native.LB_SEM_OPENCL_D2Q9I,
-               "diffusion": _native.LB_SEM_DIFFUSION, "multifield": _native.LB_SEM_MULTIFIELD, "poisson": _native.LB_SEM_POISSON}
+               "diffusion": _native.LB_SEM_DIFFUSION, "multifield": _native.LB_SEM_MULTIFIELD, "poisson": _native.LB_SEM_POISSON,
+               "porous": _native.LB_SEM_POROUS}
         if semantics not in sem:
             raise ValueError("semantics must be one of %s" % sorted(sem))
         p.semantics = sem[semantics]
@@ -131,6 +136,9 @@ class Simulation(object):
         self._shape3 = (self.nx, self.local_ny, NUM_JUMPERS)
         self.G = 0.                      # scalar lattices: growth rate of the Fisher term (set_reaction)
         self.rho_on_boundary, self.react_factor, self.tolerance = 0., 1., 1e-6      # the Poisson solver's (set_poisson)
+        self.epsilon, self.nu_fluid, self.K, self.Fe = 1., 0., 1., 0.               # the porous medium's (set_porous)
+        self.body_force = (0., 0.)                                                  # ... and its constant force (set_body_force)
+        self._force_field = None                                                    # ... and its force field, as uploaded
         self._mask_host = None
         self._mask_halo_host = None      # (south_rows, north_rows) as last given to set_obstacle_mask_halo
         if obstacle_mask is not None:
@@ -226,7 +234,7 @@ class Simulation(object):
         unchanged; the pass advances at most (n - 7) // 4 steps, a runner-up's longer comparison included) and keeps the
         fastest for this grid; shorter runs use the size heuristic (or call autotune())."""
         n = int(num_iterations)
-        if wait and n > 0 and self.semantics not in ("diffusion", "multifield", "poisson"):      # (a scalar lattice's kernel is the planner's size rule: no tuning pass)
+        if wait and n > 0 and self.semantics not in ("diffusion", "multifield", "poisson", "porous"):      # (a scalar lattice's kernel is the planner's size rule: no tuning pass)
             # (the pass costs 361 steps, 889 on grids <= 768^2, some of them in configurations several times slower than
             #  the best: it only pays for itself in a run several times that long)
             used = self._lib.lb_autotune_quick(self._h, (n - 7) // 4)
@@ -292,6 +300,13 @@ class Simulation(object):
                 out[k] = np.zeros(self._shape2, np.float32, order="F")
             ptr = lambda k: out[k].ctypes.data if k in out else None
             check(self._lib.lb_get_macro(self._h, ptr("rho"), ptr("u"), ptr("v")))
+        for a, b, get in (("u_bary", "v_bary", "lb_get_bary_velocity"), ("Gx", "Gy", "lb_get_force")):
+            if a in which or b in which:            # (semantics='porous' only: the library refuses elsewhere)
+                for k in (a, b):
+                    if k in which:
+                        out[k] = np.zeros(self._shape2, np.float32, order="F")
+                ptr = lambda k: out[k].ctypes.data if k in out else None
+                check(getattr(self._lib, get)(self._h, ptr(a), ptr(b)))
         return out
 
     # -- state I/O (the reference has none: state only leaves through get_fields) --------------
@@ -328,6 +343,14 @@ class Simulation(object):
             d["source"] = self.get_source()
             d["poisson"] = np.array([self.rho_on_boundary, self.react_factor, self.tolerance], np.float32)
             d["solve_state"] = np.array(self.solve_state(), np.int32)
+        if self.semantics == "porous":
+            g = self.get_fields(("u_bary", "v_bary", "Gx", "Gy"))
+            d["porous"] = np.array([self.epsilon, self.nu_fluid, self.K, self.Fe], np.float32)
+            d["body_force"] = np.array(self.body_force, np.float32)
+            d["bary"] = np.stack([g["u_bary"], g["v_bary"]])
+            d["force"] = np.stack([g["Gx"], g["Gy"]])
+            if self._force_field is not None:
+                d["force_field"] = np.stack(self._force_field)
         if self._mask_halo_host is not None:         # a slab: the neighbours' obstacle rows it was given
             empty = np.zeros((0, 0), np.int32)
             d["mask_halo_south"] = empty if self._mask_halo_host[0] is None else self._mask_halo_host[0]
@@ -361,7 +384,7 @@ class Simulation(object):
 
     def restore_arrays(self, d):
         self._check_compatible(d)
-        if self.semantics not in ("diffusion", "multifield", "poisson"):   # (a scalar lattice has no obstacles)
+        if self.semantics not in ("diffusion", "multifield", "poisson", "porous"):   # (a scalar lattice has no obstacles, nor has the porous medium)
             self.set_obstacle_mask(d["mask"] if d["mask"].size else None)
         if "mask_halo_south" in d:
             so, no = d["mask_halo_south"], d["mask_halo_north"]
@@ -382,6 +405,54 @@ class Simulation(object):
             self.set_source(d["source"])
             self.set_corner_state(d["corner_state"])           # (after set_f, likewise)
             check(self._lib.lb_set_solve_state(self._h, int(d["solve_state"][0]), int(d["solve_state"][1])))
+
+        if self.semantics == "porous":
+            self.set_porous(*[float(x) for x in d["porous"]])
+            self.set_body_force(*[float(x) for x in d["body_force"]])
+            self.set_force_field(*(d["force_field"] if "force_field" in d else (None, None)))
+            self.set_bary_velocity(d["bary"][0], d["bary"][1])
+            gx, gy = (_f_order(a, self._shape2) for a in d["force"])
+            check(self._lib.lb_set_force(self._h, gx.ctypes.data, gy.ctypes.data))
+
+    # -- forced flow in a porous medium (semantics='porous') -------------------------
+    def set_porous(self, epsilon=1., nu_fluid=0., K=1., Fe=0.):
+        """Porosity, the fluid's viscosity in the linear drag -epsilon nu_fluid u / K, the permeability K and the factor of the
+        quadratic drag -epsilon Fe |u| u / sqrt(K) (lb_set_porous); float32, like omega."""
+        vals = [float(np.float32(x)) for x in (epsilon, nu_fluid, K, Fe)]
+        check(self._lib.lb_set_porous(self._h, *vals))
+        self.epsilon, self.nu_fluid, self.K, self.Fe = vals
+
+    def set_body_force(self, gx, gy):
+        """The constant body force per unit mass: the sum of the reference's add_constant_body_force calls."""
+        vals = (float(np.float32(gx)), float(np.float32(gy)))
+        check(self._lib.lb_set_body_force(self._h, *vals))
+        self.body_force = vals
+
+    def set_force_field(self, gx, gy):
+        """A position-dependent body force added to the constant one in every cell: two (nx, ny) arrays; None, None drops it."""
+        if gx is None and gy is None:
+            check(self._lib.lb_set_force_field(self._h, None, None, 0))
+            self._force_field = None
+            return
+        a, b = (_f_order(x, self._shape2) for x in (gx, gy))
+        check(self._lib.lb_set_force_field(self._h, a.ctypes.data, b.ctypes.data, 0))
+        self._force_field = (a.copy(order="F"), b.copy(order="F"))
+
+    def set_bary_velocity(self, u_bary, v_bary):
+        """The barycentric velocity update_feq and collide_particles read: two (nx, ny) arrays."""
+        a, b = (_f_order(x, self._shape2) for x in (u_bary, v_bary))
+        check(self._lib.lb_set_bary_velocity(self._h, a.ctypes.data, b.ctypes.data))
+
+    def update_forces(self):
+        """G := the body force, then the porosity and the two drags from rho, u, v (the reference's Gx, Gy = 0, the additional
+        forces and update_forces_pourous: one kernel)."""
+        check(self._lib.lb_update_forces(self._h))
+        self.sync()
+
+    def update_bary_velocity(self):
+        """u_b = (sum f c + rho G / 2) / rho from the populations, rho and G.  rho = 0 gives NaN, as in the reference."""
+        check(self._lib.lb_update_bary_velocity(self._h))
+        self.sync()
 
     # -- the LB Poisson solver (semantics='poisson') --------------------------------
     def set_poisson(self, rho_on_boundary=0., react_factor=1., tolerance=1e-6):

@@ -8,7 +8,7 @@
 //   lb_hip.cpp     create / destroy / setters, state transfer, the un-fused phases, lb_run, lb_run_batch, lb_check, timers
 // Small kernels are emitted by the one unit that includes their header: kernels_phases.h + kernels_check.h by lb_hip.cpp,
 // kernels_halo.h by slab.cpp, kernels_scalar.h by scalar.cpp (its health check's first pass only: check_reduce.h is shared, the folding
-// pass is lb_hip.cpp's), kernels_multifield.h by multifield.cpp, kernels_poisson.h by poisson.cpp.
+// pass is lb_hip.cpp's), kernels_multifield.h by multifield.cpp, kernels_poisson.h by poisson.cpp, kernels_porous.h by porous.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -26,6 +26,7 @@
 #include "scalar_launch.h"      // scalar lattices (LB_SEM_DIFFUSION): AdExtra, CheckPartial, their launchers
 #include "multifield_launch.h"  // coupled scalar lattices (LB_SEM_MULTIFIELD): MfArgs, their launchers
 #include "poisson_launch.h"     // the LB Poisson solver (LB_SEM_POISSON): PsExtra, PsState, its launchers
+#include "porous_launch.h"      // forced flow in a porous medium (LB_SEM_POROUS): PmExtra, its launchers
 
 namespace {
 
@@ -53,6 +54,12 @@ struct lb_sim : PlanInputs {
     float ps_rho_b = 0.f, ps_react = 1.f, ps_tol = 1.0e-6f;     // lb_set_poisson
     int ps_iter = 0;                    // iterations since the last lb_solve_reset (solver.py's num_iterations)
     int ps_batch = 0;                   // lb_solve's launches between two reads of the stop word; 0 = PS_BATCH (LB_DIAG on such a handle: diagnosis)
+    // forced flow in a porous medium (LB_SEM_POROUS; porous_launch.h)
+    float *pm_G[2] = {nullptr, nullptr};    // [H][pitch] each: the total force of the last step
+    float *pm_ub[2] = {nullptr, nullptr};   // [H][pitch] each: the barycentric velocity
+    float *pm_field[2] = {nullptr, nullptr};    // [H][pitch] each, padding zero: the force field (lb_set_force_field), or none
+    float pm_eps = 1.f, pm_nu = 0.f, pm_K = 1.f, pm_Fe = 0.f;   // lb_set_porous
+    float pm_gx = 0.f, pm_gy = 0.f;         // lb_set_body_force
     uint8_t *mask_raw = nullptr, *mask = nullptr;   // [H+2*MASK_GHOST][pitch] + guards; mask -> row 0
     bool feq_valid = false;     // feq buffer consistent with rho,u,v
     bool macro_valid = true;    // rho,u,v hold the last step's fields (false: to be rebuilt from the populations, ensure_macro)
@@ -122,9 +129,15 @@ int fail(int code, const char *fmt, ...);       // records the message lb_last_e
     } while (0)
 
 // Scalar lattices (LB_SEM_DIFFUSION, and the fields of a coupled set: LB_SEM_MULTIFIELD) are whole-grid handles without obstacles: what only slabs, masks or the flow kernels' tuning mean refuses.
+// So is the porous-medium fluid (LB_SEM_POROUS), which is refused here under its own name.
 #define SCALAR_UNSUPPORTED(s, name)                                                                         \
     do {                                                                                                    \
         if ((s) && (s)->scalar()) return fail(LB_ERR_STATE, "%s is not available on a scalar lattice (LB_SEM_DIFFUSION)", name); \
+        NOT_POROUS(s, name);                                                                                \
+    } while (0)
+#define NOT_POROUS(s, name)                                                                                 \
+    do {                                                                                                    \
+        if ((s) && (s)->porous()) return fail(LB_ERR_STATE, "%s is not available on a porous-medium fluid (LB_SEM_POROUS)", name); \
     } while (0)
 
 // ---- transport.cpp: RCCL, loaded lazily so that single-GPU use never touches librccl ---------------------------------------------
@@ -177,6 +190,27 @@ inline PsExtra ps_extra(const lb_sim *s)
     return PsExtra{s->ps_source, s->ps_part, s->ps_state, (-1.f + w0) * s->ps_rho_b, s->ps_react, 0};
 }
 inline AdExtra ad_extra(const lb_sim *s) { return AdExtra{s->ad_edge, s->ad_G}; }
+// n time steps of forced flow in a porous medium; the last launch stores rho, u, v, G and u_b
+int run_porous(lb_sim *s, int n_steps);
+// (every derived scalar one float32 operation, here and nowhere else: porous_launch.h)
+inline PmExtra pm_extra(const lb_sim *s)
+{
+    PmExtra e;
+    e.Gx = s->pm_G[0]; e.Gy = s->pm_G[1];
+    e.ub = s->pm_ub[0]; e.vb = s->pm_ub[1];
+    e.fgx = s->pm_field[0]; e.fgy = s->pm_field[1];
+    e.gx = s->pm_gx; e.gy = s->pm_gy;
+    e.eps = s->pm_eps;
+    e.en = s->pm_eps * s->pm_nu;
+    e.ef = s->pm_eps * s->pm_Fe;
+    e.K = s->pm_K;
+    e.sqrtK = sqrtf(s->pm_K);
+    const float ie = 1.f / s->pm_eps;
+    e.a15 = 1.5f * ie; e.a45 = 4.5f * ie;
+    e.b3 = 3.f * ie; e.b9 = 9.f * ie;
+    e.hw = 1.f - 0.5f * s->p.omega;
+    return e;
+}
 
 // ---- slab.cpp --------------------------------------------------------------------------------------------------------------------
 int ensure_halo_buf(lb_sim *s);         // the send / receive buffers of the halo exchange (also lb_check's scratch across ranks)

@@ -258,3 +258,17 @@ int run_poisson(lb_sim *s, int n_steps)
     if (n_steps) { s->feq_valid = false; s->macro_valid = true; }
     return LB_OK;
 }
+
+// n time steps of forced flow in a porous medium (kernels_porous.h): k_pm_step, one launch each; the last stores rho, u, v, the total
+// force and the barycentric velocity.
+int run_porous(lb_sim *s, int n_steps)
+{
+    const PmExtra e = pm_extra(s);
+    for (int it = 0; it < n_steps; ++it) {
+        lbk_pm_step(s->p.bc_mode, it == n_steps - 1, s->stream, step_args(s, 0, 1, s->H), e);
+        HIP_TRY(hipGetLastError());
+        s->cur ^= 1;
+    }
+    if (n_steps) { s->feq_valid = false; s->macro_valid = true; }
+    return LB_OK;
+}

@@ -301,7 +301,9 @@ int lb_create(const lb_params *p, lb_sim **out)
     if (p->nx < 2 || p->ny < 2) return fail(LB_ERR_ARG, "grid must be at least 2x2 (got %dx%d)", p->nx, p->ny);
     if (p->local_ny < 1 || p->y0 < 0 || p->y0 + p->local_ny > p->ny)
         return fail(LB_ERR_ARG, "slab [%d,%d) outside 0..%d", p->y0, p->y0 + p->local_ny, p->ny);
-    if (p->bc_mode < LB_BC_PIPE || p->bc_mode > LB_BC_DIRICHLET) return fail(LB_ERR_ARG, "unknown bc_mode %d", p->bc_mode);
+    if (p->bc_mode < LB_BC_PIPE || p->bc_mode > LB_BC_ZERO_GRADIENT) return fail(LB_ERR_ARG, "unknown bc_mode %d", p->bc_mode);
+    if (p->bc_mode == LB_BC_ZERO_GRADIENT && p->semantics != LB_SEM_POROUS)
+        return fail(LB_ERR_ARG, "LB_BC_ZERO_GRADIENT exists for forced flow in a porous medium (LB_SEM_POROUS) only: unknown bc_mode %d for semantics %d", p->bc_mode, p->semantics);
     if (p->bc_mode == LB_BC_DIRICHLET && p->semantics != LB_SEM_POISSON)
         return fail(LB_ERR_ARG, "LB_BC_DIRICHLET exists for the LB Poisson solver (LB_SEM_POISSON) only: unknown bc_mode %d for semantics %d", p->bc_mode, p->semantics);
     if (p->semantics == LB_SEM_POISSON) {
@@ -311,6 +313,16 @@ int lb_create(const lb_params *p, lb_sim **out)
         if (p->local_ny != p->ny || p->y0 != 0) return fail(LB_ERR_ARG, "the LB Poisson solver (LB_SEM_POISSON) owns its whole grid: no slabs");
         if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "the LB Poisson solver (LB_SEM_POISSON) has no halo interface (LB_FLAG_HALO)");
         if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "the LB Poisson solver (LB_SEM_POISSON) runs on a GPU only (no CPU backend)");
+    }
+    if (p->semantics == LB_SEM_POROUS) {
+        // the porous-medium fluid: a whole-grid GPU handle without obstacles, refused like the scalar lattices (before any device is touched)
+        if (p->bc_mode != LB_BC_PERIODIC && p->bc_mode != LB_BC_ZERO_GRADIENT)
+            return fail(LB_ERR_ARG, "forced flow in a porous medium (LB_SEM_POROUS) takes the families LB_BC_PERIODIC and LB_BC_ZERO_GRADIENT only");
+        if (p->bc_mode == LB_BC_ZERO_GRADIENT && (p->nx < 3 || p->ny < 3))
+            return fail(LB_ERR_ARG, "LB_BC_ZERO_GRADIENT needs an interior cell: grid must be at least 3x3 (got %dx%d)", p->nx, p->ny);
+        if (p->local_ny != p->ny || p->y0 != 0) return fail(LB_ERR_ARG, "forced flow in a porous medium (LB_SEM_POROUS) owns its whole grid: no slabs");
+        if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "forced flow in a porous medium (LB_SEM_POROUS) has no halo interface (LB_FLAG_HALO)");
+        if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "forced flow in a porous medium (LB_SEM_POROUS) runs on a GPU only (no CPU backend)");
     }
     if (p->bc_mode == LB_BC_OPEN && p->semantics != LB_SEM_DIFFUSION)
         return fail(LB_ERR_ARG, "LB_BC_OPEN exists for scalar lattices (LB_SEM_DIFFUSION) only");
@@ -342,7 +354,7 @@ int lb_create(const lb_params *p, lb_sim **out)
         if (r != 0) return fail(LB_ERR_ARG, "reserved fields must be zero");
     if (p->flags & ~(LB_FLAG_HALO | LB_FLAG_PLANAR | LB_FLAG_EAGER_MACRO)) return fail(LB_ERR_ARG, "unknown flags 0x%x", p->flags);
     if (p->semantics != LB_SEM_OPENCL && p->semantics != LB_SEM_CYTHON && p->semantics != LB_SEM_OPENCL_D2Q9I && p->semantics != LB_SEM_DIFFUSION &&
-        p->semantics != LB_SEM_MULTIFIELD && p->semantics != LB_SEM_POISSON)
+        p->semantics != LB_SEM_MULTIFIELD && p->semantics != LB_SEM_POISSON && p->semantics != LB_SEM_POROUS)
         return fail(LB_ERR_ARG, "unknown semantics %d", p->semantics);
     if (p->semantics == LB_SEM_OPENCL_D2Q9I &&
         (p->bc_mode != LB_BC_PIPE || p->local_ny != p->ny || (p->flags & LB_FLAG_HALO)))
@@ -455,6 +467,14 @@ int lb_create(const lb_params *p, lb_sim **out)
         CREATE_TRY(hipMemcpy(s->ps_state, &fresh, sizeof(fresh), hipMemcpyHostToDevice));
         s->bytes += fld_bytes + part_bytes + sizeof(PsState);
     }
+    if (s->porous()) {
+        s->diag = 0;                                // (the diagnostic word of the flow kernels means nothing here)
+        for (float **q : {&s->pm_G[0], &s->pm_G[1], &s->pm_ub[0], &s->pm_ub[1]}) {
+            CREATE_TRY(hipMalloc(q, fld_bytes));
+            CREATE_TRY(hipMemsetAsync(*q, 0, fld_bytes, s->stream));
+        }
+        s->bytes += 4 * fld_bytes;
+    }
     CREATE_TRY(hipMalloc(&s->vi_corner, 8 * sizeof(float)));
     CREATE_TRY(hipMemsetAsync(s->vi_corner, 0, 8 * sizeof(float), s->stream));
     CREATE_TRY(hipMalloc(&s->mask_raw, (size_t)s->pitch * (s->H + 2 * MASK_GHOST) + 2 * GUARD));
@@ -505,7 +525,8 @@ int lb_destroy(lb_sim *s)
         }
     if (s->peer_flags) (void)hipFree(s->peer_flags);
     if (s->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(s->comm);
-    for (float *p : {s->lat[0], s->lat[1], s->feq, s->rho, s->u, s->v, s->halo_buf, s->vi_corner, s->stage, s->ad_edge, s->ps_source, s->ps_part})
+    for (float *p : {s->lat[0], s->lat[1], s->feq, s->rho, s->u, s->v, s->halo_buf, s->vi_corner, s->stage, s->ad_edge, s->ps_source, s->ps_part,
+                     s->pm_G[0], s->pm_G[1], s->pm_ub[0], s->pm_ub[1], s->pm_field[0], s->pm_field[1]})
         if (p) (void)hipFree(p);
     if (s->mask_raw) (void)hipFree(s->mask_raw);
     if (s->check_part) (void)hipFree(s->check_part);
@@ -559,6 +580,8 @@ int lb_set_variant(lb_sim *s, int variant)
         return fail(LB_ERR_ARG, "a coupled scalar lattice (LB_SEM_MULTIFIELD) takes the variants -1 and 0 only: k_mf_step, no tiles");
     if (s->poisson() && variant != -1 && variant != 0)
         return fail(LB_ERR_STATE, "the LB Poisson solver (LB_SEM_POISSON) takes the variants -1 and 0 only: k_ps_step, no tiles");
+    if (s->porous() && variant != -1 && variant != 0)
+        return fail(LB_ERR_STATE, "lb_set_variant: a porous-medium fluid (LB_SEM_POROUS) takes the variants -1 and 0 only: k_pm_step, no tiles");
     s->variant = variant;
     return LB_OK;
 }
@@ -845,6 +868,7 @@ int lb_set_mask_halo(lb_sim *s, const int32_t *south_rows, const int32_t *north_
 #define NEED_SCALAR(s, name)                                                                                 \
     do {                                                                                                     \
         if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
+        NOT_POROUS(s, name);                                                                                 \
         if (!(s)->scalar()) return fail(LB_ERR_STATE, "%s is for scalar lattices (LB_SEM_DIFFUSION)", name); \
     } while (0)
 
@@ -950,6 +974,7 @@ int lb_set_velocity_from(lb_sim *s, lb_sim *flow)
 #define NEED_POISSON(s, name)                                                                                \
     do {                                                                                                     \
         if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
+        NOT_POROUS(s, name);                                                                                 \
         if (!(s)->poisson()) return fail(LB_ERR_STATE, "%s is for the LB Poisson solver (LB_SEM_POISSON)", name); \
     } while (0)
 
@@ -1081,6 +1106,133 @@ int lb_gradient(lb_sim *s, float inv_two_dx, float *ddx, float *ddy)
     return LB_OK;
 }
 
+// ---- forced flow in a porous medium ------------------------------------------------------------
+#define NEED_POROUS(s, name)                                                                                 \
+    do {                                                                                                     \
+        if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
+        if (!(s)->porous()) return fail(LB_ERR_STATE, "%s is for forced flow in a porous medium (LB_SEM_POROUS)", name); \
+    } while (0)
+
+static bool pm_finite(float x) { return fabsf(x) <= 3.0e38f; }      // (false for NaN)
+
+int lb_set_porous(lb_sim *s, float epsilon, float nu_fluid, float K, float Fe)
+{
+    NEED_POROUS(s, "lb_set_porous");
+    if (!pm_finite(epsilon) || !pm_finite(nu_fluid) || !pm_finite(K) || !pm_finite(Fe)) return fail(LB_ERR_ARG, "epsilon, nu_fluid, K and Fe must be finite");
+    if (!(epsilon > 0.f) || !(K > 0.f)) return fail(LB_ERR_ARG, "need epsilon > 0 and K > 0 (got %g, %g)", epsilon, K);
+    s->pm_eps = epsilon; s->pm_nu = nu_fluid; s->pm_K = K; s->pm_Fe = Fe;
+    s->feq_valid = false;
+    return LB_OK;
+}
+
+int lb_set_body_force(lb_sim *s, float gx, float gy)
+{
+    NEED_POROUS(s, "lb_set_body_force");
+    if (!pm_finite(gx) || !pm_finite(gy)) return fail(LB_ERR_ARG, "the body force must be finite");
+    s->pm_gx = gx; s->pm_gy = gy;
+    return LB_OK;
+}
+
+int lb_set_force_field(lb_sim *s, const float *gx, const float *gy, int on_device)
+{
+    NEED_POROUS(s, "lb_set_force_field");
+    if ((gx == nullptr) != (gy == nullptr)) return fail(LB_ERR_ARG, "both planes of the force field, or neither");
+    DeviceGuard guard(s->p.device);
+    HIP_TRY(hipStreamSynchronize(s->stream));       // (kernels of an un-waited run may still be reading it)
+    if (!gx) {
+        for (float *&q : s->pm_field) {
+            if (q) {
+                HIP_TRY(hipFree(q));
+                s->bytes -= (int64_t)sizeof(float) * s->pitch * s->H;
+            }
+            q = nullptr;
+        }
+        s->has_field = false;
+        return LB_OK;
+    }
+    const size_t fld_bytes = sizeof(float) * s->pitch * s->H;
+    const float *from[2] = {gx, gy};
+    for (int i = 0; i < 2; ++i) {
+        if (!s->pm_field[i]) {
+            HIP_TRY(hipMalloc(&s->pm_field[i], fld_bytes));
+            s->bytes += (int64_t)fld_bytes;
+        }
+        HIP_TRY(hipMemsetAsync(s->pm_field[i], 0, fld_bytes, s->stream));
+        HIP_TRY(hipMemcpy2DAsync(s->pm_field[i], s->pitch * sizeof(float), from[i], s->p.nx * sizeof(float), s->p.nx * sizeof(float), s->H,
+                                 on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->has_field = true;
+    return LB_OK;
+}
+
+static int pm_get_pair(lb_sim *s, float *const (&pair)[2], float *a, float *b)
+{
+    DeviceGuard guard(s->p.device);
+    int rc;
+    if (a && (rc = copy_plane_d2h(s, a, pair[0]))) return rc;
+    if (b && (rc = copy_plane_d2h(s, b, pair[1]))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return LB_OK;
+}
+
+int lb_get_force(lb_sim *s, float *Gx, float *Gy)
+{
+    NEED_POROUS(s, "lb_get_force");
+    return pm_get_pair(s, s->pm_G, Gx, Gy);
+}
+
+int lb_get_bary_velocity(lb_sim *s, float *u_bary, float *v_bary)
+{
+    NEED_POROUS(s, "lb_get_bary_velocity");
+    return pm_get_pair(s, s->pm_ub, u_bary, v_bary);
+}
+
+int lb_set_bary_velocity(lb_sim *s, const float *u_bary, const float *v_bary)
+{
+    NEED_POROUS(s, "lb_set_bary_velocity");
+    if (!u_bary || !v_bary) return fail(LB_ERR_ARG, "null argument");
+    DeviceGuard guard(s->p.device);
+    int rc;
+    if ((rc = copy_plane_h2d(s, s->pm_ub[0], u_bary))) return rc;
+    if ((rc = copy_plane_h2d(s, s->pm_ub[1], v_bary))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->feq_valid = false;
+    return LB_OK;
+}
+
+// (checkpoints: the total force as the last step left it)
+int lb_set_force(lb_sim *s, const float *Gx, const float *Gy)
+{
+    NEED_POROUS(s, "lb_set_force");
+    if (!Gx || !Gy) return fail(LB_ERR_ARG, "null argument");
+    DeviceGuard guard(s->p.device);
+    int rc;
+    if ((rc = copy_plane_h2d(s, s->pm_G[0], Gx))) return rc;
+    if ((rc = copy_plane_h2d(s, s->pm_G[1], Gy))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return LB_OK;
+}
+
+int lb_update_forces(lb_sim *s)
+{
+    NEED_POROUS(s, "lb_update_forces");
+    DeviceGuard guard(s->p.device);
+    lbk_pm_forces(s->stream, step_args(s, 0, 1, s->H), pm_extra(s));
+    HIP_TRY(hipGetLastError());
+    return LB_OK;
+}
+
+int lb_update_bary_velocity(lb_sim *s)
+{
+    NEED_POROUS(s, "lb_update_bary_velocity");
+    DeviceGuard guard(s->p.device);
+    lbk_pm_bary(s->stream, step_args(s, 0, 1, s->H), pm_extra(s), s->origin(s->cur));
+    HIP_TRY(hipGetLastError());
+    s->feq_valid = false;
+    return LB_OK;
+}
+
 // ---- un-fused phases ---------------------------------------------------------------------
 
 int lb_move(lb_sim *s)
@@ -1116,7 +1268,13 @@ int lb_move_bcs(lb_sim *s)
     int rc = need_single_slab(s, "lb_move_bcs");
     if (rc) return rc;
     if (s->scalar() && s->p.bc_mode != LB_BC_BOX && !s->poisson()) return LB_OK;     // (diffusion.py:326-331: `pass`; the periodic families have none)
+    if (s->porous() && s->p.bc_mode == LB_BC_PERIODIC) return LB_OK;                 // (single_component.py:155-156: `pass`)
     DeviceGuard guard(s->p.device);
+    if (s->porous()) {                              // single_component.cl's move_open_bcs: boundary cells copy their interior neighbour
+        lbk_pm_move_bcs(s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur));
+        HIP_TRY(hipGetLastError());
+        return LB_OK;
+    }
     if (s->poisson()) {                             // D2Q9_poisson.cl's move_bcs: the prescribed value on four walls
         lbk_ps_move_bcs(s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur), ps_extra(s).wall);
         HIP_TRY(hipGetLastError());
@@ -1147,7 +1305,9 @@ int lb_update_hydro(lb_sim *s)
     int rc = need_single_slab(s, "lb_update_hydro");
     if (rc) return rc;
     DeviceGuard guard(s->p.device);
-    if (s->poisson())
+    if (s->porous())
+        lbk_pm_hydro(s->stream, step_args(s, 0, 1, s->H));       // rho, and u, v where rho > 1e-6
+    else if (s->poisson())
         lbk_ps_hydro(s->stream, step_args(s, 0, 1, s->H));       // rho = (9/5)(f1 + ... + f8)
     else if (s->scalar())
         lbk_ad_hydro(s->stream, step_args(s, 0, 1, s->H));       // rho only: u, v are imposed
@@ -1177,7 +1337,9 @@ int lb_update_feq(lb_sim *s)
     if ((rc = ensure_macro(s))) return rc;
     PhaseArgs a = phase_args(s);
     a.ny = s->H;   // rho,u,v are local: valid for slabs too
-    if (s->poisson())
+    if (s->porous())
+        lbk_pm_feq(s->stream, step_args(s, 0, 1, s->H), pm_extra(s), s->feq_origin());      // from rho and u_b
+    else if (s->poisson())
         lbk_ps_feq(s->stream, step_args(s, 0, 1, s->H), s->feq_origin());
     else if (s->scalar())
         lbk_ad_feq(s->stream, step_args(s, 0, 1, s->H), s->feq_origin());
@@ -1200,7 +1362,9 @@ int lb_collide_particles(lb_sim *s)
     if (s->multifield()) return lb_collide_coupled(&s, 1);
     DeviceGuard guard(s->p.device);
     if ((rc = ensure_macro(s))) return rc;
-    if (s->poisson())
+    if (s->porous())
+        lbk_pm_collide(s->stream, step_args(s, 0, 1, s->H), pm_extra(s), s->origin(s->cur), s->feq_origin());
+    else if (s->poisson())
         lbk_ps_collide(s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur), s->feq_origin(), s->ps_source, s->ps_react);
     else if (s->scalar())
         lbk_ad_collide(s->ad_G != 0.f, s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur), s->feq_origin(), s->ad_G);
@@ -1261,6 +1425,7 @@ int lb_run(lb_sim *s, int n_steps)
     DeviceGuard guard(s->p.device);
     if (s->multifield()) return lb_run_coupled(&s, 1, n_steps);
     if (s->poisson()) return run_poisson(s, n_steps);
+    if (s->porous()) return run_porous(s, n_steps);
     if (s->scalar()) return run_scalar(s, n_steps);
     if (!s->tune_cache_checked) (void)tune_cache_apply(s);
     if (s->p.semantics == LB_SEM_CYTHON) return run_cython(s, n_steps);
@@ -1356,6 +1521,7 @@ static int coupled_release(lb_sim **f, int count)
 
 int lb_run_coupled(lb_sim **fields, int count, int n_steps)
 {
+    for (int i = 0; fields && i < count; ++i) NOT_POROUS(fields[i], "lb_run_coupled");
     int rc = coupled_members(fields, count, "lb_run_coupled");
     if (rc) return rc;
     if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
@@ -1429,6 +1595,7 @@ int lb_check(lb_sim *s, int across_ranks, int64_t *n_nonfinite, float *max_mach,
     if (!s) return fail(LB_ERR_ARG, "null handle");
     if (s->stepping) return fail(LB_ERR_STATE, "lb_check inside a split step");
     if (s->poisson()) return fail(LB_ERR_STATE, "lb_check is not available on the LB Poisson solver (LB_SEM_POISSON): lb_solve reports its residual");
+    NOT_POROUS(s, "lb_check");
     if (across_ranks && !s->comm) return fail(LB_ERR_STATE, "lb_check across ranks needs lb_comm_init");
     DeviceGuard guard(s->p.device);
     // the pass that rebuilds rho, u, v reduces the same three numbers: one pass serves both when the fields are due (never on a

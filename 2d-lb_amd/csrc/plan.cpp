@@ -481,7 +481,7 @@ bool tune_entry_runs_here(const PlanInputs *s, int steps, int wpc)
 static const double SCALAR_TILE_MIN_CELLS = 256.0 * 256.0, SCALAR_TILE_MAX_CELLS = 8192.0 * 8192.0;
 bool scalar_use_tiles(const PlanInputs *s)
 {
-    if (s->multifield() || s->poisson()) return false;      // (no tiles for coupled sets and the Poisson solver: k_mf_step / k_ps_step, one step per launch)
+    if (s->multifield() || s->poisson() || s->porous()) return false;      // (no tiles for coupled sets, the Poisson solver and the porous-medium fluid: k_mf_step / k_ps_step / k_pm_step, one step per launch)
     if (s->variant >= 0) return (s->variant & LB_VAR_TILES) != 0;
     const double cells = (double)s->p.nx * s->H;
     return cells >= SCALAR_TILE_MIN_CELLS && cells <= SCALAR_TILE_MAX_CELLS;
@@ -503,7 +503,7 @@ int scalar_next_advance(const PlanInputs *s, int left)
 
 int plan_launches(const PlanInputs *s, int n_steps, int *depths, int max_launches)
 {
-    if (s->scalar()) {
+    if (s->scalar() || s->porous()) {
         int n = 0;
         for (int left = n_steps; left > 0; ++n) {
             const int adv = scalar_next_advance(s, left);
@@ -524,7 +524,7 @@ int plan_launches(const PlanInputs *s, int n_steps, int *depths, int max_launche
 
 int steps_per_launch(const PlanInputs *s)
 {
-    if (s->scalar()) return scalar_use_tiles(s) ? TILE_T : 1;
+    if (s->scalar() || s->porous()) return scalar_use_tiles(s) ? TILE_T : 1;
     if (s->p.semantics == LB_SEM_CYTHON) return cython_tiles(s) ? TILE_T : 1;
     const int h = s->agreed_h();
     if (s->multi_slab() && cycle_depth(s, h)) return cycle_depth(s, h);
@@ -538,6 +538,11 @@ int steps_per_launch(const PlanInputs *s)
 void hot_kernel(const PlanInputs *s, char *buf, int buflen)
 {
     static const char *const bc_names[] = {"PIPE", "PERIODIC", "CAVITY", "VELOCITY_INLET", "PIPE, D2Q9i"};
+    if (s->porous()) {
+        snprintf(buf, (size_t)buflen, "k_pm_step (forced flow in a porous medium: one fused pull-stream + moments + drag and body force + Guo-forced collide pass)<%s%s>",
+                 s->p.bc_mode == LB_BC_PERIODIC ? "PERIODIC" : "ZERO_GRADIENT", s->has_field ? ", FIELD" : "");
+        return;
+    }
     if (s->poisson()) {
         snprintf(buf, (size_t)buflen, "k_ps_step (LB Poisson solver: one fused pull-stream + prescribed-value walls + relaxation pass that also leaves the convergence sums)<DIRICHLET>");
         return;

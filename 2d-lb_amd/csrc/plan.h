@@ -17,6 +17,7 @@ struct PlanInputs {
     int H = 0;                  // rows owned
     long long pitch = 0, rowp = 0, plane = 0, lat_floats = 0;   // padded row width; lattice row / plane strides; floats per lattice
     bool has_mask = false;
+    bool has_field = false;     // LB_SEM_POROUS: a force field is set (lb_set_force_field)
     int cu_count = 256;
     int min_h = 0;              // smallest slab height over the ranks (every rank must pick the same schedule)
     int variant = -1;           // < 0: automatic (effective_variant), else an OR of LB_VAR_* (lb_variant_bits)
@@ -29,6 +30,7 @@ struct PlanInputs {
 
     bool multifield() const { return p.semantics == LB_SEM_MULTIFIELD; } // one field of a coupled set of scalar lattices (kernels_multifield.h)
     bool poisson() const { return p.semantics == LB_SEM_POISSON; }       // the LB Poisson solver (kernels_poisson.h)
+    bool porous() const { return p.semantics == LB_SEM_POROUS; }         // forced flow in a porous medium (kernels_porous.h): a fluid, not scalar()
     bool scalar() const { return p.semantics == LB_SEM_DIFFUSION || multifield() || poisson(); }  // a scalar lattice (kernels_scalar.h), on its own or coupled, or the Poisson solver's
     bool multi_slab() const { return H != p.ny || (p.flags & LB_FLAG_HALO); }
     int agreed_h() const { return min_h > 0 ? min_h : H; }      // the height all ranks decide on

@@ -62,11 +62,15 @@ typedef enum {
                              D2Q9_multifield_fisher.cl, whose move_bcs bounces every link that would enter from outside back on
                              the node itself (f1 := f3 at x = 0, ...), on all four walls.  Two links per corner are neither
                              streamed nor bounced: the handle's corner state (lb_get_corner_state). */
-    LB_BC_DIRICHLET = 6   /* the LB Poisson solver (LB_SEM_POISSON) only: the box of the reference's D2Q9_poisson.cl, whose move_bcs
+    LB_BC_DIRICHLET = 6,  /* the LB Poisson solver (LB_SEM_POISSON) only: the box of the reference's D2Q9_poisson.cl, whose move_bcs
                              prescribes a value on all four walls: on each wall and in each corner the three links pointing into the
                              box become w_k R, R = -(sum of the cell's five other non-rest links + (w0 - 1) rho_on_boundary) /
                              (sum of the three weights).  Two links per corner are neither streamed nor written, and the corner's
                              rule reads them: the handle's corner state, LB_BC_BOX's eight links in the same order. */
+    LB_BC_ZERO_GRADIENT = 7 /* forced flow in a porous medium (LB_SEM_POROUS) only: the open box of the reference's
+                             porous_media/single_component.cl, whose move_open_bcs gives every boundary cell all nine post-stream
+                             populations of the interior cell (clamp(x, 1, nx-2), clamp(y, 1, ny-2)).  Every link the push `move`
+                             leaves stale at the boundary is overwritten: no edge or corner state.  nx, ny >= 3. */
 } lb_bc_mode;
 
 /* Which of the reference's two (numerically different) paths the handle reproduces.
@@ -106,7 +110,7 @@ typedef enum {
                                  LB_BC_PERIODIC (build-defined) and LB_BC_BOX (the reference's closed box).  One fused launch
                                  per time step for the whole set (k_mf_step: 72 B of populations per field + 8 B of u, v per
                                  cell and step); lb_set_variant takes -1 and 0 only (no LDS tiles for coupled sets). */
-    LB_SEM_POISSON = 5        /* the LB POISSON SOLVER: LB_D2Q9/D2Q9_poisson.cl driven as poisson/solver.py does -- a D2Q9 relaxation
+    LB_SEM_POISSON = 5,       /* the LB POISSON SOLVER: LB_D2Q9/D2Q9_poisson.cl driven as poisson/solver.py does -- a D2Q9 relaxation
                                  whose fixed point solves a Poisson problem in a box: rho = (9/5)(f1 + ... + f8), feq_0 = (w0 - 1) rho,
                                  feq_k = w_k rho, f_k (1 - omega) + omega feq_k + w_k source react_factor, a prescribed value on the four
                                  walls (LB_BC_DIRICHLET, the only family), and a run loop that stops when rho has stopped changing.
@@ -116,6 +120,17 @@ typedef enum {
                                  sets a device-side stop word (k_ps_check), no host wait but one 4-byte read-back per batch of
                                  iterations: lb_solve, below.  u, v of such a handle are written by lb_gradient only.
                                  lb_set_variant takes -1 and 0 only. */
+    LB_SEM_POROUS = 7         /* (6 is not assigned: the suite holds lb_create to refusing semantics 6 in a periodic box as unknown,
+                                 tests/test_poisson_cpu.py.)  FORCED FLOW IN A POROUS MEDIUM: LB_D2Q9/porous_media/single_component.cl driven as
+                                 single_component.py's Simulation_Runner.run does with one fluid -- a D2Q9 BGK fluid with Guo forcing,
+                                 a porosity epsilon in the equilibrium and in the forcing term, a linear drag (nu_fluid / K), a
+                                 quadratic one (Fe / sqrt(K)) and constant or position-dependent body forces; families
+                                 LB_BC_PERIODIC and LB_BC_ZERO_GRADIENT.  Whole-grid GPU handles without obstacles; omega, nx, ny
+                                 are the only lb_params fields read (lb_set_porous, lb_set_body_force, lb_set_force_field have
+                                 the rest).  lb_run: one fused launch per step (k_pm_step: 72 B per cell, 80 B with a force
+                                 field; the last launch of a run also stores rho, u, v, the total force and the barycentric
+                                 velocity, + 28 B).  float32 like every lattice here (the reference's fork computes in
+                                 float64).  lb_set_variant takes -1 and 0 only. */
 } lb_semantics;
 
 typedef struct {
@@ -265,6 +280,40 @@ int lb_solve_reset(lb_sim *s);
 int lb_get_solve_state(lb_sim *s, int *iterations, int *stop_word);
 int lb_set_solve_state(lb_sim *s, int iterations, int stop_word);
 int lb_gradient(lb_sim *s, float inv_two_dx, float *ddx, float *ddy);
+
+/* ---- forced flow in a porous medium (LB_SEM_POROUS; LB_ERR_STATE on every other handle) ------------------------------------
+ * One time step, every stage after the first two local to the cell (single_component.py:679-751):
+ *   1. move_periodic / move + copy_streamed_onto_f                               lb_move
+ *   2. move_open_bcs (LB_BC_ZERO_GRADIENT only)                                  lb_move_bcs
+ *   3. update_hydro_pourous: rho = sum f, u, v = sum f c / rho if rho > 1e-6, else 0   lb_update_hydro
+ *   4. G := the constant body force [+ the force field]                          }
+ *   5. update_forces_pourous: if rho > 1e-6, G := epsilon G - epsilon nu_fluid u / K   } lb_update_forces
+ *      - epsilon Fe |u| u / sqrt(K) with the u, v of stage 3; else G := 0        }
+ *   6. update_bary_velocity: u_b = (sum f c + rho G / 2) / rho                    lb_update_bary_velocity
+ *      (rho = 0 gives NaN, as in the reference: not guarded)
+ *   7. update_feq_pourous: feq_k = w_k rho (1 + 3 c.u_b + 4.5 (c.u_b)^2 / epsilon - 1.5 u_b^2 / epsilon)      lb_update_feq
+ *   8. collide_particles_pourous: f_k (1 - omega) + omega feq_k
+ *      + w_k rho (1 - omega / 2)(3 c.G + 9 (c.G)(c.u_b) / epsilon - 3 u_b.G / epsilon)   lb_collide_particles
+ * lb_run(n) = n fused steps; bitwise equal to the eight stages called one by one.  rho, u, v (lb_get_macro), the total force
+ * (lb_get_force) and u_b (lb_get_bary_velocity) are those of the last step, before its collision.
+ * lb_set_porous: epsilon, nu_fluid, K, Fe (defaults 1, 0, 1, 0); LB_ERR_ARG for epsilon <= 0, K <= 0 or a non-finite value.
+ * lb_set_body_force: the sum of the constant forces (default 0, 0).
+ * lb_set_force_field: two [ny][nx] planes added to the constant force in every cell (the reference's add_radial_body_force
+ *   depends on position only); on_device != 0: device pointers.  gx = gy = NULL drops the field.
+ * lb_get_force / lb_get_bary_velocity / lb_set_bary_velocity: [ny][nx] planes; an output may be NULL.
+ * lb_set_f, lb_get_f, lb_get_feq, lb_set_macro, lb_get_macro, lb_init_pop, lb_hot_kernel, lb_plan_launches and lb_layout
+ * work as on every handle.  Masks, slabs and halo calls, lb_autotune*, lb_set_variant with a value other than -1 and 0,
+ * lb_run_batch, lb_run_coupled, lb_solve*, lb_set_reaction, lb_set_velocity_from, lb_check and the edge / corner state:
+ * LB_ERR_STATE. */
+int lb_set_porous(lb_sim *s, float epsilon, float nu_fluid, float K, float Fe);
+int lb_set_body_force(lb_sim *s, float gx, float gy);
+int lb_set_force_field(lb_sim *s, const float *gx, const float *gy, int on_device);
+int lb_get_force(lb_sim *s, float *Gx, float *Gy);
+int lb_set_force(lb_sim *s, const float *Gx, const float *Gy);     /* (checkpoints: what lb_get_force returned) */
+int lb_set_bary_velocity(lb_sim *s, const float *u_bary, const float *v_bary);
+int lb_get_bary_velocity(lb_sim *s, float *u_bary, float *v_bary);
+int lb_update_forces(lb_sim *s);            /* stages 4 and 5 */
+int lb_update_bary_velocity(lb_sim *s);     /* stage 6 */
 
 /* ---- the reference's per-phase methods, one kernel each (slow, un-fused;
  *      API and test parity).  Single-slab handles only. ------------------- */
