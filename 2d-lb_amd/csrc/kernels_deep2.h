@@ -23,11 +23,16 @@
 // + 1 LDS window (8 KB); the hand-over slot 10 KB per direction: 72 KB per workgroup, two workgroups = eight waves per CU; 256 vector
 // registers per wave, no accumulation register.
 //
-// Issue priority.  Every back wave raises its priority once, at entry (deep2_set_prio below): without it the older of a CU's two
-// workgroups is served first on every SIMD and the younger runs a third of the launch alone.
+// Roles.  Which of the four bodies a wave enters follows the SIMD it runs on, read at entry (deep2_take_role below, deep2_roles.h): every
+// SIMD of a CU with two workgroups holds a front wave of one and a back wave of the other, 4 + 3 stage bodies per row.
+//
+// Issue priority.  Every front wave raises its priority once, at entry (deep2_set_prio below): without it the older of a CU's two
+// workgroups is served first on every SIMD and the younger runs a quarter of the launch alone.
 //
 // The launch moves the same 72 B per cell; same cell functions, same operations in the same order: bitwise equal to k_step.
 #pragma once
+
+#include "deep2_roles.h"
 
 namespace {
 
@@ -45,14 +50,15 @@ constexpr int DEEP2_WAVES = 4;
 __device__ __forceinline__ void deep2_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Static issue priority by role.  The hardware gives a SIMD's vector issue to the higher priority, then to the OLDER wave: at equal
-// priority the workgroup a CU was given first wins on all four SIMDs, runs as if alone and ends at two thirds of the launch, and the
-// second runs the last third with one wave per SIMD (profiles/r06y_wave_timeline_deep2.txt).  One role raises its priority -- once,
-// at entry, never inside the march.  What then meets on a SIMD is measured (per-wave records, profiles/deep2_priority_ab.txt): on a CU
-// with two workgroups two SIMDs hold a front wave of one and a back wave of the other, one holds two front waves and one two back
-// waves.  So with one role raised each workgroup wins ONE SIMD by priority, and on the two SIMDs that hold two of a kind age decides
-// as before: the older workgroup wins three SIMDs of four, not all four.  Which role is measured too (8192^2 periodic): with the
-// FRONT waves raised the two workgroups still end 30 % of the launch apart; with the BACK waves raised they advance alike and end 1 %
-// apart, and the product's launch is the shortest of the three.
+// priority the workgroup a CU was given first wins on all four SIMDs, runs as if alone and ends at three quarters of the launch, and
+// the second runs the rest with one wave per SIMD.  One role raises its priority -- once, at entry, never inside the march.  With the
+// roles taken by SIMD (deep2_take_role) every shared SIMD holds a front wave of one workgroup and a back wave of the other, so the
+// raised role wins on every SIMD, each workgroup on two of the four, and with EITHER role raised a CU's two workgroups end within
+// 0.1 % of the launch of each other (per-wave records, profiles/deep2_roles_ab.txt).  Which role is measured (8192^2 periodic, product
+// builds alternated): with the FRONT waves raised the launch is 3-4 % shorter than with the back waves -- the front wave, four stages
+// and the gather, sets its workgroup's pace at the barriers and is served first; the back wave, three stages, lives on what is left.
+// (Under the static roles -- two front waves on one SIMD of four, where age decided -- it was the back waves:
+// profiles/deep2_priority_ab.txt.)
 // mode (StepArgs::deep2_prio): 0 none, 1 front waves, 2 back waves; the diagnostic build overrides it by LB_DIAG bits 25-26
 // (0 = as launched, 1 / 2 / 3 = mode 0 / 1 / 2) so that one library runs the A/B.
 __device__ __forceinline__ void deep2_set_prio(const StepArgs &a, const int role_mode)
@@ -181,6 +187,59 @@ __device__ __forceinline__ void deep2_back(const StepArgs &a, const int x0, cons
     }
 }
 
+// ---- which of the four bodies a wave enters: 0 front-down, 1 front-up, 2 back-down, 3 back-up ------------------------------------
+// A front wave issues four stage bodies and the gather per row, a back wave three and the stores; a CU holds two workgroups, every
+// SIMD two waves, and both workgroups advance at the pace of their slowest wave (two barriers per row).  Each SIMD should therefore
+// hold a front wave of one workgroup and a back wave of the other: 4 + 3 stage bodies per row on every SIMD.
+//
+// The static rule (deep2_static_role: the wave's number, two on for every other 256 workgroups) assumes that wave w of every
+// workgroup lands on SIMD w.  It does not: the per-wave records (tools/wave_timeline.py, profiles/deep2_priority_ab.txt section 1) have a
+// front and a back wave on two SIMDs of a CU, two front waves on one -- 8 stage bodies and two gathers per row, and BOTH workgroups
+// have a wave there -- and two back waves on one.
+//
+// By SIMD: every wave reads the SIMD it runs on (HW_REG_HW_ID, bits 5:4), lane 0 publishes it in one LDS word per wave, and behind one
+// barrier every wave works out all four roles from the same four words (deep2_roles.h: deep2_assign_roles -- a permutation of 0..3
+// whatever the words hold) and takes its own.  `flip` tells the two workgroups of a CU apart: the launch-order bit
+// (blockIdx.x >> 8) & 1 -- they are 256 apart in launch order.  Measured (profiles/deep2_roles_ab.txt): opposite on every CU of the 8192^2
+// periodic launch, of a walled one with edge items and of a 512-workgroup one, a front and a back wave on every shared SIMD.  Where it
+// failed to, that CU would hold two fronts on two SIMDs and two backs on two: slower, never wrong.
+//
+// The diagnostic build runs the A/B from one library: LB_DIAG bit 27 = the static rule, exactly the code it was; bits 28-29 = 2 / 3:
+// another flip signal, taken from wave 0's hardware state and published in bit 2 of its word -- 2 = its wave-slot parity (HW_ID bit
+// 0, the bit k_step5 reads), 3 = the workgroup's LDS does not start at the CU's (HW_REG_LDS_ALLOC: its base).  Both measured as good as
+// the launch-order bit, neither better.
+__device__ __forceinline__ int deep2_take_role(const StepArgs &a, unsigned *lds_role, unsigned &note)
+{
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.y);
+    const int launch_flip = (blockIdx.x >> 8) & 1;
+    int sig = 1;
+#ifdef LB_DIAG
+    if (a.diag & (1 << 27)) {
+        note = (unsigned)launch_flip << 30;
+        return deep2_static_role(w, launch_flip);
+    }
+    if ((a.diag >> 28) & 3) sig = (a.diag >> 28) & 3;
+#endif
+    const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);      // HW_REG_HW_ID: wave_id[3:0] simd_id[5:4]
+    unsigned word = (hw >> 4) & 3u;
+    if (sig == 2) word |= (hw & 1u) << 2;
+    if (sig == 3) word |= (__builtin_amdgcn_s_getreg((31 << 11) | 6) & 0xfffu) ? 4u : 0u;      // HW_REG_LDS_ALLOC: lds_base in the low bits
+    if (threadIdx.x == 0) lds_role[w] = word;
+    deep2_barrier();
+    int simd[DEEP2_WAVES], role[DEEP2_WAVES];
+    unsigned word0 = 0;
+#pragma unroll
+    for (int k = 0; k < DEEP2_WAVES; ++k) {
+        const unsigned v = __builtin_amdgcn_readfirstlane(lds_role[k]);
+        simd[k] = (int)(v & 3u);
+        if (k == 0) word0 = v;
+    }
+    const int flip = sig == 1 ? launch_flip : (int)((word0 >> 2) & 1u);
+    deep2_assign_roles(simd, flip, role);
+    note = ((unsigned)flip << 30) | (1u << 29);
+    return w == 0 ? role[0] : (w == 1 ? role[1] : (w == 2 ? role[2] : role[3]));     // (no indexed register array: no scratch)
+}
+
 // Launch geometry as k_deep: one workgroup = one segment pair of one strip, now four waves; XCD-transposed order, shorter segments for
 // the two wall-column strips.  LDS: front 2 x (F - 1 - RWF) windows, back 2 x (D - F - RWB) windows, 2 slots.
 template <int BC, bool MASK, bool MACRO, int D>
@@ -193,12 +252,7 @@ __global__ __launch_bounds__(64 * DEEP2_WAVES, 2) void k_deep2(const StepArgs a,
     __shared__ f4a lds_front[2][LF][64];
     __shared__ f4a lds_back[2][LBK][64];
     __shared__ f4a lds_ho[2][DEEP_HO_SLOTS][64];
-    // 0 front-down, 1 front-up, 2 back-down, 3 back-up.  The two workgroups of a CU are (in launch order) 256 apart: every other 256
-    // workgroups take the roles two waves on, meant to give every SIMD a front wave (four stages and the gather) AND a back wave (three
-    // stages and the stores).  It does on half of the shared SIMDs: per-wave records (tools/wave_timeline.py,
-    // profiles/deep2_priority_ab.txt) have a front and a back wave on two SIMDs of a CU, two front waves on one and two back waves on
-    // one -- as if the second workgroup's wave w landed on SIMD w + 1, not on SIMD w like the first's.
-    const int wy = (__builtin_amdgcn_readfirstlane(threadIdx.y) + ((blockIdx.x >> 8) & 1) * 2) & 3;
+    __shared__ unsigned lds_role[DEEP2_WAVES];          // what each wave reports of where it runs (deep2_take_role)
     const int item = xcd_item(blockIdx.x, gridDim.x);
 #ifdef LB_DIAG
     const unsigned long long diag_t0 = __builtin_amdgcn_s_memrealtime();     // 100 MHz
@@ -221,6 +275,8 @@ __global__ __launch_bounds__(64 * DEEP2_WAVES, 2) void k_deep2(const StepArgs a,
     const int ym = ya + (yb - ya) / 2;                  // the pair's middle line: the down waves march down from it, the up waves up
     const int x0 = sx * deep_valid(D) - 4 * deep_skirt_lanes(D);
     const int trips = max(ym - ya, yb - ym) + D;        // front: len + D - 1 iterations from trip 0; back: len + D - F from trip F
+    unsigned role_note = 0;
+    const int wy = deep2_take_role(a, lds_role, role_note);       // (behind the two returns above: its barrier is the whole workgroup's)
     if (wy == 0) deep2_front<BC, MASK, D, F, RWF, true>(a, x0, ym, ym - ya, trips, lds_front[0], lds_front[1], lds_ho[0], lds_dma[0]);
     else if (wy == 1) deep2_front<BC, MASK, D, F, RWF, false>(a, x0, ym, yb - ym, trips, lds_front[1], lds_front[0], lds_ho[1], lds_dma[1]);
     else if (wy == 2) deep2_back<BC, MASK, MACRO, D, F, RWB, true>(a, x0, ym, ym - ya, trips, lds_back[0], lds_back[1], lds_ho[0]);
@@ -234,7 +290,8 @@ __global__ __launch_bounds__(64 * DEEP2_WAVES, 2) void k_deep2(const StepArgs a,
         o[0] = (unsigned)diag_t0; o[1] = (unsigned)(diag_t0 >> 32); o[2] = (unsigned)t1; o[3] = (unsigned)(t1 >> 32);
         o[4] = __builtin_amdgcn_s_getreg((31 << 11) | 20);      // HW_REG_XCC_ID
         o[5] = __builtin_amdgcn_s_getreg((31 << 11) | 4);       // HW_REG_HW_ID
-        o[6] = (unsigned)(item * DEEP2_WAVES + wy); o[7] = (unsigned)((wy & 1) ? yb - ym : ym - ya);
+        // [6]: the role TAKEN; [7]: the march's rows, bit 30 = the workgroup's flip, bit 29 = roles by SIMD (deep2_take_role)
+        o[6] = (unsigned)(item * DEEP2_WAVES + wy); o[7] = (unsigned)((wy & 1) ? yb - ym : ym - ya) | role_note;
     }
 #endif
 }

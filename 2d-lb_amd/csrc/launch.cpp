@@ -73,9 +73,12 @@ static bool launch_march(const lb_sim *s, hipStream_t st, const StepArgs &a, con
 }
 
 // k_deep2: which role of a workgroup raises its issue priority at entry (kernels_deep2.h: deep2_set_prio): 0 none, 1 the front
-// waves, 2 the back waves.  The back waves: the one mode in which a CU's two workgroups end together and the launch is shorter
-// (profiles/deep2_priority_ab.txt); the diagnostic build overrides it per run (LB_DIAG bits 25-26).
-constexpr int DEEP2_PRIO = 2;
+// waves, 2 the back waves.  The front waves, since every shared SIMD holds a front and a back wave (roles by SIMD, kernels_deep2.h:
+// deep2_take_role): a CU's two workgroups end together with either role raised, and the launch is 3-4 % shorter with the front
+// waves -- four stages and the gather, the pace of their workgroup -- served first and the back waves on what they leave
+// (profiles/deep2_roles_ab.txt; under the static roles it was the back waves: profiles/deep2_priority_ab.txt).  The diagnostic build
+// overrides it per run (LB_DIAG bits 25-26).
+constexpr int DEEP2_PRIO = 1;
 
 int launch_marching(lb_sim *s, const MarchRows &r)
 {

@@ -5,7 +5,9 @@ XCD / CU / SIMD.  Usage (GPU box): [LB_TIMELINE_BC=pipe] [LB_TIMELINE_DEPTH=6|7]
 k_deep2<7> (four waves per item): LB_TIMELINE_DEEP2=1 LB_TIMELINE_DEPTH=7; the report adds, per CU with two workgroups, when each ended,
 and what shares a SIMD.  Its issue-priority mode (csrc/kernels_deep2.h: deep2_set_prio; 0 none, 1 front waves, 2 back waves) is chosen
 per run by LB_DIAG bits 25-26 of the diagnostic build: LB_DIAG = 4096 | ((mode + 1) << 25), i.e. 33558528 / 67112960 / 100667392 for
-modes 0 / 1 / 2; plain 4096 runs the mode the library launches with.  (profiles/deep2_priority_ab.txt)"""
+modes 0 / 1 / 2; plain 4096 runs the mode the library launches with.  (profiles/deep2_priority_ab.txt)
+Which body a wave enters (deep2_take_role): + 134217728 (bit 27) = the static roles (by the wave's number) instead of roles by SIMD;
++ (s << 28), s = 2 / 3 = another flip signal (wave-slot parity / LDS half) than the launch-order bit.  (profiles/deep2_roles_ab.txt)"""
 import os
 import sys
 
@@ -91,7 +93,8 @@ def main():
 
 
 def deep2_report(u, strips, segs, n, ny):
-    items = 4 * strips * segs
+    # (boxes with walls: the wall strips' edge items follow the interior's, in other numbers than `segs`: read what is there)
+    items = min(4 * (strips * segs + 8 * segs), u.size // 8)
     rec = u[:8 * items].reshape(items, 8).astype(np.int64)
     t0 = rec[:, 0] | (rec[:, 1] << 32)
     t1 = rec[:, 2] | (rec[:, 3] << 32)
@@ -142,6 +145,21 @@ def deep2_report(u, strips, segs, n, ny):
     pairs = [sorted(v) for v in per_simd.values() if len(v) == 2]
     print("SIMDs holding two waves: %d; a front and a back wave on %d, two front waves on %d, two back waves on %d" % (
         len(pairs), pairs.count([0, 1]), pairs.count([0, 0]), pairs.count([1, 1])))
+    # how the roles were taken (kernels_deep2.h: deep2_take_role): record [7] bit 29 = by SIMD, bit 30 = the workgroup's flip
+    by_simd, flip = (rec[:, 7] >> 29) & 1, (rec[:, 7] >> 30) & 1
+    per_wg = {}
+    for g, sd, r, b in zip(wg.tolist(), simd.tolist(), role.tolist(), by_simd.tolist()):
+        per_wg.setdefault(g, []).append((sd, r, b))
+    whole = [v for v in per_wg.values() if len(v) == 4]
+    perm = [v for v in whole if sorted(x[0] for x in v) == [0, 1, 2, 3]]
+    follows = [v for v in perm if len({(x[1] - x[0]) & 3 for x in v}) == 1 and ((v[0][1] - v[0][0]) & 1) == 0]
+    print("workgroups: %d; roles by SIMD in %d; their four waves on four different SIMDs in %d; role = SIMD (+ 2 under flip) in %d" % (
+        len(whole), sum(1 for v in whole if v[0][2]), len(perm), len(follows)))
+    cu_flip = {}
+    for k, g, fl in zip(key.tolist(), wg.tolist(), flip.tolist()):
+        cu_flip.setdefault(k, {})[g] = fl
+    twof = [sorted(d.values()) for d in cu_flip.values() if len(d) == 2]
+    print("CUs with two workgroups: flip 0 and 1 on %d, both 0 on %d, both 1 on %d" % (twof.count([0, 1]), twof.count([0, 0]), twof.count([1, 1])))
     hist, edges = np.histogram(end, bins=12)
     print("wave ends, histogram:", " ".join("%.0f-%.0f:%d" % (edges[i], edges[i + 1], hist[i]) for i in range(len(hist))))
     hist, edges = np.histogram(start, bins=8)
