@@ -18,6 +18,10 @@ LB_PEER_HANDLE_BYTES = 384
 LB_DEVICE_CPU = -1
 LB_SEM_OPENCL, LB_SEM_CYTHON, LB_SEM_OPENCL_D2Q9I, LB_SEM_DIFFUSION, LB_SEM_MULTIFIELD, LB_SEM_POISSON = 0, 1, 2, 3, 4, 5
 LB_SEM_POROUS = 7        # (6 is not assigned: include/lb_hip.h)
+LB_SEM_MULTIFLUID = 9    # (nor is 8)
+LB_PSI_LINEAR, LB_PSI_SHAN_CHEN, LB_PSI_POW = 0, 1, 2
+LB_REACT_EAT, LB_REACT_GROW = 0, 1
+MC_MAX, MC_MAX_INTER, MC_MAX_REACT = 3, 6, 4
 BC_NAMES = {"pipe": LB_BC_PIPE, "periodic": LB_BC_PERIODIC, "cavity": LB_BC_CAVITY,
             "velocity_inlet": LB_BC_VELOCITY_INLET, "open": LB_BC_OPEN, "box": LB_BC_BOX, "dirichlet": LB_BC_DIRICHLET,
             "zero_gradient": LB_BC_ZERO_GRADIENT}
@@ -42,6 +46,8 @@ EXPORTS = (
     "lb_gradient",
     "lb_set_porous", "lb_set_body_force", "lb_set_force_field", "lb_get_force", "lb_set_force", "lb_set_bary_velocity",
     "lb_get_bary_velocity", "lb_update_forces", "lb_update_bary_velocity",
+    "lb_run_fluids", "lb_set_interactions", "lb_set_reactions", "lb_get_interactions", "lb_get_reactions",
+    "lb_update_forces_fluids", "lb_update_bary_fluids", "lb_react_fluids",
 )
 
 
@@ -51,6 +57,16 @@ class LbParams(ct.Structure):
                 ("omega", ct.c_float), ("inlet_rho", ct.c_float), ("outlet_rho", ct.c_float),
                 ("lid_u", ct.c_float), ("rho0", ct.c_float), ("flags", ct.c_int32), ("semantics", ct.c_int32),
                 ("inlet_u", ct.c_float), ("outlet_u", ct.c_float), ("reserved", ct.c_int32 * 1)]
+
+
+class Interaction(ct.Structure):         # lb_interaction
+    _fields_ = [("fluid_1", ct.c_int32), ("fluid_2", ct.c_int32), ("potential", ct.c_int32), ("boundary", ct.c_int32),
+                ("G_int", ct.c_float), ("parameter", ct.c_float)]
+
+
+class FluidReaction(ct.Structure):       # lb_fluid_reaction
+    _fields_ = [("kind", ct.c_int32), ("fluid_a", ct.c_int32), ("fluid_b", ct.c_int32),
+                ("p0", ct.c_float), ("p1", ct.c_float), ("p2", ct.c_float)]
 
 
 class LbError(RuntimeError):
@@ -134,6 +150,15 @@ def lib():
             getattr(L, name).argtypes = [h, vp, vp]
         L.lb_update_forces.argtypes = [h]
         L.lb_update_bary_velocity.argtypes = [h]
+    if hasattr(L, "lb_run_fluids"):                 # (likewise: multicomponent Shan-Chen fluids)
+        hp, ip = ct.POINTER(h), ct.POINTER(ct.c_int)
+        L.lb_run_fluids.argtypes = [hp, I, I]
+        L.lb_set_interactions.argtypes = [hp, I, ct.POINTER(Interaction), I]
+        L.lb_set_reactions.argtypes = [hp, I, ct.POINTER(FluidReaction), I]
+        L.lb_get_interactions.argtypes = [h, ct.POINTER(Interaction), ip]
+        L.lb_get_reactions.argtypes = [h, ct.POINTER(FluidReaction), ip]
+        for name in ("lb_update_forces_fluids", "lb_update_bary_fluids", "lb_react_fluids"):
+            getattr(L, name).argtypes = [hp, I]
     L.lb_comm_init.argtypes = [h, vp, I, I]
     L.lb_timer_stop.argtypes = [h, fp]
     L.lb_layout.argtypes = [h, ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64)]

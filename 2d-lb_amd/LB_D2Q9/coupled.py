@@ -128,3 +128,174 @@ class Coupled_Scalars(object):
     def check(self):
         """Per member: Simulation.check() (non-finite cells, max Mach number of the imposed field, sum of rho)."""
         return [m.check() for m in self.members]
+
+
+class Shan_Chen_Fluids(object):
+    """A set of 1..3 fluids on one grid (``Simulation(semantics='multifluid')``, its own ``omega`` each) that relax towards
+    their common barycentric velocity and act on each other through pseudopotential forces and reactions: the reference's
+    ``multicomponent_multiphase/multi.py``.  ``run(n)`` advances all of them with one launch per time step and no host
+    wait (``lb_run_fluids``: the densities of a workgroup's rows and their halo in LDS; ``set_variant(0)``: two launches, the
+    densities through memory; the same bits); the phase methods run the reference's stages one by one and equal it bitwise.  Arrays are
+    shaped like the reference's, ``(nx, ny, num_populations[, 9])`` in Fortran order; ``u_bary``, ``v_bary`` are ``(nx, ny)``.
+
+    ``interactions``: rows ``(fluid_1, fluid_2, G_int, potential, parameter)`` with potential ``'linear'``, ``'shan_chen'``
+    (parameter rho_0) or ``'pow'`` (parameter alpha); the stencil's boundary rule is the set's family.  ``reactions``: rows
+    ``('eat', eater, eatee, rate, cutoff)`` or ``('grow', fluid, min, max, rate)``, applied in order."""
+    MAX_POPULATIONS = _native.MC_MAX
+    POTENTIALS = {"linear": _native.LB_PSI_LINEAR, "shan_chen": _native.LB_PSI_SHAN_CHEN, "pow": _native.LB_PSI_POW}
+    _STACKED = ("f", "feq", "rho", "u", "v", "Gx", "Gy")
+
+    def __init__(self, nx, ny, omegas, bc="periodic", device=0, planar=None):
+        omegas = [float(o) for o in np.atleast_1d(omegas)]
+        if not 1 <= len(omegas) <= self.MAX_POPULATIONS:
+            raise NotImplementedError("1..%d fluids are built (more than %d fluids are not)" % (self.MAX_POPULATIONS, self.MAX_POPULATIONS))
+        if bc not in ("periodic", "zero_gradient"):
+            raise ValueError("bc must be 'periodic' or 'zero_gradient'")
+        self.nx, self.ny, self.num_populations, self.num_jumpers = int(nx), int(ny), len(omegas), NUM_JUMPERS
+        self.omegas, self.bc = omegas, bc
+        self.members = [Simulation(nx, ny, om, bc=bc, semantics="multifluid", device=device, planar=planar) for om in omegas]
+        self._lib = _native.lib()
+        self._handles = (ct.c_void_p * len(omegas))(*[m._h for m in self.members])
+        self.interactions, self.reactions = [], []
+
+    @classmethod
+    def of(cls, members):
+        """The set made of existing ``Simulation(semantics='multifluid')`` objects, in this order (they stay their owners')."""
+        members = list(members)
+        if not 1 <= len(members) <= cls.MAX_POPULATIONS:
+            raise NotImplementedError("1..%d fluids are built (more than %d fluids are not)" % (cls.MAX_POPULATIONS, cls.MAX_POPULATIONS))
+        if len({m.bc_mode for m in members}) != 1:
+            raise NotImplementedError("fluids of different families in one set are not built")
+        self = cls.__new__(cls)
+        m0 = members[0]
+        self.nx, self.ny, self.num_populations, self.num_jumpers = m0.nx, m0.ny, len(members), NUM_JUMPERS
+        self.omegas = [m.omega for m in members]
+        self.bc = "periodic" if m0.bc_mode == _native.LB_BC_PERIODIC else "zero_gradient"
+        self.members = members
+        self._lib = _native.lib()
+        self._handles = (ct.c_void_p * len(members))(*[m._h for m in members])
+        self.interactions, self.reactions = [], []
+        return self
+
+    close, sync, _per_field = Coupled_Scalars.close, Coupled_Scalars.sync, Coupled_Scalars._per_field
+    set_f, init_pop = Coupled_Scalars.set_f, Coupled_Scalars.init_pop
+    move, move_bcs, update_hydro, update_feq = Coupled_Scalars.move, Coupled_Scalars.move_bcs, Coupled_Scalars.update_hydro, Coupled_Scalars.update_feq
+
+    # -- the tables ---------------------------------------------------------------------------------------------------------
+    def set_interactions(self, table):
+        rows = []
+        for f1, f2, G_int, potential, parameter in table:
+            if potential not in self.POTENTIALS:
+                raise NotImplementedError("potential %r is not built (linear, shan_chen and pow are; vdw is not)" % (potential,))
+            rows.append((int(f1), int(f2), self.POTENTIALS[potential], 0 if self.bc == "periodic" else 1, G_int, parameter))
+        self.members[0]._set_tables(self._handles, self.num_populations, rows, None)
+        self.interactions = [tuple(r) for r in table]
+
+    def set_reactions(self, table):
+        rows = []
+        for r in table:
+            if r[0] == "eat":
+                rows.append((_native.LB_REACT_EAT, int(r[1]), int(r[2]), r[3], r[4], 0.))
+            elif r[0] == "grow":
+                rows.append((_native.LB_REACT_GROW, int(r[1]), 0, r[2], r[3], r[4]))
+            else:
+                raise ValueError("a reaction is ('eat', eater, eatee, rate, cutoff) or ('grow', fluid, min, max, rate)")
+        self.members[0]._set_tables(self._handles, self.num_populations, None, rows)
+        self.reactions = [tuple(r) for r in table]
+
+    # -- state --------------------------------------------------------------------------------------------------------------
+    def set_fields(self, rho, u=None, v=None):
+        """rho, and optionally the stored component velocities u, v: (nx, ny, num_populations) each."""
+        rho = self._per_field(rho)
+        zero = np.zeros((self.nx, self.ny), np.float32)
+        for i, m in enumerate(self.members):
+            m.set_fields(rho[:, :, i], zero if u is None else self._per_field(u)[:, :, i], zero if v is None else self._per_field(v)[:, :, i])
+
+    def set_bary_velocity(self, u_bary, v_bary):
+        for m in self.members:
+            m.set_bary_velocity(u_bary, v_bary)
+
+    def set_body_force(self, fluid, gx, gy):
+        self.members[int(fluid)].set_body_force(gx, gy)
+
+    def set_force_field(self, fluid, gx, gy):
+        self.members[int(fluid)].set_force_field(gx, gy)
+
+    def get_fields(self, which=("f", "feq", "rho", "u", "v", "Gx", "Gy", "u_bary", "v_bary")):
+        out = {}
+        stacked = tuple(k for k in which if k in self._STACKED)
+        if stacked:
+            per = [m.get_fields(stacked) for m in self.members]
+            for k in stacked:
+                out[k] = np.asfortranarray(np.stack([g[k] for g in per], axis=2))
+        shared = tuple(k for k in which if k in ("u_bary", "v_bary"))
+        if shared:
+            out.update(self.members[0].get_fields(shared))
+        return out
+
+    # -- the reference's stages that involve the whole set, un-fused -------------------------------------------------------
+    def update_forces(self):
+        check(self._lib.lb_update_forces_fluids(self._handles, self.num_populations))
+        self.sync()
+
+    def update_bary_velocity(self):
+        check(self._lib.lb_update_bary_fluids(self._handles, self.num_populations))
+        self.sync()
+
+    def collide_particles(self):
+        for m in self.members:
+            m.collide_particles()
+
+    def react(self):
+        check(self._lib.lb_react_fluids(self._handles, self.num_populations))
+        self.sync()
+
+    def step_phases(self):
+        """One time step as the reference's run loop makes it, stage by stage (each call waits)."""
+        self.move()
+        self.move_bcs()
+        self.update_hydro()
+        self.update_forces()
+        self.update_bary_velocity()
+        self.update_feq()
+        self.collide_particles()
+        self.react()
+
+    # -- the hot path -----------------------------------------------------------------------------------------------------
+    def run(self, num_iterations, wait=True):
+        check(self._lib.lb_run_fluids(self._handles, self.num_populations, int(num_iterations)))
+        if wait:
+            self.sync()
+
+    def step(self):
+        self.run(1)
+
+    def set_variant(self, variant):
+        for m in self.members:
+            m.set_variant(variant)
+
+    def hot_kernel(self):
+        return self.members[0].hot_kernel()
+
+    # -- checkpoints: every member's arrays under 'm<i>_', the tables with the first ----------------------------------------
+    def save_checkpoint(self, path):
+        d = {"num_populations": self.num_populations}
+        for i, m in enumerate(self.members):
+            for k, a in m.checkpoint_arrays().items():
+                d["m%d_%s" % (i, k)] = a
+        np.savez(Simulation._ckpt_path(path), **d)
+
+    @classmethod
+    def from_checkpoint(cls, path, device=0):
+        with np.load(Simulation._ckpt_path(path)) as d:
+            n = int(d["num_populations"])
+            per = [{k[len("m%d_" % i):]: d[k] for k in d.files if k.startswith("m%d_" % i)} for i in range(n)]
+        bc = {_native.LB_BC_PERIODIC: "periodic", _native.LB_BC_ZERO_GRADIENT: "zero_gradient"}[int(per[0]["bc_mode"])]
+        out = cls(int(per[0]["nx"]), int(per[0]["ny"]), [float(p["omega"]) for p in per], bc=bc, device=device)
+        for m, p in zip(out.members, per):
+            m.restore_arrays(p)
+        names = {v: k for k, v in cls.POTENTIALS.items()}
+        out.set_interactions([(int(r[0]), int(r[1]), r[4], names[int(r[2])], r[5]) for r in per[0]["interactions"]])
+        out.set_reactions([("eat", int(r[1]), int(r[2]), r[3], r[4]) if int(r[0]) == _native.LB_REACT_EAT else ("grow", int(r[1]), r[3], r[4], r[5])
+                           for r in per[0]["reactions"]])
+        return out

@@ -13,7 +13,8 @@ equal to it.
 ``np.float32`` here.  Arrays are ``(nx, ny, 1[, 9])`` F-ordered, as in the reference with one population.
 
 Not built: several fluids (``num_populations > 1``), the Shan-Chen interaction forces (``add_interaction_force``,
-``add_interaction_force_second_belt``) and ``add_eating_rate``: they raise ``NotImplementedError``.  Differences:
+``add_interaction_force_second_belt``) and ``add_eating_rate``: they raise ``NotImplementedError`` here
+(``LB_D2Q9.multicomponent_multiphase.multi`` has them, without the porous medium).  Differences:
 ``Pourous_Media.update_forces`` is the reference's ``Gx, Gy = 0`` + additional forces + ``update_forces_pourous`` in one
 kernel (the reference's kernel alone, applied twice, would scale the force by ``epsilon`` twice); ``initialize`` runs it
 with no additional force, which is what the reference's buffers hold at that point; ``init_pop`` takes a ``seed``; the

@@ -85,6 +85,12 @@ class Simulation(object):
                fluid): a Guo-forced BGK fluid with porosity, linear and quadratic drag (set_porous) and body forces
                (set_body_force, set_force_field); bc='periodic' or 'zero_gradient'; whole grid, no obstacles.  float32 like
                every lattice here (the reference's fork is float64).  get_fields adds 'u_bary', 'v_bary', 'Gx', 'Gy'.
+               'multifluid': one fluid of a set of Shan-Chen fluids (the reference's multicomponent_multiphase/multi.cl /
+               multi.py): a Guo-forced BGK fluid relaxing towards the barycentric velocity of the set, with body forces
+               (set_body_force, set_force_field: accelerations, multiplied by rho), pseudopotential interaction forces
+               (set_interactions) and reactions (set_reactions); bc='periodic' or 'zero_gradient'; whole grid, at least 3x3, no
+               obstacles.  One launch per step (set_variant(0): two).  A handle on its own is a set of one; LB_D2Q9.coupled.Shan_Chen_Fluids advances several.
+               get_fields keys are those of 'porous'.
         :param planar: device layout of the lattices: False = the nine planes of a row stored together (default),
                True = each plane contiguous (LB_FLAG_PLANAR); results are identical.  None: environment variable
                LB_LAYOUT=planar selects True (tuning aid).
@@ -116,7 +122,7 @@ class Simulation(object):
                    (_native.LB_FLAG_EAGER_MACRO if self.eager_macro else 0))
         sem = {"opencl": _native.LB_SEM_OPENCL, "cython": _native.LB_SEM_CYTHON, "d2q9i": _native.LB_SEM_OPENCL_D2Q9I,
                "diffusion": _native.LB_SEM_DIFFUSION, "multifield": _native.LB_SEM_MULTIFIELD, "poisson": _native.LB_SEM_POISSON,
-               "porous": _native.LB_SEM_POROUS}
+               "porous": _native.LB_SEM_POROUS, "multifluid": _native.LB_SEM_MULTIFLUID}
         if semantics not in sem:
             raise ValueError("semantics must be one of %s" % sorted(sem))
         p.semantics = sem[semantics]
@@ -139,6 +145,7 @@ class Simulation(object):
         self.epsilon, self.nu_fluid, self.K, self.Fe = 1., 0., 1., 0.               # the porous medium's (set_porous)
         self.body_force = (0., 0.)                                                  # ... and its constant force (set_body_force)
         self._force_field = None                                                    # ... and its force field, as uploaded
+        self.interactions, self.reactions = [], []                                  # a set of fluids' tables, kept by its first handle (set_interactions, set_reactions)
         self._mask_host = None
         self._mask_halo_host = None      # (south_rows, north_rows) as last given to set_obstacle_mask_halo
         if obstacle_mask is not None:
@@ -234,7 +241,7 @@ class Simulation(object):
         unchanged; the pass advances at most (n - 7) // 4 steps, a runner-up's longer comparison included) and keeps the
         fastest for this grid; shorter runs use the size heuristic (or call autotune())."""
         n = int(num_iterations)
-        if wait and n > 0 and self.semantics not in ("diffusion", "multifield", "poisson", "porous"):      # (a scalar lattice's kernel is the planner's size rule: no tuning pass)
+        if wait and n > 0 and self.semantics not in ("diffusion", "multifield", "poisson", "porous", "multifluid"):      # (a scalar lattice's kernel is the planner's size rule: no tuning pass)
             # (the pass costs 361 steps, 889 on grids <= 768^2, some of them in configurations several times slower than
             #  the best: it only pays for itself in a run several times that long)
             used = self._lib.lb_autotune_quick(self._h, (n - 7) // 4)
@@ -351,6 +358,16 @@ class Simulation(object):
             d["force"] = np.stack([g["Gx"], g["Gy"]])
             if self._force_field is not None:
                 d["force_field"] = np.stack(self._force_field)
+        if self.semantics == "multifluid":
+            g = self.get_fields(("u_bary", "v_bary", "Gx", "Gy"))
+            d["body_force"] = np.array(self.body_force, np.float32)
+            d["bary"] = np.stack([g["u_bary"], g["v_bary"]])
+            d["force"] = np.stack([g["Gx"], g["Gy"]])
+            if self._force_field is not None:
+                d["force_field"] = np.stack(self._force_field)
+            # the tables as rows of float64 (exact for the int32 and float32 they hold)
+            d["interactions"] = np.array(self.interactions, np.float64).reshape(len(self.interactions), 6)
+            d["reactions"] = np.array(self.reactions, np.float64).reshape(len(self.reactions), 6)
         if self._mask_halo_host is not None:         # a slab: the neighbours' obstacle rows it was given
             empty = np.zeros((0, 0), np.int32)
             d["mask_halo_south"] = empty if self._mask_halo_host[0] is None else self._mask_halo_host[0]
@@ -384,7 +401,7 @@ class Simulation(object):
 
     def restore_arrays(self, d):
         self._check_compatible(d)
-        if self.semantics not in ("diffusion", "multifield", "poisson", "porous"):   # (a scalar lattice has no obstacles, nor has the porous medium)
+        if self.semantics not in ("diffusion", "multifield", "poisson", "porous", "multifluid"):   # (a scalar lattice has no obstacles, nor have the porous medium and the fluids of a set)
             self.set_obstacle_mask(d["mask"] if d["mask"].size else None)
         if "mask_halo_south" in d:
             so, no = d["mask_halo_south"], d["mask_halo_north"]
@@ -413,6 +430,50 @@ class Simulation(object):
             self.set_bary_velocity(d["bary"][0], d["bary"][1])
             gx, gy = (_f_order(a, self._shape2) for a in d["force"])
             check(self._lib.lb_set_force(self._h, gx.ctypes.data, gy.ctypes.data))
+
+        if self.semantics == "multifluid":
+            self.set_body_force(*[float(x) for x in d["body_force"]])
+            self.set_force_field(*(d["force_field"] if "force_field" in d else (None, None)))
+            self.set_bary_velocity(d["bary"][0], d["bary"][1])
+            gx, gy = (_f_order(a, self._shape2) for a in d["force"])
+            check(self._lib.lb_set_force(self._h, gx.ctypes.data, gy.ctypes.data))
+            inter, react = [tuple(r) for r in d["interactions"]], [tuple(r) for r in d["reactions"]]
+            others = [r[0] for r in inter] + [r[1] for r in inter] + [r[1] for r in react] + [r[2] for r in react]
+            if not others or max(others) == 0:      # (tables that name further fluids are restored by the set: Shan_Chen_Fluids)
+                self.set_interactions(inter)
+                self.set_reactions(react)
+
+    # -- one fluid of a set of Shan-Chen fluids (semantics='multifluid'); the calls below this block are shared -------------
+    def _set_tables(self, handles, count, interactions, reactions):
+        """Validate and store both tables with this handle, the first of `handles` (a ctypes array of `count` handles)."""
+        if interactions is not None:
+            rows = [(int(r[0]), int(r[1]), int(r[2]), int(r[3]), float(np.float32(r[4])), float(np.float32(r[5]))) for r in interactions]
+            arr = (_native.Interaction * max(1, len(rows)))(*[_native.Interaction(*r) for r in rows])
+            check(self._lib.lb_set_interactions(handles, count, arr, len(rows)))
+            self.interactions = rows
+        if reactions is not None:
+            rows = [(int(r[0]), int(r[1]), int(r[2]), float(np.float32(r[3])), float(np.float32(r[4])), float(np.float32(r[5]))) for r in reactions]
+            arr = (_native.FluidReaction * max(1, len(rows)))(*[_native.FluidReaction(*r) for r in rows])
+            check(self._lib.lb_set_reactions(handles, count, arr, len(rows)))
+            self.reactions = rows
+
+    def _own_set(self):
+        return (ct.c_void_p * 1)(self._h)
+
+    def set_interactions(self, table):
+        """The interaction table of this fluid as a set of one (self terms only): rows (fluid_1, fluid_2, potential, boundary,
+        G_int, parameter) -- potential 0 linear, 1 shan_chen, 2 pow; boundary 0 periodic, 1 zero gradient = this handle's family."""
+        self._set_tables(self._own_set(), 1, table, None)
+
+    def set_reactions(self, table):
+        """The reaction table of this fluid as a set of one: rows (kind, fluid_a, fluid_b, p0, p1, p2) -- kind 1 (grow): fluid,
+        -, min, max, rate; kind 0 (eat) needs two fluids."""
+        self._set_tables(self._own_set(), 1, None, table)
+
+    def react(self):
+        """The reaction table on the populations, from the stored rho (the reference's additional collisions)."""
+        check(self._lib.lb_react_fluids(self._own_set(), 1))
+        self.sync()
 
     # -- forced flow in a porous medium (semantics='porous') -------------------------
     def set_porous(self, epsilon=1., nu_fluid=0., K=1., Fe=0.):

@@ -8,7 +8,8 @@
 //   lb_hip.cpp     create / destroy / setters, state transfer, the un-fused phases, lb_run, lb_run_batch, lb_check, timers
 // Small kernels are emitted by the one unit that includes their header: kernels_phases.h + kernels_check.h by lb_hip.cpp,
 // kernels_halo.h by slab.cpp, kernels_scalar.h by scalar.cpp (its health check's first pass only: check_reduce.h is shared, the folding
-// pass is lb_hip.cpp's), kernels_multifield.h by multifield.cpp, kernels_poisson.h by poisson.cpp, kernels_porous.h by porous.cpp.
+// pass is lb_hip.cpp's), kernels_multifield.h by multifield.cpp, kernels_poisson.h by poisson.cpp, kernels_porous.h by porous.cpp,
+// kernels_multifluid.h by multifluid.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -27,6 +28,7 @@
 #include "multifield_launch.h"  // coupled scalar lattices (LB_SEM_MULTIFIELD): MfArgs, their launchers
 #include "poisson_launch.h"     // the LB Poisson solver (LB_SEM_POISSON): PsExtra, PsState, its launchers
 #include "porous_launch.h"      // forced flow in a porous medium (LB_SEM_POROUS): PmExtra, its launchers
+#include "multifluid_launch.h"  // multicomponent Shan-Chen fluids (LB_SEM_MULTIFLUID): McArgs, their launchers
 
 namespace {
 
@@ -60,6 +62,11 @@ struct lb_sim : PlanInputs {
     float *pm_field[2] = {nullptr, nullptr};    // [H][pitch] each, padding zero: the force field (lb_set_force_field), or none
     float pm_eps = 1.f, pm_nu = 0.f, pm_K = 1.f, pm_Fe = 0.f;   // lb_set_porous
     float pm_gx = 0.f, pm_gy = 0.f;         // lb_set_body_force
+    // multicomponent Shan-Chen fluids (LB_SEM_MULTIFLUID; multifluid_launch.h): a member uses pm_G, pm_ub, pm_field, pm_gx, pm_gy as
+    // the porous fluid does; the tables of a set live in its first handle
+    McInter mc_inter[MC_MAX_INTER] = {};
+    McReact mc_react[MC_MAX_REACT] = {};
+    int mc_n_inter = 0, mc_n_react = 0;
     uint8_t *mask_raw = nullptr, *mask = nullptr;   // [H+2*MASK_GHOST][pitch] + guards; mask -> row 0
     bool feq_valid = false;     // feq buffer consistent with rho,u,v
     bool macro_valid = true;    // rho,u,v hold the last step's fields (false: to be rebuilt from the populations, ensure_macro)
@@ -129,7 +136,7 @@ int fail(int code, const char *fmt, ...);       // records the message lb_last_e
     } while (0)
 
 // Scalar lattices (LB_SEM_DIFFUSION, and the fields of a coupled set: LB_SEM_MULTIFIELD) are whole-grid handles without obstacles: what only slabs, masks or the flow kernels' tuning mean refuses.
-// So is the porous-medium fluid (LB_SEM_POROUS), which is refused here under its own name.
+// So are the porous-medium fluid (LB_SEM_POROUS) and the fluids of a multicomponent set (LB_SEM_MULTIFLUID), which are refused here under their own names.
 #define SCALAR_UNSUPPORTED(s, name)                                                                         \
     do {                                                                                                    \
         if ((s) && (s)->scalar()) return fail(LB_ERR_STATE, "%s is not available on a scalar lattice (LB_SEM_DIFFUSION)", name); \
@@ -138,6 +145,7 @@ int fail(int code, const char *fmt, ...);       // records the message lb_last_e
 #define NOT_POROUS(s, name)                                                                                 \
     do {                                                                                                    \
         if ((s) && (s)->porous()) return fail(LB_ERR_STATE, "%s is not available on a porous-medium fluid (LB_SEM_POROUS)", name); \
+        if ((s) && (s)->multifluid()) return fail(LB_ERR_STATE, "%s is not available on a fluid of a multicomponent set (LB_SEM_MULTIFLUID)", name); \
     } while (0)
 
 // ---- transport.cpp: RCCL, loaded lazily so that single-GPU use never touches librccl ---------------------------------------------

@@ -302,7 +302,7 @@ int lb_create(const lb_params *p, lb_sim **out)
     if (p->local_ny < 1 || p->y0 < 0 || p->y0 + p->local_ny > p->ny)
         return fail(LB_ERR_ARG, "slab [%d,%d) outside 0..%d", p->y0, p->y0 + p->local_ny, p->ny);
     if (p->bc_mode < LB_BC_PIPE || p->bc_mode > LB_BC_ZERO_GRADIENT) return fail(LB_ERR_ARG, "unknown bc_mode %d", p->bc_mode);
-    if (p->bc_mode == LB_BC_ZERO_GRADIENT && p->semantics != LB_SEM_POROUS)
+    if (p->bc_mode == LB_BC_ZERO_GRADIENT && p->semantics != LB_SEM_POROUS && p->semantics != LB_SEM_MULTIFLUID)
         return fail(LB_ERR_ARG, "LB_BC_ZERO_GRADIENT exists for forced flow in a porous medium (LB_SEM_POROUS) only: unknown bc_mode %d for semantics %d", p->bc_mode, p->semantics);
     if (p->bc_mode == LB_BC_DIRICHLET && p->semantics != LB_SEM_POISSON)
         return fail(LB_ERR_ARG, "LB_BC_DIRICHLET exists for the LB Poisson solver (LB_SEM_POISSON) only: unknown bc_mode %d for semantics %d", p->bc_mode, p->semantics);
@@ -323,6 +323,16 @@ int lb_create(const lb_params *p, lb_sim **out)
         if (p->local_ny != p->ny || p->y0 != 0) return fail(LB_ERR_ARG, "forced flow in a porous medium (LB_SEM_POROUS) owns its whole grid: no slabs");
         if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "forced flow in a porous medium (LB_SEM_POROUS) has no halo interface (LB_FLAG_HALO)");
         if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "forced flow in a porous medium (LB_SEM_POROUS) runs on a GPU only (no CPU backend)");
+    }
+    if (p->semantics == LB_SEM_MULTIFLUID) {
+        // a fluid of a multicomponent set: a whole-grid GPU handle without obstacles, refused likewise
+        if (p->bc_mode != LB_BC_PERIODIC && p->bc_mode != LB_BC_ZERO_GRADIENT)
+            return fail(LB_ERR_ARG, "a fluid of a multicomponent set (LB_SEM_MULTIFLUID) takes the families LB_BC_PERIODIC and LB_BC_ZERO_GRADIENT only");
+        if (p->nx < 3 || p->ny < 3)
+            return fail(LB_ERR_ARG, "a fluid of a multicomponent set (LB_SEM_MULTIFLUID) needs a cell with eight neighbours: grid must be at least 3x3 (got %dx%d)", p->nx, p->ny);
+        if (p->local_ny != p->ny || p->y0 != 0) return fail(LB_ERR_ARG, "a fluid of a multicomponent set (LB_SEM_MULTIFLUID) owns its whole grid: no slabs");
+        if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "a fluid of a multicomponent set (LB_SEM_MULTIFLUID) has no halo interface (LB_FLAG_HALO)");
+        if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "a fluid of a multicomponent set (LB_SEM_MULTIFLUID) runs on a GPU only (no CPU backend)");
     }
     if (p->bc_mode == LB_BC_OPEN && p->semantics != LB_SEM_DIFFUSION)
         return fail(LB_ERR_ARG, "LB_BC_OPEN exists for scalar lattices (LB_SEM_DIFFUSION) only");
@@ -354,7 +364,7 @@ int lb_create(const lb_params *p, lb_sim **out)
         if (r != 0) return fail(LB_ERR_ARG, "reserved fields must be zero");
     if (p->flags & ~(LB_FLAG_HALO | LB_FLAG_PLANAR | LB_FLAG_EAGER_MACRO)) return fail(LB_ERR_ARG, "unknown flags 0x%x", p->flags);
     if (p->semantics != LB_SEM_OPENCL && p->semantics != LB_SEM_CYTHON && p->semantics != LB_SEM_OPENCL_D2Q9I && p->semantics != LB_SEM_DIFFUSION &&
-        p->semantics != LB_SEM_MULTIFIELD && p->semantics != LB_SEM_POISSON && p->semantics != LB_SEM_POROUS)
+        p->semantics != LB_SEM_MULTIFIELD && p->semantics != LB_SEM_POISSON && p->semantics != LB_SEM_POROUS && p->semantics != LB_SEM_MULTIFLUID)
         return fail(LB_ERR_ARG, "unknown semantics %d", p->semantics);
     if (p->semantics == LB_SEM_OPENCL_D2Q9I &&
         (p->bc_mode != LB_BC_PIPE || p->local_ny != p->ny || (p->flags & LB_FLAG_HALO)))
@@ -467,7 +477,7 @@ int lb_create(const lb_params *p, lb_sim **out)
         CREATE_TRY(hipMemcpy(s->ps_state, &fresh, sizeof(fresh), hipMemcpyHostToDevice));
         s->bytes += fld_bytes + part_bytes + sizeof(PsState);
     }
-    if (s->porous()) {
+    if (s->porous() || s->multifluid()) {
         s->diag = 0;                                // (the diagnostic word of the flow kernels means nothing here)
         for (float **q : {&s->pm_G[0], &s->pm_G[1], &s->pm_ub[0], &s->pm_ub[1]}) {
             CREATE_TRY(hipMalloc(q, fld_bytes));
@@ -582,6 +592,8 @@ int lb_set_variant(lb_sim *s, int variant)
         return fail(LB_ERR_STATE, "the LB Poisson solver (LB_SEM_POISSON) takes the variants -1 and 0 only: k_ps_step, no tiles");
     if (s->porous() && variant != -1 && variant != 0)
         return fail(LB_ERR_STATE, "lb_set_variant: a porous-medium fluid (LB_SEM_POROUS) takes the variants -1 and 0 only: k_pm_step, no tiles");
+    if (s->multifluid() && (variant < -1 || variant > 1))
+        return fail(LB_ERR_STATE, "lb_set_variant: a fluid of a multicomponent set (LB_SEM_MULTIFLUID) takes the variants -1 (the planner's choice), 0 (the two-launch step k_mc_moments + k_mc_collide) and 1 (the one-launch step k_mc_step) only");
     s->variant = variant;
     return LB_OK;
 }
@@ -1110,7 +1122,15 @@ int lb_gradient(lb_sim *s, float inv_two_dx, float *ddx, float *ddy)
 #define NEED_POROUS(s, name)                                                                                 \
     do {                                                                                                     \
         if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
+        if ((s)->multifluid()) return fail(LB_ERR_STATE, "%s is not available on a fluid of a multicomponent set (LB_SEM_MULTIFLUID)", name); \
         if (!(s)->porous()) return fail(LB_ERR_STATE, "%s is for forced flow in a porous medium (LB_SEM_POROUS)", name); \
+    } while (0)
+// (the calls a fluid of a multicomponent set shares with the porous-medium fluid: its g, its force field, G and u_b)
+#define NEED_FORCED(s, name)                                                                                 \
+    do {                                                                                                     \
+        if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
+        if (!(s)->porous() && !(s)->multifluid())                                                            \
+            return fail(LB_ERR_STATE, "%s is for forced flow in a porous medium (LB_SEM_POROUS) and the fluids of a multicomponent set (LB_SEM_MULTIFLUID)", name); \
     } while (0)
 
 static bool pm_finite(float x) { return fabsf(x) <= 3.0e38f; }      // (false for NaN)
@@ -1127,7 +1147,7 @@ int lb_set_porous(lb_sim *s, float epsilon, float nu_fluid, float K, float Fe)
 
 int lb_set_body_force(lb_sim *s, float gx, float gy)
 {
-    NEED_POROUS(s, "lb_set_body_force");
+    NEED_FORCED(s, "lb_set_body_force");
     if (!pm_finite(gx) || !pm_finite(gy)) return fail(LB_ERR_ARG, "the body force must be finite");
     s->pm_gx = gx; s->pm_gy = gy;
     return LB_OK;
@@ -1135,7 +1155,7 @@ int lb_set_body_force(lb_sim *s, float gx, float gy)
 
 int lb_set_force_field(lb_sim *s, const float *gx, const float *gy, int on_device)
 {
-    NEED_POROUS(s, "lb_set_force_field");
+    NEED_FORCED(s, "lb_set_force_field");
     if ((gx == nullptr) != (gy == nullptr)) return fail(LB_ERR_ARG, "both planes of the force field, or neither");
     DeviceGuard guard(s->p.device);
     HIP_TRY(hipStreamSynchronize(s->stream));       // (kernels of an un-waited run may still be reading it)
@@ -1178,19 +1198,19 @@ static int pm_get_pair(lb_sim *s, float *const (&pair)[2], float *a, float *b)
 
 int lb_get_force(lb_sim *s, float *Gx, float *Gy)
 {
-    NEED_POROUS(s, "lb_get_force");
+    NEED_FORCED(s, "lb_get_force");
     return pm_get_pair(s, s->pm_G, Gx, Gy);
 }
 
 int lb_get_bary_velocity(lb_sim *s, float *u_bary, float *v_bary)
 {
-    NEED_POROUS(s, "lb_get_bary_velocity");
+    NEED_FORCED(s, "lb_get_bary_velocity");
     return pm_get_pair(s, s->pm_ub, u_bary, v_bary);
 }
 
 int lb_set_bary_velocity(lb_sim *s, const float *u_bary, const float *v_bary)
 {
-    NEED_POROUS(s, "lb_set_bary_velocity");
+    NEED_FORCED(s, "lb_set_bary_velocity");
     if (!u_bary || !v_bary) return fail(LB_ERR_ARG, "null argument");
     DeviceGuard guard(s->p.device);
     int rc;
@@ -1204,7 +1224,7 @@ int lb_set_bary_velocity(lb_sim *s, const float *u_bary, const float *v_bary)
 // (checkpoints: the total force as the last step left it)
 int lb_set_force(lb_sim *s, const float *Gx, const float *Gy)
 {
-    NEED_POROUS(s, "lb_set_force");
+    NEED_FORCED(s, "lb_set_force");
     if (!Gx || !Gy) return fail(LB_ERR_ARG, "null argument");
     DeviceGuard guard(s->p.device);
     int rc;
@@ -1216,7 +1236,8 @@ int lb_set_force(lb_sim *s, const float *Gx, const float *Gy)
 
 int lb_update_forces(lb_sim *s)
 {
-    NEED_POROUS(s, "lb_update_forces");
+    NEED_FORCED(s, "lb_update_forces");
+    if (s->multifluid()) return lb_update_forces_fluids(&s, 1);
     DeviceGuard guard(s->p.device);
     lbk_pm_forces(s->stream, step_args(s, 0, 1, s->H), pm_extra(s));
     HIP_TRY(hipGetLastError());
@@ -1225,7 +1246,8 @@ int lb_update_forces(lb_sim *s)
 
 int lb_update_bary_velocity(lb_sim *s)
 {
-    NEED_POROUS(s, "lb_update_bary_velocity");
+    NEED_FORCED(s, "lb_update_bary_velocity");
+    if (s->multifluid()) return lb_update_bary_fluids(&s, 1);
     DeviceGuard guard(s->p.device);
     lbk_pm_bary(s->stream, step_args(s, 0, 1, s->H), pm_extra(s), s->origin(s->cur));
     HIP_TRY(hipGetLastError());
@@ -1268,9 +1290,9 @@ int lb_move_bcs(lb_sim *s)
     int rc = need_single_slab(s, "lb_move_bcs");
     if (rc) return rc;
     if (s->scalar() && s->p.bc_mode != LB_BC_BOX && !s->poisson()) return LB_OK;     // (diffusion.py:326-331: `pass`; the periodic families have none)
-    if (s->porous() && s->p.bc_mode == LB_BC_PERIODIC) return LB_OK;                 // (single_component.py:155-156: `pass`)
+    if ((s->porous() || s->multifluid()) && s->p.bc_mode == LB_BC_PERIODIC) return LB_OK;                 // (single_component.py:155-156: `pass`)
     DeviceGuard guard(s->p.device);
-    if (s->porous()) {                              // single_component.cl's move_open_bcs: boundary cells copy their interior neighbour
+    if (s->porous() || s->multifluid()) {           // single_component.cl's and multi.cl's move_open_bcs: boundary cells copy their interior neighbour
         lbk_pm_move_bcs(s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur));
         HIP_TRY(hipGetLastError());
         return LB_OK;
@@ -1305,7 +1327,9 @@ int lb_update_hydro(lb_sim *s)
     int rc = need_single_slab(s, "lb_update_hydro");
     if (rc) return rc;
     DeviceGuard guard(s->p.device);
-    if (s->porous())
+    if (s->multifluid())
+        lbk_mc_hydro(s->stream, step_args(s, 0, 1, s->H));       // rho, and u, v where rho > 1e-12
+    else if (s->porous())
         lbk_pm_hydro(s->stream, step_args(s, 0, 1, s->H));       // rho, and u, v where rho > 1e-6
     else if (s->poisson())
         lbk_ps_hydro(s->stream, step_args(s, 0, 1, s->H));       // rho = (9/5)(f1 + ... + f8)
@@ -1337,8 +1361,8 @@ int lb_update_feq(lb_sim *s)
     if ((rc = ensure_macro(s))) return rc;
     PhaseArgs a = phase_args(s);
     a.ny = s->H;   // rho,u,v are local: valid for slabs too
-    if (s->porous())
-        lbk_pm_feq(s->stream, step_args(s, 0, 1, s->H), pm_extra(s), s->feq_origin());      // from rho and u_b
+    if (s->porous() || s->multifluid())
+        lbk_pm_feq(s->stream, step_args(s, 0, 1, s->H), pm_extra(s), s->feq_origin());      // from rho and u_b (a fluid of a multicomponent set: epsilon = 1)
     else if (s->poisson())
         lbk_ps_feq(s->stream, step_args(s, 0, 1, s->H), s->feq_origin());
     else if (s->scalar())
@@ -1362,7 +1386,9 @@ int lb_collide_particles(lb_sim *s)
     if (s->multifield()) return lb_collide_coupled(&s, 1);
     DeviceGuard guard(s->p.device);
     if ((rc = ensure_macro(s))) return rc;
-    if (s->porous())
+    if (s->multifluid())
+        lbk_mc_relax(s->stream, step_args(s, 0, 1, s->H), pm_extra(s), s->origin(s->cur), s->feq_origin());
+    else if (s->porous())
         lbk_pm_collide(s->stream, step_args(s, 0, 1, s->H), pm_extra(s), s->origin(s->cur), s->feq_origin());
     else if (s->poisson())
         lbk_ps_collide(s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur), s->feq_origin(), s->ps_source, s->ps_react);
@@ -1426,6 +1452,7 @@ int lb_run(lb_sim *s, int n_steps)
     if (s->multifield()) return lb_run_coupled(&s, 1, n_steps);
     if (s->poisson()) return run_poisson(s, n_steps);
     if (s->porous()) return run_porous(s, n_steps);
+    if (s->multifluid()) return lb_run_fluids(&s, 1, n_steps);
     if (s->scalar()) return run_scalar(s, n_steps);
     if (!s->tune_cache_checked) (void)tune_cache_apply(s);
     if (s->p.semantics == LB_SEM_CYTHON) return run_cython(s, n_steps);
@@ -1565,6 +1592,183 @@ int lb_collide_coupled(lb_sim **fields, int count)
     lbk_mf_collide(count, s0->stream, m);
     HIP_TRY(hipGetLastError());
     return coupled_release(fields, count);
+}
+
+// ---- multicomponent Shan-Chen fluids: the members of a set, checked alike for every set call ---------------------------------
+static int fluid_members(lb_sim **f, int count, const char *what)
+{
+    if (!f) return fail(LB_ERR_ARG, "%s: null handle array", what);
+    if (count < 1 || count > MC_MAX) return fail(LB_ERR_ARG, "%s takes 1..%d handles (more than %d fluids are not built)", what, MC_MAX, MC_MAX);
+    for (int i = 0; i < count; ++i) {
+        lb_sim *s = f[i];
+        if (!s) return fail(LB_ERR_ARG, "null handle in the set of fluids");
+        if (s->cpu || !s->multifluid()) return fail(LB_ERR_STATE, "%s is for the fluids of a multicomponent set (LB_SEM_MULTIFLUID)", what);
+        if (s->p.nx != f[0]->p.nx || s->p.ny != f[0]->p.ny || s->p.bc_mode != f[0]->p.bc_mode || s->p.device != f[0]->p.device ||
+            (s->p.flags & LB_FLAG_PLANAR) != (f[0]->p.flags & LB_FLAG_PLANAR))
+            return fail(LB_ERR_ARG, "the fluids of a set must share grid, boundary family, layout flag and device (fluids of different families in one set are not built)");
+        for (int j = 0; j < i; ++j)
+            if (f[j] == s) return fail(LB_ERR_ARG, "a handle appears twice in the set of fluids");
+    }
+    // the tables name fluids by their place in the set
+    for (int t = 0; t < f[0]->mc_n_inter; ++t)
+        if (f[0]->mc_inter[t].i >= count || f[0]->mc_inter[t].j >= count)
+            return fail(LB_ERR_STATE, "%s: the interaction table of the first handle names fluid %d of a set of %d", what,
+                        f[0]->mc_inter[t].i > f[0]->mc_inter[t].j ? f[0]->mc_inter[t].i : f[0]->mc_inter[t].j, count);
+    for (int t = 0; t < f[0]->mc_n_react; ++t)
+        if (f[0]->mc_react[t].a >= count || f[0]->mc_react[t].b >= count)
+            return fail(LB_ERR_STATE, "%s: the reaction table of the first handle names a fluid outside a set of %d", what, count);
+    return LB_OK;
+}
+
+// (src = dst = the current lattice: what the phases read and write in place; the two-launch step sets dst itself)
+static McArgs fluid_args(lb_sim **f, int count)
+{
+    McArgs m = {};
+    for (int i = 0; i < count; ++i) {
+        m.a[i] = step_args(f[i], 0, 1, f[i]->H);
+        m.e[i] = pm_extra(f[i]);
+    }
+    for (int t = 0; t < f[0]->mc_n_inter; ++t) m.inter[t] = f[0]->mc_inter[t];
+    for (int t = 0; t < f[0]->mc_n_react; ++t) m.react[t] = f[0]->mc_react[t];
+    m.n_inter = f[0]->mc_n_inter;
+    m.n_react = f[0]->mc_n_react;
+    return m;
+}
+
+int lb_run_fluids(lb_sim **fluids, int count, int n_steps)
+{
+    int rc = fluid_members(fluids, count, "lb_run_fluids");
+    if (rc) return rc;
+    if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
+    if (n_steps == 0) return LB_OK;
+    lb_sim *s0 = fluids[0];
+    DeviceGuard guard(s0->p.device);
+    if ((rc = coupled_join(fluids, count))) return rc;
+    for (int it = 0; it < n_steps; ++it) {
+        const McArgs m = fluid_args(fluids, count);
+        if (multifluid_one_launch(s0)) {            // (the set's first handle chooses: lb_set_variant; plan.cpp)
+            lbk_mc_step(s0->p.bc_mode, count, it == n_steps - 1, s0->stream, m);        // the last one stores rho, u, v, G and u_b
+            HIP_TRY(hipGetLastError());
+        } else {
+            lbk_mc_moments(s0->p.bc_mode, count, s0->stream, m);
+            HIP_TRY(hipGetLastError());
+            lbk_mc_collide(s0->p.bc_mode, count, it == n_steps - 1, s0->stream, m);     // the last one stores u, v, G and u_b
+            HIP_TRY(hipGetLastError());
+        }
+        for (int i = 0; i < count; ++i) fluids[i]->cur ^= 1;
+    }
+    for (int i = 0; i < count; ++i) {
+        fluids[i]->feq_valid = false;
+        fluids[i]->macro_valid = true;
+    }
+    return coupled_release(fluids, count);
+}
+
+static bool mc_finite(float x) { return fabsf(x) <= 3.0e38f; }      // (false for NaN)
+
+int lb_set_interactions(lb_sim **fluids, int count, const lb_interaction *table, int n)
+{
+    int rc = fluid_members(fluids, count, "lb_set_interactions");
+    if (rc) return rc;
+    if (n < 0 || n > MC_MAX_INTER || (n > 0 && !table)) return fail(LB_ERR_ARG, "lb_set_interactions takes 0..%d entries", MC_MAX_INTER);
+    McInter in[MC_MAX_INTER] = {};
+    for (int t = 0; t < n; ++t) {
+        const lb_interaction &e = table[t];
+        if (e.fluid_1 < 0 || e.fluid_1 >= count || e.fluid_2 < 0 || e.fluid_2 >= count)
+            return fail(LB_ERR_ARG, "interaction %d names fluids %d and %d of a set of %d", t, e.fluid_1, e.fluid_2, count);
+        if (e.potential != LB_PSI_LINEAR && e.potential != LB_PSI_SHAN_CHEN && e.potential != LB_PSI_POW)
+            return fail(LB_ERR_ARG, "interaction %d: unknown potential %d (linear, shan_chen and pow are built; vdw is not)", t, e.potential);
+        if (e.boundary != (fluids[0]->p.bc_mode == LB_BC_PERIODIC ? 0 : 1))
+            return fail(LB_ERR_ARG, "interaction %d: the stencil's boundary rule (%d) must be the set's family (%s)", t, e.boundary,
+                        fluids[0]->p.bc_mode == LB_BC_PERIODIC ? "0, periodic" : "1, zero gradient");
+        if (!mc_finite(e.G_int) || !mc_finite(e.parameter)) return fail(LB_ERR_ARG, "interaction %d: G_int and the parameter must be finite", t);
+        if (e.potential == LB_PSI_SHAN_CHEN && e.parameter == 0.f) return fail(LB_ERR_ARG, "interaction %d: shan_chen needs rho_0 != 0", t);
+        in[t] = McInter{e.fluid_1, e.fluid_2, e.potential, e.G_int, e.parameter};
+    }
+    for (int t = 0; t < MC_MAX_INTER; ++t) fluids[0]->mc_inter[t] = in[t];
+    fluids[0]->mc_n_inter = n;
+    return LB_OK;
+}
+
+int lb_set_reactions(lb_sim **fluids, int count, const lb_fluid_reaction *table, int n)
+{
+    int rc = fluid_members(fluids, count, "lb_set_reactions");
+    if (rc) return rc;
+    if (n < 0 || n > MC_MAX_REACT || (n > 0 && !table)) return fail(LB_ERR_ARG, "lb_set_reactions takes 0..%d entries", MC_MAX_REACT);
+    McReact re[MC_MAX_REACT] = {};
+    for (int t = 0; t < n; ++t) {
+        const lb_fluid_reaction &e = table[t];
+        if (e.kind != LB_REACT_EAT && e.kind != LB_REACT_GROW) return fail(LB_ERR_ARG, "reaction %d: unknown kind %d", t, e.kind);
+        if (e.fluid_a < 0 || e.fluid_a >= count) return fail(LB_ERR_ARG, "reaction %d names fluid %d of a set of %d", t, e.fluid_a, count);
+        if (e.kind == LB_REACT_EAT && (e.fluid_b < 0 || e.fluid_b >= count || e.fluid_b == e.fluid_a))
+            return fail(LB_ERR_ARG, "reaction %d: the eatee must be another fluid of the set (got %d, eater %d)", t, e.fluid_b, e.fluid_a);
+        if (!mc_finite(e.p0) || !mc_finite(e.p1) || !mc_finite(e.p2)) return fail(LB_ERR_ARG, "reaction %d: the parameters must be finite", t);
+        re[t] = McReact{e.kind, e.fluid_a, e.kind == LB_REACT_EAT ? e.fluid_b : 0, e.p0, e.p1, e.p2};
+    }
+    for (int t = 0; t < MC_MAX_REACT; ++t) fluids[0]->mc_react[t] = re[t];
+    fluids[0]->mc_n_react = n;
+    return LB_OK;
+}
+
+int lb_get_interactions(lb_sim *first, lb_interaction *table, int *n)
+{
+    if (!first) return fail(LB_ERR_ARG, "null handle");
+    if (first->cpu || !first->multifluid()) return fail(LB_ERR_STATE, "lb_get_interactions is for the fluids of a multicomponent set (LB_SEM_MULTIFLUID)");
+    if (n) *n = first->mc_n_inter;
+    for (int t = 0; table && t < first->mc_n_inter; ++t) {
+        const McInter &e = first->mc_inter[t];
+        table[t] = lb_interaction{e.i, e.j, e.potential, first->p.bc_mode == LB_BC_PERIODIC ? 0 : 1, e.G, e.par};
+    }
+    return LB_OK;
+}
+
+int lb_get_reactions(lb_sim *first, lb_fluid_reaction *table, int *n)
+{
+    if (!first) return fail(LB_ERR_ARG, "null handle");
+    if (first->cpu || !first->multifluid()) return fail(LB_ERR_STATE, "lb_get_reactions is for the fluids of a multicomponent set (LB_SEM_MULTIFLUID)");
+    if (n) *n = first->mc_n_react;
+    for (int t = 0; table && t < first->mc_n_react; ++t) {
+        const McReact &e = first->mc_react[t];
+        table[t] = lb_fluid_reaction{e.kind, e.a, e.b, e.p0, e.p1, e.p2};
+    }
+    return LB_OK;
+}
+
+int lb_update_forces_fluids(lb_sim **fluids, int count)
+{
+    int rc = fluid_members(fluids, count, "lb_update_forces_fluids");
+    if (rc) return rc;
+    DeviceGuard guard(fluids[0]->p.device);
+    if ((rc = coupled_join(fluids, count))) return rc;
+    lbk_mc_forces(fluids[0]->p.bc_mode, count, fluids[0]->stream, fluid_args(fluids, count));
+    HIP_TRY(hipGetLastError());
+    return coupled_release(fluids, count);
+}
+
+int lb_update_bary_fluids(lb_sim **fluids, int count)
+{
+    int rc = fluid_members(fluids, count, "lb_update_bary_fluids");
+    if (rc) return rc;
+    DeviceGuard guard(fluids[0]->p.device);
+    if ((rc = coupled_join(fluids, count))) return rc;
+    lbk_mc_bary(count, fluids[0]->stream, fluid_args(fluids, count));
+    HIP_TRY(hipGetLastError());
+    for (int i = 0; i < count; ++i) fluids[i]->feq_valid = false;
+    return coupled_release(fluids, count);
+}
+
+int lb_react_fluids(lb_sim **fluids, int count)
+{
+    int rc = fluid_members(fluids, count, "lb_react_fluids");
+    if (rc) return rc;
+    if (fluids[0]->mc_n_react == 0) return LB_OK;
+    DeviceGuard guard(fluids[0]->p.device);
+    if ((rc = coupled_join(fluids, count))) return rc;
+    McArgs m = fluid_args(fluids, count);
+    for (int i = 0; i < count; ++i) m.a[i].dst = fluids[i]->origin(fluids[i]->cur);       // in place
+    lbk_mc_react(count, fluids[0]->stream, m);
+    HIP_TRY(hipGetLastError());
+    return coupled_release(fluids, count);
 }
 
 // ---- health check ------------------------------------------------------------------------

@@ -479,9 +479,14 @@ bool tune_entry_runs_here(const PlanInputs *s, int steps, int wpc)
 // The shape by size as for k_tile4 (tile_shape_of) is the sweep's best one at 256^2 (16 x 16), 512^2 (32 x 16, one cell per thread) and
 // from 2048^2 (two per thread); at 1024^2 it is the periodic family's best and 5 % behind the other 32 x 16 shape in the OPEN family.
 static const double SCALAR_TILE_MIN_CELLS = 256.0 * 256.0, SCALAR_TILE_MAX_CELLS = 8192.0 * 8192.0;
+// Multicomponent Shan-Chen fluids: variant 0 = the two-launch step, 1 = the one-launch step.  The planner's choice (-1) is the
+// one-launch step at every size: on one MI355X it is 1.00-1.21 x the two-launch step at 256^2 ... 8192^2 with one, two and three
+// fluids, but for 0.97 x at 1024^2 with two (profiles/multifluid_bench.txt, tools/multifluid_bench.py) -- no size rule to draw from that.
+bool multifluid_one_launch(const PlanInputs *s) { return s->variant != 0; }
+
 bool scalar_use_tiles(const PlanInputs *s)
 {
-    if (s->multifield() || s->poisson() || s->porous()) return false;      // (no tiles for coupled sets, the Poisson solver and the porous-medium fluid: k_mf_step / k_ps_step / k_pm_step, one step per launch)
+    if (s->multifield() || s->poisson() || s->porous() || s->multifluid()) return false;      // (no tiles for coupled sets, the Poisson solver and the porous-medium fluid: k_mf_step / k_ps_step / k_pm_step, one step per launch)
     if (s->variant >= 0) return (s->variant & LB_VAR_TILES) != 0;
     const double cells = (double)s->p.nx * s->H;
     return cells >= SCALAR_TILE_MIN_CELLS && cells <= SCALAR_TILE_MAX_CELLS;
@@ -503,7 +508,7 @@ int scalar_next_advance(const PlanInputs *s, int left)
 
 int plan_launches(const PlanInputs *s, int n_steps, int *depths, int max_launches)
 {
-    if (s->scalar() || s->porous()) {
+    if (s->scalar() || s->porous() || s->multifluid()) {
         int n = 0;
         for (int left = n_steps; left > 0; ++n) {
             const int adv = scalar_next_advance(s, left);
@@ -524,7 +529,7 @@ int plan_launches(const PlanInputs *s, int n_steps, int *depths, int max_launche
 
 int steps_per_launch(const PlanInputs *s)
 {
-    if (s->scalar() || s->porous()) return scalar_use_tiles(s) ? TILE_T : 1;
+    if (s->scalar() || s->porous() || s->multifluid()) return scalar_use_tiles(s) ? TILE_T : 1;
     if (s->p.semantics == LB_SEM_CYTHON) return cython_tiles(s) ? TILE_T : 1;
     const int h = s->agreed_h();
     if (s->multi_slab() && cycle_depth(s, h)) return cycle_depth(s, h);
@@ -538,6 +543,16 @@ int steps_per_launch(const PlanInputs *s)
 void hot_kernel(const PlanInputs *s, char *buf, int buflen)
 {
     static const char *const bc_names[] = {"PIPE", "PERIODIC", "CAVITY", "VELOCITY_INLET", "PIPE, D2Q9i"};
+    if (s->multifluid()) {
+        if (multifluid_one_launch(s)) {
+            snprintf(buf, (size_t)buflen, "k_mc_step (multicomponent Shan-Chen fluids: one launch per step -- pull-stream + densities of the owned rows and their halo into LDS, barrier, interaction forces + barycentric velocity + Guo-forced collide + reactions)<%s%s>",
+                     s->p.bc_mode == LB_BC_PERIODIC ? "PERIODIC" : "ZERO_GRADIENT", s->has_field ? ", FIELD" : "");
+            return;
+        }
+        snprintf(buf, (size_t)buflen, "k_mc_moments + k_mc_collide (multicomponent Shan-Chen fluids: two launches per step -- pull-stream + densities, then pull-stream + interaction forces + barycentric velocity + Guo-forced collide + reactions)<%s%s>",
+                 s->p.bc_mode == LB_BC_PERIODIC ? "PERIODIC" : "ZERO_GRADIENT", s->has_field ? ", FIELD" : "");
+        return;
+    }
     if (s->porous()) {
         snprintf(buf, (size_t)buflen, "k_pm_step (forced flow in a porous medium: one fused pull-stream + moments + drag and body force + Guo-forced collide pass)<%s%s>",
                  s->p.bc_mode == LB_BC_PERIODIC ? "PERIODIC" : "ZERO_GRADIENT", s->has_field ? ", FIELD" : "");

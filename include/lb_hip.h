@@ -120,7 +120,7 @@ typedef enum {
                                  sets a device-side stop word (k_ps_check), no host wait but one 4-byte read-back per batch of
                                  iterations: lb_solve, below.  u, v of such a handle are written by lb_gradient only.
                                  lb_set_variant takes -1 and 0 only. */
-    LB_SEM_POROUS = 7         /* (6 is not assigned: the suite holds lb_create to refusing semantics 6 in a periodic box as unknown,
+    LB_SEM_POROUS = 7,        /* (6 is not assigned: the suite holds lb_create to refusing semantics 6 in a periodic box as unknown,
                                  tests/test_poisson_cpu.py.)  FORCED FLOW IN A POROUS MEDIUM: LB_D2Q9/porous_media/single_component.cl driven as
                                  single_component.py's Simulation_Runner.run does with one fluid -- a D2Q9 BGK fluid with Guo forcing,
                                  a porosity epsilon in the equilibrium and in the forcing term, a linear drag (nu_fluid / K), a
@@ -131,6 +131,14 @@ typedef enum {
                                  field; the last launch of a run also stores rho, u, v, the total force and the barycentric
                                  velocity, + 28 B).  float32 like every lattice here (the reference's fork computes in
                                  float64).  lb_set_variant takes -1 and 0 only. */
+    LB_SEM_MULTIFLUID = 9     /* (8 is not assigned either: tests/test_porous_cpu.py holds lb_create to refusing semantics 8 in a
+                                 periodic box as unknown.)  MULTICOMPONENT SHAN-CHEN FLUIDS: LB_D2Q9/multicomponent_multiphase/multi.cl
+                                 driven as multi.py's Simulation_Runner.run does -- 1 ... 3 D2Q9 BGK fluids on one grid, one handle
+                                 each, relaxing towards an equilibrium at the barycentric velocity of all of them, with Guo forcing by
+                                 body forces and by pseudopotential interaction forces (a D2Q9 stencil over a function of the
+                                 neighbours' density: the step is not local to the cell), and with mass-exchange reactions; families
+                                 LB_BC_PERIODIC and LB_BC_ZERO_GRADIENT, nx, ny >= 3.  Whole-grid GPU handles without obstacles;
+                                 omega, nx, ny are the only lb_params fields read.  lb_run_fluids advances a set (below). */
 } lb_semantics;
 
 typedef struct {
@@ -314,6 +322,63 @@ int lb_set_bary_velocity(lb_sim *s, const float *u_bary, const float *v_bary);
 int lb_get_bary_velocity(lb_sim *s, float *u_bary, float *v_bary);
 int lb_update_forces(lb_sim *s);            /* stages 4 and 5 */
 int lb_update_bary_velocity(lb_sim *s);     /* stage 6 */
+
+/* ---- multicomponent Shan-Chen fluids (LB_SEM_MULTIFLUID; LB_ERR_STATE on every other handle) --------------------------------
+ * A SET is 1 ... 3 handles of one geometry, family, layout flag and device, advanced together; fluid i of a table is the i-th
+ * handle of the array a call is given.  One time step (multi.py:729-803):
+ *   1. per fluid: move_periodic / move + copy_streamed_onto_f, then move_open_bcs (LB_BC_ZERO_GRADIENT)     lb_move, lb_move_bcs
+ *   2. per fluid: update_hydro_fluid: rho = sum f; u, v = sum f c / rho if rho > 1e-12, else 0              lb_update_hydro
+ *      (u, v are stored and never read by the dynamics)
+ *   3. G_i := (g_i [+ the force field]) rho_i, then for every entry of the interaction table, in order,     lb_update_forces_fluids
+ *      with S_j(x) = sum_k w_k c_k psi(rho_j(x + c_k)): G_i -= G_int psi(rho_i) S_j, G_j -= G_int psi(rho_j) S_i.
+ *      The neighbour is the wrapped cell (LB_BC_PERIODIC) or the cell clamped to [0, n-1] (LB_BC_ZERO_GRADIENT).
+ *      G is a FORCE here (a force per density on a porous handle).  fluid_1 == fluid_2: both increments land on
+ *      the one fluid, a self-interaction acts with 2 G_int, as in the reference.
+ *   4. u_b = sum_i (sum_k f_ik c_k + G_i / 2) / sum_i rho_i (NaN where the total density is 0: not guarded)  lb_update_bary_fluids
+ *   5. per fluid: feq_k = w_k rho_i (1 + 3 c.u_b + 4.5 (c.u_b)^2 - 1.5 u_b^2)                                 lb_update_feq
+ *   6. per fluid: f_k (1 - omega_i) + omega_i feq_k + (1 - omega_i / 2) w_k (3 c.G_i + 9 (c.G_i)(c.u_b) - 3 u_b.G_i)   lb_collide_particles
+ *   7. the reaction table, in order, on the rho of stage 2:                                                  lb_react_fluids
+ *      LB_REACT_EAT   phi = (a - b) / (a + b); growth = rate a b where |phi| < cutoff, else 0; f_eater,k += w_k growth, f_eatee,k -= w_k growth
+ *      LB_REACT_GROW  f_k += w_k rate where min < rho < max
+ * lb_run_fluids(n) = n steps on one stream without a host wait, of ONE launch each (k_mc_step: a workgroup puts rho_i of its rows
+ * and their halo into LDS and runs stages 3-7 in registers) or of two (lb_set_variant(0): k_mc_moments stores every rho_i, k_mc_collide
+ * gathers again and reads rho around the cell); both bitwise equal to the stages called one by one.
+ * lb_run on such a handle is the set of one; so are lb_update_forces and lb_update_bary_velocity.  The tables are stored with the
+ * set's FIRST handle and read from there by every set call.  rho, u, v (lb_get_macro), G (lb_get_force) and u_b
+ * (lb_get_bary_velocity, the same on every member) are those of the last step, before its collision.
+ * lb_set_body_force: this fluid's acceleration g; lb_set_force_field: a position-dependent acceleration added to it; both are
+ * multiplied by rho in the kernel.  lb_get_force / lb_set_force / lb_set_bary_velocity / lb_get_bary_velocity as on a porous handle.
+ * lb_set_interactions: n <= 6 entries; potential LB_PSI_LINEAR (psi = rho), LB_PSI_SHAN_CHEN (psi = rho_0 (1 - exp(-rho / rho_0)),
+ *   parameter = rho_0 != 0), LB_PSI_POW (psi = rho^alpha, parameter = alpha); rho < 0 counts as 0.  boundary = the stencil's rule:
+ *   0 periodic, 1 zero gradient -- it must be the set's family (LB_ERR_ARG otherwise).  n = 0 clears the table.
+ * lb_set_reactions: n <= 4 entries; an eater must differ from its eatee.
+ * lb_set_variant on the set's first handle: -1 (the planner's choice: the one-launch step at every size, profiles/multifluid_bench.txt), 0 (the two-launch step),
+ *   1 (the one-launch step k_mc_step: a workgroup owns six rows -- three fluids: two -- of a 256-cell tile, puts rho_i of them, of
+ *   one halo row above and below and one halo cell left and right into LDS, and runs stages 3-7 after one barrier; bitwise the
+ *   same result).  lb_hot_kernel and lb_steps_per_launch report what runs.
+ * Masks, slabs and halo calls, lb_autotune*, lb_run_group / batch / coupled, lb_solve*, lb_set_reaction, lb_set_velocity_from,
+ * lb_check, the edge / corner state and lb_set_porous: LB_ERR_STATE naming LB_SEM_MULTIFLUID. */
+enum { LB_PSI_LINEAR = 0, LB_PSI_SHAN_CHEN = 1, LB_PSI_POW = 2 };
+enum { LB_REACT_EAT = 0, LB_REACT_GROW = 1 };
+typedef struct {
+    int32_t fluid_1, fluid_2;   /* indices into the set */
+    int32_t potential;          /* LB_PSI_* */
+    int32_t boundary;           /* 0 periodic, 1 zero gradient: the set's family */
+    float G_int, parameter;
+} lb_interaction;
+typedef struct {
+    int32_t kind;               /* LB_REACT_* */
+    int32_t fluid_a, fluid_b;   /* eat: eater, eatee; grow: the fluid, unused */
+    float p0, p1, p2;           /* eat: rate, cutoff, unused; grow: min, max, rate */
+} lb_fluid_reaction;
+int lb_run_fluids(lb_sim **fluids, int count, int n_steps);
+int lb_set_interactions(lb_sim **fluids, int count, const lb_interaction *table, int n);
+int lb_set_reactions(lb_sim **fluids, int count, const lb_fluid_reaction *table, int n);
+int lb_get_interactions(lb_sim *first, lb_interaction *table, int *n);      /* table: room for 6; either may be NULL */
+int lb_get_reactions(lb_sim *first, lb_fluid_reaction *table, int *n);      /* table: room for 4 */
+int lb_update_forces_fluids(lb_sim **fluids, int count);    /* stage 3 */
+int lb_update_bary_fluids(lb_sim **fluids, int count);      /* stage 4 */
+int lb_react_fluids(lb_sim **fluids, int count);            /* stage 7 */
 
 /* ---- the reference's per-phase methods, one kernel each (slow, un-fused;
  *      API and test parity).  Single-slab handles only. ------------------- */
