@@ -24,7 +24,8 @@ O2  LB_D2Q9/D2Q9.cl is OpenCL C and there is no OpenCL device or pyopencl in the
     -ffp-contract=off.  A real OpenCL device may contract a*b+c to FMA, so O2
     fixtures pin the arithmetic up to that freedom (tolerances in the tests).
 
-Usage:  python oracle/make_golden.py
+Usage:  python oracle/make_golden.py            (--only-<group>: that group's fixtures alone, e.g. --only-d2q9i,
+                                                 --only-boundary-densities)
 """
 import ctypes as ct
 import importlib
@@ -418,6 +419,65 @@ def gen_o2_d2q9i(L):
     save("o2_d2q9i_53x27", **out)
 
 
+BOUNDARY_DENSITIES = ((0.9337, 0.93), (1.0743, 1.07))     # (inlet_rho, outlet_rho); the fluid starts at the outlet's density
+
+
+def gen_o2_boundary_densities(L):
+    """outlet_rho != 1 and a fluid density != 1: every other O2 fixture has rout = 1.0, where `x / rout` and the products
+    with rout lose a rounding step and where a rule that read the wrong one of its two densities would compute the same.
+    State, mask and stale f_streamed of o2_kernels_37x19 (same seed, same draws), f0 scaled to the fluid density; one call each
+    of `move_bcs` and `update_hydro` on it, then the run.  Densities within 0.9 ... 1.1: w_k rho stays in w_k's binade."""
+    nx, ny, omega = 37, 19, 1.2
+    rng = np.random.default_rng(2015)
+    mask = disc(nx, ny, 12.0, 9.0, 4.0)
+    base = Wv[None, None, :] * (1 + 0.05 * rng.standard_normal((nx, ny, 9)))
+    fs0 = np.asfortranarray(rng.standard_normal((nx, ny, 9)).astype(np.float32))
+    out = {"nx": nx, "ny": ny, "omega": omega, "mask": mask, "fs0": fs0,
+           "inlet_rho": np.array([p[0] for p in BOUNDARY_DENSITIES]), "outlet_rho": np.array([p[1] for p in BOUNDARY_DENSITIES])}
+    for i, (rin, rout) in enumerate(BOUNDARY_DENSITIES):
+        f0 = np.asfortranarray((rout * base).astype(np.float32))
+        d = {"f0": f0}
+        s = RefOpenCL(L, nx, ny, omega, rin, rout, mask)
+        s.f[...] = f0; s.fs[...] = fs0
+        L.k_move_bcs(P(s.f), P(s.u), s.rin, s.rout, nx, ny)
+        d["after_bcs_f"] = s.f.copy(order="F")
+        s.f[...] = f0
+        s.update_hydro()
+        d["hydro_rho"], d["hydro_u"], d["hydro_v"] = s.rho.copy(order="F"), s.u.copy(order="F"), s.v.copy(order="F")
+        s.f[...] = f0; s.fs[...] = f0
+        done = 0
+        for n in (1, 10, 50):
+            s.run(n - done); done = n
+            d.update(flat("s%d" % n, s.snap()))
+        assert all(np.isfinite(v).all() for v in d.values())
+        assert np.abs(d["s50_u"]).max() < 0.1 and 0.85 < d["s50_rho"].min() and d["s50_rho"].max() < 1.15
+        out.update(flat("p%d" % i, d))
+    save("o2_offone_37x19", **out)
+
+
+def gen_o2_d2q9i_boundary_densities(L):
+    """The fork with outlet_rho != 1: fluid at 1 (a fluid density of 0.93 or 1.07 drives it to |u| ~ 0.4 in five steps and NaN
+    in ten), 0.1 % noise, omega 1.0; one `move_bcs` call, then 1 and 8 steps in the host order of gen_o2_d2q9i (NaN by 19)."""
+    nx, ny, omega, rin, rout = 37, 19, 1.0, 1.0002, 0.9998
+    rng = np.random.default_rng(2016)
+    mask = disc(nx, ny, 12.0, 9.0, 4.0)
+    f0 = np.asfortranarray((Wv[None, None, :] * (1 + 0.001 * rng.standard_normal((nx, ny, 9)))).astype(np.float32))
+    out = {"nx": nx, "ny": ny, "omega": omega, "inlet_rho": rin, "outlet_rho": rout, "mask": mask, "f0": f0}
+    s = RefOpenCL(L, nx, ny, omega, rin, rout, mask)
+    s.f[...] = f0; s.fs[...] = f0
+    L.k_move_bcs(P(s.f), P(s.u), s.rin, s.rout, nx, ny)
+    out["after_bcs_f"] = s.f.copy(order="F")
+    s.f[...] = f0; s.fs[...] = f0
+    done = 0
+    for n in (1, 8):
+        for _ in range(n - done):
+            s.move(); s.move_bcs(); s.update_hydro(); s.zero_vel(); s.update_feq(); s.collide()
+        done = n
+        out.update(flat("s%d" % n, s.snap()))
+    assert all(np.isfinite(v).all() for k, v in out.items() if k.startswith("s"))
+    save("o2_d2q9i_offone_37x19", **out)
+
+
 # --------------------------------------------------------------------------
 #  O1: cython_dim.pyx compiled and imported
 # --------------------------------------------------------------------------
@@ -624,16 +684,23 @@ def main():
         gen_o1_config1(build_o1(tmp))
         return
     L = build_o2(tmp)
+    if "--only-boundary-densities" in sys.argv:
+        gen_o2_boundary_densities(L)
+        gen_o2_d2q9i_boundary_densities(build_o2(tmp, "D2Q9i.cl"))
+        return
     if "--only-velocity-inlet" not in sys.argv and "--only-d2q9i" not in sys.argv:
         gen_o2(L)
         gen_o2_edge_mask(L)
+        gen_o2_boundary_densities(L)
     if "--only-d2q9i" not in sys.argv:
         gen_o2_velocity_inlet(L)
     if "--only-velocity-inlet" in sys.argv:
         return
-    gen_o2_d2q9i(build_o2(tmp, "D2Q9i.cl"))
+    Li = build_o2(tmp, "D2Q9i.cl")
+    gen_o2_d2q9i(Li)
     if "--only-d2q9i" in sys.argv:
         return
+    gen_o2_d2q9i_boundary_densities(Li)
     gen_move_periodic(tmp)
     m = build_o1(tmp)
     gen_o1(m)

@@ -87,6 +87,39 @@ def test_cpu_backend_cylinder_on_the_boundary_bit_exact(lbhip, name, edge):
         assert np.all(g["u"][d["mask"]] == 0) and np.all(g["v"][d["mask"]] == 0)
 
 
+@pytest.mark.parametrize("inlet_rho,outlet_rho", [(0.9337, 0.93), (1.0743, 1.07)])
+@pytest.mark.parametrize("nx,ny,masked", [(33, 17, False), (5, 4, False), (3, 3, False), (61, 41, True)])
+def test_cpu_backend_boundary_densities_off_one_vs_oracle(lbhip, oracle, inlet_rho, outlet_rho, nx, ny, masked):
+    """outlet_rho != 1 and a fluid at that density (the reference's classes always set outlet_rho = 1, and so do the fixtures
+    above): against the oracle's restatement of the Cython path, which those fixtures pin bit for bit.  The moment override
+    stores the outlet's density itself."""
+    from LB_D2Q9.simulation import Simulation
+    rng = np.random.default_rng(nx * 100 + ny)
+    w = np.array([4. / 9.] + [1. / 9.] * 4 + [1. / 36.] * 4)
+    # the fluid at rest at the outlet's density, perturbed as the reference's init_pop does: one draw per cell, 0.1 %
+    f0 = (outlet_rho * w[None, None, :] * (1 + 0.001 * rng.standard_normal((nx, ny, 1)))).astype(np.float32)
+    mask = None
+    if masked:
+        mask = rng.random((nx, ny)) < 0.05
+    # (omega 1.3: at 1.6 this path's plain bounce-back walls drive the 3 x 3 box to NaN within 50 steps, in the oracle as here)
+    sim = Simulation(nx, ny, 1.3, bc="pipe", inlet_rho=inlet_rho, outlet_rho=outlet_rho, obstacle_mask=mask,
+                     semantics="cython", device=-1)
+    ref = oracle.O1Sim(nx, ny, 1.3, inlet_rho, outlet_rho, mask=mask)
+    sim.set_f(f0)
+    ref.f[...] = f0.transpose(2, 0, 1)
+    done = 0
+    for n in (1, 5, 50):
+        sim.run(n - done); ref.run(n - done)
+        done = n
+        g = sim.get_fields()
+        got = dict(f=g["f"].transpose(2, 0, 1), feq=g["feq"].transpose(2, 0, 1), rho=g["rho"], u=g["u"], v=g["v"])
+        same_fields(got, ref.get_fields(), "")
+        assert np.all(g["rho"][-1, :] == np.float32(outlet_rho)) and np.all(g["rho"][0, :] == np.float32(inlet_rho))
+        print("step %d: max |u| %.3f, rho %.3f ... %.3f" % (n, np.abs(g["u"]).max(), g["rho"].min(), g["rho"].max()))
+        assert np.all(np.isfinite(g["f"])) and g["rho"].min() > 0.9 and g["rho"].max() < 1.1       # (w_k rho stays in w_k's binade)
+    sim.close()
+
+
 def test_config1_256_poiseuille_on_the_cpu_backend_without_a_gpu(lbhip):
     """BASELINE.json configs[0] -- 256 x 256 Poiseuille pipe flow on the CPU path, no GPU -- through the product: 1000 steps from
     f = feq against the imported reference's own run of that case (rows / columns / means stored in o1_config1_256; rho bit for

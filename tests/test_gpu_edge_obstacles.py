@@ -103,15 +103,17 @@ def edge_mask(rng, nx, ny, bc, solid_wall_rows=False):
     return m
 
 
-def make_pair(oracle, bc, nx, ny, omega, mask, f0, rng=None, planar=False):
+def make_pair(oracle, bc, nx, ny, omega, mask, f0, rng=None, planar=False, **extra):
     """An engine handle and the oracle on the same state; the velocity-inlet family also gets stored u, v (its inlet and
-    outlet columns take their moments from them)."""
+    outlet columns take their moments from them).  `extra` overrides KW for both (outlet_rho, rho0, semantics='d2q9i', ...)."""
     from LB_D2Q9.simulation import Simulation
-    sim = Simulation(nx, ny, omega, bc=bc, obstacle_mask=mask, planar=planar, **KW)
+    kw = dict(KW, **extra)
+    sim = Simulation(nx, ny, omega, bc=bc, obstacle_mask=mask, planar=planar, **kw)
     ref = None
     if oracle is not None:
         code = {"pipe": oracle.BC_PIPE, "cavity": oracle.BC_CAVITY, "velocity_inlet": oracle.BC_VELOCITY_INLET}[bc]
-        ref = oracle.O2Sim(nx, ny, omega, code, KW["inlet_rho"], 1., KW["lid_u"], 1., mask=mask, u_w=KW["inlet_u"], u_e=KW["outlet_u"])
+        ref = oracle.O2Sim(nx, ny, omega, code, kw["inlet_rho"], kw.get("outlet_rho", 1.), kw["lid_u"], kw.get("rho0", 1.), mask=mask,
+                           u_w=kw["inlet_u"], u_e=kw["outlet_u"], d2q9i=kw.get("semantics") == "d2q9i")
     if bc == "velocity_inlet":
         u0 = (UV0 * rng.standard_normal((nx, ny))).astype(np.float32)
         v0 = (UV0 * rng.standard_normal((nx, ny))).astype(np.float32)

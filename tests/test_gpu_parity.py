@@ -399,9 +399,28 @@ def test_tile_kernel_equals_single_step_kernel_small_grids(lbhip, bc, nx, ny, ma
 
 
 # ---- row slabs ---------------------------------------------------------------------------------------
-@pytest.mark.parametrize("bc", ["periodic", "pipe", "cavity"])
+# The walled families' slab tests also run with outlet_rho, rho0 and the fluid's density off 1 (the sets of
+# tests/test_gpu_boundary_densities.py: fluid density -> inlet_rho): a slab's edge-band kernels and halo lanes get their boundary
+# parameters through the same StepArgs as the whole grid's kernels, filled once more per slab.  Density 1 is the case these
+# tests always ran, under the test ids they always had.
+OFF_ONE_INLET = {0.93: 0.9337, 1.07: 1.0743}
+WALLED_DENSITIES = [pytest.param(bc, 1.0, id=bc) for bc in ("pipe", "cavity")] + \
+                   [pytest.param(bc, rho, id="%s-%s" % (bc, rho)) for bc in ("pipe", "cavity") for rho in sorted(OFF_ONE_INLET)]
+ALL_DENSITIES = [pytest.param("periodic", 1.0, id="periodic")] + WALLED_DENSITIES
+
+
+def _at_density(kw, f0, density):
+    """The handle's keywords and the state for a fluid of `density`: unchanged at 1; else inlet_rho from OFF_ONE_INLET,
+    outlet_rho = rho0 = density and the populations scaled to it."""
+    if density == 1.0:
+        return kw, f0
+    kw = dict(kw, inlet_rho=OFF_ONE_INLET[density], outlet_rho=density, rho0=density)
+    return kw, (density * f0.astype(np.float64)).astype(np.float32)
+
+
+@pytest.mark.parametrize("bc,density", ALL_DENSITIES)
 @pytest.mark.parametrize("nslabs", [2, 3])
-def test_virtual_slabs_equal_single_slab_bitwise(lbhip, bc, nslabs):
+def test_virtual_slabs_equal_single_slab_bitwise(lbhip, bc, density, nslabs):
     """G row slabs on one device, halos moved with lb_halo_export/import, must equal the
     one-slab run bit for bit (same arithmetic, different partition)."""
     from LB_D2Q9.simulation import Simulation
@@ -411,7 +430,7 @@ def test_virtual_slabs_equal_single_slab_bitwise(lbhip, bc, nslabs):
     f0 = _random_state(rng, nx, ny)
     mask = rng.random((nx, ny)) < 0.04
     mask[:, 0] = mask[:, -1] = False
-    kw = dict(inlet_rho=1.01, lid_u=0.05)
+    kw, f0 = _at_density(dict(inlet_rho=1.01, lid_u=0.05), f0, density)
     one = Simulation(nx, ny, 1.5, bc=bc, obstacle_mask=mask, **kw)
     one.set_f(f0)
     ring = LocalSlabRing(nx, ny, 1.5, nslabs, bc=bc, obstacle_mask=mask, **kw)
@@ -423,9 +442,9 @@ def test_virtual_slabs_equal_single_slab_bitwise(lbhip, bc, nslabs):
         assert np.array_equal(a[k], b[k]), k
 
 
-@pytest.mark.parametrize("bc", ["periodic", "pipe", "cavity"])
+@pytest.mark.parametrize("bc,density", ALL_DENSITIES)
 @pytest.mark.parametrize("nslabs", [2, 3])
-def test_in_library_slab_schedule_with_two_step_kernel_bitwise(lbhip, bc, nslabs):
+def test_in_library_slab_schedule_with_two_step_kernel_bitwise(lbhip, bc, density, nslabs):
     """lb_run_group = the multi-GPU schedule (edge bands on a priority stream, interior on the compute
     stream, six-step halo cycles with the 6-deep halo, launch-by-launch exchange of the 3-deep halo for
     the remainder) with device-to-device copies instead of RCCL.  Must equal the undivided run bit for
@@ -439,7 +458,7 @@ def test_in_library_slab_schedule_with_two_step_kernel_bitwise(lbhip, bc, nslabs
     mask[0, :] = mask[-1, :] = False
     if bc != "periodic":
         mask[:, 0] = mask[:, -1] = False
-    kw = dict(inlet_rho=1.006, lid_u=0.05)
+    kw, f0 = _at_density(dict(inlet_rho=1.006, lid_u=0.05), f0, density)
     one = Simulation(nx, ny, 1.55, bc=bc, obstacle_mask=mask, **kw)
     one.set_variant(K_STEP)
     one.set_f(f0)
@@ -492,8 +511,8 @@ def test_rccl_self_ring_cycles_with_mask(lbhip):
         two.close()
 
 
-@pytest.mark.parametrize("bc", ["pipe", "cavity"])
-def test_slab_schedule_inside_lb_run_wall_families_single_rank(lbhip, bc):
+@pytest.mark.parametrize("bc,density", WALLED_DENSITIES)
+def test_slab_schedule_inside_lb_run_wall_families_single_rank(lbhip, bc, density):
     """lb_run's own slab schedule (edge bands, halo cycles, the lone first half, launch-by-launch remainders, MACRO on the
     last launch) for the walled families: a whole grid flagged as a slab with a 1-rank RCCL communicator has no neighbour
     (the exchange degenerates to an empty group), so the result must equal the plain run bit for bit."""
@@ -504,7 +523,7 @@ def test_slab_schedule_inside_lb_run_wall_families_single_rank(lbhip, bc):
     mask = rng.random((nx, ny)) < 0.02
     mask[0, :] = mask[-1, :] = False
     mask[:, 0] = mask[:, -1] = False
-    kw = dict(inlet_rho=1.004, lid_u=0.05)
+    kw, f0 = _at_density(dict(inlet_rho=1.004, lid_u=0.05), f0, density)
     one = Simulation(nx, ny, 1.4, bc=bc, obstacle_mask=mask, **kw)
     one.set_variant(K_STEP)
     one.set_f(f0)

@@ -334,6 +334,132 @@ def test_o2_d2q9i_fork_bit_exact_and_unstable(oracle):
     assert np.isnan(d["s60_u"]).any()                                     # the reference execution blew up
 
 
+# ---- outlet_rho, rho0 and the fluid's density off 1 ------------------------------------------------------------------------
+# Every fixture above has outlet_rho = 1.0 and the oracle's other users pass rho0 = 1.0: there `x / rout` and the products with
+# rout lose a rounding step, and a rule reading the wrong one of its two densities computes the same.
+def test_o2_boundary_densities_off_one_bit_exact(oracle):
+    """o2_offone_37x19 (D2Q9.cl executed at (0.9337, 0.93) and (1.0743, 1.07), the fluid at the outlet's density): `move_bcs`,
+    `update_hydro`, then 1, 10 and 50 steps."""
+    O = oracle
+    d = golden("o2_offone_37x19")
+    nx, ny = int(d["nx"]), int(d["ny"])
+    assert [tuple(p) for p in zip(d["inlet_rho"], d["outlet_rho"])] == [(0.9337, 0.93), (1.0743, 1.07)]
+    for i, (rin, rout) in enumerate(zip(d["inlet_rho"], d["outlet_rho"])):
+        p = "p%d_" % i
+
+        def fresh():
+            s = O.O2Sim(nx, ny, float(d["omega"]), O.BC_PIPE, float(rin), float(rout), mask=d["mask"])
+            s.set_f(d[p + "f0"])
+            return s
+
+        assert abs(float(d[p + "f0"].sum(axis=2, dtype=np.float64).mean()) / rout - 1) < 2e-3      # (the fluid IS off 1)
+        s = fresh()
+        s.fs[...] = d["fs0"].transpose(2, 1, 0)
+        O.lib().o2_bc_pipe(O._f(s.f), np.float32(rin), np.float32(rout), nx, ny)
+        assert exact(s.f.transpose(2, 1, 0), d[p + "after_bcs_f"])
+        s = fresh()
+        s.update_hydro()
+        assert exact(s.rho.T, d[p + "hydro_rho"]) and exact(s.u.T, d[p + "hydro_u"]) and exact(s.v.T, d[p + "hydro_v"])
+        s = fresh()
+        done = 0
+        for n in (1, 10, 50):
+            s.run(n - done)
+            done = n
+            g = s.get_fields()
+            for k in ("f", "feq", "rho", "u", "v"):
+                assert exact(g[k], d["%ss%d_%s" % (p, n, k)]), (i, n, k)
+        # the parameter is visible: the same run with outlet_rho = 1 leaves the fixture on the outlet column at once
+        t = O.O2Sim(nx, ny, float(d["omega"]), O.BC_PIPE, float(rin), 1., mask=d["mask"])
+        t.set_f(d[p + "f0"])
+        t.run(1)
+        diff = np.abs(t.get_fields()["f"] - d[p + "s1_f"]).max(axis=2)
+        assert diff[-1].min() > 1e-2 and diff[:-1].max() == 0
+
+
+def test_o2_d2q9i_boundary_densities_off_one_bit_exact(oracle):
+    """o2_d2q9i_offone_37x19: D2Q9i.cl executed at (1.0002, 0.9998), fluid at 1, inside the fork's stable window."""
+    O = oracle
+    d = golden("o2_d2q9i_offone_37x19")
+    nx, ny = int(d["nx"]), int(d["ny"])
+    assert (float(d["inlet_rho"]), float(d["outlet_rho"])) == (1.0002, 0.9998)
+
+    def fresh():
+        s = O.O2Sim(nx, ny, float(d["omega"]), O.BC_PIPE, float(d["inlet_rho"]), float(d["outlet_rho"]), mask=d["mask"], d2q9i=True)
+        s.set_f(d["f0"])
+        return s
+
+    s = fresh()
+    O.lib().o2i_bc_pipe(O._f(s.f), np.float32(s.inlet_rho), np.float32(s.outlet_rho), nx, ny)
+    assert exact(s.f.transpose(2, 1, 0), d["after_bcs_f"])
+    s = fresh()
+    done = 0
+    for n in (1, 8):
+        s.run(n - done)
+        done = n
+        g = s.get_fields()
+        for k in ("f", "feq", "rho", "u", "v"):
+            assert exact(g[k], d["s%d_%s" % (n, k)]), (n, k)
+    assert np.abs(d["s8_u"]).max() < 0.02
+
+
+def column_sums(f_xyk):
+    """sum_k f in float64: (nx, ny)"""
+    return np.asarray(f_xyk, np.float64).sum(axis=2)
+
+
+def assert_imposed_density(f_xyk, mask, bc, rho_w, rho_e, rho_corner=None):
+    """What the boundary rules were derived from, on the populations one `move_bcs` call leaves: a pressure inlet / outlet
+    closes its three unknown links so that sum_k f = the imposed density (uu = +-(1 - S / rho) with S the known links counted
+    as the column sees them, and the three new links add rho uu to them), a corner's two free links are set to half of what
+    the density lacks.  Each rule ends in three or four float32 roundings: 4 * 2^-24 rho.  Non-solid cells (the swap that
+    follows the rule permutes a solid cell's links; it is left out all the same).  Pipe: inlet and outlet column, corners
+    included; cavity: the four corners (rho_corner)."""
+    S = column_sums(f_xyk)
+    fluid = ~np.asarray(mask, bool) if mask is not None else np.ones(S.shape, bool)
+    checks = []
+    if bc == "pipe":
+        checks += [("inlet", S[0][fluid[0]], rho_w), ("outlet", S[-1][fluid[-1]], rho_e)]
+    else:
+        corners = [(0, 0), (0, -1), (-1, 0), (-1, -1)]
+        checks += [("corners", np.array([S[c] for c in corners if fluid[c]]), rho_corner)]
+    worst = 0.
+    for what, sums, rho in checks:
+        if sums.size:
+            err = float(np.abs(sums - float(np.float32(rho))).max())
+            worst = max(worst, err / (4 * 2.0 ** -24 * rho))
+            assert err <= 4 * 2.0 ** -24 * rho, (bc, what, err, 4 * 2.0 ** -24 * rho)
+    return worst
+
+
+@pytest.mark.parametrize("nx,ny", [(37, 19), (5, 7), (3, 3)])
+def test_boundary_rules_impose_their_density(oracle, nx, ny):
+    """The analytic property on the oracle's own output, in float64.  For the cavity closure the oracle is otherwise its own
+    definition: this is its check."""
+    O = oracle
+    w = np.array([4. / 9.] + [1. / 9.] * 4 + [1. / 36.] * 4)
+    rng = np.random.default_rng(nx * 100 + ny)
+    mask = rng.random((nx, ny)) < 0.05
+    mask[0, ny // 2] = mask[-1, ny // 2] = True                      # (one solid cell on the inlet and on the outlet column)
+    for bc, kw, fluid in ([(O.BC_PIPE, dict(inlet_rho=a, outlet_rho=b), b) for a, b in ((0.9337, 0.93), (1.0743, 1.07), (1.004, 1.0))] +
+                          [(O.BC_CAVITY, dict(lid_u=0.06, rho0=r), r) for r in (0.93, 1.07, 1.0)]):
+        for m in (None, mask):
+            f0 = (fluid * w[None, None, :] * (1 + 0.02 * rng.standard_normal((nx, ny, 9)))).astype(np.float32)
+            s = O.O2Sim(nx, ny, 1.6, bc, mask=m, **kw)
+            s.set_f(f0)
+            s.move_bcs()
+            f = s.get_fields()["f"]
+            if bc == O.BC_PIPE:
+                assert_imposed_density(f, m, "pipe", kw["inlet_rho"], kw["outlet_rho"])
+            else:
+                assert_imposed_density(f, m, "cavity", None, None, kw["rho0"])
+    for rin, rout in ((1.0002, 0.9998), (1.0004, 1.0002)):           # the fork's own inlet and outlet
+        f0 = (w[None, None, :] * (1 + 0.001 * rng.standard_normal((nx, ny, 9)))).astype(np.float32)
+        s = O.O2Sim(nx, ny, 1.0, O.BC_PIPE, rin, rout, mask=mask, d2q9i=True)
+        s.set_f(f0)
+        s.move_bcs()
+        assert_imposed_density(s.get_fields()["f"], mask, "pipe", rin, rout)
+
+
 def test_periodic_family_taylor_green_decay_rate(oracle):
     """The periodic family is build-defined (the reference's `dimensionless` package has no periodic streaming), so the
     oracle's [BD] routine is anchored to physics instead: a Taylor-Green vortex must decay with the lattice viscosity
