@@ -1,4 +1,4 @@
-"""A numpy float32 model of coupled scalar lattices in pull form (test infrastructure; not a test module).
+"""A numpy model of coupled scalar lattices in pull form, float32 or float64 (test infrastructure; not a test module).
 
 What LB_D2Q9/D2Q9_multifield_fisher.cl computes per iteration of advecting_range_expansion/deterministic_fisher_waves.py's run
 loop, written for whole arrays: stream (pull), the box's bounce-back, rho_i = sum f, feq_k = w_k rho_i (1 + 3 c_k.u) with the
@@ -10,8 +10,8 @@ imposed u, v, f = f (1 - omega_i) + omega_i feq + w_k G_i rho_i (1 - rho_tot), r
               field in the ABI's order (include/lb_hip.h).
 Against the fixtures recorded from the reference's C (tests/golden/mf_*.npz) it is checked by tests/test_multifield_cpu.py.
 
-Arrays: float32 (nx, ny) / (nx, ny, nf) / (nx, ny, nf, 9).  Every scalar is a float32 and every operation one float32
-operation; 1/cs^2 is the constant 3, as in tests/scalar_model.py.
+Arrays: (nx, ny) / (nx, ny, nf) / (nx, ny, nf, 9) of `dtype` (float32 unless asked otherwise).  Every scalar is a `dtype` and every
+operation one operation in it; 1/cs^2 is the constant 3, as in tests/scalar_model.py.
 """
 import numpy as np
 
@@ -23,31 +23,33 @@ OPPOSITE = (0, 3, 4, 1, 2, 7, 8, 5, 6)
 
 
 class MultifieldModel(object):
-    def __init__(self, nx, ny, omegas, Gs, bc="box"):
+    def __init__(self, nx, ny, omegas, Gs, bc="box", dtype=F):
         assert bc in ("box", "periodic")
+        T = self.T = np.dtype(dtype).type                 # (a scalar type: T(x) makes one value, whatever names the dtype)
         self.nx, self.ny, self.bc = int(nx), int(ny), bc
-        self.omega, self.G = np.array(omegas, F).reshape(-1), np.array(Gs, F).reshape(-1)
+        self.omega, self.G = np.array(omegas, F).reshape(-1).astype(T), np.array(Gs, F).reshape(-1).astype(T)      # (the handles' parameters are float32)
         self.nf = len(self.omega)
         assert len(self.G) == self.nf
-        self.f = np.zeros((nx, ny, self.nf, 9), F)
-        self.stale = np.zeros((nx, ny, self.nf, 9), F)      # box: the populations as last set; only never-streamed links are read
-        self.feq = np.zeros((nx, ny, self.nf, 9), F)
-        self.rho = np.zeros((nx, ny, self.nf), F)
-        self.u = np.zeros((nx, ny), F)
-        self.v = np.zeros((nx, ny), F)
+        self.w = W if T == F else np.array([4. / 9.] + [1. / 9.] * 4 + [1. / 36.] * 4, dtype=T)
+        self.f = np.zeros((nx, ny, self.nf, 9), T)
+        self.stale = np.zeros((nx, ny, self.nf, 9), T)      # box: the populations as last set; only never-streamed links are read
+        self.feq = np.zeros((nx, ny, self.nf, 9), T)
+        self.rho = np.zeros((nx, ny, self.nf), T)
+        self.u = np.zeros((nx, ny), T)
+        self.v = np.zeros((nx, ny), T)
 
     def set_fields(self, rho, u, v):
-        self.rho, self.u, self.v = (np.array(a, dtype=F) for a in (rho, u, v))
+        self.rho, self.u, self.v = (np.array(a, dtype=self.T) for a in (rho, u, v))
 
     def set_f(self, f):
-        self.f = np.array(f, dtype=F)
+        self.f = np.array(f, dtype=self.T)
         self.stale = self.f.copy()
 
     def get_corner_state(self):
-        return np.stack([self.stale[x, y, :, k] for k, x, y in CORNER_LINKS], axis=1).astype(F)      # (nf, 8)
+        return np.stack([self.stale[x, y, :, k] for k, x, y in CORNER_LINKS], axis=1).astype(self.T)      # (nf, 8)
 
     def set_corner_state(self, values):
-        values = np.asarray(values, F)
+        values = np.asarray(values, self.T)
         for j, (k, x, y) in enumerate(CORNER_LINKS):
             self.stale[x, y, :, k] = values[:, j]
 
@@ -89,22 +91,23 @@ class MultifieldModel(object):
         self.rho = rho
 
     def update_feq(self):
+        T = self.T
         for k in range(9):
-            cu = (F(CX[k]) * self.u + F(CY[k]) * self.v)[:, :, None]
-            self.feq[..., k] = W[k] * self.rho * (F(1.) + cu * F(3.))
+            cu = (T(CX[k]) * self.u + T(CY[k]) * self.v)[:, :, None]
+            self.feq[..., k] = self.w[k] * self.rho * (T(1.) + cu * T(3.))
 
     def collide_particles(self):
         rho_tot = self.rho[..., 0].copy()
         for i in range(1, self.nf):
             rho_tot = rho_tot + self.rho[..., i]
-        room = F(1.) - rho_tot
+        room = self.T(1.) - rho_tot
         for i in range(self.nf):
-            keep = F(1.) - self.omega[i]
+            keep = self.T(1.) - self.omega[i]
             react = (self.G[i] * self.rho[..., i]) * room
             for k in range(9):
                 new = self.f[:, :, i, k] * keep + self.omega[i] * self.feq[:, :, i, k]
                 if self.G[i] != 0:
-                    new = new + W[k] * react
+                    new = new + self.w[k] * react
                 self.f[:, :, i, k] = new
 
     def step(self):

@@ -1,4 +1,4 @@
-"""A numpy float32 model of a scalar lattice in pull form (test infrastructure; not a test module).
+"""A numpy model of a scalar lattice in pull form, float32 or float64 (test infrastructure; not a test module).
 
 What LB_D2Q9/D2Q9_diffusion.cl computes per iteration of reaction_diffusion/diffusion.py's run loop, written for whole
 arrays: stream (pull), rho = sum f, feq_k = w_k rho (1 + 3 c_k.u) with the imposed u, v, f = f (1 - omega) + omega feq
@@ -9,8 +9,8 @@ arrays: stream (pull), rho = sum f, feq_k = w_k rho (1 + 3 c_k.u) with the impos
 It is the yardstick where no fixture reaches (the periodic family, larger boxes, the coupling).  Against the fixtures
 recorded from the reference's C (tests/golden/ad_*.npz) it is checked by tests/test_scalar_cpu.py.
 
-Arrays: float32 (nx, ny) / (nx, ny, 9).  Every scalar is a float32 and every operation one float32 operation; 1/cs^2 is
-the constant 3 (the reference divides by cs*cs of its float32 cs).
+Arrays: (nx, ny) / (nx, ny, 9) of `dtype` (float32 unless asked otherwise).  Every scalar is a `dtype` and every operation one
+operation in it; 1/cs^2 is the constant 3 (the reference divides by cs*cs of its float32 cs).
 """
 import numpy as np
 
@@ -39,35 +39,40 @@ def edge_index(nx, ny):
 
 
 class ScalarModel(object):
-    def __init__(self, nx, ny, omega, G=0., bc="open"):
+    def __init__(self, nx, ny, omega, G=0., bc="open", dtype=F):
         assert bc in ("open", "periodic")
+        T = self.T = np.dtype(dtype).type                 # (a scalar type: T(x) makes one value, whatever names the dtype)
         self.nx, self.ny, self.bc = int(nx), int(ny), bc
-        self.omega, self.G = F(omega), F(G)
-        self.f = np.zeros((nx, ny, 9), F)
-        self.frozen = np.zeros((nx, ny, 9), F)        # open: the populations as last set; only its edge links are ever read
-        self.feq = np.zeros((nx, ny, 9), F)
-        self.rho = np.zeros((nx, ny), F)
-        self.u = np.zeros((nx, ny), F)
-        self.v = np.zeros((nx, ny), F)
+        self.omega, self.G = T(F(omega)), T(F(G))        # (the handle's parameters are float32)
+        self.w = W if T == F else np.array([4. / 9.] + [1. / 9.] * 4 + [1. / 36.] * 4, dtype=T)
+        self.f = np.zeros((nx, ny, 9), T)
+        self.frozen = np.zeros((nx, ny, 9), T)        # open: the populations as last set; only its edge links are ever read
+        self.feq = np.zeros((nx, ny, 9), T)
+        self.rho = np.zeros((nx, ny), T)
+        self.u = np.zeros((nx, ny), T)
+        self.v = np.zeros((nx, ny), T)
+
+    def set_reaction(self, G):
+        self.G = self.T(F(G))
 
     def set_fields(self, rho, u, v):
-        self.rho, self.u, self.v = (np.array(a, dtype=F) for a in (rho, u, v))
+        self.rho, self.u, self.v = (np.array(a, dtype=self.T) for a in (rho, u, v))
 
     def set_f(self, f):
-        self.f = np.array(f, dtype=F)
+        self.f = np.array(f, dtype=self.T)
         self.frozen = self.f.copy()
 
     # -- edge state in the ABI's order ---------------------------------------------------------------------------------
     def get_edge_state(self):
         if self.bc != "open":
-            return np.zeros(0, F)
+            return np.zeros(0, self.T)
         west, east, south, north = edge_index(self.nx, self.ny)
-        return np.concatenate([self.frozen[x, y, k] for k, x, y in west + east + south + north]).astype(F)
+        return np.concatenate([self.frozen[x, y, k] for k, x, y in west + east + south + north]).astype(self.T)
 
     def set_edge_state(self, e):
         if self.bc != "open":
             return
-        e = np.asarray(e, F)
+        e = np.asarray(e, self.T)
         west, east, south, north = edge_index(self.nx, self.ny)
         cols, rows = west + east, south + north
         o = sum(len(x) for _, x, _ in cols)
@@ -101,17 +106,19 @@ class ScalarModel(object):
         self.rho = rho
 
     def update_feq(self):
+        T = self.T
         for k in range(9):
-            cu = F(CX[k]) * self.u + F(CY[k]) * self.v
-            self.feq[:, :, k] = W[k] * self.rho * (F(1.) + cu * F(3.))
+            cu = T(CX[k]) * self.u + T(CY[k]) * self.v
+            self.feq[:, :, k] = self.w[k] * self.rho * (T(1.) + cu * T(3.))
 
     def collide_particles(self):
-        keep = F(1.) - self.omega
-        react = self.G * self.rho * (F(1.) - self.rho)
+        T = self.T
+        keep = T(1.) - self.omega
+        react = self.G * self.rho * (T(1.) - self.rho)
         for k in range(9):
             new = self.f[:, :, k] * keep + self.omega * self.feq[:, :, k]
             if self.G != 0:
-                new = new + W[k] * react
+                new = new + self.w[k] * react
             self.f[:, :, k] = new
 
     def step(self):

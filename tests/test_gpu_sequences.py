@@ -1,0 +1,76 @@
+"""Random call sequences on every handle kind against the models (the generator and the players: tests/sequence_scenarios.py).
+
+The other GPU files meet one entry point with one reference at a time.  Between those points sits host state that decides which
+kernel runs on which buffer and what a read returns -- the current lattice, macro_valid / feq_valid, the captured graph's key, the
+mask and field flags, the `G != 0` template switch, the multifluid variant word, the edge and corner states, the Poisson iteration
+counter, the last launch that alone stores u, v, G -- each correct for the sequences somebody thought of.  Here a handle lives
+through a seeded interleaving of its calls, and two properties are held at two cut points inside the sequence and at its end:
+
+  A, bitwise    the SUBJECT (effective and transparent ops, starting from the automatic variant) equals the TWIN (a second handle
+                pinned to the plainest kernel that makes the effective ops only, every run(n) as n x run(1)) on every array the kind
+                exposes: an observation or a kernel choice never changes the trajectory.
+  B, contract   the twin equals the REFERENCE (oracle.O2Sim for the flow kinds, the kind's numpy model in float64 otherwise) within
+                the kind's existing comparison for the n steps since the populations were last set: a state-changing call in the
+                middle of a life means what the reference says it means.  No new tolerance.
+
+The comparisons follow a stepping op, where every array is fresh, or a set_f behind one, where the populations are new and rho, u, v,
+feq and the forces are still the last step's (the populations are then held to the bound of the steps since they were set, the rest
+to that of the steps behind it).  On a Poisson handle the iteration count is held to the model's as well.
+
+Shapes: sequence_scenarios.FLOW_SHAPES and its neighbours, with the reason for each.  That the references alone stay inside the
+contract on exactly these inputs: tests/test_sequences_cpu.py.
+
+Measured on an MI355X, all 102 cases green, the largest share of its bound that property B used per kind: flow f 95 % (velocity inlet,
+seed 5, the one step by phases behind an init_equilibrium: 2.38e-7 of 2.5e-7), rho 60 %, u 17 %, v 8 %; scalar f 43 %, rho 31 %, feq
+27 %; multifield f 12 %, rho 8 %, feq 8 %; poisson f 19 %, rho 14 %, feq 20 %; porous f 56 %, feq 40 %, rho 42 %, u, v, u_b, G 5 %;
+multifluid f 60 %, feq 40 %, rho 41 %, u, v, u_b, G 5 %.  The flow cases take up to half a second each, the others less.
+
+One-line defects tried against this file (value-changing only; none kept), with the cases each turned red:
+  lb_set_f without its ensure_macro                                      ->  4 (flow: pipe 3, periodic 1 and 3, cavity 4 -- lazy
+                                                                            families, compared behind a set_f; one by A, three by B)
+  the captured graph's key without its `cur` bit                         ->  3 (flow: pipe 4, cavity 4, velocity_inlet 4, by A: the graph
+                                                                            replays only under a forced K_STEP in runs of > 16 steps)
+  lb_run_fluids' one-launch step storing u, v, G, u_b on the FIRST launch -> 12 of 12 multifluid
+  lb_set_reaction ignoring a change back to G = 0                        ->  7 of 12 scalar (six by B, one by A)
+  lb_solve_reset leaving the iteration counter                           ->  5 of 6 poisson (the count held to the model's)
+  lb_set_mask(NULL) leaving has_mask set                                 -> 35 of 48 flow
+  run_porous storing rho, u, v, G, u_b on the FIRST launch               -> 12 of 12 porous
+  lb_run_coupled storing every field's rho on the FIRST launch           -> 12 of 12 multifield
+  lb_set_corner_state without its upload                                 -> 14 (5 of 6 multifield box, 5 of 6 poisson, 4 of 12 velocity
+                                                                            inlet: wherever a restored handle gets its corner links)
+"""
+import numpy as np
+import pytest
+
+import sequence_scenarios as S
+from kernel_variants import same_bits
+
+pytestmark = pytest.mark.gpu
+
+CASES = [(k, f, s) for k in S.KINDS for f in S.FAMILIES[k] for s in S.SEEDS]
+
+
+@pytest.mark.parametrize("kind,family,seed", CASES, ids=["%s-%s-%d" % c for c in CASES])
+def test_random_call_sequence(lbhip, oracle, tmp_path, kind, family, seed):
+    case, ops = S.case_of(kind, family, seed), S.generate(kind, family, seed)
+    cuts = S.cut_points(ops, kind, family, seed)
+    subject, twin = S.GpuPlayer(case, tmpdir=tmp_path), S.GpuPlayer(case, plain=True)
+    ref = S.RefPlayer(case, np.float64, oracle)
+    try:
+        for i, op in enumerate(ops):
+            if S.is_effective(op):
+                for p in (subject, twin, ref):
+                    p.effective(op)
+            else:
+                subject.transparent(op)
+            if i in cuts:
+                what = "%s %s seed %d, behind op %d %r of %r" % (kind, family, seed, i, op, ops[:i + 1])
+                want = twin.snapshot()
+                same_bits(subject.snapshot(), want, what, fields=tuple(want))
+                assert (twin.steps, twin.macro_steps) == (ref.steps, ref.macro_steps) and ref.macro_steps >= 1
+                S.hold_to_contract(kind, "%s %s seed %d op %d, twin / reference" % (kind, family, seed, i), twin.fields(), ref)
+                if kind == "poisson":               # the iterations since the last solve_reset: run and solve count, the phases do not
+                    assert twin.h.solve_state()[0] == ref.m.iterations, (what, twin.h.solve_state(), ref.m.iterations)
+    finally:
+        subject.close()
+        twin.close()

@@ -1,0 +1,141 @@
+"""The random call sequences of tests/test_gpu_sequences.py without a GPU (tests/sequence_scenarios.py): the generator is
+deterministic and covers its tables; on exactly these inputs -- mid-life parameter, table and mask changes included -- the float32
+model of every kind that has one stays within the kind's contract of the float64 model, and
+the flow kinds' oracle stays in the range the contract was established in."""
+import numpy as np
+import pytest
+
+import sequence_scenarios as S
+
+CASES = [(k, f, s) for k in S.KINDS for f in S.FAMILIES[k] for s in S.SEEDS]
+ids = lambda cases: ["%s-%s-%d" % c for c in cases]
+HAVE_DTYPE = ("scalar", "multifield", "poisson", "porous", "multifluid")
+
+
+@pytest.mark.parametrize("kind,family,seed", CASES, ids=ids(CASES))
+def test_generator_is_deterministic_and_within_its_limits(kind, family, seed):
+    ops = S.generate(kind, family, seed)
+    assert ops == S.generate(kind, family, seed)
+    e, t, steps = S.counts(ops)
+    assert 1 <= e <= S.MAX_E and 1 <= t <= S.MAX_T and 1 <= steps <= S.MAX_STEPS, (e, t, steps)
+    assert ops[-1][0] == "run"
+    for op in ops:                                      # plain values only: the lists above compare by value
+        assert all(isinstance(a, (str, int, float, tuple, type(None))) and not isinstance(a, np.generic) for a in op), op
+        if op[0] in ("run", "solve", "plan_launches"):
+            assert op[1] in S.RUN_LENGTHS
+    cuts = S.cut_points(ops, kind, family, seed)
+    assert cuts == S.cut_points(ops, kind, family, seed) and cuts[-1] == len(ops) - 1 and len(cuts) == 3
+    assert all(ops[i][0] in S.STEPPING + ("set_f",) for i in cuts) and len(set(cuts)) == 3
+    a, b = S.case_of(kind, family, seed), S.case_of(kind, family, seed)
+    assert np.array_equal(a["f0"], b["f0"]) and a["f0"].dtype == np.float32
+
+
+@pytest.mark.parametrize("kind", S.KINDS)
+def test_every_op_of_the_tables_occurs(kind):
+    """Over the committed seeds of a kind: every effective and every transparent op, every variant word the kind's handles accept,
+    every run length, both directions of a toggle."""
+    ops = [op for f in S.FAMILIES[kind] for s in S.SEEDS for op in S.generate(kind, f, s)]
+    names = {op[0] for op in ops}
+    assert set(S.E_OPS[kind]) <= names, set(S.E_OPS[kind]) - names
+    assert set(S.T_OPS[kind]) - {"split_run"} <= names, set(S.T_OPS[kind]) - names
+    assert any(op[0] == "run" and op[2] for op in ops)                                          # split_run
+    assert {op[1] for op in ops if op[0] == "set_variant"} == set(S.variant_words(kind))
+    assert {op[1] for op in ops if op[0] in ("run", "solve")} == set(S.RUN_LENGTHS)
+    assert any("feq" in op[1] for op in ops if op[0] == "get_fields")
+    behind = {S.generate(kind, f, s)[i][0] for f in S.FAMILIES[kind] for s in S.SEEDS for i in S.cut_points(S.generate(kind, f, s), kind, f, s)}
+    assert behind >= {"run", "phase_step", "set_f"}, behind                                   # what a comparison follows
+    if kind == "multifluid":
+        for name in ("set_interactions", "set_reactions"):
+            assert {op[1] for op in ops if op[0] == name} == {0, 1, 2}
+        assert {S.case_of(kind, "periodic", s)["nf"] for s in S.SEEDS} == {2, 3}
+    if kind == "flow":
+        assert {S.case_of(kind, f, s)["mask"] is None for f in S.FAMILIES[kind] for s in S.SEEDS} == {True, False}
+    if kind == "scalar":
+        assert {S.case_of(kind, f, s)["G"] for f in S.FAMILIES[kind] for s in S.SEEDS} == {0., 0.01}
+
+
+@pytest.mark.parametrize("kind,family,seed", CASES, ids=ids(CASES))
+def test_transparent_ops_sit_where_they_can_matter(kind, family, seed):
+    """In every sequence: a read lies behind a stepping op (only there can it find macro_valid / feq_valid stale, and only from there
+    can it disturb what follows); every variant word stands directly in front of a run, so each selects something; the mask is uploaded
+    again, and taken off and put back, only while a mask is set."""
+    ops = S.generate(kind, family, seed)
+    stepped = [any(o[0] in S.STEPPING for o in ops[:i]) for i in range(len(ops))]
+    assert any(op[0] == "get_fields" and stepped[i] for i, op in enumerate(ops))
+    words = [i for i, op in enumerate(ops) if op[0] == "set_variant"]
+    assert len(words) == (S.N_VARIANTS if S.variant_words(kind) else 0)
+    assert all(ops[i + 1][0] == "run" for i in words)
+    has_mask = kind == "flow" and S.case_of(kind, family, seed)["mask"] is not None
+    for op in ops:
+        if op[0] in ("reupload_mask", "mask_off_on"):
+            assert has_mask, ops
+        has_mask = op[0] == "set_obstacle_mask" or (has_mask and op[0] != "clear_obstacle_mask")
+
+
+@pytest.mark.parametrize("kind", S.KINDS)
+def test_transparent_ops_are_interleaved_at_random(kind):
+    """Over the committed seeds of a kind: no two sequences play their transparent ops in the same order; reads, check() and the
+    checkpoint round trip each occur behind a stepping op, a checkpoint also behind a variant word that a run has used; every
+    variant word occurs directly in front of a run of at least VARIANT_DEPTH steps in one call, where its kernel can run."""
+    lists = [S.generate(kind, f, s) for f in S.FAMILIES[kind] for s in S.SEEDS]
+    orders = {tuple(op[0] for op in ops if not S.is_effective(op)) for ops in lists}
+    assert len(orders) == len(lists)
+    behind_step, behind_word, deep = set(), set(), set()
+    for ops in lists:
+        stepped = word_used = False
+        for op, nxt in zip(ops, ops[1:]):
+            if not S.is_effective(op):
+                behind_step |= {op[0]} if stepped else set()
+                behind_word |= {op[0]} if word_used else set()
+            stepped |= op[0] in S.STEPPING
+            if op[0] == "set_variant":
+                word_used = True                        # (nxt is its run: test_transparent_ops_sit_where_they_can_matter)
+                if max(nxt[2], nxt[1] - nxt[2]) >= S.VARIANT_DEPTH:
+                    deep.add(op[1])
+    assert behind_step >= set(S.T_OPS[kind]) - {"split_run", "set_variant"}, behind_step
+    assert deep == set(S.variant_words(kind)), set(S.variant_words(kind)) - deep
+    if S.variant_words(kind):
+        assert behind_word >= {"checkpoint", "get_fields", "set_variant"}, behind_word
+
+
+DTYPE_CASES = [c for c in CASES if c[0] in HAVE_DTYPE]
+
+
+@pytest.mark.parametrize("kind,family,seed", DTYPE_CASES, ids=ids(DTYPE_CASES))
+def test_float32_model_stays_within_the_contract_of_the_float64_model(kind, family, seed):
+    """Property B of the GPU file with the float32 model in the GPU's place: the reference alone is inside the contract on these
+    inputs, so a GPU handle that is not has no excuse in them."""
+    case, ops = S.case_of(kind, family, seed), S.generate(kind, family, seed)
+    m32, m64 = S.RefPlayer(case, np.float32), S.RefPlayer(case, np.float64)
+    cuts = S.cut_points(ops, kind, family, seed)
+    for i, op in enumerate(ops):
+        if S.is_effective(op):
+            m32.effective(op)
+            m64.effective(op)
+        if i in cuts:
+            assert (m64.steps, m64.macro_steps) == (m32.steps, m32.macro_steps) and m64.macro_steps >= 1
+            S.hold_to_contract(kind, "%s %s seed %d op %d, float32 model / float64 model" % (kind, family, seed, i), m32.fields(), m64)
+    if kind in ("porous", "multifluid"):
+        rho = np.asarray(m64.m.rho)
+        speed = np.sqrt(np.asarray(m64.m.ub) ** 2 + np.asarray(m64.m.vb) ** 2)
+        assert rho.min() > 0.5 and rho.max() < 1.5 and speed.max() < 0.15, (rho.min(), rho.max(), speed.max())
+
+
+FLOW_CASES = [c for c in CASES if c[0] == "flow"]
+
+
+@pytest.mark.parametrize("kind,family,seed", FLOW_CASES, ids=ids(FLOW_CASES))
+def test_flow_oracle_stays_in_the_contracts_range(oracle, kind, family, seed):
+    """rho in 0.5 ... 1.5 and |u| < 0.15 after every stepping op of the sequence: the range the parity contract was established in."""
+    case, ops = S.case_of(kind, family, seed), S.generate(kind, family, seed)
+    o = S.RefPlayer(case, oracle=oracle)
+    worst = [1., 1., 0.]
+
+    def look(i):
+        g = o.m
+        speed = float(np.sqrt(g.u.astype(np.float64) ** 2 + g.v.astype(np.float64) ** 2).max())
+        worst[:] = [min(worst[0], float(g.rho.min())), max(worst[1], float(g.rho.max())), max(worst[2], speed)]
+        assert 0.5 < g.rho.min() and g.rho.max() < 1.5 and speed < 0.15, (i, ops[i], float(g.rho.min()), float(g.rho.max()), speed)
+
+    S.play(o, ops, look, [i for i, op in enumerate(ops) if op[0] in S.STEPPING])
+    print("%s seed %d: rho %.3f ... %.3f, max |u| %.4f" % (family, seed, worst[0], worst[1], worst[2]))
