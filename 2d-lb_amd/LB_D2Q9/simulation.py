@@ -671,7 +671,13 @@ class Simulation(object):
         check(self._lib.lb_halo_import(self._h, int(side), _address(buf)))
 
     def use_stream(self, hip_stream):
-        """Run on an external hipStream_t (integer handle, e.g. torch's current stream); None = own."""
+        """Run on an external hipStream_t (integer handle, e.g. torch.cuda.Stream(...).cuda_stream); None = back to the handle's own
+        stream.  Waits for the work enqueued on the stream it leaves.  The legacy default stream cannot be named: its handle is 0,
+        which lb_set_stream reads as None -- and the own stream is ordered with nothing else (torch's current stream is that
+        default stream unless the caller made another one current), so 0 is refused here instead of silently meaning `own`."""
+        if hip_stream is not None and int(hip_stream) == 0:
+            raise ValueError("stream handle 0 is the legacy default stream, which lb_set_stream cannot name (NULL = the handle's own "
+                             "stream): run the torch side on a torch.cuda.Stream and pass its cuda_stream, or pass None")
         check(self._lib.lb_set_stream(self._h, hip_stream))
 
     def comm_init(self, unique_id, rank, nranks):

@@ -191,6 +191,7 @@ class DistributedSlab(_SlabSet):
             self.engine.set_obstacle_mask_halo(*self._mask_halo_rows(obstacle_mask, self.y0, self.h, ny, self.periodic))
         self._ghosts_valid = False
         self._bufs = None
+        self._stream = None              # transport='torch' on the GPU: the stream the exchange and the engine share (_torch_buffers)
         if transport == "rccl":
             self._attach_rccl()
         elif transport == "peer":
@@ -285,13 +286,30 @@ class DistributedSlab(_SlabSet):
             import torch
             on_gpu = self._dist.get_backend(self.group) == "nccl"
             dev = torch.device("cuda", self.engine.device) if on_gpu else torch.device("cpu")
+            mk = lambda: torch.zeros(18 * self.nx, dtype=torch.float32, device=dev)
             if on_gpu:
                 torch.cuda.set_device(dev)
-                # one stream for kernels, halo copies and torch's collectives' stream dependencies
-                self.engine.use_stream(torch.cuda.current_stream().cuda_stream)
-            mk = lambda: torch.zeros(18 * self.nx, dtype=torch.float32, device=dev)
-            self._bufs = {"send_s": mk(), "send_n": mk(), "recv_s": mk(), "recv_n": mk(), "gpu": on_gpu}
+                # One stream for kernels, halo copies and torch's copies / collectives, so that they follow each other with no host
+                # wait: a torch stream of the slab's own, on which _exchange_torch runs its torch side.  Never torch's current
+                # stream: by default that is the legacy default stream, whose handle is 0 -- which lb_set_stream reads as `back to
+                # the handle's own stream`, a non-blocking stream that nothing orders with the default one (the exchange then sent
+                # rows the export had not written yet and imported buffers the receive had not filled: tests/test_gpu_streams.py).
+                self._stream = torch.cuda.Stream(dev)
+                with torch.cuda.stream(self._stream):
+                    bufs = {"send_s": mk(), "send_n": mk(), "recv_s": mk(), "recv_n": mk(), "gpu": True}
+                self.engine.use_stream(self._stream.cuda_stream)
+            else:
+                bufs = {"send_s": mk(), "send_n": mk(), "recv_s": mk(), "recv_n": mk(), "gpu": False}
+            self._bufs = bufs
         return self._bufs
+
+    def exchange_stream(self):
+        """transport='torch' under the nccl backend: the torch stream this slab's engine runs on and its exchange is enqueued on
+        (a caller's torch ops that feed or read the slab go there, or wait for it); None on every other path."""
+        if self.transport != "torch":
+            return None
+        self._torch_buffers()
+        return self._stream
 
     @staticmethod
     def _ptr(t):
@@ -299,13 +317,27 @@ class DistributedSlab(_SlabSet):
 
     def _exchange_torch(self):
         """Edge rows of the lattice the next step reads -> neighbours' ghost rows."""
-        import torch
         dist, b = self._dist, self._torch_buffers()
         eng = self.engine
         eng.halo_export(SOUTH, self._ptr(b["send_s"]))
         eng.halo_export(NORTH, self._ptr(b["send_n"]))
         if not b["gpu"]:
             eng.sync()
+            self._move_torch(b)
+        else:
+            import torch
+            with torch.cuda.stream(self._stream):       # behind the exports, in front of the imports: the engine's stream
+                self._move_torch(b)
+        if self.south >= 0:
+            eng.halo_import(SOUTH, self._ptr(b["recv_s"]))
+        if self.north >= 0:
+            eng.halo_import(NORTH, self._ptr(b["recv_n"]))
+        if not b["gpu"]:
+            eng.sync()
+
+    def _move_torch(self, b):
+        """send buffers -> the neighbours' receive buffers, on torch's current stream"""
+        dist = self._dist
         grank = (lambda r: dist.get_global_rank(self.group, r)) if self.group is not None else (lambda r: r)
         if self.nranks == 1:
             if self.periodic:
@@ -325,12 +357,6 @@ class DistributedSlab(_SlabSet):
                 ops.append(dist.P2POp(dist.irecv, b["recv_n"], grank(self.north), self.group))
             for req in dist.batch_isend_irecv(ops):
                 req.wait()
-        if self.south >= 0:
-            eng.halo_import(SOUTH, self._ptr(b["recv_s"]))
-        if self.north >= 0:
-            eng.halo_import(NORTH, self._ptr(b["recv_n"]))
-        if not b["gpu"]:
-            eng.sync()
 
     # -- public API -------------------------------------------------------------------------------------
     def set_f(self, f_global):

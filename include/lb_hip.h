@@ -207,8 +207,14 @@ int lb_destroy(lb_sim *s);
  * (the device kernels compute in float32 throughout). */
 int lb_set_params_f64(lb_sim *s, double omega, double inlet_rho, double outlet_rho);
 int lb_sync(lb_sim *s);
-/* Run everything on an externally owned hipStream_t (e.g. torch's current
- * stream) instead of the handle's own; pass NULL to go back. */
+/* Run everything on an externally owned hipStream_t (e.g. a stream the caller
+ * made with hipStreamCreate, or torch.cuda.Stream().cuda_stream) instead of the
+ * handle's own; pass NULL to go back.  Waits for the work enqueued on the stream
+ * it leaves.  NULL always means the handle's own stream (hipStreamNonBlocking:
+ * ordered with no other stream), so the legacy default stream -- whose handle is
+ * NULL, and which is torch's current stream unless the caller made another one
+ * current -- cannot be named: a caller whose other work runs there moves it to a
+ * stream of its own and passes that one, or orders the two with events. */
 int lb_set_stream(lb_sim *s, void *hip_stream);
 
 /* ---- host <-> device state (replaces cl.Buffer(COPY_HOST_PTR, hostbuf=...)
@@ -307,7 +313,9 @@ int lb_gradient(lb_sim *s, float inv_two_dx, float *ddx, float *ddy);
  * lb_set_porous: epsilon, nu_fluid, K, Fe (defaults 1, 0, 1, 0); LB_ERR_ARG for epsilon <= 0, K <= 0 or a non-finite value.
  * lb_set_body_force: the sum of the constant forces (default 0, 0).
  * lb_set_force_field: two [ny][nx] planes added to the constant force in every cell (the reference's add_radial_body_force
- *   depends on position only); on_device != 0: device pointers.  gx = gy = NULL drops the field.
+ *   depends on position only); on_device != 0: device pointers to that dense layout, copied device to device on the handle's
+ *   stream (the caller has finished writing them, or wrote them on that stream; the call returns with the copy complete).
+ *   gx = gy = NULL drops the field.
  * lb_get_force / lb_get_bary_velocity / lb_set_bary_velocity: [ny][nx] planes; an output may be NULL.
  * lb_set_f, lb_get_f, lb_get_feq, lb_set_macro, lb_get_macro, lb_init_pop, lb_hot_kernel, lb_plan_launches and lb_layout
  * work as on every handle.  Masks, slabs and halo calls, lb_autotune*, lb_set_variant with a value other than -1 and 0,
