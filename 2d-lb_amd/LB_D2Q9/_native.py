@@ -22,6 +22,9 @@ LB_SEM_MULTIFLUID = 9    # (nor is 8)
 LB_PSI_LINEAR, LB_PSI_SHAN_CHEN, LB_PSI_POW = 0, 1, 2
 LB_REACT_EAT, LB_REACT_GROW = 0, 1
 MC_MAX, MC_MAX_INTER, MC_MAX_REACT = 3, 6, 4
+LB_SEM_ROCKET = 11       # (nor is 10)
+LB_ROCKET_FLOW, LB_ROCKET_FORCES = 0, 1
+RY_ROWS = 10             # rows of a 256-cell tile a workgroup of k_ry_step owns (csrc/plan_consts.h; lb_hot_kernel names it)
 BC_NAMES = {"pipe": LB_BC_PIPE, "periodic": LB_BC_PERIODIC, "cavity": LB_BC_CAVITY,
             "velocity_inlet": LB_BC_VELOCITY_INLET, "open": LB_BC_OPEN, "box": LB_BC_BOX, "dirichlet": LB_BC_DIRICHLET,
             "zero_gradient": LB_BC_ZERO_GRADIENT}
@@ -48,6 +51,8 @@ EXPORTS = (
     "lb_get_bary_velocity", "lb_update_forces", "lb_update_bary_velocity",
     "lb_run_fluids", "lb_set_interactions", "lb_set_reactions", "lb_get_interactions", "lb_get_reactions",
     "lb_update_forces_fluids", "lb_update_bary_fluids", "lb_react_fluids",
+    "lb_set_rocket", "lb_get_rocket", "lb_run_rocket", "lb_update_velocity_rocket", "lb_update_forces_rocket", "lb_collide_rocket",
+    "lb_get_rocket_fields",
 )
 
 
@@ -67,6 +72,11 @@ class Interaction(ct.Structure):         # lb_interaction
 class FluidReaction(ct.Structure):       # lb_fluid_reaction
     _fields_ = [("kind", ct.c_int32), ("fluid_a", ct.c_int32), ("fluid_b", ct.c_int32),
                 ("p0", ct.c_float), ("p1", ct.c_float), ("p2", ct.c_float)]
+
+
+class RocketParams(ct.Structure):        # lb_rocket_params
+    _fields_ = [("mode", ct.c_int32), ("G", ct.c_float), ("G_c", ct.c_float), ("epsilon", ct.c_float), ("rho_o", ct.c_float),
+                ("G_chen", ct.c_float), ("c_o", ct.c_float), ("alpha", ct.c_float)]
 
 
 class LbError(RuntimeError):
@@ -159,6 +169,14 @@ def lib():
         L.lb_get_reactions.argtypes = [h, ct.POINTER(FluidReaction), ip]
         for name in ("lb_update_forces_fluids", "lb_update_bary_fluids", "lb_react_fluids"):
             getattr(L, name).argtypes = [hp, I]
+    if hasattr(L, "lb_run_rocket"):                 # (likewise: surfactant-propelled colonies)
+        hp = ct.POINTER(h)
+        L.lb_set_rocket.argtypes = [hp, I, ct.POINTER(RocketParams)]
+        L.lb_get_rocket.argtypes = [h, ct.POINTER(RocketParams)]
+        L.lb_run_rocket.argtypes = [hp, I, I]
+        for name in ("lb_update_velocity_rocket", "lb_update_forces_rocket", "lb_collide_rocket"):
+            getattr(L, name).argtypes = [hp, I]
+        L.lb_get_rocket_fields.argtypes = [hp, I, vp, vp, vp, vp, vp]
     L.lb_comm_init.argtypes = [h, vp, I, I]
     L.lb_timer_stop.argtypes = [h, fp]
     L.lb_layout.argtypes = [h, ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64), ct.POINTER(ct.c_int64)]

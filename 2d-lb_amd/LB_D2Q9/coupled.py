@@ -299,3 +299,140 @@ class Shan_Chen_Fluids(object):
         out.set_reactions([("eat", int(r[1]), int(r[2]), r[3], r[4]) if int(r[0]) == _native.LB_REACT_EAT else ("grow", int(r[1]), r[3], r[4], r[5])
                            for r in per[0]["reactions"]])
         return out
+
+
+class Surfactant_Colony(object):
+    """A growing population and the surfactant it secretes, two scalar lattices in one periodic box
+    (``Simulation(semantics='rocket')``, ``omega`` and ``omega_c``): the reference's ``rocket_yeast/rocket_yeast.py``
+    (``mode='flow'``: the velocity that advects both is ``-epsilon / cs^2`` times the D2Q9 stencil over the surfactant, and the
+    population feels the Shan-Chen force ``-G_chen psi grad psi``) and ``rocket_yeast_forces_only.py`` (``mode='forces'``: the
+    velocity is the sum of a surface force over ``S(c)`` and a pressure force over the population).  ``run(n)`` advances both
+    with one launch per time step and no host wait (``lb_run_rocket``: the stencil operands of a workgroup's rows and their halo in
+    LDS; ``set_variant(0)``: two launches, the densities through memory; the same bits); the phase methods run the reference's
+    stages one by one and equal it bitwise.  Arrays are shaped like the reference's, ``(nx, ny, 2[, 9])`` in Fortran order with
+    the population at index 0 and the surfactant at 1; ``u``, ``v``, ``psi`` / ``S`` and the forces are ``(nx, ny)``."""
+    MODES = {"flow": _native.LB_ROCKET_FLOW, "forces": _native.LB_ROCKET_FORCES}
+    PARAMS = ("G", "G_c", "epsilon", "rho_o", "G_chen", "c_o", "alpha")
+    _STACKED = ("f", "feq", "rho")
+    _OWN = ("psi", "S", "pseudo_force_x", "pseudo_force_y", "surface_force_x", "surface_force_y")
+
+    def __init__(self, nx, ny, omega, omega_c, mode="flow", device=0, planar=None):
+        if mode not in self.MODES:
+            raise ValueError("mode must be 'flow' or 'forces'")
+        self.nx, self.ny, self.num_populations, self.num_jumpers = int(nx), int(ny), 2, NUM_JUMPERS
+        self.omega, self.omega_c, self.mode = float(omega), float(omega_c), mode
+        self.members = [Simulation(nx, ny, om, bc="periodic", semantics="rocket", device=device, planar=planar) for om in (omega, omega_c)]
+        self._lib = _native.lib()
+        self._handles = (ct.c_void_p * 2)(*[m._h for m in self.members])
+        self.params = dict(G=0., G_c=0., epsilon=0., rho_o=1., G_chen=0., c_o=1., alpha=1.)
+        self.set_params()
+
+    close, sync, _per_field = Coupled_Scalars.close, Coupled_Scalars.sync, Coupled_Scalars._per_field
+    set_f, set_fields, init_pop = Coupled_Scalars.set_f, Coupled_Scalars.set_fields, Coupled_Scalars.init_pop
+    move, move_bcs, update_hydro, update_feq = Coupled_Scalars.move, Coupled_Scalars.move_bcs, Coupled_Scalars.update_hydro, Coupled_Scalars.update_feq
+    check = Coupled_Scalars.check
+
+    def set_params(self, **kw):
+        """G, G_c (growth and secretion rate per step), epsilon, rho_o, G_chen, c_o, alpha: float32, stored with the first member."""
+        for k in kw:
+            if k not in self.PARAMS:
+                raise TypeError("unknown parameter %r (one of %s)" % (k, ", ".join(self.PARAMS)))
+        self.params.update({k: float(np.float32(v)) for k, v in kw.items()})
+        p = _native.RocketParams(self.MODES[self.mode], *[self.params[k] for k in self.PARAMS])
+        check(self._lib.lb_set_rocket(self._handles, 2, ct.byref(p)))
+
+    def get_params(self):
+        p = _native.RocketParams()
+        check(self._lib.lb_get_rocket(self.members[0]._h, ct.byref(p)))
+        return dict(mode=[k for k, v in self.MODES.items() if v == p.mode][0], **{k: getattr(p, k) for k in self.PARAMS})
+
+    def get_fields(self, which=("f", "feq", "rho", "u", "v")):
+        """f, feq: (nx, ny, 2, 9); rho: (nx, ny, 2); u, v: (nx, ny); 'psi' and 'pseudo_force_x/y' (flow), 'S',
+        'surface_force_x/y' and 'pseudo_force_x/y' = the pressure force (forces): (nx, ny), those of the last step."""
+        out = {}
+        stacked = tuple(k for k in which if k in self._STACKED)
+        if stacked:
+            per = [m.get_fields(stacked) for m in self.members]
+            for k in stacked:
+                out[k] = np.asfortranarray(np.stack([g[k] for g in per], axis=2))
+        shared = tuple(k for k in which if k in ("u", "v"))
+        if shared:
+            out.update(self.members[0].get_fields(shared))
+        own = [k for k in which if k in self._OWN]
+        if own:
+            for k in own:
+                out[k] = np.zeros((self.nx, self.ny), np.float32, order="F")
+            ptr = lambda *ks: next((out[k].ctypes.data for k in ks if k in out), None)
+            check(self._lib.lb_get_rocket_fields(self._handles, 2, ptr("psi", "S"), ptr("pseudo_force_x"), ptr("pseudo_force_y"),
+                                                 ptr("surface_force_x"), ptr("surface_force_y")))
+            if "psi" in out and "S" in out:
+                out["S"][...] = out["psi"]
+        return out
+
+    # -- the reference's stages that involve both lattices, un-fused -----------------------------------------------------------
+    def update_velocity(self):
+        check(self._lib.lb_update_velocity_rocket(self._handles, 2))
+        self.sync()
+
+    def update_forces(self):
+        check(self._lib.lb_update_forces_rocket(self._handles, 2))
+        self.sync()
+
+    def collide_particles(self):
+        check(self._lib.lb_collide_rocket(self._handles, 2))
+        self.sync()
+
+    def step_phases(self):
+        """One time step as the reference's run loop makes it, stage by stage (each call waits): the velocity before the forces
+        in mode 'flow', from them in mode 'forces'."""
+        self.move()
+        self.move_bcs()
+        self.update_hydro()
+        if self.mode == "flow":
+            self.update_velocity()
+            self.update_forces()
+        else:
+            self.update_forces()
+            self.update_velocity()
+        self.update_feq()
+        self.collide_particles()
+
+    # -- the hot path -----------------------------------------------------------------------------------------------------
+    def run(self, num_iterations, wait=True):
+        check(self._lib.lb_run_rocket(self._handles, 2, int(num_iterations)))
+        if wait:
+            self.sync()
+
+    def step(self):
+        self.run(1)
+
+    def set_variant(self, variant):
+        for m in self.members:
+            m.set_variant(variant)
+
+    def hot_kernel(self):
+        return self.members[0].hot_kernel()
+
+    def use_stream(self, hip_stream):
+        for m in self.members:
+            m.use_stream(hip_stream)
+
+    # -- checkpoints: every member's arrays under 'm<i>_', the parameters with the first -----------------------------------------
+    def save_checkpoint(self, path):
+        d = {"mode": np.array(self.mode), "params": np.array([self.params[k] for k in self.PARAMS], np.float32)}
+        for i, m in enumerate(self.members):
+            for k, a in m.checkpoint_arrays().items():
+                d["m%d_%s" % (i, k)] = a
+        np.savez(Simulation._ckpt_path(path), **d)
+
+    @classmethod
+    def from_checkpoint(cls, path, device=0):
+        with np.load(Simulation._ckpt_path(path)) as d:
+            per = [{k[len("m%d_" % i):]: d[k] for k in d.files if k.startswith("m%d_" % i)} for i in range(2)]
+            mode, params = str(d["mode"]), [float(x) for x in d["params"]]
+        out = cls(int(per[0]["nx"]), int(per[0]["ny"]), float(per[0]["omega"]), float(per[1]["omega"]), mode=mode, device=device)
+        out.set_params(**dict(zip(cls.PARAMS, params)))
+        for m, p in zip(out.members, per):
+            m.restore_arrays(p)
+        out.update_forces()             # psi / S and the forces of the last step follow from its densities
+        return out

@@ -91,6 +91,10 @@ class Simulation(object):
                (set_interactions) and reactions (set_reactions); bc='periodic' or 'zero_gradient'; whole grid, at least 3x3, no
                obstacles.  One launch per step (set_variant(0): two).  A handle on its own is a set of one; LB_D2Q9.coupled.Shan_Chen_Fluids advances several.
                get_fields keys are those of 'porous'.
+               'rocket': one of the two lattices of a surfactant-propelled colony (the reference's rocket_yeast/rocket_yeast.cl and
+               rocket_yeast_forces_only.cl): a scalar lattice with the linear equilibrium whose velocity the set computes from the
+               surfactant; bc='periodic', whole grid, at least 3x3.  It advances only as a set of two:
+               LB_D2Q9.coupled.Surfactant_Colony (run() and collide_particles() on the member itself are refused).
         :param planar: device layout of the lattices: False = the nine planes of a row stored together (default),
                True = each plane contiguous (LB_FLAG_PLANAR); results are identical.  None: environment variable
                LB_LAYOUT=planar selects True (tuning aid).
@@ -122,7 +126,7 @@ class Simulation(object):
                    (_native.LB_FLAG_EAGER_MACRO if self.eager_macro else 0))
         sem = {"opencl": _native.LB_SEM_OPENCL, "cython": _native.LB_SEM_CYTHON, "d2q9i": _native.LB_SEM_OPENCL_D2Q9I,
                "diffusion": _native.LB_SEM_DIFFUSION, "multifield": _native.LB_SEM_MULTIFIELD, "poisson": _native.LB_SEM_POISSON,
-               "porous": _native.LB_SEM_POROUS, "multifluid": _native.LB_SEM_MULTIFLUID}
+               "porous": _native.LB_SEM_POROUS, "multifluid": _native.LB_SEM_MULTIFLUID, "rocket": _native.LB_SEM_ROCKET}
         if semantics not in sem:
             raise ValueError("semantics must be one of %s" % sorted(sem))
         p.semantics = sem[semantics]
@@ -241,7 +245,7 @@ class Simulation(object):
         unchanged; the pass advances at most (n - 7) // 4 steps, a runner-up's longer comparison included) and keeps the
         fastest for this grid; shorter runs use the size heuristic (or call autotune())."""
         n = int(num_iterations)
-        if wait and n > 0 and self.semantics not in ("diffusion", "multifield", "poisson", "porous", "multifluid"):      # (a scalar lattice's kernel is the planner's size rule: no tuning pass)
+        if wait and n > 0 and self.semantics not in ("diffusion", "multifield", "poisson", "porous", "multifluid", "rocket"):      # (a scalar lattice's kernel is the planner's size rule: no tuning pass)
             # (the pass costs 361 steps, 889 on grids <= 768^2, some of them in configurations several times slower than
             #  the best: it only pays for itself in a run several times that long)
             used = self._lib.lb_autotune_quick(self._h, (n - 7) // 4)
@@ -401,7 +405,7 @@ class Simulation(object):
 
     def restore_arrays(self, d):
         self._check_compatible(d)
-        if self.semantics not in ("diffusion", "multifield", "poisson", "porous", "multifluid"):   # (a scalar lattice has no obstacles, nor have the porous medium and the fluids of a set)
+        if self.semantics not in ("diffusion", "multifield", "poisson", "porous", "multifluid", "rocket"):   # (a scalar lattice has no obstacles, nor have the porous medium and the fluids of a set)
             self.set_obstacle_mask(d["mask"] if d["mask"].size else None)
         if "mask_halo_south" in d:
             so, no = d["mask_halo_south"], d["mask_halo_north"]

@@ -9,7 +9,7 @@
 // Small kernels are emitted by the one unit that includes their header: kernels_phases.h + kernels_check.h by lb_hip.cpp,
 // kernels_halo.h by slab.cpp, kernels_scalar.h by scalar.cpp (its health check's first pass only: check_reduce.h is shared, the folding
 // pass is lb_hip.cpp's), kernels_multifield.h by multifield.cpp, kernels_poisson.h by poisson.cpp, kernels_porous.h by porous.cpp,
-// kernels_multifluid.h by multifluid.cpp.
+// kernels_multifluid.h by multifluid.cpp, kernels_rocket.h by rocket.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -29,6 +29,7 @@
 #include "poisson_launch.h"     // the LB Poisson solver (LB_SEM_POISSON): PsExtra, PsState, its launchers
 #include "porous_launch.h"      // forced flow in a porous medium (LB_SEM_POROUS): PmExtra, its launchers
 #include "multifluid_launch.h"  // multicomponent Shan-Chen fluids (LB_SEM_MULTIFLUID): McArgs, their launchers
+#include "rocket_launch.h"      // surfactant-propelled colonies (LB_SEM_ROCKET): RyArgs, their launchers
 
 namespace {
 
@@ -67,6 +68,10 @@ struct lb_sim : PlanInputs {
     McInter mc_inter[MC_MAX_INTER] = {};
     McReact mc_react[MC_MAX_REACT] = {};
     int mc_n_inter = 0, mc_n_react = 0;
+    // surfactant-propelled colonies (LB_SEM_ROCKET; rocket_launch.h): the parameters of a set and what its last step left live in its
+    // first handle -- pm_G the pseudo-force (FLOW) / the pressure force (FORCES), pm_ub the surface force, ry_op psi / S
+    lb_rocket_params ry = {LB_ROCKET_FLOW, 0.f, 0.f, 0.f, 1.f, 0.f, 1.f, 1.f};
+    float *ry_op = nullptr;     // [H][pitch]
     uint8_t *mask_raw = nullptr, *mask = nullptr;   // [H+2*MASK_GHOST][pitch] + guards; mask -> row 0
     bool feq_valid = false;     // feq buffer consistent with rho,u,v
     bool macro_valid = true;    // rho,u,v hold the last step's fields (false: to be rebuilt from the populations, ensure_macro)
@@ -139,8 +144,15 @@ int fail(int code, const char *fmt, ...);       // records the message lb_last_e
 // So are the porous-medium fluid (LB_SEM_POROUS) and the fluids of a multicomponent set (LB_SEM_MULTIFLUID), which are refused here under their own names.
 #define SCALAR_UNSUPPORTED(s, name)                                                                         \
     do {                                                                                                    \
+        NOT_ROCKET(s, name);                                                                                \
         if ((s) && (s)->scalar()) return fail(LB_ERR_STATE, "%s is not available on a scalar lattice (LB_SEM_DIFFUSION)", name); \
         NOT_POROUS(s, name);                                                                                \
+    } while (0)
+// A lattice of a surfactant-propelled colony (LB_SEM_ROCKET) is a scalar lattice that is refused under its own name, and by more calls:
+// its velocity is the set's own, its collision needs both members.
+#define NOT_ROCKET(s, name)                                                                                 \
+    do {                                                                                                    \
+        if ((s) && (s)->rocket()) return fail(LB_ERR_STATE, "%s is not available on a lattice of a surfactant-propelled colony (LB_SEM_ROCKET)", name); \
     } while (0)
 #define NOT_POROUS(s, name)                                                                                 \
     do {                                                                                                    \

@@ -334,6 +334,16 @@ int lb_create(const lb_params *p, lb_sim **out)
         if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "a fluid of a multicomponent set (LB_SEM_MULTIFLUID) has no halo interface (LB_FLAG_HALO)");
         if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "a fluid of a multicomponent set (LB_SEM_MULTIFLUID) runs on a GPU only (no CPU backend)");
     }
+    if (p->semantics == LB_SEM_ROCKET) {
+        // a lattice of a surfactant-propelled colony: a whole-grid GPU scalar lattice, refused likewise
+        if (p->bc_mode != LB_BC_PERIODIC)
+            return fail(LB_ERR_ARG, "a lattice of a surfactant-propelled colony (LB_SEM_ROCKET) takes the family LB_BC_PERIODIC only (box boundaries are not built)");
+        if (p->nx < 3 || p->ny < 3)
+            return fail(LB_ERR_ARG, "a lattice of a surfactant-propelled colony (LB_SEM_ROCKET) needs a cell with eight neighbours: grid must be at least 3x3 (got %dx%d)", p->nx, p->ny);
+        if (p->local_ny != p->ny || p->y0 != 0) return fail(LB_ERR_ARG, "a lattice of a surfactant-propelled colony (LB_SEM_ROCKET) owns its whole grid: no slabs");
+        if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "a lattice of a surfactant-propelled colony (LB_SEM_ROCKET) has no halo interface (LB_FLAG_HALO)");
+        if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "a lattice of a surfactant-propelled colony (LB_SEM_ROCKET) runs on a GPU only (no CPU backend)");
+    }
     if (p->bc_mode == LB_BC_OPEN && p->semantics != LB_SEM_DIFFUSION)
         return fail(LB_ERR_ARG, "LB_BC_OPEN exists for scalar lattices (LB_SEM_DIFFUSION) only");
     if (p->bc_mode == LB_BC_BOX && p->semantics != LB_SEM_MULTIFIELD)
@@ -364,7 +374,8 @@ int lb_create(const lb_params *p, lb_sim **out)
         if (r != 0) return fail(LB_ERR_ARG, "reserved fields must be zero");
     if (p->flags & ~(LB_FLAG_HALO | LB_FLAG_PLANAR | LB_FLAG_EAGER_MACRO)) return fail(LB_ERR_ARG, "unknown flags 0x%x", p->flags);
     if (p->semantics != LB_SEM_OPENCL && p->semantics != LB_SEM_CYTHON && p->semantics != LB_SEM_OPENCL_D2Q9I && p->semantics != LB_SEM_DIFFUSION &&
-        p->semantics != LB_SEM_MULTIFIELD && p->semantics != LB_SEM_POISSON && p->semantics != LB_SEM_POROUS && p->semantics != LB_SEM_MULTIFLUID)
+        p->semantics != LB_SEM_MULTIFIELD && p->semantics != LB_SEM_POISSON && p->semantics != LB_SEM_POROUS && p->semantics != LB_SEM_MULTIFLUID &&
+        p->semantics != LB_SEM_ROCKET)
         return fail(LB_ERR_ARG, "unknown semantics %d", p->semantics);
     if (p->semantics == LB_SEM_OPENCL_D2Q9I &&
         (p->bc_mode != LB_BC_PIPE || p->local_ny != p->ny || (p->flags & LB_FLAG_HALO)))
@@ -477,13 +488,19 @@ int lb_create(const lb_params *p, lb_sim **out)
         CREATE_TRY(hipMemcpy(s->ps_state, &fresh, sizeof(fresh), hipMemcpyHostToDevice));
         s->bytes += fld_bytes + part_bytes + sizeof(PsState);
     }
-    if (s->porous() || s->multifluid()) {
+    if (s->porous() || s->multifluid() || s->rocket()) {
         s->diag = 0;                                // (the diagnostic word of the flow kernels means nothing here)
         for (float **q : {&s->pm_G[0], &s->pm_G[1], &s->pm_ub[0], &s->pm_ub[1]}) {
             CREATE_TRY(hipMalloc(q, fld_bytes));
             CREATE_TRY(hipMemsetAsync(*q, 0, fld_bytes, s->stream));
         }
         s->bytes += 4 * fld_bytes;
+    }
+    if (s->rocket()) {
+        // (every handle can be a set's first: psi / S and the forces of the last step live there)
+        CREATE_TRY(hipMalloc(&s->ry_op, fld_bytes));
+        CREATE_TRY(hipMemsetAsync(s->ry_op, 0, fld_bytes, s->stream));
+        s->bytes += fld_bytes;
     }
     CREATE_TRY(hipMalloc(&s->vi_corner, 8 * sizeof(float)));
     CREATE_TRY(hipMemsetAsync(s->vi_corner, 0, 8 * sizeof(float), s->stream));
@@ -536,7 +553,7 @@ int lb_destroy(lb_sim *s)
     if (s->peer_flags) (void)hipFree(s->peer_flags);
     if (s->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(s->comm);
     for (float *p : {s->lat[0], s->lat[1], s->feq, s->rho, s->u, s->v, s->halo_buf, s->vi_corner, s->stage, s->ad_edge, s->ps_source, s->ps_part,
-                     s->pm_G[0], s->pm_G[1], s->pm_ub[0], s->pm_ub[1], s->pm_field[0], s->pm_field[1]})
+                     s->pm_G[0], s->pm_G[1], s->pm_ub[0], s->pm_ub[1], s->pm_field[0], s->pm_field[1], s->ry_op})
         if (p) (void)hipFree(p);
     if (s->mask_raw) (void)hipFree(s->mask_raw);
     if (s->check_part) (void)hipFree(s->check_part);
@@ -594,6 +611,8 @@ int lb_set_variant(lb_sim *s, int variant)
         return fail(LB_ERR_STATE, "lb_set_variant: a porous-medium fluid (LB_SEM_POROUS) takes the variants -1 and 0 only: k_pm_step, no tiles");
     if (s->multifluid() && (variant < -1 || variant > 1))
         return fail(LB_ERR_STATE, "lb_set_variant: a fluid of a multicomponent set (LB_SEM_MULTIFLUID) takes the variants -1 (the planner's choice), 0 (the two-launch step k_mc_moments + k_mc_collide) and 1 (the one-launch step k_mc_step) only");
+    if (s->rocket() && (variant < -1 || variant > 1))
+        return fail(LB_ERR_STATE, "lb_set_variant: a lattice of a surfactant-propelled colony (LB_SEM_ROCKET) takes the variants -1 (the planner's choice), 0 (the two-launch step k_ry_moments + k_ry_collide) and 1 (the one-launch step k_ry_step) only");
     s->variant = variant;
     return LB_OK;
 }
@@ -881,6 +900,7 @@ int lb_set_mask_halo(lb_sim *s, const int32_t *south_rows, const int32_t *north_
     do {                                                                                                     \
         if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
         NOT_POROUS(s, name);                                                                                 \
+        NOT_ROCKET(s, name);                                                                                 \
         if (!(s)->scalar()) return fail(LB_ERR_STATE, "%s is for scalar lattices (LB_SEM_DIFFUSION)", name); \
     } while (0)
 
@@ -987,6 +1007,7 @@ int lb_set_velocity_from(lb_sim *s, lb_sim *flow)
     do {                                                                                                     \
         if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
         NOT_POROUS(s, name);                                                                                 \
+        NOT_ROCKET(s, name);                                                                                 \
         if (!(s)->poisson()) return fail(LB_ERR_STATE, "%s is for the LB Poisson solver (LB_SEM_POISSON)", name); \
     } while (0)
 
@@ -1122,6 +1143,7 @@ int lb_gradient(lb_sim *s, float inv_two_dx, float *ddx, float *ddy)
 #define NEED_POROUS(s, name)                                                                                 \
     do {                                                                                                     \
         if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
+        NOT_ROCKET(s, name);                                                                                 \
         if ((s)->multifluid()) return fail(LB_ERR_STATE, "%s is not available on a fluid of a multicomponent set (LB_SEM_MULTIFLUID)", name); \
         if (!(s)->porous()) return fail(LB_ERR_STATE, "%s is for forced flow in a porous medium (LB_SEM_POROUS)", name); \
     } while (0)
@@ -1129,6 +1151,7 @@ int lb_gradient(lb_sim *s, float inv_two_dx, float *ddx, float *ddy)
 #define NEED_FORCED(s, name)                                                                                 \
     do {                                                                                                     \
         if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
+        NOT_ROCKET(s, name);                                                                                 \
         if (!(s)->porous() && !(s)->multifluid())                                                            \
             return fail(LB_ERR_STATE, "%s is for forced flow in a porous medium (LB_SEM_POROUS) and the fluids of a multicomponent set (LB_SEM_MULTIFLUID)", name); \
     } while (0)
@@ -1382,6 +1405,7 @@ int lb_collide_particles(lb_sim *s)
     if (!s) return fail(LB_ERR_ARG, "null handle");
     int rc = need_single_slab(s, "lb_collide_particles");
     if (rc) return rc;
+    NOT_ROCKET(s, "lb_collide_particles (the collision needs both members: lb_collide_rocket)");
     if (!s->feq) return fail(LB_ERR_STATE, "lb_collide_particles before any lb_update_feq");
     if (s->multifield()) return lb_collide_coupled(&s, 1);
     DeviceGuard guard(s->p.device);
@@ -1448,6 +1472,7 @@ int lb_run(lb_sim *s, int n_steps)
     if (!s) return fail(LB_ERR_ARG, "null handle");
     if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
     if (s->stepping) return fail(LB_ERR_STATE, "lb_run between lb_step_boundary and lb_step_finish");
+    NOT_ROCKET(s, "lb_run (a colony advances as a set of two: lb_run_rocket)");
     DeviceGuard guard(s->p.device);
     if (s->multifield()) return lb_run_coupled(&s, 1, n_steps);
     if (s->poisson()) return run_poisson(s, n_steps);
@@ -1549,6 +1574,7 @@ static int coupled_release(lb_sim **f, int count)
 int lb_run_coupled(lb_sim **fields, int count, int n_steps)
 {
     for (int i = 0; fields && i < count; ++i) NOT_POROUS(fields[i], "lb_run_coupled");
+    for (int i = 0; fields && i < count; ++i) NOT_ROCKET(fields[i], "lb_run_coupled");
     int rc = coupled_members(fields, count, "lb_run_coupled");
     if (rc) return rc;
     if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
@@ -1602,6 +1628,7 @@ static int fluid_members(lb_sim **f, int count, const char *what)
     for (int i = 0; i < count; ++i) {
         lb_sim *s = f[i];
         if (!s) return fail(LB_ERR_ARG, "null handle in the set of fluids");
+        NOT_ROCKET(s, what);
         if (s->cpu || !s->multifluid()) return fail(LB_ERR_STATE, "%s is for the fluids of a multicomponent set (LB_SEM_MULTIFLUID)", what);
         if (s->p.nx != f[0]->p.nx || s->p.ny != f[0]->p.ny || s->p.bc_mode != f[0]->p.bc_mode || s->p.device != f[0]->p.device ||
             (s->p.flags & LB_FLAG_PLANAR) != (f[0]->p.flags & LB_FLAG_PLANAR))
@@ -1713,6 +1740,7 @@ int lb_set_reactions(lb_sim **fluids, int count, const lb_fluid_reaction *table,
 int lb_get_interactions(lb_sim *first, lb_interaction *table, int *n)
 {
     if (!first) return fail(LB_ERR_ARG, "null handle");
+    NOT_ROCKET(first, "lb_get_interactions");
     if (first->cpu || !first->multifluid()) return fail(LB_ERR_STATE, "lb_get_interactions is for the fluids of a multicomponent set (LB_SEM_MULTIFLUID)");
     if (n) *n = first->mc_n_inter;
     for (int t = 0; table && t < first->mc_n_inter; ++t) {
@@ -1725,6 +1753,7 @@ int lb_get_interactions(lb_sim *first, lb_interaction *table, int *n)
 int lb_get_reactions(lb_sim *first, lb_fluid_reaction *table, int *n)
 {
     if (!first) return fail(LB_ERR_ARG, "null handle");
+    NOT_ROCKET(first, "lb_get_reactions");
     if (first->cpu || !first->multifluid()) return fail(LB_ERR_STATE, "lb_get_reactions is for the fluids of a multicomponent set (LB_SEM_MULTIFLUID)");
     if (n) *n = first->mc_n_react;
     for (int t = 0; table && t < first->mc_n_react; ++t) {
@@ -1769,6 +1798,152 @@ int lb_react_fluids(lb_sim **fluids, int count)
     lbk_mc_react(count, fluids[0]->stream, m);
     HIP_TRY(hipGetLastError());
     return coupled_release(fluids, count);
+}
+
+// ---- surfactant-propelled colonies: the two members of a set, checked alike for every set call -----------------------------------
+static int rocket_members(lb_sim **f, int count, const char *what)
+{
+    if (!f) return fail(LB_ERR_ARG, "%s: null handle array", what);
+    if (count != 2) return fail(LB_ERR_ARG, "%s takes exactly 2 handles, the population and the surfactant (got a count of %d)", what, count);
+    for (int i = 0; i < 2; ++i) {
+        lb_sim *s = f[i];
+        if (!s) return fail(LB_ERR_ARG, "%s: null handle in the set", what);
+        if (s->cpu || !s->rocket()) return fail(LB_ERR_ARG, "%s: handle %d is not a lattice of a surfactant-propelled colony (a non-rocket handle: LB_SEM_ROCKET is required)", what, i);
+        if (s->stepping) return fail(LB_ERR_STATE, "%s inside a split step", what);
+    }
+    if (f[0] == f[1]) return fail(LB_ERR_ARG, "%s: a handle appears twice in the set", what);
+    if (f[1]->p.nx != f[0]->p.nx || f[1]->p.ny != f[0]->p.ny || f[1]->p.device != f[0]->p.device ||
+        (f[1]->p.flags & LB_FLAG_PLANAR) != (f[0]->p.flags & LB_FLAG_PLANAR))
+        return fail(LB_ERR_ARG, "%s: the two lattices of a colony must share grid (geometry), layout flag and device", what);
+    return LB_OK;
+}
+
+// (src = the current lattice, dst = the other one: what the fused steps read and write; the stages set dst themselves.  Every derived
+//  scalar is one float32 operation, here and nowhere else: rocket_launch.h)
+static RyArgs rocket_args(lb_sim **f)
+{
+    RyArgs m = {};
+    for (int i = 0; i < 2; ++i) m.a[i] = step_args(f[i], 0, 1, f[i]->H);
+    const lb_rocket_params &r = f[0]->ry;
+    const float cs = (float)(1.0 / sqrt(3.0));          // np.float32(1. / np.sqrt(3))
+    const float cs2 = cs * cs;
+    m.inv_cs2 = (float)(1.0 / (double)cs2);             // the kernels' `1. / (cs * cs)`: a double quotient rounded once
+    m.G = r.G; m.Gc = r.G_c;
+    m.ke = (-r.epsilon) * m.inv_cs2;
+    m.ngc = -r.G_chen;
+    m.rho_o = r.rho_o; m.c_o = r.c_o; m.alpha = r.alpha;
+    m.op = f[0]->ry_op;
+    m.Fx = f[0]->pm_G[0]; m.Fy = f[0]->pm_G[1];
+    m.Sx = f[0]->pm_ub[0]; m.Sy = f[0]->pm_ub[1];
+    return m;
+}
+
+static bool ry_finite(float x) { return fabsf(x) <= 3.0e38f; }      // (false for NaN)
+
+int lb_set_rocket(lb_sim **fields, int count, const lb_rocket_params *params)
+{
+    int rc = rocket_members(fields, count, "lb_set_rocket");
+    if (rc) return rc;
+    if (!params) return fail(LB_ERR_ARG, "lb_set_rocket: null parameters");
+    const lb_rocket_params &r = *params;
+    if (r.mode != LB_ROCKET_FLOW && r.mode != LB_ROCKET_FORCES) return fail(LB_ERR_ARG, "lb_set_rocket: unknown mode %d (LB_ROCKET_FLOW and LB_ROCKET_FORCES are built)", r.mode);
+    for (float x : {r.G, r.G_c, r.epsilon, r.rho_o, r.G_chen, r.c_o, r.alpha})
+        if (!ry_finite(x)) return fail(LB_ERR_ARG, "lb_set_rocket: the parameters must be finite");
+    if (r.mode == LB_ROCKET_FLOW && r.rho_o == 0.f) return fail(LB_ERR_ARG, "lb_set_rocket: LB_ROCKET_FLOW needs rho_o != 0");
+    if (r.mode == LB_ROCKET_FORCES && r.c_o == 0.f) return fail(LB_ERR_ARG, "lb_set_rocket: LB_ROCKET_FORCES needs c_o != 0");
+    fields[0]->ry = r;
+    return LB_OK;
+}
+
+int lb_get_rocket(lb_sim *first, lb_rocket_params *params)
+{
+    if (!first || !params) return fail(LB_ERR_ARG, "null argument");
+    if (first->cpu || !first->rocket()) return fail(LB_ERR_STATE, "lb_get_rocket is for the lattices of a surfactant-propelled colony (LB_SEM_ROCKET)");
+    *params = first->ry;
+    return LB_OK;
+}
+
+int lb_run_rocket(lb_sim **fields, int count, int n_steps)
+{
+    int rc = rocket_members(fields, count, "lb_run_rocket");
+    if (rc) return rc;
+    if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
+    if (n_steps == 0) return LB_OK;
+    lb_sim *s0 = fields[0];
+    DeviceGuard guard(s0->p.device);
+    if ((rc = coupled_join(fields, 2))) return rc;
+    const int mode = s0->ry.mode;
+    for (int it = 0; it < n_steps; ++it) {
+        const RyArgs m = rocket_args(fields);
+        const bool last = it == n_steps - 1;            // the last launch stores rho, u, v, psi / S and the forces
+        if (rocket_one_launch(s0)) {                    // (the set's first handle chooses: lb_set_variant; plan.cpp)
+            lbk_ry_step(mode, last, s0->stream, m);
+            HIP_TRY(hipGetLastError());
+        } else {
+            lbk_ry_moments(s0->stream, m);
+            HIP_TRY(hipGetLastError());
+            lbk_ry_collide(mode, last, s0->stream, m);
+            HIP_TRY(hipGetLastError());
+        }
+        for (int i = 0; i < 2; ++i) fields[i]->cur ^= 1;
+    }
+    for (int i = 0; i < 2; ++i) {
+        fields[i]->feq_valid = false;
+        fields[i]->macro_valid = true;
+    }
+    return coupled_release(fields, 2);
+}
+
+int lb_update_velocity_rocket(lb_sim **fields, int count)
+{
+    int rc = rocket_members(fields, count, "lb_update_velocity_rocket");
+    if (rc) return rc;
+    DeviceGuard guard(fields[0]->p.device);
+    if ((rc = coupled_join(fields, 2))) return rc;
+    lbk_ry_velocity(fields[0]->ry.mode, fields[0]->stream, rocket_args(fields));
+    HIP_TRY(hipGetLastError());
+    for (int i = 0; i < 2; ++i) fields[i]->feq_valid = false;
+    return coupled_release(fields, 2);
+}
+
+int lb_update_forces_rocket(lb_sim **fields, int count)
+{
+    int rc = rocket_members(fields, count, "lb_update_forces_rocket");
+    if (rc) return rc;
+    DeviceGuard guard(fields[0]->p.device);
+    if ((rc = coupled_join(fields, 2))) return rc;
+    lbk_ry_forces(fields[0]->ry.mode, fields[0]->stream, rocket_args(fields));
+    HIP_TRY(hipGetLastError());
+    return coupled_release(fields, 2);
+}
+
+int lb_collide_rocket(lb_sim **fields, int count)
+{
+    int rc = rocket_members(fields, count, "lb_collide_rocket");
+    if (rc) return rc;
+    for (int i = 0; i < 2; ++i)
+        if (!fields[i]->feq) return fail(LB_ERR_STATE, "lb_collide_rocket before lb_update_feq on both members");
+    DeviceGuard guard(fields[0]->p.device);
+    if ((rc = coupled_join(fields, 2))) return rc;
+    RyArgs m = rocket_args(fields);
+    for (int i = 0; i < 2; ++i) m.a[i].dst = fields[i]->origin(fields[i]->cur);      // relaxed in place
+    lbk_ry_relax(fields[0]->ry.mode, fields[0]->stream, m, fields[0]->feq_origin(), fields[1]->feq_origin());
+    HIP_TRY(hipGetLastError());
+    return coupled_release(fields, 2);
+}
+
+int lb_get_rocket_fields(lb_sim **fields, int count, float *psi_or_S, float *Fx, float *Fy, float *Fsx, float *Fsy)
+{
+    int rc = rocket_members(fields, count, "lb_get_rocket_fields");
+    if (rc) return rc;
+    lb_sim *s = fields[0];
+    DeviceGuard guard(s->p.device);
+    float *out[5] = {psi_or_S, Fx, Fy, Fsx, Fsy};
+    const float *from[5] = {s->ry_op, s->pm_G[0], s->pm_G[1], s->pm_ub[0], s->pm_ub[1]};
+    for (int i = 0; i < 5; ++i)
+        if (out[i] && (rc = copy_plane_d2h(s, out[i], from[i]))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return LB_OK;
 }
 
 // ---- health check ------------------------------------------------------------------------

@@ -483,10 +483,13 @@ static const double SCALAR_TILE_MIN_CELLS = 256.0 * 256.0, SCALAR_TILE_MAX_CELLS
 // one-launch step at every size: on one MI355X it is 1.00-1.21 x the two-launch step at 256^2 ... 8192^2 with one, two and three
 // fluids, but for 0.97 x at 1024^2 with two (profiles/multifluid_bench.txt, tools/multifluid_bench.py) -- no size rule to draw from that.
 bool multifluid_one_launch(const PlanInputs *s) { return s->variant != 0; }
+// Surfactant-propelled colonies: the same two variants.  The planner's choice (-1) is the one-launch step at every size: on one MI355X
+// it is 1.19-1.61 x the two-launch step at 256^2 ... 8192^2 in both modes (profiles/rocket_bench.txt, tools/rocket_bench.py).
+bool rocket_one_launch(const PlanInputs *s) { return s->variant != 0; }
 
 bool scalar_use_tiles(const PlanInputs *s)
 {
-    if (s->multifield() || s->poisson() || s->porous() || s->multifluid()) return false;      // (no tiles for coupled sets, the Poisson solver and the porous-medium fluid: k_mf_step / k_ps_step / k_pm_step, one step per launch)
+    if (s->multifield() || s->poisson() || s->porous() || s->multifluid() || s->rocket()) return false;      // (no tiles for coupled sets, the Poisson solver and the porous-medium fluid: k_mf_step / k_ps_step / k_pm_step, one step per launch)
     if (s->variant >= 0) return (s->variant & LB_VAR_TILES) != 0;
     const double cells = (double)s->p.nx * s->H;
     return cells >= SCALAR_TILE_MIN_CELLS && cells <= SCALAR_TILE_MAX_CELLS;
@@ -551,6 +554,13 @@ void hot_kernel(const PlanInputs *s, char *buf, int buflen)
         }
         snprintf(buf, (size_t)buflen, "k_mc_moments + k_mc_collide (multicomponent Shan-Chen fluids: two launches per step -- pull-stream + densities, then pull-stream + interaction forces + barycentric velocity + Guo-forced collide + reactions)<%s%s>",
                  s->p.bc_mode == LB_BC_PERIODIC ? "PERIODIC" : "ZERO_GRADIENT", s->has_field ? ", FIELD" : "");
+        return;
+    }
+    if (s->rocket()) {
+        if (rocket_one_launch(s))
+            snprintf(buf, (size_t)buflen, "k_ry_step (surfactant-propelled colony: one launch per step -- pull-stream of both lattices + the two stencil operands of the %d owned rows and their halo into LDS, barrier, velocity and forces + linear-equilibrium collide)<PERIODIC>", RY_ROWS);
+        else
+            snprintf(buf, (size_t)buflen, "k_ry_moments + k_ry_collide (surfactant-propelled colony: two launches per step -- pull-stream + densities, then pull-stream + velocity and forces + linear-equilibrium collide)<PERIODIC>");
         return;
     }
     if (s->porous()) {

@@ -32,7 +32,8 @@ struct PlanInputs {
     bool poisson() const { return p.semantics == LB_SEM_POISSON; }       // the LB Poisson solver (kernels_poisson.h)
     bool porous() const { return p.semantics == LB_SEM_POROUS; }         // forced flow in a porous medium (kernels_porous.h): a fluid, not scalar()
     bool multifluid() const { return p.semantics == LB_SEM_MULTIFLUID; } // one fluid of a set of Shan-Chen fluids (kernels_multifluid.h): a fluid, not scalar()
-    bool scalar() const { return p.semantics == LB_SEM_DIFFUSION || multifield() || poisson(); }  // a scalar lattice (kernels_scalar.h), on its own or coupled, or the Poisson solver's
+    bool rocket() const { return p.semantics == LB_SEM_ROCKET; }         // one lattice of a surfactant-propelled colony (kernels_rocket.h): a scalar lattice whose velocity the set computes
+    bool scalar() const { return p.semantics == LB_SEM_DIFFUSION || multifield() || poisson() || rocket(); }  // a scalar lattice (kernels_scalar.h), on its own or coupled, or the Poisson solver's
     bool multi_slab() const { return H != p.ny || (p.flags & LB_FLAG_HALO); }
     int agreed_h() const { return min_h > 0 ? min_h : H; }      // the height all ranks decide on
 };
@@ -91,6 +92,8 @@ void hot_kernel(const PlanInputs *s, char *buf, int buflen);
 bool scalar_use_tiles(const PlanInputs *s);
 // a set of Shan-Chen fluids (s = its first handle): the one-launch step k_mc_step, not k_mc_moments + k_mc_collide
 bool multifluid_one_launch(const PlanInputs *s);
+// a surfactant-propelled colony (s = its first handle): the one-launch step k_ry_step, not k_ry_moments + k_ry_collide
+bool rocket_one_launch(const PlanInputs *s);
 int scalar_tile_shape(const PlanInputs *s);
 int scalar_next_advance(const PlanInputs *s, int left);
 

@@ -34,4 +34,6 @@ constexpr int deep_strips(int nx, int D) { return (nx + deep_valid(D) - 1) / dee
 
 constexpr int TILE_T = 4;                   // time steps per pass of the LDS tiles = halo width (kernels_tile.h)
 
+constexpr int RY_ROWS = 10;                 // rows of a 256-cell tile a workgroup of k_ry_step owns (kernels_rocket.h, rocket.cpp)
+
 }  // namespace

@@ -131,7 +131,7 @@ typedef enum {
                                  field; the last launch of a run also stores rho, u, v, the total force and the barycentric
                                  velocity, + 28 B).  float32 like every lattice here (the reference's fork computes in
                                  float64).  lb_set_variant takes -1 and 0 only. */
-    LB_SEM_MULTIFLUID = 9     /* (8 is not assigned either: tests/test_porous_cpu.py holds lb_create to refusing semantics 8 in a
+    LB_SEM_MULTIFLUID = 9,    /* (8 is not assigned either: tests/test_porous_cpu.py holds lb_create to refusing semantics 8 in a
                                  periodic box as unknown.)  MULTICOMPONENT SHAN-CHEN FLUIDS: LB_D2Q9/multicomponent_multiphase/multi.cl
                                  driven as multi.py's Simulation_Runner.run does -- 1 ... 3 D2Q9 BGK fluids on one grid, one handle
                                  each, relaxing towards an equilibrium at the barycentric velocity of all of them, with Guo forcing by
@@ -139,6 +139,16 @@ typedef enum {
                                  neighbours' density: the step is not local to the cell), and with mass-exchange reactions; families
                                  LB_BC_PERIODIC and LB_BC_ZERO_GRADIENT, nx, ny >= 3.  Whole-grid GPU handles without obstacles;
                                  omega, nx, ny are the only lb_params fields read.  lb_run_fluids advances a set (below). */
+    LB_SEM_ROCKET = 11        /* (10 is not assigned either: tests/test_multifluid_cpu.py holds lb_create to refusing semantics 10 in a
+                                 periodic box as unknown.)  SURFACTANT-PROPELLED COLONIES: LB_D2Q9/rocket_yeast/rocket_yeast.cl and
+                                 rocket_yeast_forces_only.cl driven as rocket_yeast.py's Rocket_Yeast.run does -- ONE LATTICE of a set
+                                 of exactly two scalar lattices on one periodic grid, the growing population and the surfactant it
+                                 secretes; the velocity that advects both is a D2Q9 stencil over the surfactant (a Marangoni flow)
+                                 and the population feels a Shan-Chen self-attraction (a second stencil): the step is not local to
+                                 the cell.  A scalar lattice in every respect above (whole-grid GPU handle, linear equilibrium, rho
+                                 always stored, lb_check), except that no call imposes its velocity; family LB_BC_PERIODIC only,
+                                 nx, ny >= 3.  omega, nx, ny are the only lb_params fields read (lb_set_rocket has the rest).
+                                 lb_run_rocket advances a set (below). */
 } lb_semantics;
 
 typedef struct {
@@ -387,6 +397,51 @@ int lb_get_reactions(lb_sim *first, lb_fluid_reaction *table, int *n);      /* t
 int lb_update_forces_fluids(lb_sim **fluids, int count);    /* stage 3 */
 int lb_update_bary_fluids(lb_sim **fluids, int count);      /* stage 4 */
 int lb_react_fluids(lb_sim **fluids, int count);            /* stage 7 */
+
+/* ---- surfactant-propelled colonies (LB_SEM_ROCKET; LB_ERR_ARG, with the reason, for a count other than 2, a handle given twice,
+ *      a handle of another semantics or members of different geometry, layout or device) ---------------------------------------
+ * A SET is exactly two handles of one geometry, layout flag and device: fields[0] the population p, fields[1] the surfactant c,
+ * each with its own omega.  With grad_w a (x) = sum_k w_k c_k a(x + c_k), the D2Q9 stencil with periodic wrap, and
+ * 1 / cs^2 = float32(1. / (cs cs)) of cs = float32(1 / sqrt(3)), one time step (rocket_yeast.py:469-483) is
+ *   1. both lattices stream periodically (move_periodic, then the copy back)                                  lb_move
+ *   2. rho_i = sum_k f_ik, k = 0 ... 8                                                                         lb_update_hydro
+ *   3. LB_ROCKET_FLOW (the class Rocket_Yeast):                                                                lb_update_velocity_rocket,
+ *        (u, v) = -epsilon (1 / cs^2) grad_w rho_c                                                             lb_update_forces_rocket
+ *        psi = rho_o (1 - exp(-max(rho_p, 0) / rho_o));  F = -G_chen psi(x) grad_w psi
+ *      LB_ROCKET_FORCES (the class Rocket_Yeast_Forces_Only; forces first, then the velocity):
+ *        S = pow(1 - exp(-max(rho_c, 0) / c_o), alpha);  F_s = -epsilon (1 / cs^2) grad_w S
+ *        F_p = -G_chen (1 / cs^2) grad_w rho_p (rho_p - rho_o);  (u, v) = F_p + F_s
+ *   4. feq_ik = w_k rho_i (1 + 3 c_k.u) for both lattices                                                      lb_update_feq
+ *   5. population: max(0, f_k (1 - omega) + omega feq_k + w_k G rho_p (1 - rho_p) [FLOW: + w_k (c_k.F) / cs^2]);  lb_collide_rocket
+ *      FORCES: no growth where rho_p > 1.  Surfactant: f_k (1 - omega_c) + omega_c feq_k + w_k G_c rho_p.
+ * lb_run_rocket(n) = n steps on one stream without a host wait, of ONE launch each (k_ry_step: a workgroup puts the two stencil
+ * operands of its ten rows of a 256-cell tile and of their halo into LDS and runs stages 3-5 on populations kept in registers) or of
+ * two (lb_set_variant(0) on the set's first handle: k_ry_moments stores both densities, k_ry_collide gathers again and reads them
+ * around the cell); both bitwise equal to the stages called one by one.  lb_set_variant takes -1 (the planner's choice), 0 and 1;
+ * lb_hot_kernel, lb_steps_per_launch and lb_plan_launches report what runs.
+ * The parameters are stored with the set's FIRST handle.  A run leaves f after the last collision, and rho (lb_get_macro: the
+ * member's own), u, v (lb_get_macro on either member: the set's), psi / S and the forces (lb_get_rocket_fields) of the last step,
+ * before its collision; they are stored by the run's last launch only.
+ * lb_run, lb_run_coupled / batch / fluids / group, masks, slab and halo calls, lb_autotune*, lb_solve*, lb_set_reaction,
+ * lb_set_velocity_from, lb_set_porous, the interaction and reaction tables, the edge and corner state and lb_collide_particles:
+ * LB_ERR_STATE naming LB_SEM_ROCKET. */
+enum { LB_ROCKET_FLOW = 0, LB_ROCKET_FORCES = 1 };
+typedef struct {
+    int32_t mode;               /* LB_ROCKET_* */
+    float G, G_c;               /* the population's growth rate and the surfactant's secretion rate, in lattice units */
+    float epsilon;              /* the velocity's coupling to the surfactant */
+    float rho_o, G_chen;        /* the self-attraction: saturation density (FLOW: != 0) and strength */
+    float c_o, alpha;           /* FORCES: the surfactant concentration at which the surface saturates (!= 0), its exponent */
+} lb_rocket_params;
+int lb_set_rocket(lb_sim **fields, int count, const lb_rocket_params *params);
+int lb_get_rocket(lb_sim *first, lb_rocket_params *params);
+int lb_run_rocket(lb_sim **fields, int count, int n_steps);
+int lb_update_velocity_rocket(lb_sim **fields, int count);   /* stage 3: u, v (FORCES: from the stored forces) */
+int lb_update_forces_rocket(lb_sim **fields, int count);     /* stage 3: psi and F / S, F_s and F_p */
+int lb_collide_rocket(lb_sim **fields, int count);           /* stage 5 */
+/* [ny][nx] each, any may be NULL: psi (FLOW) or S (FORCES); the pseudo-force F (FLOW) or the pressure force F_p (FORCES); the
+ * surface force F_s (FORCES; zeros in FLOW) */
+int lb_get_rocket_fields(lb_sim **fields, int count, float *psi_or_S, float *Fx, float *Fy, float *Fsx, float *Fsy);
 
 /* ---- the reference's per-phase methods, one kernel each (slow, un-fused;
  *      API and test parity).  Single-slab handles only. ------------------- */
