@@ -82,7 +82,7 @@ struct lb_sim : PlanInputs {
     // (ev_interior also orders a scalar lattice and the flow handle it takes its velocity from, lb_set_velocity_from: both are whole-grid
     //  handles there, whose runs never record it -- the slab schedules and lb_run_batch are its other users)
     ncclComm_t comm = nullptr;
-    int rank = 0, nranks = 1;
+    int rank = 0;               // (nranks: PlanInputs)
     float *halo_buf = nullptr;  // 4 x HALO_SEGS_DEEP (117) x nx floats: send north, send south, recv south, recv north (ensure_halo_buf)
     int ghost_depth = 0;        // ghost rows of lat[cur] hold this many of the neighbours' edge rows (0, 3, 6 or 8)
     hipGraph_t graph = nullptr;            // GRAPH_STEPS single-step launches, captured for small grids

@@ -1,5 +1,6 @@
 // plan.cpp -- the launch planner (plan.h): host arithmetic only.  The thresholds below are measurements; the comments beside them
-// say which, and name the files under profiles/ that hold them.
+// say which, and name the files under profiles/ that hold them.  tests/plan_props.cpp sweeps what this file promises on a host (every
+// row of every strip marched once, one round of wave slots, the ranks' agreement ...): a change to the item table runs it first.
 #include "plan.h"
 
 #include <algorithm>
@@ -122,7 +123,19 @@ bool deep2_chosen(const PlanInputs *s)
 // The marching kernels address the nine planes of a row through ONE scalar base and a 32-bit byte offset per lane that carries the
 // plane (store_row9): (x + 8 plane) * 4 must stay below 4 GB.  Always true for the default layout (plane = the padded row);
 // LB_FLAG_PLANAR lattices of more than ~11000^2 cells take the single-step kernel and the tiles instead.
-bool marching_planes_fit(const PlanInputs *s) { return (8.0 * (double)s->plane + (double)s->rowp) * 4.0 < 4294967296.0; }
+// (Slabs: the halo cycle's depth hangs on this, and every rank of a run must arrive at the same one.  The plane stride of an
+//  LB_FLAG_PLANAR slab grows with its OWN height, so a tall slab beside a short one -- 11264 and 1024 rows of 12288^2 -- found
+//  its planes too far apart and dropped the cycle its neighbour kept.  The ranks agree on ny, min_h and their number: each decides on
+//  the tallest slab such a run can hold, ny - (nranks - 1) min_h rows, which is at least its own -- and its own where the rows are
+//  shared out evenly.  An uneven run whose tallest slab could be too tall, though none is, takes single steps: the price of
+//  agreeing without a further exchange.)
+bool marching_planes_fit(const PlanInputs *s)
+{
+    double plane = (double)s->plane;
+    if (s->multi_slab() && (s->p.flags & LB_FLAG_PLANAR) && s->min_h > 0 && s->nranks > 1)
+        plane = (double)(std::max(s->H, s->p.ny - (s->nranks - 1) * s->min_h) + 2 * GHOST) * (double)s->pitch;
+    return (8.0 * plane + (double)s->rowp) * 4.0 < 4294967296.0;
+}
 
 bool step3_applicable(const PlanInputs *s, int h)
 {

@@ -20,6 +20,7 @@ struct PlanInputs {
     bool has_field = false;     // LB_SEM_POROUS: a force field is set (lb_set_force_field)
     int cu_count = 256;
     int min_h = 0;              // smallest slab height over the ranks (every rank must pick the same schedule)
+    int nranks = 1;             // slabs of the run (lb_comm_init / lb_peer_connect): with min_h, the tallest slab the run can hold
     int variant = -1;           // < 0: automatic (effective_variant), else an OR of LB_VAR_* (lb_variant_bits)
     int tuned_steps = 0;        // 0: not tuned; else the fused kernel depth (1..7) chosen by lb_autotune
     int tuned_wpc = 0;          // and its waves per CU for the marching kernels (-1: the LDS tiles)
