@@ -6,7 +6,8 @@
 
 hipcc cross-compiles without a GPU; the .so is git-ignored but travels with the tree.  One translation unit per kernel
 family (csrc/launchers.h), compiled in parallel; objects under 2d-lb_amd/build/ (git- and gpurun-ignored) are reused while
-neither their source nor any header is newer.  The host side is cut by concern (csrc/host.h); plan.cpp, the launch planner, is plain C++.
+neither their source nor any header is newer.  The host side is cut by concern and, beyond flow, by handle kind (csrc/host.h); plan.cpp, the
+launch planner, is plain C++.
 """
 import os
 import shutil

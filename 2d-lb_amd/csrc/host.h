@@ -1,11 +1,14 @@
-// host.h -- what the host-side translation units of liblbhip.so share: the handle, error reporting, the RCCL entry points and the
-// functions one unit offers the others.  Who holds what:
+// host.h -- what the host-side translation units of liblbhip.so share: the handle, error reporting, the table of handle kinds, the RCCL
+// entry points and the functions one unit offers the others.  Who holds what:
 //   plan.cpp       the launch planner (plan.h): every decision that is arithmetic over PlanInputs; no HIP
-//   launch.cpp     kernel arguments and launches of the fused kernels, hipGraph replay, a whole grid's run
+//   launch.cpp     kernel arguments and launches of the fused flow kernels, hipGraph replay, a whole grid's run
 //   slab.cpp       halo tables, pack / unpack, the exchanges, a slab's halo cycle and run, lb_run_group, lb_step_*, lb_halo_*
 //   transport.cpp  the RCCL loader, lb_comm_*, lb_peer_*
 //   tune.cpp       lb_autotune* and what they found, remembered (LB_TUNE_CACHE)
-//   lb_hip.cpp     create / destroy / setters, state transfer, the un-fused phases, lb_run, lb_run_batch, lb_check, timers
+//   lb_hip.cpp     create / destroy / setters, state transfer, the entry points every kind shares (the un-fused phases, lb_run: common
+//                  checks, then the kind's row), the flow kind's row, lb_run_batch, what set calls share, lb_check, timers
+//   scalar.cpp, multifield.cpp, poisson.cpp, porous.cpp, multifluid.cpp, rocket.cpp
+//                  one handle kind each: its kernels, their launches, its row of the kind table, its own entry points of the C ABI
 // Small kernels are emitted by the one unit that includes their header: kernels_phases.h + kernels_check.h by lb_hip.cpp,
 // kernels_halo.h by slab.cpp, kernels_scalar.h by scalar.cpp (its health check's first pass only: check_reduce.h is shared, the folding
 // pass is lb_hip.cpp's), kernels_multifield.h by multifield.cpp, kernels_poisson.h by poisson.cpp, kernels_porous.h by porous.cpp,
@@ -24,12 +27,9 @@
 #include "cpu_backend.h"
 #include "plan.h"
 #include "launchers.h"          // StepArgs; the fused kernels are instantiated in their own translation units
-#include "scalar_launch.h"      // scalar lattices (LB_SEM_DIFFUSION): AdExtra, CheckPartial, their launchers
-#include "multifield_launch.h"  // coupled scalar lattices (LB_SEM_MULTIFIELD): MfArgs, their launchers
-#include "poisson_launch.h"     // the LB Poisson solver (LB_SEM_POISSON): PsExtra, PsState, its launchers
-#include "porous_launch.h"      // forced flow in a porous medium (LB_SEM_POROUS): PmExtra, its launchers
-#include "multifluid_launch.h"  // multicomponent Shan-Chen fluids (LB_SEM_MULTIFLUID): McArgs, their launchers
-#include "rocket_launch.h"      // surfactant-propelled colonies (LB_SEM_ROCKET): RyArgs, their launchers
+#include "check_reduce.h"       // CheckPartial
+#include "poisson_launch.h"     // PsState
+#include "multifluid_launch.h"  // McInter, McReact; PmExtra (porous_launch.h)
 
 namespace {
 
@@ -47,7 +47,7 @@ struct lb_sim : PlanInputs {
     float *feq = nullptr;       // raw allocation, lazily created
     float *rho = nullptr, *u = nullptr, *v = nullptr;
     float *stage = nullptr;     // [H][pitch], lazily: one plane on its way between the host and interleaved rows (lattice_plane_*)
-    float *ad_edge = nullptr;   // scalar lattice, OPEN family: the edge state on the device (scalar_launch.h)
+    float *ad_edge = nullptr;   // scalar lattice, OPEN family: the edge state on the device (scalar_launch.h: AdExtra)
     float ad_G = 0.f;           // scalar lattice: growth rate of the Fisher term (lb_set_reaction); 0 = plain relaxation
     float *vi_corner = nullptr; // VELOCITY_INLET: the eight corner links nothing ever writes (bc_vel_cell), device; LB_BC_BOX, LB_BC_DIRICHLET: likewise (mf_box_cell, ps_box_cell)
     // the LB Poisson solver (LB_SEM_POISSON; poisson_launch.h)
@@ -160,6 +160,67 @@ int fail(int code, const char *fmt, ...);       // records the message lb_last_e
         if ((s) && (s)->multifluid()) return fail(LB_ERR_STATE, "%s is not available on a fluid of a multicomponent set (LB_SEM_MULTIFLUID)", name); \
     } while (0)
 
+// ---- handle kinds -----------------------------------------------------------------------------------------------------------------
+// What differs by the kind of a handle (its semantics), one row per kind; the three flow semantics share one.  The row is defined by the
+// unit that holds the kind (flow: lb_hip.cpp); the entry points of lb_hip.cpp do their common checks and call through it.
+struct KindOps {
+    // What lb_create refuses before any device is touched, in this order: a family outside `families` ("<noun> takes <families_text>"),
+    // a grid below 3x3 where every cell needs eight neighbours, a slab, the halo flag, the CPU backend.  noun == nullptr (flow): none
+    // of this; lb_create's own rules for the flow semantics follow.
+    const char *noun;
+    unsigned families;              // bit b set: bc_mode b
+    const char *families_text;
+    bool eight_neighbours;
+    bool before_exists;             // refused before (true) or after lb_create's "LB_BC_OPEN / LB_BC_BOX exists for ..." checks
+    // lb_set_variant: -1 ... variant_max, else variant_text with variant_code (variant_text == nullptr: every word is taken)
+    int variant_max;
+    const char *variant_text;
+    int variant_code;
+    // nullptr: nothing to do (`pass` in the reference).  Called with the handle's device current and the common checks made.
+    int (*create)(lb_sim *s);       // the kind's own buffers, on s->stream; lb_create destroys the handle if it fails
+    int (*move_bcs)(lb_sim *s);
+    int (*hydro)(lb_sim *s);
+    int (*feq)(lb_sim *s);          // into s->feq_origin(), which exists
+    int (*collide)(lb_sim *s);      // (collide_ready first, or the kind's refusal)
+    int (*run)(lb_sim *s, int n_steps);
+};
+// (functions, not objects: a constant at namespace scope would be emitted into the device code of its unit as well)
+const KindOps &kind_flow(), &kind_scalar(), &kind_multifield(), &kind_poisson(), &kind_porous(), &kind_multifluid(), &kind_rocket();
+#define KIND_ROW(name, ...) const KindOps &name() { static const KindOps k = {__VA_ARGS__}; return k; }
+const KindOps &kind_of(int semantics);          // (a semantics lb_create does not know: the flow row)
+inline const KindOps &kind_of(const lb_sim *s) { return kind_of(s->p.semantics); }
+
+// a HIP call inside a kind's create: the message lb_create reports, without a source line
+#define CREATE_TRY(expr)                                                                       \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess) return fail(LB_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+// ---- lb_hip.cpp ------------------------------------------------------------------------------------------------------------------
+bool finite32(float x);                         // false for NaN and the infinities
+int ensure_macro(lb_sim *s);                    // rho, u, v as of the last time step
+int collide_ready(lb_sim *s);                   // lb_collide_particles: feq exists, rho, u, v are current
+int copy_plane_h2d(lb_sim *s, float *dev, const float *host);   // host [rows][nx] <-> device [rows][pitch], on s->stream
+int copy_plane_d2h(lb_sim *s, float *host, const float *dev);
+int copy_quads(hipStream_t st, float *dst, const float *src, long long n4);     // k_copy4 over n4 aligned float4
+// Set calls (lb_run_batch, lb_*_coupled, lb_*_fluids, lb_*_rocket): the members checked, everything enqueued on the first member's
+// stream behind whatever the others still have in flight (set_join), the other members' streams made to see the result (set_release).
+struct SetRules {
+    int semantics, min, max;
+    const char *null_array, *count;     // (what, max, max)
+    const char *null_member;            // (what)
+    bool rocket_named;                  // a rocket handle is refused under its own name first (NOT_ROCKET)
+    int kind_code;
+    const char *kind;                   // (what, index)
+    const char *share;                  // (what): grid, boundary family, layout flag, device
+    bool split_checked;                 // "<what> inside a split step"
+    const char *twice;                  // (what)
+};
+int set_members(lb_sim **f, int count, const char *what, const SetRules &r);
+int set_join(lb_sim **f, int count);
+int set_release(lb_sim **f, int count);
+
 // ---- transport.cpp: RCCL, loaded lazily so that single-GPU use never touches librccl ---------------------------------------------
 struct Rccl {
     void *lib = nullptr;
@@ -185,6 +246,20 @@ int rccl_load();
 
 // ---- launch.cpp ------------------------------------------------------------------------------------------------------------------
 StepArgs step_args(const lb_sim *s, int row_begin, int row_step, int row_count);
+// the launch grids of the kinds' kernels over a whole grid: one thread per cell in workgroups of 256; 64 x 4 lanes of four cells each
+inline dim3 cells_grid(const StepArgs &a) { return dim3((unsigned)((a.nx + 255) / 256), (unsigned)a.ny); }
+inline dim3 step_grid(const StepArgs &a) { return dim3((unsigned)((a.fpitch / 4 + 63) / 64), (unsigned)((a.ny + 3) / 4)); }
+// An un-fused phase of a whole-grid handle on its stream: k(step_args(s, 0, 1, H), more...) over grid x 256 threads -- one per cell
+// (grid_cells) or, for the in-place boundary phases, one per cell of the longer edge (grid_edge)
+inline dim3 grid_cells(const lb_sim *s) { return dim3((unsigned)((s->p.nx + 255) / 256), (unsigned)s->p.ny); }
+inline dim3 grid_edge(const lb_sim *s) { return dim3((unsigned)((std::max(s->p.nx, s->p.ny) + 255) / 256)); }
+template <typename K, typename... A>
+int launch_phase(lb_sim *s, dim3 grid, K k, const A &...more)
+{
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, s->stream, step_args(s, 0, 1, s->H), more...);
+    HIP_TRY(hipGetLastError());
+    return LB_OK;
+}
 // the single-step kernel over local rows row_begin + i*row_step, i < row_count
 int launch_step(lb_sim *s, int row_begin, int row_step, int row_count, bool macro);
 // A marching launch (k_step2 ... k_step5, k_deep: `depth` time steps per pass) over output rows [row_begin, row_end).
@@ -200,37 +275,23 @@ int launch_marching(lb_sim *s, const MarchRows &r);
 void drop_graph(lb_sim *s);
 // n time steps on a whole-grid handle
 int run_whole_grid(lb_sim *s, int n_steps, bool final_macro = true);
-// n time steps on a scalar lattice; the last launch stores rho
-int run_scalar(lb_sim *s, int n_steps);
-// n iterations of the Poisson solver with no check and no early out; the last launch stores rho
-int run_poisson(lb_sim *s, int n_steps);
-inline PsExtra ps_extra(const lb_sim *s)
-{
-    const float w0 = 4.f / 9.f;
-    return PsExtra{s->ps_source, s->ps_part, s->ps_state, (-1.f + w0) * s->ps_rho_b, s->ps_react, 0};
-}
-inline AdExtra ad_extra(const lb_sim *s) { return AdExtra{s->ad_edge, s->ad_G}; }
-// n time steps of forced flow in a porous medium; the last launch stores rho, u, v, G and u_b
-int run_porous(lb_sim *s, int n_steps);
-// (every derived scalar one float32 operation, here and nowhere else: porous_launch.h)
-inline PmExtra pm_extra(const lb_sim *s)
-{
-    PmExtra e;
-    e.Gx = s->pm_G[0]; e.Gy = s->pm_G[1];
-    e.ub = s->pm_ub[0]; e.vb = s->pm_ub[1];
-    e.fgx = s->pm_field[0]; e.fgy = s->pm_field[1];
-    e.gx = s->pm_gx; e.gy = s->pm_gy;
-    e.eps = s->pm_eps;
-    e.en = s->pm_eps * s->pm_nu;
-    e.ef = s->pm_eps * s->pm_Fe;
-    e.K = s->pm_K;
-    e.sqrtK = sqrtf(s->pm_K);
-    const float ie = 1.f / s->pm_eps;
-    e.a15 = 1.5f * ie; e.a45 = 4.5f * ie;
-    e.b3 = 3.f * ie; e.b9 = 9.f * ie;
-    e.hw = 1.f - 0.5f * s->p.omega;
-    return e;
-}
+
+// ---- scalar.cpp ------------------------------------------------------------------------------------------------------------------
+// the un-fused phases the coupled lattices and the colonies share with the scalar lattice: rho = sum f; feq from rho, u, v
+int scalar_hydro(lb_sim *s);
+int scalar_feq(lb_sim *s);
+// OPEN: the edge state copied out of (k_ad_edge_capture) / patch: written back into (k_ad_edge_patch) the lattice at `f`
+void lbk_ad_edge(bool patch, hipStream_t st, const StepArgs &a, float *f, float *edge);
+// the health check's first pass over the lattice at a.src and the fields a.u, a.v: one record per workgroup, ad_check_blocks(a) of
+// them, into part (k_check_final, lb_hip.cpp, folds them)
+long long ad_check_blocks(const StepArgs &a);
+void lbk_ad_check(hipStream_t st, const StepArgs &a, CheckPartial *part);
+
+// ---- porous.cpp: what a fluid of a multicomponent set shares with the porous-medium fluid (and a colony: the four planes) -------------
+PmExtra pm_extra(const lb_sim *s);
+int forced_create(lb_sim *s);                   // pm_G, pm_ub
+int porous_move_bcs(lb_sim *s);
+int porous_feq(lb_sim *s);
 
 // ---- slab.cpp --------------------------------------------------------------------------------------------------------------------
 int ensure_halo_buf(lb_sim *s);         // the send / receive buffers of the halo exchange (also lb_check's scratch across ranks)

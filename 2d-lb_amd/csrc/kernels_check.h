@@ -1,5 +1,6 @@
 // kernels_check.h -- rho, u, v rebuilt from the populations on demand and the device-side health check (k_macro_check, k_check_final,
-// k_check_spread; the reduction itself: check_reduce.h).  Included by lb_hip.cpp only: its plain kernels must be emitted by exactly one translation unit.
+// k_check_spread; the reduction itself: check_reduce.h).  Included by lb_hip.cpp only: its plain kernels must be emitted by exactly one translation unit
+// (a scalar lattice's first pass, k_ad_check, is scalar.cpp's: host.h, lbk_ad_check).
 #pragma once
 #include "d2q9_cell.h"
 #include "check_reduce.h"

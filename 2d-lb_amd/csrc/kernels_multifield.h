@@ -1,7 +1,7 @@
 // kernels_multifield.h -- the kernels of coupled scalar lattices (LB_SEM_MULTIFIELD: the reference's LB_D2Q9/D2Q9_multifield_fisher.cl,
 // driven as advecting_range_expansion/deterministic_fisher_waves.py:436-450 does: move + copy_buffer -> move_bcs -> update_hydro ->
 // update_feq -> collide_particles, five launches and five host waits per step, each looping over the fields in every work-item).
-// Included by multifield.cpp only (multifield_launch.h is what the host units see).
+// Included by multifield.cpp only (multifield_launch.h: what the kernels and their host code share; host.h: what the other host units see).
 //   k_mf_step<BC, NF, RHO>   the fused step of NF fields: k_ad_step's plan (kernels_scalar.h) -- a lane owns four consecutive cells of
 //                            a row; per field nine 16-byte loads (six displaced by one element: k_step's gather) and nine aligned
 //                            16-byte stores, u and v loaded once for all fields, rho of every field when asked: 72 NF + 8 B per cell

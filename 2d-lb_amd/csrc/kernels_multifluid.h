@@ -2,7 +2,7 @@
 // LB_D2Q9/multicomponent_multiphase/multi.cl, driven as multi.py:729-803 does: per fluid move[_periodic] -> copy_streamed_onto_f ->
 // move_open_bcs -> update_hydro_fluid, then Gx, Gy = 0 -> the additional forces -> update_bary_velocity -> per fluid update_feq_fluid
 // -> collide_particles_fluid -> the additional collisions: about 6 NF + 4 + entries launches and as many host waits per step).
-// Included by multifluid.cpp only (multifluid_launch.h is what the host units see).
+// Included by multifluid.cpp only (multifluid_launch.h: what the kernels, their host code and the handle share; host.h: what the other host units see).
 //
 // The step is NOT local to the cell after streaming: the interaction force on a cell reads the post-stream density of its eight
 // neighbours.  Two forms of the step, bitwise equal (one body, mc_collide_lane).  The one-launch form:

@@ -1,5 +1,5 @@
 // kernels_phases.h -- one kernel per reference kernel (un-fused, API / test parity), the reference's CPU ("Cython") path as GPU
-// kernels (k1_*) and the row copy of the state transfer.  Included by lb_hip.cpp only, after kernels_tile.h (TileShape): its plain
+// kernels (k1_*) and the row copy of the state transfer: the flow kind's phases (the other kinds' are in their own units).  Included by lb_hip.cpp only, after kernels_tile.h (TileShape): its plain
 // kernels must be emitted by exactly one translation unit.  (The health check: kernels_check.h; halo and peer transport: kernels_halo.h.)
 #pragma once
 #include "d2q9_cell.h"

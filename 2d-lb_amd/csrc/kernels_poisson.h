@@ -1,7 +1,7 @@
 // kernels_poisson.h -- the kernels of the LB Poisson solver (LB_SEM_POISSON: the reference's LB_D2Q9/D2Q9_poisson.cl, driven as
 // poisson/solver.py:324-358 does: rho_before = rho, move + copy_buffer -> move_bcs (nine times over) -> update_hydro -> update_feq ->
 // collide_particles, six launches and six host waits per iteration, then two reductions and two host read-backs to decide whether to
-// stop).  Included by poisson.cpp only (poisson_launch.h is what the host units see).
+// stop).  Included by poisson.cpp only (poisson_launch.h: what the kernels, their host code and the handle share; host.h: what the other host units see).
 //   k_ps_step<RHO_ALWAYS>   the fused iteration on k_ad_step's plan (kernels_scalar.h): a lane owns four consecutive cells of a row; nine
 //                           16-byte loads (six displaced by one element: k_step's gather without a wrap), the prescribed-density rule
 //                           in registers on the lanes that hold a wall cell, one 16-byte load of the source, nine aligned 16-byte

@@ -2,7 +2,7 @@
 // LB_D2Q9/porous_media/single_component.cl, driven as single_component.py:679-751 does with one fluid: move[_periodic] ->
 // copy_streamed_onto_f -> move_open_bcs -> update_hydro_pourous -> Gx, Gy = 0 -> the additional forces -> update_forces_pourous ->
 // update_bary_velocity -> update_feq_pourous -> collide_particles_pourous, eleven launches and eleven host waits per step).  Included
-// by porous.cpp only (porous_launch.h is what the host units see).
+// by porous.cpp only (porous_launch.h: what the kernels and their host code share; host.h: what the other host units see).
 //   k_pm_step<BC, FIELD, LAST>   the fused step on k_ad_step's plan (kernels_scalar.h): a lane owns four consecutive cells of a row; nine
 //                                16-byte loads (six displaced by one element: k_step's gather), FIELD: two 16-byte loads of the
 //                                force field, the eight stages in registers (porous_cell.h), nine aligned 16-byte stores; LAST (a

@@ -1,7 +1,7 @@
 // kernels_rocket.h -- the kernels of surfactant-propelled colonies (LB_SEM_ROCKET: the reference's LB_D2Q9/rocket_yeast/
 // rocket_yeast.cl and rocket_yeast_forces_only.cl, driven as rocket_yeast.py:469-483 does: move_periodic -> copy -> update_hydro ->
 // update_u_and_v -> update_psi -> update_pseudo_force -> update_feq -> collide_particles, nine launches, nine host waits and a full
-// copy of f per step).  Included by rocket.cpp only (rocket_launch.h is what the host units see).
+// copy of f per step).  Included by rocket.cpp only (rocket_launch.h: what the kernels and their host code share; host.h: what the other host units see).
 //
 // Two scalar lattices in a periodic box, the population p and the surfactant c.  The velocity that advects both is a D2Q9 stencil over
 // the surfactant (MODE = LB_ROCKET_FLOW) or the sum of two stencil forces (LB_ROCKET_FORCES), so the step is NOT local to the cell

@@ -1,7 +1,7 @@
 // kernels_scalar.h -- the kernels of scalar lattices (LB_SEM_DIFFUSION: the reference's LB_D2Q9/D2Q9_diffusion.cl, driven as
 // reaction_diffusion/diffusion.py:365-380 does: move + copy_buffer -> move_bcs (`pass`) -> update_hydro_diffusion ->
 // update_feq_diffusion -> collide_particles[_fisher], five launches and five host waits per step).  Included by scalar.cpp only: its
-// plain kernels must be emitted by exactly one translation unit (scalar_launch.h is what the host units see).
+// plain kernels must be emitted by exactly one translation unit (scalar_launch.h: what the kernels and their host code share; host.h: what the other host units see).
 //   k_ad_step<BC, REACT, RHO>   the fused step: pull-stream, rho = sum f, linear equilibrium with the imposed u, v, relaxation
 //                               [+ growth term]; a lane owns four consecutive cells of one row: nine 16-byte loads (six displaced
 //                               by one element: k_step's gather), one 16-byte load each of u and v, nine aligned 16-byte stores,

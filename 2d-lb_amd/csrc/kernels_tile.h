@@ -1,5 +1,5 @@
 // kernels_tile.h -- four time steps per pass for SMALL grids: 2-D tiles staged in LDS.
-// Included after kernels_fused.h by tile.cpp (k_tile4, k_vel_band) and lb_hip.cpp (TileLaunch, for k1_tile4); scalar.cpp takes the tile plan for k_ad_tile4.
+// Included after kernels_fused.h by tile.cpp (k_tile4, k_vel_band) and lb_hip.cpp (TileLaunch, for k1_tile4); scalar.cpp (through kernels_scalar.h) takes the tile plan for k_ad_tile4.
 //
 // Grids below ~1600^2 cells live in the Infinity Cache and are not bandwidth-bound: a single-step launch costs
 // its ~2 us of dependent-kernel boundary plus one global-memory round trip per step, and the marching kernels

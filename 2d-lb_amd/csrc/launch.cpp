@@ -1,6 +1,7 @@
-// launch.cpp -- the launches of the fused kernels: their argument block, the single-step kernel, the marching kernels in the geometry
-// the planner gives them (plan_march), the LDS tiles, hipGraph replay for small grids, the velocity-inlet family's band scheme, and a
-// whole grid's run of n steps.  The kernels themselves are instantiated in the translation units of launchers.h.
+// launch.cpp -- the launches of the fused flow kernels: their argument block (step_args: every kind's kernels take it), the single-step
+// kernel, the marching kernels in the geometry the planner gives them (plan_march), the LDS tiles, hipGraph replay for small grids, the
+// velocity-inlet family's band scheme, and a whole grid's run of n steps.  The kernels themselves are instantiated in the translation
+// units of launchers.h.
 #include "host.h"
 
 StepArgs step_args(const lb_sim *s, int row_begin, int row_step, int row_count)
@@ -224,54 +225,5 @@ int run_whole_grid(lb_sim *s, int n_steps, bool final_macro)
         // (final_macro = false) on the others leaves the fields of an earlier step in place until its closing MACRO step
         s->macro_valid = store_macro || !lazy_macro(s) || (s->diag & 4096);      // (LB_DIAG bit 12: the rho array carries the diagnostic build's per-wave timeline)
     }
-    return LB_OK;
-}
-
-// n time steps on a scalar lattice (kernels_scalar.h): k_ad_tile4 / k_ad_step launch by launch, as scalar_next_advance splits the run; the last
-// launch stores rho (with a growth term rho is not a moment of the populations a run leaves behind: never rebuilt on demand)
-int run_scalar(lb_sim *s, int n_steps)
-{
-    const AdExtra e = ad_extra(s);
-    int left = n_steps;
-    while (left > 0) {
-        const int adv = scalar_next_advance(s, left);
-        const StepArgs a = step_args(s, 0, 1, s->H);
-        if (adv == TILE_T) lbk_ad_tile4(s->p.bc_mode, s->ad_G != 0.f, left == adv, scalar_tile_shape(s), s->stream, a, e);
-        else lbk_ad_step(s->p.bc_mode, s->ad_G != 0.f, left == adv, s->stream, a, e);
-        HIP_TRY(hipGetLastError());
-        s->cur ^= 1;
-        left -= adv;
-    }
-    if (n_steps) { s->feq_valid = false; s->macro_valid = true; }
-    return LB_OK;
-}
-
-// n iterations of the LB Poisson solver (kernels_poisson.h) in lb_run's form: k_ps_step<false>, one launch each, no stop word, no sums;
-// the last launch stores rho, which is the next iteration's rho_before.  They count as iterations of the solve (solver.py:346).
-int run_poisson(lb_sim *s, int n_steps)
-{
-    PsExtra e = ps_extra(s);
-    for (int it = 0; it < n_steps; ++it) {
-        e.store_rho = it == n_steps - 1;
-        lbk_ps_step(false, s->stream, step_args(s, 0, 1, s->H), e);
-        HIP_TRY(hipGetLastError());
-        s->cur ^= 1;
-    }
-    s->ps_iter += n_steps;
-    if (n_steps) { s->feq_valid = false; s->macro_valid = true; }
-    return LB_OK;
-}
-
-// n time steps of forced flow in a porous medium (kernels_porous.h): k_pm_step, one launch each; the last stores rho, u, v, the total
-// force and the barycentric velocity.
-int run_porous(lb_sim *s, int n_steps)
-{
-    const PmExtra e = pm_extra(s);
-    for (int it = 0; it < n_steps; ++it) {
-        lbk_pm_step(s->p.bc_mode, it == n_steps - 1, s->stream, step_args(s, 0, 1, s->H), e);
-        HIP_TRY(hipGetLastError());
-        s->cur ^= 1;
-    }
-    if (n_steps) { s->feq_valid = false; s->macro_valid = true; }
     return LB_OK;
 }

@@ -3,8 +3,9 @@
 // Until round 5 liblbhip.so was ONE translation unit: 368 kernel instantiations compiled one after the other, six and a half
 // minutes on eight cores.  Now every kernel family is instantiated in a file of its own (step1.cpp, march23.cpp, march4.cpp,
 // march5.cpp, deep2.cpp, deep6.cpp, deep7.cpp, tile.cpp), which build.py compiles in parallel; the host side and the C ABI are cut by
-// concern (host.h: plan.cpp, launch.cpp, slab.cpp, transport.cpp, tune.cpp, lb_hip.cpp), the small un-fused kernels are emitted by the
-// one host unit that launches them.  A family's file exports one plain function -- below -- that picks the instantiation (boundary family,
+// concern (host.h: plan.cpp, launch.cpp, slab.cpp, transport.cpp, tune.cpp, lb_hip.cpp) and, for every handle kind but flow, by kind
+// (scalar.cpp ... rocket.cpp: kernels, launches and entry points in one unit, no launcher seam), the small un-fused kernels are emitted
+// by the one host unit that launches them.  A family's file exports one plain function -- below -- that picks the instantiation (boundary family,
 // obstacle mask, rho/u/v epilogue, ...) and launches it; arguments are the kernels' own (StepArgs, kernels_fused.h) plus the launch
 // geometry.  Every kernel stays a template in a header: a translation unit only pays for what it launches.
 #pragma once

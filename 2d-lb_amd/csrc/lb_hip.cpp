@@ -23,14 +23,15 @@
 // Source layout: d2q9_cell.h (cell arithmetic), kernels_fused.h (k_step, k_step2, k_step3), kernels_step4.h / 5 (k_step4,
 // k_step5), kernels_deep.h (k_deep: six and seven steps per pass), kernels_tile.h (k_tile4, k_vel_band); every fused kernel family
 // is instantiated in a translation unit of its own (launchers.h).  The host side is cut by concern (host.h): plan.cpp (what to launch:
-// plain C++), launch.cpp (the launches), slab.cpp (halo exchange and the slab schedules), transport.cpp (RCCL, peer set-up),
-// tune.cpp (lb_autotune*), and this file: the handle's life, state transfer, the un-fused phases and the Cython path
-// (kernels_phases.h), the health check (kernels_check.h), lb_run's dispatch, lb_run_batch, timers.
+// plain C++), launch.cpp (the flow launches), slab.cpp (halo exchange and the slab schedules), transport.cpp (RCCL, peer set-up),
+// tune.cpp (lb_autotune*), one unit per handle kind other than flow (scalar.cpp ... rocket.cpp: its kernels, its row of the kind table,
+// its own entry points), and this file: the handle's life, state transfer, the entry points every kind shares -- common checks, then the
+// kind's row --, the flow kind's row with its un-fused phases and the Cython path (kernels_phases.h), the health check (kernels_check.h),
+// lb_run_batch and what set calls share, timers.
 // All stores of the fused kernel are 16-byte aligned; the six planes with cx != 0 are read through
 // 16-byte loads that are misaligned by one element (gfx950 global loads only need dword alignment).
 #include "host.h"
 
-#include <cmath>
 #include <initializer_list>
 #include <stdarg.h>
 
@@ -116,6 +117,10 @@ int check_pass(lb_sim *s, bool store)
     return LB_OK;
 }
 
+}  // namespace
+
+bool finite32(float x) { return fabsf(x) <= 3.0e38f; }
+
 // rho, u, v as of the last time step, before anybody reads them or overwrites the populations they are derived from
 int ensure_macro(lb_sim *s)
 {
@@ -137,14 +142,14 @@ int ensure_macro(lb_sim *s)
 // A whole lattice copied on the device by a kernel on the handle's stream (k_copy4: it runs at the streaming ceiling, and it
 // is ordered like every other kernel of that stream; hipMemcpyAsync device-to-device goes through the runtime's copy path,
 // whose completion the stream did not always wait for when several processes shared the GPU: tools/slab_stress.py).
-int copy_lattice(lb_sim *s, float *dst, const float *src)
+int copy_quads(hipStream_t st, float *dst, const float *src, long long n4)
 {
-    const long long n4 = s->lat_floats / 4;              // (lat_floats is a multiple of 64)
-    hipLaunchKernelGGL(k_copy4<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s->stream,
+    hipLaunchKernelGGL(k_copy4<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
                        reinterpret_cast<const f4a *>(src), reinterpret_cast<f4a *>(dst), n4);
     HIP_TRY(hipGetLastError());
     return LB_OK;
 }
+static int copy_lattice(lb_sim *s, float *dst, const float *src) { return copy_quads(s->stream, dst, src, s->lat_floats / 4); }    // (lat_floats is a multiple of 64)
 
 // host [rows][nx] <-> device [rows][pitch]
 int copy_plane_h2d(lb_sim *s, float *dev, const float *host)
@@ -165,7 +170,7 @@ int copy_plane_d2h(lb_sim *s, float *host, const float *dev)
 // row copies.  The staging plane is reused plane after plane; the stream is synchronised between the scatter / gather
 // kernel and the next copy from / to (pageable) host memory instead of relying on the runtime ordering its staged copies
 // behind kernels already enqueued -- a precaution (nine cheap synchronisations per set / get), not a measured necessity.
-int lattice_plane_h2d(lb_sim *s, float *origin, int k, const float *host)
+static int lattice_plane_h2d(lb_sim *s, float *origin, int k, const float *host)
 {
     if (s->rowp == s->pitch) return copy_plane_h2d(s, origin + k * s->plane, host);
     if (!s->stage) HIP_TRY(hipMalloc(&s->stage, sizeof(float) * s->pitch * s->H));
@@ -179,7 +184,7 @@ int lattice_plane_h2d(lb_sim *s, float *origin, int k, const float *host)
     HIP_TRY(hipStreamSynchronize(s->stream));           // the staging plane is free again
     return LB_OK;
 }
-int lattice_plane_d2h(lb_sim *s, float *host, const float *origin, int k)
+static int lattice_plane_d2h(lb_sim *s, float *host, const float *origin, int k)
 {
     if (s->rowp == s->pitch) return copy_plane_d2h(s, host, origin + k * s->plane);
     if (!s->stage) HIP_TRY(hipMalloc(&s->stage, sizeof(float) * s->pitch * s->H));
@@ -199,7 +204,7 @@ int lattice_plane_d2h(lb_sim *s, float *host, const float *origin, int k)
 // a coupled scalar lattice's LB_BC_BOX (vi_corner), the edge state of a scalar lattice's OPEN family (ad_edge, scalar_launch.h); no other handle has any.  They are kept apart because
 // fused launches swap the lattices, so "whatever f_streamed held" would not survive them.  !patch: copied out of lattice `which`;
 // patch: written back into it.
-int frozen_links(lb_sim *s, int which, bool patch)
+static int frozen_links(lb_sim *s, int which, bool patch)
 {
     if (s->p.bc_mode == LB_BC_VELOCITY_INLET || s->p.bc_mode == LB_BC_BOX || s->p.bc_mode == LB_BC_DIRICHLET) {
         const int X = s->p.nx - 1, Y = s->p.ny - 1;
@@ -213,22 +218,18 @@ int frozen_links(lb_sim *s, int which, bool patch)
         }
     } else if (s->ad_edge) {
         const StepArgs a = step_args(s, 0, 1, s->H);
-        if (patch) lbk_ad_edge_patch(s->stream, a, s->origin(which), s->ad_edge);
-        else lbk_ad_edge_capture(s->stream, a, s->origin(which), s->ad_edge);
+        lbk_ad_edge(patch, s->stream, a, s->origin(which), s->ad_edge);
         HIP_TRY(hipGetLastError());
     }
     return LB_OK;
 }
 // ... whenever the populations are set as a whole (lb_set_f, lb_init_pop)
-int frozen_capture(lb_sim *s, int which) { return frozen_links(s, which, false); }
+static int frozen_capture(lb_sim *s, int which) { return frozen_links(s, which, false); }
 // ... behind the un-fused streaming phase (lb_move), where the boundary phase reads them
-int frozen_patch(lb_sim *s, int which) { return frozen_links(s, which, true); }
-
-// ABI order of the edge state (include/lb_hip.h: west, east, south, north; unpadded) <-> device order (scalar_launch.h)
-long long edge_host_floats(const lb_sim *s) { return s->ad_edge ? 6LL * (s->p.nx + s->p.ny) : 0; }
+static int frozen_patch(lb_sim *s, int which) { return frozen_links(s, which, true); }
 
 // lb_run in Cython-path semantics
-int run_cython(lb_sim *s, int n_steps)
+static int run_cython(lb_sim *s, int n_steps)
 {
     // cython_dim.pyx:346-359: move_bcs, move, update_hydro, update_feq, collide_particles.  The boundary phase of the
     // FIRST step in place (k1_bcs); then one pass per step (k1_fstep: restricted pull, moments with their overrides,
@@ -278,7 +279,194 @@ int run_cython(lb_sim *s, int n_steps)
     return LB_OK;
 }
 
-}  // namespace
+// ---- the flow kind's row: the un-fused phases of the three flow semantics, lb_run's dispatch -------------------------------------------
+static int flow_move_bcs(lb_sim *s)
+{
+    int rc = ensure_macro(s);
+    if (rc) return rc;
+    if (s->p.semantics == LB_SEM_CYTHON)
+        hipLaunchKernelGGL(k1_bcs, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
+    else if (s->p.bc_mode == LB_BC_VELOCITY_INLET) {
+        hipLaunchKernelGGL(k_bcs_vel, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
+        HIP_TRY(hipGetLastError());
+        if (s->has_mask) hipLaunchKernelGGL(k_bounce, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
+    } else
+        hipLaunchKernelGGL(k_bcs, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
+    HIP_TRY(hipGetLastError());
+    return LB_OK;
+}
+
+static int flow_hydro(lb_sim *s)
+{
+    if (s->p.semantics == LB_SEM_CYTHON)
+        hipLaunchKernelGGL(k1_hydro, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
+    else if (s->p.bc_mode == LB_BC_VELOCITY_INLET)
+        hipLaunchKernelGGL(k_hydro_vel, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
+    else if (s->p.semantics == LB_SEM_OPENCL_D2Q9I) {
+        // D2Q9i.cl:67-97 + the cylinder class's override (opencl_dim_D2Q9i.py:494-503): u, v zeroed in the obstacle
+        hipLaunchKernelGGL(k_hydro_i, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
+        HIP_TRY(hipGetLastError());
+        if (s->has_mask) hipLaunchKernelGGL(k_zero_vel, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
+    } else
+        hipLaunchKernelGGL(k_hydro, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
+    HIP_TRY(hipGetLastError());
+    return LB_OK;
+}
+
+static int flow_feq(lb_sim *s)
+{
+    PhaseArgs a = phase_args(s);
+    a.ny = s->H;   // rho,u,v are local: valid for slabs too
+    if (s->p.semantics == LB_SEM_OPENCL_D2Q9I)
+        hipLaunchKernelGGL(k_feq_i, dim3((s->p.nx + 255) / 256, s->H, 1), dim3(256), 0, s->stream, a);
+    else
+        hipLaunchKernelGGL(k_feq, dim3((s->p.nx + 255) / 256, s->H, 1), dim3(256), 0, s->stream, a);
+    HIP_TRY(hipGetLastError());
+    return LB_OK;
+}
+
+int collide_ready(lb_sim *s)
+{
+    if (!s->feq) return fail(LB_ERR_STATE, "lb_collide_particles before any lb_update_feq");
+    return ensure_macro(s);
+}
+
+static int flow_collide(lb_sim *s)
+{
+    if (int rc = collide_ready(s)) return rc;
+    hipLaunchKernelGGL(k_collide, cells_grid(s, 9), dim3(256), 0, s->stream, phase_args(s));
+    HIP_TRY(hipGetLastError());
+    return LB_OK;
+}
+
+static int run_flow(lb_sim *s, int n_steps)
+{
+    if (!s->tune_cache_checked) (void)tune_cache_apply(s);
+    if (s->p.semantics == LB_SEM_CYTHON) return run_cython(s, n_steps);
+    if (!s->multi_slab()) return run_whole_grid(s, n_steps);     // (never blocks the host: tuning is lb_autotune*'s job)
+    return run_slab(s, n_steps);
+}
+
+KIND_ROW(kind_flow, nullptr, 0, nullptr, false, false, 0, nullptr, 0, nullptr, flow_move_bcs, flow_hydro, flow_feq, flow_collide, run_flow)
+
+const KindOps &kind_of(int semantics)
+{
+    switch (semantics) {
+    case LB_SEM_DIFFUSION: return kind_scalar();
+    case LB_SEM_MULTIFIELD: return kind_multifield();
+    case LB_SEM_POISSON: return kind_poisson();
+    case LB_SEM_POROUS: return kind_porous();
+    case LB_SEM_MULTIFLUID: return kind_multifluid();
+    case LB_SEM_ROCKET: return kind_rocket();
+    default: return kind_flow();
+    }
+}
+
+// What lb_create refuses of a kind other than flow (KindOps, host.h), before any device is touched.
+static int kind_refusals(const KindOps &k, const lb_params *p)
+{
+    if (!(k.families >> p->bc_mode & 1u)) {
+        if (&k == &kind_poisson()) return fail(LB_ERR_ARG, "%s takes %s: unknown semantics %d for bc_mode %d", k.noun, k.families_text, p->semantics, p->bc_mode);
+        return fail(LB_ERR_ARG, "%s takes %s", k.noun, k.families_text);
+    }
+    if (&k == &kind_porous() && p->bc_mode == LB_BC_ZERO_GRADIENT && (p->nx < 3 || p->ny < 3))
+        return fail(LB_ERR_ARG, "LB_BC_ZERO_GRADIENT needs an interior cell: grid must be at least 3x3 (got %dx%d)", p->nx, p->ny);
+    if (k.eight_neighbours && (p->nx < 3 || p->ny < 3))
+        return fail(LB_ERR_ARG, "%s needs a cell with eight neighbours: grid must be at least 3x3 (got %dx%d)", k.noun, p->nx, p->ny);
+    if (p->local_ny != p->ny || p->y0 != 0) return fail(LB_ERR_ARG, "%s owns its whole grid: no slabs", k.noun);
+    if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "%s has no halo interface (LB_FLAG_HALO)", k.noun);
+    if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "%s runs on a GPU only (no CPU backend)", k.noun);
+    return LB_OK;
+}
+
+// ---- what set calls share (host.h) ---------------------------------------------------------------------------------------------------
+int set_members(lb_sim **f, int count, const char *what, const SetRules &r)
+{
+    if (!f) return fail(LB_ERR_ARG, r.null_array, what, r.max, r.max);
+    if (count < r.min || count > r.max) return fail(LB_ERR_ARG, r.count, what, r.max, r.max);
+    for (int i = 0; i < count; ++i) {
+        lb_sim *s = f[i];
+        if (!s) return fail(LB_ERR_ARG, r.null_member, what);
+        if (r.rocket_named) NOT_ROCKET(s, what);
+        if (s->cpu || s->p.semantics != r.semantics) return fail(r.kind_code, r.kind, what, i);
+        if (s->p.nx != f[0]->p.nx || s->p.ny != f[0]->p.ny || s->p.bc_mode != f[0]->p.bc_mode || s->p.device != f[0]->p.device ||
+            (s->p.flags & LB_FLAG_PLANAR) != (f[0]->p.flags & LB_FLAG_PLANAR))
+            return fail(LB_ERR_ARG, r.share, what);
+        if (r.split_checked && s->stepping) return fail(LB_ERR_STATE, "%s inside a split step", what);
+        for (int j = 0; j < i; ++j)
+            if (f[j] == s) return fail(LB_ERR_ARG, r.twice, what);
+    }
+    return LB_OK;
+}
+
+int set_join(lb_sim **f, int count)
+{
+    for (int i = 1; i < count; ++i) {
+        HIP_TRY(hipEventRecord(f[i]->ev_interior, f[i]->stream));
+        HIP_TRY(hipStreamWaitEvent(f[0]->stream, f[i]->ev_interior, 0));
+    }
+    return LB_OK;
+}
+
+int set_release(lb_sim **f, int count)
+{
+    if (count < 2) return LB_OK;
+    HIP_TRY(hipEventRecord(f[0]->ev_interior, f[0]->stream));
+    for (int i = 1; i < count; ++i) HIP_TRY(hipStreamWaitEvent(f[i]->stream, f[0]->ev_interior, 0));
+    return LB_OK;
+}
+
+// The buffers every GPU handle has, the kind's own among them (KindOps::create).  A failure leaves what was allocated to lb_destroy.
+static int create_device(lb_sim *s)
+{
+    CREATE_TRY(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
+    s->stream = s->own_stream;
+    // (Three streams that must not share a hardware queue -- interior, edge bands, halo exchange.  HIP maps a process's streams onto
+    //  GPU_MAX_HW_QUEUES queues, four by default, per priority, and not once and for all: a probe at creation saw three queues in a
+    //  process whose timeline later shows the exchange on the interior's queue.  The process decides -- bench.py sets 8 --; a
+    //  communication stream at the highest priority, a queue pool of its own, pushed the EDGE stream onto the interior's queue in
+    //  bench.py's process structure, 370 -> 230 k MLUPS: profiles/r06_experiments.txt section 10c, r06h_bench_comm_prio.txt.)
+    CREATE_TRY(hipStreamCreateWithFlags(&s->comm_stream, hipStreamNonBlocking));
+    // The edge stream (edge bands, halo push / RCCL) at NORMAL priority, like the other two.  Rounds 1-2 created it at the
+    // device's highest priority; with it, ~2 % of random slab partitions run through lb_run_group with events alone differed from
+    // the undivided run when four other processes kept the GPU busy (17 of ~900, tools/slab_stress.py), none of 1650 without,
+    // while a stand-alone stress of HIP's cross-queue ordering finds nothing (tools/queue_order_repro.hip) and an audit of
+    // every read-after-write and write-after-read pair of the cycle finds every one ordered (DESIGN.md section 6).  The
+    // priority bought nothing measurable (profiles/r03_experiments.txt section 6), so there is no such stream and no switch for one.
+    // (Rounds 3-5 passed the FIRST value hipDeviceGetStreamPriorityRange returns -- the LEAST priority, not the normal one the
+    //  comment claimed: the edge bands, which gate the halo, ran on a low-priority queue.  Round 6: no priority argument at all.)
+    CREATE_TRY(hipStreamCreateWithFlags(&s->edge_stream, hipStreamNonBlocking));
+    const unsigned ev_flags = hipEventDisableTiming;
+    CREATE_TRY(hipEventCreateWithFlags(&s->ev_boundary, ev_flags));
+    CREATE_TRY(hipEventCreateWithFlags(&s->ev_halo, ev_flags));
+    CREATE_TRY(hipEventCreateWithFlags(&s->ev_interior, ev_flags));
+    CREATE_TRY(hipEventCreateWithFlags(&s->ev_packed, ev_flags));
+    CREATE_TRY(hipEventCreateWithFlags(&s->ev_edge, ev_flags));
+    CREATE_TRY(hipEventCreate(&s->ev_t0));
+    CREATE_TRY(hipEventCreate(&s->ev_t1));
+    const size_t lat_bytes = sizeof(float) * s->lat_floats;
+    const size_t fld_bytes = sizeof(float) * s->pitch * s->H;
+    for (int i = 0; i < 2; ++i) {
+        CREATE_TRY(hipMalloc(&s->lat[i], lat_bytes));
+        CREATE_TRY(hipMemsetAsync(s->lat[i], 0, lat_bytes, s->stream));
+    }
+    CREATE_TRY(hipMalloc(&s->rho, fld_bytes));
+    CREATE_TRY(hipMalloc(&s->u, fld_bytes));
+    CREATE_TRY(hipMalloc(&s->v, fld_bytes));
+    const KindOps &k = kind_of(s);
+    if (k.create && k.create(s)) return LB_ERR_HIP;
+    CREATE_TRY(hipMalloc(&s->vi_corner, 8 * sizeof(float)));
+    CREATE_TRY(hipMemsetAsync(s->vi_corner, 0, 8 * sizeof(float), s->stream));
+    CREATE_TRY(hipMalloc(&s->mask_raw, (size_t)s->pitch * (s->H + 2 * MASK_GHOST) + 2 * GUARD));
+    s->mask = s->mask_raw + GUARD + MASK_GHOST * s->pitch;
+    CREATE_TRY(hipMemsetAsync(s->rho, 0, fld_bytes, s->stream));
+    CREATE_TRY(hipMemsetAsync(s->u, 0, fld_bytes, s->stream));
+    CREATE_TRY(hipMemsetAsync(s->v, 0, fld_bytes, s->stream));
+    CREATE_TRY(hipMemsetAsync(s->mask_raw, 0, (size_t)s->pitch * (s->H + 2 * MASK_GHOST) + 2 * GUARD, s->stream));
+    CREATE_TRY(hipStreamSynchronize(s->stream));
+    s->bytes += 2 * lat_bytes + 3 * fld_bytes + (size_t)s->pitch * s->H;
+    return LB_OK;
+}
 
 extern "C" {
 
@@ -306,64 +494,15 @@ int lb_create(const lb_params *p, lb_sim **out)
         return fail(LB_ERR_ARG, "LB_BC_ZERO_GRADIENT exists for forced flow in a porous medium (LB_SEM_POROUS) only: unknown bc_mode %d for semantics %d", p->bc_mode, p->semantics);
     if (p->bc_mode == LB_BC_DIRICHLET && p->semantics != LB_SEM_POISSON)
         return fail(LB_ERR_ARG, "LB_BC_DIRICHLET exists for the LB Poisson solver (LB_SEM_POISSON) only: unknown bc_mode %d for semantics %d", p->bc_mode, p->semantics);
-    if (p->semantics == LB_SEM_POISSON) {
-        // the LB Poisson solver: a scalar lattice, refused likewise (before any device is touched)
-        if (p->bc_mode != LB_BC_DIRICHLET)
-            return fail(LB_ERR_ARG, "the LB Poisson solver (LB_SEM_POISSON) takes the family LB_BC_DIRICHLET only: unknown semantics %d for bc_mode %d", p->semantics, p->bc_mode);
-        if (p->local_ny != p->ny || p->y0 != 0) return fail(LB_ERR_ARG, "the LB Poisson solver (LB_SEM_POISSON) owns its whole grid: no slabs");
-        if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "the LB Poisson solver (LB_SEM_POISSON) has no halo interface (LB_FLAG_HALO)");
-        if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "the LB Poisson solver (LB_SEM_POISSON) runs on a GPU only (no CPU backend)");
-    }
-    if (p->semantics == LB_SEM_POROUS) {
-        // the porous-medium fluid: a whole-grid GPU handle without obstacles, refused like the scalar lattices (before any device is touched)
-        if (p->bc_mode != LB_BC_PERIODIC && p->bc_mode != LB_BC_ZERO_GRADIENT)
-            return fail(LB_ERR_ARG, "forced flow in a porous medium (LB_SEM_POROUS) takes the families LB_BC_PERIODIC and LB_BC_ZERO_GRADIENT only");
-        if (p->bc_mode == LB_BC_ZERO_GRADIENT && (p->nx < 3 || p->ny < 3))
-            return fail(LB_ERR_ARG, "LB_BC_ZERO_GRADIENT needs an interior cell: grid must be at least 3x3 (got %dx%d)", p->nx, p->ny);
-        if (p->local_ny != p->ny || p->y0 != 0) return fail(LB_ERR_ARG, "forced flow in a porous medium (LB_SEM_POROUS) owns its whole grid: no slabs");
-        if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "forced flow in a porous medium (LB_SEM_POROUS) has no halo interface (LB_FLAG_HALO)");
-        if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "forced flow in a porous medium (LB_SEM_POROUS) runs on a GPU only (no CPU backend)");
-    }
-    if (p->semantics == LB_SEM_MULTIFLUID) {
-        // a fluid of a multicomponent set: a whole-grid GPU handle without obstacles, refused likewise
-        if (p->bc_mode != LB_BC_PERIODIC && p->bc_mode != LB_BC_ZERO_GRADIENT)
-            return fail(LB_ERR_ARG, "a fluid of a multicomponent set (LB_SEM_MULTIFLUID) takes the families LB_BC_PERIODIC and LB_BC_ZERO_GRADIENT only");
-        if (p->nx < 3 || p->ny < 3)
-            return fail(LB_ERR_ARG, "a fluid of a multicomponent set (LB_SEM_MULTIFLUID) needs a cell with eight neighbours: grid must be at least 3x3 (got %dx%d)", p->nx, p->ny);
-        if (p->local_ny != p->ny || p->y0 != 0) return fail(LB_ERR_ARG, "a fluid of a multicomponent set (LB_SEM_MULTIFLUID) owns its whole grid: no slabs");
-        if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "a fluid of a multicomponent set (LB_SEM_MULTIFLUID) has no halo interface (LB_FLAG_HALO)");
-        if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "a fluid of a multicomponent set (LB_SEM_MULTIFLUID) runs on a GPU only (no CPU backend)");
-    }
-    if (p->semantics == LB_SEM_ROCKET) {
-        // a lattice of a surfactant-propelled colony: a whole-grid GPU scalar lattice, refused likewise
-        if (p->bc_mode != LB_BC_PERIODIC)
-            return fail(LB_ERR_ARG, "a lattice of a surfactant-propelled colony (LB_SEM_ROCKET) takes the family LB_BC_PERIODIC only (box boundaries are not built)");
-        if (p->nx < 3 || p->ny < 3)
-            return fail(LB_ERR_ARG, "a lattice of a surfactant-propelled colony (LB_SEM_ROCKET) needs a cell with eight neighbours: grid must be at least 3x3 (got %dx%d)", p->nx, p->ny);
-        if (p->local_ny != p->ny || p->y0 != 0) return fail(LB_ERR_ARG, "a lattice of a surfactant-propelled colony (LB_SEM_ROCKET) owns its whole grid: no slabs");
-        if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "a lattice of a surfactant-propelled colony (LB_SEM_ROCKET) has no halo interface (LB_FLAG_HALO)");
-        if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "a lattice of a surfactant-propelled colony (LB_SEM_ROCKET) runs on a GPU only (no CPU backend)");
-    }
+    // a kind other than flow: a whole-grid GPU handle without obstacles, refused from its row before any device is touched
+    const KindOps &k = kind_of(p->semantics);
+    int rc;
+    if (k.noun && k.before_exists && (rc = kind_refusals(k, p))) return rc;
     if (p->bc_mode == LB_BC_OPEN && p->semantics != LB_SEM_DIFFUSION)
         return fail(LB_ERR_ARG, "LB_BC_OPEN exists for scalar lattices (LB_SEM_DIFFUSION) only");
     if (p->bc_mode == LB_BC_BOX && p->semantics != LB_SEM_MULTIFIELD)
         return fail(LB_ERR_ARG, "bc_mode LB_BC_BOX exists for coupled scalar lattices (LB_SEM_MULTIFIELD) only");
-    if (p->semantics == LB_SEM_MULTIFIELD) {
-        // the fields of a coupled set: scalar lattices, refused likewise
-        if (p->bc_mode != LB_BC_PERIODIC && p->bc_mode != LB_BC_BOX)
-            return fail(LB_ERR_ARG, "a coupled scalar lattice (LB_SEM_MULTIFIELD) takes the families LB_BC_PERIODIC and LB_BC_BOX only");
-        if (p->local_ny != p->ny || p->y0 != 0) return fail(LB_ERR_ARG, "a coupled scalar lattice (LB_SEM_MULTIFIELD) owns its whole grid: no slabs");
-        if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "a coupled scalar lattice (LB_SEM_MULTIFIELD) has no halo interface (LB_FLAG_HALO)");
-        if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "a coupled scalar lattice (LB_SEM_MULTIFIELD) runs on a GPU only (no CPU backend)");
-    }
-    if (p->semantics == LB_SEM_DIFFUSION) {
-        // scalar lattices (refused before any device is touched)
-        if (p->bc_mode != LB_BC_PERIODIC && p->bc_mode != LB_BC_OPEN)
-            return fail(LB_ERR_ARG, "a scalar lattice (LB_SEM_DIFFUSION) takes the families LB_BC_PERIODIC and LB_BC_OPEN only");
-        if (p->local_ny != p->ny || p->y0 != 0) return fail(LB_ERR_ARG, "a scalar lattice (LB_SEM_DIFFUSION) owns its whole grid: no slabs");
-        if (p->flags & LB_FLAG_HALO) return fail(LB_ERR_ARG, "a scalar lattice (LB_SEM_DIFFUSION) has no halo interface (LB_FLAG_HALO)");
-        if (p->device == LB_DEVICE_CPU) return fail(LB_ERR_ARG, "a scalar lattice (LB_SEM_DIFFUSION) runs on a GPU only (no CPU backend)");
-    }
+    if (k.noun && !k.before_exists && (rc = kind_refusals(k, p))) return rc;
     if (p->bc_mode == LB_BC_VELOCITY_INLET &&
         (p->local_ny != p->ny || (p->flags & LB_FLAG_HALO) || p->semantics != LB_SEM_OPENCL))
         return fail(LB_ERR_ARG, "the velocity-inlet family exists for whole-grid OpenCL-path handles only");
@@ -373,9 +512,7 @@ int lb_create(const lb_params *p, lb_sim **out)
     for (int r : p->reserved)
         if (r != 0) return fail(LB_ERR_ARG, "reserved fields must be zero");
     if (p->flags & ~(LB_FLAG_HALO | LB_FLAG_PLANAR | LB_FLAG_EAGER_MACRO)) return fail(LB_ERR_ARG, "unknown flags 0x%x", p->flags);
-    if (p->semantics != LB_SEM_OPENCL && p->semantics != LB_SEM_CYTHON && p->semantics != LB_SEM_OPENCL_D2Q9I && p->semantics != LB_SEM_DIFFUSION &&
-        p->semantics != LB_SEM_MULTIFIELD && p->semantics != LB_SEM_POISSON && p->semantics != LB_SEM_POROUS && p->semantics != LB_SEM_MULTIFLUID &&
-        p->semantics != LB_SEM_ROCKET)
+    if (!k.noun && p->semantics != LB_SEM_OPENCL && p->semantics != LB_SEM_CYTHON && p->semantics != LB_SEM_OPENCL_D2Q9I)
         return fail(LB_ERR_ARG, "unknown semantics %d", p->semantics);
     if (p->semantics == LB_SEM_OPENCL_D2Q9I &&
         (p->bc_mode != LB_BC_PIPE || p->local_ny != p->ny || (p->flags & LB_FLAG_HALO)))
@@ -426,93 +563,10 @@ int lb_create(const lb_params *p, lb_sim **out)
             s->cu_count = prop.multiProcessorCount;
     }
 
-#define CREATE_TRY(expr)                                                                       \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            fail(LB_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));                   \
-            lb_destroy(s);                                                                     \
-            return LB_ERR_HIP;                                                                 \
-        }                                                                                      \
-    } while (0)
-    CREATE_TRY(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
-    s->stream = s->own_stream;
-    // (Three streams that must not share a hardware queue -- interior, edge bands, halo exchange.  HIP maps a process's streams onto
-    //  GPU_MAX_HW_QUEUES queues, four by default, per priority, and not once and for all: a probe at creation saw three queues in a
-    //  process whose timeline later shows the exchange on the interior's queue.  The process decides -- bench.py sets 8 --; a
-    //  communication stream at the highest priority, a queue pool of its own, pushed the EDGE stream onto the interior's queue in
-    //  bench.py's process structure, 370 -> 230 k MLUPS: profiles/r06_experiments.txt section 10c, r06h_bench_comm_prio.txt.)
-    CREATE_TRY(hipStreamCreateWithFlags(&s->comm_stream, hipStreamNonBlocking));
-    // The edge stream (edge bands, halo push / RCCL) at NORMAL priority, like the other two.  Rounds 1-2 created it at the
-    // device's highest priority; with it, ~2 % of random slab partitions run through lb_run_group with events alone differed from
-    // the undivided run when four other processes kept the GPU busy (17 of ~900, tools/slab_stress.py), none of 1650 without,
-    // while a stand-alone stress of HIP's cross-queue ordering finds nothing (tools/queue_order_repro.hip) and an audit of
-    // every read-after-write and write-after-read pair of the cycle finds every one ordered (DESIGN.md section 6).  The
-    // priority bought nothing measurable (profiles/r03_experiments.txt section 6), so there is no such stream and no switch for one.
-    // (Rounds 3-5 passed the FIRST value hipDeviceGetStreamPriorityRange returns -- the LEAST priority, not the normal one the
-    //  comment claimed: the edge bands, which gate the halo, ran on a low-priority queue.  Round 6: no priority argument at all.)
-    CREATE_TRY(hipStreamCreateWithFlags(&s->edge_stream, hipStreamNonBlocking));
-    const unsigned ev_flags = hipEventDisableTiming;
-    CREATE_TRY(hipEventCreateWithFlags(&s->ev_boundary, ev_flags));
-    CREATE_TRY(hipEventCreateWithFlags(&s->ev_halo, ev_flags));
-    CREATE_TRY(hipEventCreateWithFlags(&s->ev_interior, ev_flags));
-    CREATE_TRY(hipEventCreateWithFlags(&s->ev_packed, ev_flags));
-    CREATE_TRY(hipEventCreateWithFlags(&s->ev_edge, ev_flags));
-    CREATE_TRY(hipEventCreate(&s->ev_t0));
-    CREATE_TRY(hipEventCreate(&s->ev_t1));
-    const size_t lat_bytes = sizeof(float) * s->lat_floats;
-    const size_t fld_bytes = sizeof(float) * s->pitch * s->H;
-    for (int i = 0; i < 2; ++i) {
-        CREATE_TRY(hipMalloc(&s->lat[i], lat_bytes));
-        CREATE_TRY(hipMemsetAsync(s->lat[i], 0, lat_bytes, s->stream));
+    if (create_device(s)) {
+        lb_destroy(s);
+        return LB_ERR_HIP;
     }
-    CREATE_TRY(hipMalloc(&s->rho, fld_bytes));
-    CREATE_TRY(hipMalloc(&s->u, fld_bytes));
-    CREATE_TRY(hipMalloc(&s->v, fld_bytes));
-    if (s->scalar() && p->bc_mode == LB_BC_OPEN) {
-        const size_t edge_bytes = sizeof(float) * (size_t)ad_edge_device_floats(s->pitch, p->ny);
-        CREATE_TRY(hipMalloc(&s->ad_edge, edge_bytes));
-        CREATE_TRY(hipMemsetAsync(s->ad_edge, 0, edge_bytes, s->stream));
-    }
-    if (s->poisson()) {
-        // (the diagnostic word of the flow kernels means nothing here: on this handle it is lb_solve's batch length)
-        s->ps_batch = s->diag > 0 ? s->diag : 0;
-        s->diag = 0;
-        const size_t part_bytes = 2 * sizeof(float) * (size_t)ps_step_blocks(step_args(s, 0, 1, s->H));
-        CREATE_TRY(hipMalloc(&s->ps_source, fld_bytes));
-        CREATE_TRY(hipMemsetAsync(s->ps_source, 0, fld_bytes, s->stream));
-        CREATE_TRY(hipMalloc(&s->ps_part, part_bytes));
-        CREATE_TRY(hipMemsetAsync(s->ps_part, 0, part_bytes, s->stream));
-        CREATE_TRY(hipMalloc(&s->ps_state, sizeof(PsState)));
-        const PsState fresh = {0, nanf(""), 0, 0};
-        CREATE_TRY(hipMemcpy(s->ps_state, &fresh, sizeof(fresh), hipMemcpyHostToDevice));
-        s->bytes += fld_bytes + part_bytes + sizeof(PsState);
-    }
-    if (s->porous() || s->multifluid() || s->rocket()) {
-        s->diag = 0;                                // (the diagnostic word of the flow kernels means nothing here)
-        for (float **q : {&s->pm_G[0], &s->pm_G[1], &s->pm_ub[0], &s->pm_ub[1]}) {
-            CREATE_TRY(hipMalloc(q, fld_bytes));
-            CREATE_TRY(hipMemsetAsync(*q, 0, fld_bytes, s->stream));
-        }
-        s->bytes += 4 * fld_bytes;
-    }
-    if (s->rocket()) {
-        // (every handle can be a set's first: psi / S and the forces of the last step live there)
-        CREATE_TRY(hipMalloc(&s->ry_op, fld_bytes));
-        CREATE_TRY(hipMemsetAsync(s->ry_op, 0, fld_bytes, s->stream));
-        s->bytes += fld_bytes;
-    }
-    CREATE_TRY(hipMalloc(&s->vi_corner, 8 * sizeof(float)));
-    CREATE_TRY(hipMemsetAsync(s->vi_corner, 0, 8 * sizeof(float), s->stream));
-    CREATE_TRY(hipMalloc(&s->mask_raw, (size_t)s->pitch * (s->H + 2 * MASK_GHOST) + 2 * GUARD));
-    s->mask = s->mask_raw + GUARD + MASK_GHOST * s->pitch;
-    CREATE_TRY(hipMemsetAsync(s->rho, 0, fld_bytes, s->stream));
-    CREATE_TRY(hipMemsetAsync(s->u, 0, fld_bytes, s->stream));
-    CREATE_TRY(hipMemsetAsync(s->v, 0, fld_bytes, s->stream));
-    CREATE_TRY(hipMemsetAsync(s->mask_raw, 0, (size_t)s->pitch * (s->H + 2 * MASK_GHOST) + 2 * GUARD, s->stream));
-    CREATE_TRY(hipStreamSynchronize(s->stream));
-#undef CREATE_TRY
-    s->bytes += 2 * lat_bytes + 3 * fld_bytes + (size_t)s->pitch * s->H;
     // A periodic box whose width is not a multiple of 4 cannot use the marching kernels (their lanes hold four consecutive
     // cells, and the wrap at x = nx must fall on a lane boundary): above the Infinity Cache that costs a factor of two or
     // more (LDS tiles / single steps instead of k_step5 / k_step6).  Say so once instead of being silently slow; LB_QUIET=1 mutes it.
@@ -603,16 +657,8 @@ int lb_set_variant(lb_sim *s, int variant)
 {
     if (s && s->cpu) return LB_OK;                 // (one code path: nothing to select)
     if (!s) return fail(LB_ERR_ARG, "null handle");
-    if (s->multifield() && variant != -1 && variant != 0)
-        return fail(LB_ERR_ARG, "a coupled scalar lattice (LB_SEM_MULTIFIELD) takes the variants -1 and 0 only: k_mf_step, no tiles");
-    if (s->poisson() && variant != -1 && variant != 0)
-        return fail(LB_ERR_STATE, "the LB Poisson solver (LB_SEM_POISSON) takes the variants -1 and 0 only: k_ps_step, no tiles");
-    if (s->porous() && variant != -1 && variant != 0)
-        return fail(LB_ERR_STATE, "lb_set_variant: a porous-medium fluid (LB_SEM_POROUS) takes the variants -1 and 0 only: k_pm_step, no tiles");
-    if (s->multifluid() && (variant < -1 || variant > 1))
-        return fail(LB_ERR_STATE, "lb_set_variant: a fluid of a multicomponent set (LB_SEM_MULTIFLUID) takes the variants -1 (the planner's choice), 0 (the two-launch step k_mc_moments + k_mc_collide) and 1 (the one-launch step k_mc_step) only");
-    if (s->rocket() && (variant < -1 || variant > 1))
-        return fail(LB_ERR_STATE, "lb_set_variant: a lattice of a surfactant-propelled colony (LB_SEM_ROCKET) takes the variants -1 (the planner's choice), 0 (the two-launch step k_ry_moments + k_ry_collide) and 1 (the one-launch step k_ry_step) only");
+    const KindOps &k = kind_of(s);
+    if (k.variant_text && (variant < -1 || variant > k.variant_max)) return fail(k.variant_code, "%s", k.variant_text);
     s->variant = variant;
     return LB_OK;
 }
@@ -895,389 +941,6 @@ int lb_set_mask_halo(lb_sim *s, const int32_t *south_rows, const int32_t *north_
     return LB_OK;
 }
 
-// ---- scalar lattices -----------------------------------------------------------------------
-#define NEED_SCALAR(s, name)                                                                                 \
-    do {                                                                                                     \
-        if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
-        NOT_POROUS(s, name);                                                                                 \
-        NOT_ROCKET(s, name);                                                                                 \
-        if (!(s)->scalar()) return fail(LB_ERR_STATE, "%s is for scalar lattices (LB_SEM_DIFFUSION)", name); \
-    } while (0)
-
-// ... whose velocity is imposed: the Poisson solver has none, and its source term is lb_set_source's
-#define NOT_POISSON(s, name)                                                                                 \
-    do {                                                                                                     \
-        if ((s)->poisson()) return fail(LB_ERR_STATE, "%s is not available on the LB Poisson solver (LB_SEM_POISSON)", name); \
-    } while (0)
-
-int lb_set_reaction(lb_sim *s, float G)
-{
-    NEED_SCALAR(s, "lb_set_reaction");
-    NOT_POISSON(s, "lb_set_reaction");
-    if (!(fabsf(G) <= 3.0e38f)) return fail(LB_ERR_ARG, "the growth rate must be finite");
-    s->ad_G = G;
-    return LB_OK;
-}
-
-int lb_edge_floats(lb_sim *s)
-{
-    NEED_SCALAR(s, "lb_edge_floats");
-    return (int)edge_host_floats(s);
-}
-
-int lb_get_edge_state(lb_sim *s, float *out)
-{
-    NEED_SCALAR(s, "lb_get_edge_state");
-    if (!s->ad_edge) return LB_OK;                  // (PERIODIC: zero floats)
-    if (!out) return fail(LB_ERR_ARG, "null argument");
-    DeviceGuard guard(s->p.device);
-    const int nx = s->p.nx, ny = s->p.ny;
-    const size_t n = (size_t)ad_edge_device_floats(s->pitch, ny);
-    float *tmp = (float *)malloc(n * sizeof(float));
-    if (!tmp) return fail(LB_ERR_ARG, "out of host memory");
-    hipError_t e = hipMemcpyAsync(tmp, s->ad_edge, n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    if (e != hipSuccess) {
-        free(tmp);
-        return fail(LB_ERR_HIP, "edge state download: %s", hipGetErrorString(e));
-    }
-    memcpy(out, tmp + 6 * s->pitch, sizeof(float) * 6 * (size_t)ny);
-    float *rows = out + 6 * (size_t)ny;
-    for (int r = 0; r < 6; ++r) memcpy(rows + (size_t)r * nx, tmp + (size_t)r * s->pitch, sizeof(float) * (size_t)nx);
-    // the four corner links a column and a row share: the column's entry is the one that counts
-    rows[1 * (size_t)nx] = out[1 * (size_t)ny];                                 // south f5(0,0) = west f5[0]
-    rows[2 * (size_t)nx + nx - 1] = out[4 * (size_t)ny];                        // south f6(nx-1,0) = east f6[0]
-    rows[4 * (size_t)nx + nx - 1] = out[5 * (size_t)ny + ny - 1];               // north f7(nx-1,ny-1) = east f7[ny-1]
-    rows[5 * (size_t)nx] = out[2 * (size_t)ny + ny - 1];                        // north f8(0,ny-1) = west f8[ny-1]
-    free(tmp);
-    return LB_OK;
-}
-
-int lb_set_edge_state(lb_sim *s, const float *in)
-{
-    NEED_SCALAR(s, "lb_set_edge_state");
-    if (!s->ad_edge) return LB_OK;
-    if (!in) return fail(LB_ERR_ARG, "null argument");
-    DeviceGuard guard(s->p.device);
-    const int nx = s->p.nx, ny = s->p.ny;
-    const size_t n = (size_t)ad_edge_device_floats(s->pitch, ny);
-    float *tmp = (float *)calloc(n, sizeof(float));
-    if (!tmp) return fail(LB_ERR_ARG, "out of host memory");
-    memcpy(tmp + 6 * s->pitch, in, sizeof(float) * 6 * (size_t)ny);
-    const float *rows = in + 6 * (size_t)ny;
-    for (int r = 0; r < 6; ++r) memcpy(tmp + (size_t)r * s->pitch, rows + (size_t)r * nx, sizeof(float) * (size_t)nx);
-    hipError_t e = hipStreamSynchronize(s->stream);       // (kernels of an un-waited run may still be reading it)
-    if (e == hipSuccess) e = hipMemcpy(s->ad_edge, tmp, n * sizeof(float), hipMemcpyHostToDevice);
-    free(tmp);
-    if (e != hipSuccess) return fail(LB_ERR_HIP, "edge state upload: %s", hipGetErrorString(e));
-    return LB_OK;
-}
-
-int lb_set_velocity_from(lb_sim *s, lb_sim *flow)
-{
-    NEED_SCALAR(s, "lb_set_velocity_from");
-    NOT_POISSON(s, "lb_set_velocity_from");
-    if (!flow) return fail(LB_ERR_ARG, "null flow handle");
-    if (flow->cpu || flow->scalar() || flow->multi_slab())
-        return fail(LB_ERR_ARG, "lb_set_velocity_from takes a whole-grid GPU flow handle");
-    if (flow->p.nx != s->p.nx || flow->p.ny != s->p.ny || flow->p.device != s->p.device)
-        return fail(LB_ERR_ARG, "the flow handle must have the scalar lattice's grid (%d x %d) and device", s->p.nx, s->p.ny);
-    if (flow->stepping) return fail(LB_ERR_STATE, "lb_set_velocity_from inside a split step of the flow handle");
-    DeviceGuard guard(s->p.device);
-    int rc = ensure_macro(flow);                    // the flow's lazily rebuilt rho, u, v
-    if (rc) return rc;
-    // on the FLOW handle's stream, behind its work; this handle's kernels may still read u, v, and its later ones must see the new
-    HIP_TRY(hipEventRecord(s->ev_interior, s->stream));
-    HIP_TRY(hipStreamWaitEvent(flow->stream, s->ev_interior, 0));
-    // (rho, u, v are [H][pitch] whatever the layout of the lattices: LB_FLAG_PLANAR on either handle does not matter here)
-    const long long n4 = s->pitch * s->H / 4;       // (same pitch: same nx)
-    for (int i = 0; i < 2; ++i) {
-        hipLaunchKernelGGL(k_copy4<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, flow->stream,
-                           reinterpret_cast<const f4a *>(i ? flow->v : flow->u), reinterpret_cast<f4a *>(i ? s->v : s->u), n4);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(flow->ev_interior, flow->stream));
-    HIP_TRY(hipStreamWaitEvent(s->stream, flow->ev_interior, 0));
-    s->feq_valid = false;
-    return LB_OK;
-}
-
-// ---- the LB Poisson solver ---------------------------------------------------------------------
-#define NEED_POISSON(s, name)                                                                                \
-    do {                                                                                                     \
-        if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
-        NOT_POROUS(s, name);                                                                                 \
-        NOT_ROCKET(s, name);                                                                                 \
-        if (!(s)->poisson()) return fail(LB_ERR_STATE, "%s is for the LB Poisson solver (LB_SEM_POISSON)", name); \
-    } while (0)
-
-// lb_solve's launches between two reads of the stop word.  profiles/poisson_bench.txt: the read-back is one host round trip per batch,
-// the launches behind a stop inside a batch are empty early-outs.
-static const int PS_BATCH = 32;
-
-int lb_set_poisson(lb_sim *s, float rho_on_boundary, float react_factor, float tolerance)
-{
-    NEED_POISSON(s, "lb_set_poisson");
-    if (!(fabsf(rho_on_boundary) <= 3.0e38f) || !(fabsf(react_factor) <= 3.0e38f)) return fail(LB_ERR_ARG, "rho_on_boundary and react_factor must be finite");
-    if (!(tolerance >= 0.f)) return fail(LB_ERR_ARG, "the tolerance must be >= 0");
-    s->ps_rho_b = rho_on_boundary;
-    s->ps_react = react_factor;
-    s->ps_tol = tolerance;
-    return LB_OK;
-}
-
-int lb_set_source(lb_sim *s, const float *src, int on_device)
-{
-    NEED_POISSON(s, "lb_set_source");
-    if (!src) return fail(LB_ERR_ARG, "null argument");
-    DeviceGuard guard(s->p.device);
-    HIP_TRY(hipMemcpy2DAsync(s->ps_source, s->pitch * sizeof(float), src, s->p.nx * sizeof(float), s->p.nx * sizeof(float), s->H,
-                             on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return LB_OK;
-}
-
-int lb_get_source(lb_sim *s, float *src)
-{
-    NEED_POISSON(s, "lb_get_source");
-    if (!src) return fail(LB_ERR_ARG, "null argument");
-    DeviceGuard guard(s->p.device);
-    int rc = copy_plane_d2h(s, src, s->ps_source);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return LB_OK;
-}
-
-int lb_solve_reset(lb_sim *s)
-{
-    NEED_POISSON(s, "lb_solve_reset");
-    s->ps_iter = 0;
-    return LB_OK;
-}
-
-int lb_get_solve_state(lb_sim *s, int *iterations, int *stop_word)
-{
-    NEED_POISSON(s, "lb_get_solve_state");
-    DeviceGuard guard(s->p.device);
-    PsState h;
-    HIP_TRY(hipMemcpyAsync(&h, s->ps_state, sizeof(h), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (iterations) *iterations = s->ps_iter;
-    if (stop_word) *stop_word = h.stop;
-    return LB_OK;
-}
-
-int lb_set_solve_state(lb_sim *s, int iterations, int stop_word)
-{
-    NEED_POISSON(s, "lb_set_solve_state");
-    if (iterations < 0 || stop_word < 0 || stop_word > iterations) return fail(LB_ERR_ARG, "need 0 <= stop_word <= iterations");
-    DeviceGuard guard(s->p.device);
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipMemcpy(&s->ps_state->stop, &stop_word, sizeof(int), hipMemcpyHostToDevice));
-    s->ps_iter = iterations;
-    return LB_OK;
-}
-
-// solver.py:324-358 without its host waits: per iteration one k_ps_step<true> and -- from the second iteration since the last reset --
-// one k_ps_check, PS_BATCH iterations enqueued at a time; after each batch the stop word comes back (4 bytes).  A stop at iteration
-// n* leaves the launches behind it as empty early-outs, so the populations and rho are those after n* iterations; which lattice of the
-// pair holds them follows from n*.
-int lb_solve(lb_sim *s, int max_iterations, int *iterations_done, int *converged, float *last_ratio)
-{
-    NEED_POISSON(s, "lb_solve");
-    if (max_iterations < 0) return fail(LB_ERR_ARG, "negative iteration count");
-    DeviceGuard guard(s->p.device);
-    const int batch = s->ps_batch > 0 ? s->ps_batch : PS_BATCH, first = s->ps_iter, cur0 = s->cur;
-    const long long blocks = ps_step_blocks(step_args(s, 0, 1, s->H));
-    const PsExtra e = ps_extra(s);
-    HIP_TRY(hipMemsetAsync(&s->ps_state->stop, 0, sizeof(int), s->stream));     // (a call after a stop goes on, as the reference's run does)
-    int launched = 0, stop = 0;
-    while (launched < max_iterations && !stop) {
-        const int nb = std::min(batch, max_iterations - launched);
-        for (int i = 0; i < nb; ++i, ++launched) {
-            const int it = first + launched + 1;
-            lbk_ps_step(true, s->stream, step_args(s, 0, 1, s->H), e);
-            HIP_TRY(hipGetLastError());
-            s->cur ^= 1;
-            if (it >= 2) {
-                lbk_ps_check(s->stream, s->ps_part, blocks, s->ps_state, it, s->ps_tol);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-        HIP_TRY(hipMemcpyAsync(&stop, &s->ps_state->stop, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-    }
-    const int done = stop ? stop - first : launched;
-    s->cur = cur0 ^ (done & 1);
-    s->ps_iter = first + done;
-    if (done) { s->feq_valid = false; s->macro_valid = true; }
-    if (last_ratio) {
-        HIP_TRY(hipMemcpyAsync(last_ratio, &s->ps_state->ratio, sizeof(float), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-    }
-    if (iterations_done) *iterations_done = done;
-    if (converged) *converged = stop ? 1 : 0;
-    return LB_OK;
-}
-
-// One launch into the handle's u, v planes -- which no other kernel of this semantics writes: they hold the last gradient, lb_get_macro
-// returns it --, then one pitched copy each to wherever the caller's pointers lead.
-int lb_gradient(lb_sim *s, float inv_two_dx, float *ddx, float *ddy)
-{
-    NEED_POISSON(s, "lb_gradient");
-    if (!(fabsf(inv_two_dx) <= 3.0e38f)) return fail(LB_ERR_ARG, "inv_two_dx must be finite");
-    DeviceGuard guard(s->p.device);
-    lbk_ps_gradient(s->stream, step_args(s, 0, 1, s->H), inv_two_dx);
-    HIP_TRY(hipGetLastError());
-    float *out[2] = {ddx, ddy};
-    const float *from[2] = {s->u, s->v};
-    for (int i = 0; i < 2; ++i)
-        if (out[i])
-            HIP_TRY(hipMemcpy2DAsync(out[i], s->p.nx * sizeof(float), from[i], s->pitch * sizeof(float), s->p.nx * sizeof(float), s->H,
-                                     hipMemcpyDefault, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return LB_OK;
-}
-
-// ---- forced flow in a porous medium ------------------------------------------------------------
-#define NEED_POROUS(s, name)                                                                                 \
-    do {                                                                                                     \
-        if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
-        NOT_ROCKET(s, name);                                                                                 \
-        if ((s)->multifluid()) return fail(LB_ERR_STATE, "%s is not available on a fluid of a multicomponent set (LB_SEM_MULTIFLUID)", name); \
-        if (!(s)->porous()) return fail(LB_ERR_STATE, "%s is for forced flow in a porous medium (LB_SEM_POROUS)", name); \
-    } while (0)
-// (the calls a fluid of a multicomponent set shares with the porous-medium fluid: its g, its force field, G and u_b)
-#define NEED_FORCED(s, name)                                                                                 \
-    do {                                                                                                     \
-        if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
-        NOT_ROCKET(s, name);                                                                                 \
-        if (!(s)->porous() && !(s)->multifluid())                                                            \
-            return fail(LB_ERR_STATE, "%s is for forced flow in a porous medium (LB_SEM_POROUS) and the fluids of a multicomponent set (LB_SEM_MULTIFLUID)", name); \
-    } while (0)
-
-static bool pm_finite(float x) { return fabsf(x) <= 3.0e38f; }      // (false for NaN)
-
-int lb_set_porous(lb_sim *s, float epsilon, float nu_fluid, float K, float Fe)
-{
-    NEED_POROUS(s, "lb_set_porous");
-    if (!pm_finite(epsilon) || !pm_finite(nu_fluid) || !pm_finite(K) || !pm_finite(Fe)) return fail(LB_ERR_ARG, "epsilon, nu_fluid, K and Fe must be finite");
-    if (!(epsilon > 0.f) || !(K > 0.f)) return fail(LB_ERR_ARG, "need epsilon > 0 and K > 0 (got %g, %g)", epsilon, K);
-    s->pm_eps = epsilon; s->pm_nu = nu_fluid; s->pm_K = K; s->pm_Fe = Fe;
-    s->feq_valid = false;
-    return LB_OK;
-}
-
-int lb_set_body_force(lb_sim *s, float gx, float gy)
-{
-    NEED_FORCED(s, "lb_set_body_force");
-    if (!pm_finite(gx) || !pm_finite(gy)) return fail(LB_ERR_ARG, "the body force must be finite");
-    s->pm_gx = gx; s->pm_gy = gy;
-    return LB_OK;
-}
-
-int lb_set_force_field(lb_sim *s, const float *gx, const float *gy, int on_device)
-{
-    NEED_FORCED(s, "lb_set_force_field");
-    if ((gx == nullptr) != (gy == nullptr)) return fail(LB_ERR_ARG, "both planes of the force field, or neither");
-    DeviceGuard guard(s->p.device);
-    HIP_TRY(hipStreamSynchronize(s->stream));       // (kernels of an un-waited run may still be reading it)
-    if (!gx) {
-        for (float *&q : s->pm_field) {
-            if (q) {
-                HIP_TRY(hipFree(q));
-                s->bytes -= (int64_t)sizeof(float) * s->pitch * s->H;
-            }
-            q = nullptr;
-        }
-        s->has_field = false;
-        return LB_OK;
-    }
-    const size_t fld_bytes = sizeof(float) * s->pitch * s->H;
-    const float *from[2] = {gx, gy};
-    for (int i = 0; i < 2; ++i) {
-        if (!s->pm_field[i]) {
-            HIP_TRY(hipMalloc(&s->pm_field[i], fld_bytes));
-            s->bytes += (int64_t)fld_bytes;
-        }
-        HIP_TRY(hipMemsetAsync(s->pm_field[i], 0, fld_bytes, s->stream));
-        HIP_TRY(hipMemcpy2DAsync(s->pm_field[i], s->pitch * sizeof(float), from[i], s->p.nx * sizeof(float), s->p.nx * sizeof(float), s->H,
-                                 on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    s->has_field = true;
-    return LB_OK;
-}
-
-static int pm_get_pair(lb_sim *s, float *const (&pair)[2], float *a, float *b)
-{
-    DeviceGuard guard(s->p.device);
-    int rc;
-    if (a && (rc = copy_plane_d2h(s, a, pair[0]))) return rc;
-    if (b && (rc = copy_plane_d2h(s, b, pair[1]))) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return LB_OK;
-}
-
-int lb_get_force(lb_sim *s, float *Gx, float *Gy)
-{
-    NEED_FORCED(s, "lb_get_force");
-    return pm_get_pair(s, s->pm_G, Gx, Gy);
-}
-
-int lb_get_bary_velocity(lb_sim *s, float *u_bary, float *v_bary)
-{
-    NEED_FORCED(s, "lb_get_bary_velocity");
-    return pm_get_pair(s, s->pm_ub, u_bary, v_bary);
-}
-
-int lb_set_bary_velocity(lb_sim *s, const float *u_bary, const float *v_bary)
-{
-    NEED_FORCED(s, "lb_set_bary_velocity");
-    if (!u_bary || !v_bary) return fail(LB_ERR_ARG, "null argument");
-    DeviceGuard guard(s->p.device);
-    int rc;
-    if ((rc = copy_plane_h2d(s, s->pm_ub[0], u_bary))) return rc;
-    if ((rc = copy_plane_h2d(s, s->pm_ub[1], v_bary))) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    s->feq_valid = false;
-    return LB_OK;
-}
-
-// (checkpoints: the total force as the last step left it)
-int lb_set_force(lb_sim *s, const float *Gx, const float *Gy)
-{
-    NEED_FORCED(s, "lb_set_force");
-    if (!Gx || !Gy) return fail(LB_ERR_ARG, "null argument");
-    DeviceGuard guard(s->p.device);
-    int rc;
-    if ((rc = copy_plane_h2d(s, s->pm_G[0], Gx))) return rc;
-    if ((rc = copy_plane_h2d(s, s->pm_G[1], Gy))) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return LB_OK;
-}
-
-int lb_update_forces(lb_sim *s)
-{
-    NEED_FORCED(s, "lb_update_forces");
-    if (s->multifluid()) return lb_update_forces_fluids(&s, 1);
-    DeviceGuard guard(s->p.device);
-    lbk_pm_forces(s->stream, step_args(s, 0, 1, s->H), pm_extra(s));
-    HIP_TRY(hipGetLastError());
-    return LB_OK;
-}
-
-int lb_update_bary_velocity(lb_sim *s)
-{
-    NEED_FORCED(s, "lb_update_bary_velocity");
-    if (s->multifluid()) return lb_update_bary_fluids(&s, 1);
-    DeviceGuard guard(s->p.device);
-    lbk_pm_bary(s->stream, step_args(s, 0, 1, s->H), pm_extra(s), s->origin(s->cur));
-    HIP_TRY(hipGetLastError());
-    s->feq_valid = false;
-    return LB_OK;
-}
-
 // ---- un-fused phases ---------------------------------------------------------------------
 
 int lb_move(lb_sim *s)
@@ -1312,35 +975,10 @@ int lb_move_bcs(lb_sim *s)
     if (!s) return fail(LB_ERR_ARG, "null handle");
     int rc = need_single_slab(s, "lb_move_bcs");
     if (rc) return rc;
-    if (s->scalar() && s->p.bc_mode != LB_BC_BOX && !s->poisson()) return LB_OK;     // (diffusion.py:326-331: `pass`; the periodic families have none)
-    if ((s->porous() || s->multifluid()) && s->p.bc_mode == LB_BC_PERIODIC) return LB_OK;                 // (single_component.py:155-156: `pass`)
+    const KindOps &k = kind_of(s);
+    if (!k.move_bcs) return LB_OK;
     DeviceGuard guard(s->p.device);
-    if (s->porous() || s->multifluid()) {           // single_component.cl's and multi.cl's move_open_bcs: boundary cells copy their interior neighbour
-        lbk_pm_move_bcs(s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur));
-        HIP_TRY(hipGetLastError());
-        return LB_OK;
-    }
-    if (s->poisson()) {                             // D2Q9_poisson.cl's move_bcs: the prescribed value on four walls
-        lbk_ps_move_bcs(s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur), ps_extra(s).wall);
-        HIP_TRY(hipGetLastError());
-        return LB_OK;
-    }
-    if (s->scalar()) {                              // D2Q9_multifield_fisher.cl's move_bcs: on-node bounce-back on four walls
-        lbk_mf_move_bcs(s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur));
-        HIP_TRY(hipGetLastError());
-        return LB_OK;
-    }
-    if ((rc = ensure_macro(s))) return rc;
-    if (s->p.semantics == LB_SEM_CYTHON)
-        hipLaunchKernelGGL(k1_bcs, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
-    else if (s->p.bc_mode == LB_BC_VELOCITY_INLET) {
-        hipLaunchKernelGGL(k_bcs_vel, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
-        HIP_TRY(hipGetLastError());
-        if (s->has_mask) hipLaunchKernelGGL(k_bounce, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
-    } else
-        hipLaunchKernelGGL(k_bcs, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
-    HIP_TRY(hipGetLastError());
-    return LB_OK;
+    return k.move_bcs(s);
 }
 
 int lb_update_hydro(lb_sim *s)
@@ -1350,26 +988,7 @@ int lb_update_hydro(lb_sim *s)
     int rc = need_single_slab(s, "lb_update_hydro");
     if (rc) return rc;
     DeviceGuard guard(s->p.device);
-    if (s->multifluid())
-        lbk_mc_hydro(s->stream, step_args(s, 0, 1, s->H));       // rho, and u, v where rho > 1e-12
-    else if (s->porous())
-        lbk_pm_hydro(s->stream, step_args(s, 0, 1, s->H));       // rho, and u, v where rho > 1e-6
-    else if (s->poisson())
-        lbk_ps_hydro(s->stream, step_args(s, 0, 1, s->H));       // rho = (9/5)(f1 + ... + f8)
-    else if (s->scalar())
-        lbk_ad_hydro(s->stream, step_args(s, 0, 1, s->H));       // rho only: u, v are imposed
-    else if (s->p.semantics == LB_SEM_CYTHON)
-        hipLaunchKernelGGL(k1_hydro, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
-    else if (s->p.bc_mode == LB_BC_VELOCITY_INLET)
-        hipLaunchKernelGGL(k_hydro_vel, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
-    else if (s->p.semantics == LB_SEM_OPENCL_D2Q9I) {
-        // D2Q9i.cl:67-97 + the cylinder class's override (opencl_dim_D2Q9i.py:494-503): u, v zeroed in the obstacle
-        hipLaunchKernelGGL(k_hydro_i, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
-        HIP_TRY(hipGetLastError());
-        if (s->has_mask) hipLaunchKernelGGL(k_zero_vel, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
-    } else
-        hipLaunchKernelGGL(k_hydro, cells_grid(s, 1), dim3(256), 0, s->stream, phase_args(s));
-    HIP_TRY(hipGetLastError());
+    if ((rc = kind_of(s).hydro(s))) return rc;
     s->macro_valid = true;
     return LB_OK;   // feq keeps its previous content, as the reference's feq buffer does
 }
@@ -1382,19 +1001,7 @@ int lb_update_feq(lb_sim *s)
     int rc = ensure_feq(s);
     if (rc) return rc;
     if ((rc = ensure_macro(s))) return rc;
-    PhaseArgs a = phase_args(s);
-    a.ny = s->H;   // rho,u,v are local: valid for slabs too
-    if (s->porous() || s->multifluid())
-        lbk_pm_feq(s->stream, step_args(s, 0, 1, s->H), pm_extra(s), s->feq_origin());      // from rho and u_b (a fluid of a multicomponent set: epsilon = 1)
-    else if (s->poisson())
-        lbk_ps_feq(s->stream, step_args(s, 0, 1, s->H), s->feq_origin());
-    else if (s->scalar())
-        lbk_ad_feq(s->stream, step_args(s, 0, 1, s->H), s->feq_origin());
-    else if (s->p.semantics == LB_SEM_OPENCL_D2Q9I)
-        hipLaunchKernelGGL(k_feq_i, dim3((s->p.nx + 255) / 256, s->H, 1), dim3(256), 0, s->stream, a);
-    else
-        hipLaunchKernelGGL(k_feq, dim3((s->p.nx + 255) / 256, s->H, 1), dim3(256), 0, s->stream, a);
-    HIP_TRY(hipGetLastError());
+    if ((rc = kind_of(s).feq(s))) return rc;
     s->feq_valid = true;
     return LB_OK;
 }
@@ -1405,23 +1012,8 @@ int lb_collide_particles(lb_sim *s)
     if (!s) return fail(LB_ERR_ARG, "null handle");
     int rc = need_single_slab(s, "lb_collide_particles");
     if (rc) return rc;
-    NOT_ROCKET(s, "lb_collide_particles (the collision needs both members: lb_collide_rocket)");
-    if (!s->feq) return fail(LB_ERR_STATE, "lb_collide_particles before any lb_update_feq");
-    if (s->multifield()) return lb_collide_coupled(&s, 1);
     DeviceGuard guard(s->p.device);
-    if ((rc = ensure_macro(s))) return rc;
-    if (s->multifluid())
-        lbk_mc_relax(s->stream, step_args(s, 0, 1, s->H), pm_extra(s), s->origin(s->cur), s->feq_origin());
-    else if (s->porous())
-        lbk_pm_collide(s->stream, step_args(s, 0, 1, s->H), pm_extra(s), s->origin(s->cur), s->feq_origin());
-    else if (s->poisson())
-        lbk_ps_collide(s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur), s->feq_origin(), s->ps_source, s->ps_react);
-    else if (s->scalar())
-        lbk_ad_collide(s->ad_G != 0.f, s->stream, step_args(s, 0, 1, s->H), s->origin(s->cur), s->feq_origin(), s->ad_G);
-    else
-        hipLaunchKernelGGL(k_collide, cells_grid(s, 9), dim3(256), 0, s->stream, phase_args(s));
-    HIP_TRY(hipGetLastError());
-    return LB_OK;
+    return kind_of(s).collide(s);
 }
 
 int lb_zero_velocity_in_obstacle(lb_sim *s)
@@ -1472,17 +1064,8 @@ int lb_run(lb_sim *s, int n_steps)
     if (!s) return fail(LB_ERR_ARG, "null handle");
     if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
     if (s->stepping) return fail(LB_ERR_STATE, "lb_run between lb_step_boundary and lb_step_finish");
-    NOT_ROCKET(s, "lb_run (a colony advances as a set of two: lb_run_rocket)");
     DeviceGuard guard(s->p.device);
-    if (s->multifield()) return lb_run_coupled(&s, 1, n_steps);
-    if (s->poisson()) return run_poisson(s, n_steps);
-    if (s->porous()) return run_porous(s, n_steps);
-    if (s->multifluid()) return lb_run_fluids(&s, 1, n_steps);
-    if (s->scalar()) return run_scalar(s, n_steps);
-    if (!s->tune_cache_checked) (void)tune_cache_apply(s);
-    if (s->p.semantics == LB_SEM_CYTHON) return run_cython(s, n_steps);
-    if (!s->multi_slab()) return run_whole_grid(s, n_steps);     // (never blocks the host: tuning is lb_autotune*'s job)
-    return run_slab(s, n_steps);
+    return kind_of(s).run(s, n_steps);
 }
 
 // Population sets: `count` periodic whole-grid lattices of one geometry (one per population of a multi-population
@@ -1508,11 +1091,8 @@ int lb_run_batch(lb_sim **sims, int count, int n_steps)
     if (n_steps == 0) return LB_OK;
     lb_sim *s0 = sims[0];
     DeviceGuard guard(s0->p.device);
-    // everything is enqueued on the first member's stream, behind whatever the others still have in flight
-    for (int i = 1; i < count; ++i) {
-        HIP_TRY(hipEventRecord(sims[i]->ev_interior, sims[i]->stream));
-        HIP_TRY(hipStreamWaitEvent(s0->stream, sims[i]->ev_interior, 0));
-    }
+    int rc = set_join(sims, count);
+    if (rc) return rc;
     const dim3 block(256, 1);
     const dim3 grid((unsigned)((s0->pitch / 4 + 255) / 256), (unsigned)s0->H, (unsigned)count);
     bool lazy = true;              // (one launch serves all members: rho, u, v are stored unless every member rebuilds them on demand)
@@ -1525,425 +1105,11 @@ int lb_run_batch(lb_sim **sims, int count, int n_steps)
         HIP_TRY(hipGetLastError());
         for (int i = 0; i < count; ++i) sims[i]->cur ^= 1;
     }
-    // the other members' streams see the result
-    HIP_TRY(hipEventRecord(s0->ev_interior, s0->stream));
     for (int i = 0; i < count; ++i) {
-        if (i) HIP_TRY(hipStreamWaitEvent(sims[i]->stream, s0->ev_interior, 0));
         sims[i]->feq_valid = false;
         sims[i]->macro_valid = !lazy;
     }
-    return LB_OK;
-}
-
-// Coupled scalar lattices: the members of a set, checked alike for lb_run_coupled and lb_collide_coupled.
-static int coupled_members(lb_sim **f, int count, const char *what)
-{
-    if (!f || count < 1 || count > MF_MAX) return fail(LB_ERR_ARG, "%s takes 1..%d handles", what, MF_MAX);
-    for (int i = 0; i < count; ++i) {
-        lb_sim *s = f[i];
-        if (!s) return fail(LB_ERR_ARG, "null handle in the coupled set");
-        if (s->cpu || !s->multifield()) return fail(LB_ERR_ARG, "the members of a coupled set must be LB_SEM_MULTIFIELD handles");
-        if (s->p.nx != f[0]->p.nx || s->p.ny != f[0]->p.ny || s->p.bc_mode != f[0]->p.bc_mode || s->p.device != f[0]->p.device ||
-            (s->p.flags & LB_FLAG_PLANAR) != (f[0]->p.flags & LB_FLAG_PLANAR))
-            return fail(LB_ERR_ARG, "the members of a coupled set must share grid, boundary family, layout flag and device");
-        if (s->stepping) return fail(LB_ERR_STATE, "%s inside a split step", what);
-        for (int j = 0; j < i; ++j)
-            if (f[j] == s) return fail(LB_ERR_ARG, "a handle appears twice in the coupled set");
-    }
-    return LB_OK;
-}
-
-// everything of a coupled call is enqueued on the first member's stream, behind whatever the others still have in flight ...
-static int coupled_join(lb_sim **f, int count)
-{
-    for (int i = 1; i < count; ++i) {
-        HIP_TRY(hipEventRecord(f[i]->ev_interior, f[i]->stream));
-        HIP_TRY(hipStreamWaitEvent(f[0]->stream, f[i]->ev_interior, 0));
-    }
-    return LB_OK;
-}
-// ... and the other members' streams see the result
-static int coupled_release(lb_sim **f, int count)
-{
-    if (count < 2) return LB_OK;
-    HIP_TRY(hipEventRecord(f[0]->ev_interior, f[0]->stream));
-    for (int i = 1; i < count; ++i) HIP_TRY(hipStreamWaitEvent(f[i]->stream, f[0]->ev_interior, 0));
-    return LB_OK;
-}
-
-int lb_run_coupled(lb_sim **fields, int count, int n_steps)
-{
-    for (int i = 0; fields && i < count; ++i) NOT_POROUS(fields[i], "lb_run_coupled");
-    for (int i = 0; fields && i < count; ++i) NOT_ROCKET(fields[i], "lb_run_coupled");
-    int rc = coupled_members(fields, count, "lb_run_coupled");
-    if (rc) return rc;
-    if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
-    if (n_steps == 0) return LB_OK;
-    lb_sim *s0 = fields[0];
-    DeviceGuard guard(s0->p.device);
-    if ((rc = coupled_join(fields, count))) return rc;
-    for (int it = 0; it < n_steps; ++it) {
-        MfArgs m = {};
-        for (int i = 0; i < count; ++i) {
-            m.a[i] = step_args(fields[i], 0, 1, fields[i]->H);
-            m.G[i] = fields[i]->ad_G;
-        }
-        lbk_mf_step(s0->p.bc_mode, count, it == n_steps - 1, s0->stream, m);      // the last launch stores every field's rho
-        HIP_TRY(hipGetLastError());
-        for (int i = 0; i < count; ++i) fields[i]->cur ^= 1;
-    }
-    for (int i = 0; i < count; ++i) {
-        fields[i]->feq_valid = false;
-        fields[i]->macro_valid = true;
-    }
-    return coupled_release(fields, count);
-}
-
-int lb_collide_coupled(lb_sim **fields, int count)
-{
-    int rc = coupled_members(fields, count, "lb_collide_coupled");
-    if (rc) return rc;
-    for (int i = 0; i < count; ++i)
-        if (!fields[i]->feq) return fail(LB_ERR_STATE, "lb_collide_coupled before lb_update_feq on every member");
-    lb_sim *s0 = fields[0];
-    DeviceGuard guard(s0->p.device);
-    if ((rc = coupled_join(fields, count))) return rc;
-    MfArgs m = {};
-    for (int i = 0; i < count; ++i) {
-        m.a[i] = step_args(fields[i], 0, 1, fields[i]->H);
-        m.a[i].dst = fields[i]->origin(fields[i]->cur);         // relaxed in place
-        m.G[i] = fields[i]->ad_G;
-        m.feq[i] = fields[i]->feq_origin();
-    }
-    lbk_mf_collide(count, s0->stream, m);
-    HIP_TRY(hipGetLastError());
-    return coupled_release(fields, count);
-}
-
-// ---- multicomponent Shan-Chen fluids: the members of a set, checked alike for every set call ---------------------------------
-static int fluid_members(lb_sim **f, int count, const char *what)
-{
-    if (!f) return fail(LB_ERR_ARG, "%s: null handle array", what);
-    if (count < 1 || count > MC_MAX) return fail(LB_ERR_ARG, "%s takes 1..%d handles (more than %d fluids are not built)", what, MC_MAX, MC_MAX);
-    for (int i = 0; i < count; ++i) {
-        lb_sim *s = f[i];
-        if (!s) return fail(LB_ERR_ARG, "null handle in the set of fluids");
-        NOT_ROCKET(s, what);
-        if (s->cpu || !s->multifluid()) return fail(LB_ERR_STATE, "%s is for the fluids of a multicomponent set (LB_SEM_MULTIFLUID)", what);
-        if (s->p.nx != f[0]->p.nx || s->p.ny != f[0]->p.ny || s->p.bc_mode != f[0]->p.bc_mode || s->p.device != f[0]->p.device ||
-            (s->p.flags & LB_FLAG_PLANAR) != (f[0]->p.flags & LB_FLAG_PLANAR))
-            return fail(LB_ERR_ARG, "the fluids of a set must share grid, boundary family, layout flag and device (fluids of different families in one set are not built)");
-        for (int j = 0; j < i; ++j)
-            if (f[j] == s) return fail(LB_ERR_ARG, "a handle appears twice in the set of fluids");
-    }
-    // the tables name fluids by their place in the set
-    for (int t = 0; t < f[0]->mc_n_inter; ++t)
-        if (f[0]->mc_inter[t].i >= count || f[0]->mc_inter[t].j >= count)
-            return fail(LB_ERR_STATE, "%s: the interaction table of the first handle names fluid %d of a set of %d", what,
-                        f[0]->mc_inter[t].i > f[0]->mc_inter[t].j ? f[0]->mc_inter[t].i : f[0]->mc_inter[t].j, count);
-    for (int t = 0; t < f[0]->mc_n_react; ++t)
-        if (f[0]->mc_react[t].a >= count || f[0]->mc_react[t].b >= count)
-            return fail(LB_ERR_STATE, "%s: the reaction table of the first handle names a fluid outside a set of %d", what, count);
-    return LB_OK;
-}
-
-// (src = dst = the current lattice: what the phases read and write in place; the two-launch step sets dst itself)
-static McArgs fluid_args(lb_sim **f, int count)
-{
-    McArgs m = {};
-    for (int i = 0; i < count; ++i) {
-        m.a[i] = step_args(f[i], 0, 1, f[i]->H);
-        m.e[i] = pm_extra(f[i]);
-    }
-    for (int t = 0; t < f[0]->mc_n_inter; ++t) m.inter[t] = f[0]->mc_inter[t];
-    for (int t = 0; t < f[0]->mc_n_react; ++t) m.react[t] = f[0]->mc_react[t];
-    m.n_inter = f[0]->mc_n_inter;
-    m.n_react = f[0]->mc_n_react;
-    return m;
-}
-
-int lb_run_fluids(lb_sim **fluids, int count, int n_steps)
-{
-    int rc = fluid_members(fluids, count, "lb_run_fluids");
-    if (rc) return rc;
-    if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
-    if (n_steps == 0) return LB_OK;
-    lb_sim *s0 = fluids[0];
-    DeviceGuard guard(s0->p.device);
-    if ((rc = coupled_join(fluids, count))) return rc;
-    for (int it = 0; it < n_steps; ++it) {
-        const McArgs m = fluid_args(fluids, count);
-        if (multifluid_one_launch(s0)) {            // (the set's first handle chooses: lb_set_variant; plan.cpp)
-            lbk_mc_step(s0->p.bc_mode, count, it == n_steps - 1, s0->stream, m);        // the last one stores rho, u, v, G and u_b
-            HIP_TRY(hipGetLastError());
-        } else {
-            lbk_mc_moments(s0->p.bc_mode, count, s0->stream, m);
-            HIP_TRY(hipGetLastError());
-            lbk_mc_collide(s0->p.bc_mode, count, it == n_steps - 1, s0->stream, m);     // the last one stores u, v, G and u_b
-            HIP_TRY(hipGetLastError());
-        }
-        for (int i = 0; i < count; ++i) fluids[i]->cur ^= 1;
-    }
-    for (int i = 0; i < count; ++i) {
-        fluids[i]->feq_valid = false;
-        fluids[i]->macro_valid = true;
-    }
-    return coupled_release(fluids, count);
-}
-
-static bool mc_finite(float x) { return fabsf(x) <= 3.0e38f; }      // (false for NaN)
-
-int lb_set_interactions(lb_sim **fluids, int count, const lb_interaction *table, int n)
-{
-    int rc = fluid_members(fluids, count, "lb_set_interactions");
-    if (rc) return rc;
-    if (n < 0 || n > MC_MAX_INTER || (n > 0 && !table)) return fail(LB_ERR_ARG, "lb_set_interactions takes 0..%d entries", MC_MAX_INTER);
-    McInter in[MC_MAX_INTER] = {};
-    for (int t = 0; t < n; ++t) {
-        const lb_interaction &e = table[t];
-        if (e.fluid_1 < 0 || e.fluid_1 >= count || e.fluid_2 < 0 || e.fluid_2 >= count)
-            return fail(LB_ERR_ARG, "interaction %d names fluids %d and %d of a set of %d", t, e.fluid_1, e.fluid_2, count);
-        if (e.potential != LB_PSI_LINEAR && e.potential != LB_PSI_SHAN_CHEN && e.potential != LB_PSI_POW)
-            return fail(LB_ERR_ARG, "interaction %d: unknown potential %d (linear, shan_chen and pow are built; vdw is not)", t, e.potential);
-        if (e.boundary != (fluids[0]->p.bc_mode == LB_BC_PERIODIC ? 0 : 1))
-            return fail(LB_ERR_ARG, "interaction %d: the stencil's boundary rule (%d) must be the set's family (%s)", t, e.boundary,
-                        fluids[0]->p.bc_mode == LB_BC_PERIODIC ? "0, periodic" : "1, zero gradient");
-        if (!mc_finite(e.G_int) || !mc_finite(e.parameter)) return fail(LB_ERR_ARG, "interaction %d: G_int and the parameter must be finite", t);
-        if (e.potential == LB_PSI_SHAN_CHEN && e.parameter == 0.f) return fail(LB_ERR_ARG, "interaction %d: shan_chen needs rho_0 != 0", t);
-        in[t] = McInter{e.fluid_1, e.fluid_2, e.potential, e.G_int, e.parameter};
-    }
-    for (int t = 0; t < MC_MAX_INTER; ++t) fluids[0]->mc_inter[t] = in[t];
-    fluids[0]->mc_n_inter = n;
-    return LB_OK;
-}
-
-int lb_set_reactions(lb_sim **fluids, int count, const lb_fluid_reaction *table, int n)
-{
-    int rc = fluid_members(fluids, count, "lb_set_reactions");
-    if (rc) return rc;
-    if (n < 0 || n > MC_MAX_REACT || (n > 0 && !table)) return fail(LB_ERR_ARG, "lb_set_reactions takes 0..%d entries", MC_MAX_REACT);
-    McReact re[MC_MAX_REACT] = {};
-    for (int t = 0; t < n; ++t) {
-        const lb_fluid_reaction &e = table[t];
-        if (e.kind != LB_REACT_EAT && e.kind != LB_REACT_GROW) return fail(LB_ERR_ARG, "reaction %d: unknown kind %d", t, e.kind);
-        if (e.fluid_a < 0 || e.fluid_a >= count) return fail(LB_ERR_ARG, "reaction %d names fluid %d of a set of %d", t, e.fluid_a, count);
-        if (e.kind == LB_REACT_EAT && (e.fluid_b < 0 || e.fluid_b >= count || e.fluid_b == e.fluid_a))
-            return fail(LB_ERR_ARG, "reaction %d: the eatee must be another fluid of the set (got %d, eater %d)", t, e.fluid_b, e.fluid_a);
-        if (!mc_finite(e.p0) || !mc_finite(e.p1) || !mc_finite(e.p2)) return fail(LB_ERR_ARG, "reaction %d: the parameters must be finite", t);
-        re[t] = McReact{e.kind, e.fluid_a, e.kind == LB_REACT_EAT ? e.fluid_b : 0, e.p0, e.p1, e.p2};
-    }
-    for (int t = 0; t < MC_MAX_REACT; ++t) fluids[0]->mc_react[t] = re[t];
-    fluids[0]->mc_n_react = n;
-    return LB_OK;
-}
-
-int lb_get_interactions(lb_sim *first, lb_interaction *table, int *n)
-{
-    if (!first) return fail(LB_ERR_ARG, "null handle");
-    NOT_ROCKET(first, "lb_get_interactions");
-    if (first->cpu || !first->multifluid()) return fail(LB_ERR_STATE, "lb_get_interactions is for the fluids of a multicomponent set (LB_SEM_MULTIFLUID)");
-    if (n) *n = first->mc_n_inter;
-    for (int t = 0; table && t < first->mc_n_inter; ++t) {
-        const McInter &e = first->mc_inter[t];
-        table[t] = lb_interaction{e.i, e.j, e.potential, first->p.bc_mode == LB_BC_PERIODIC ? 0 : 1, e.G, e.par};
-    }
-    return LB_OK;
-}
-
-int lb_get_reactions(lb_sim *first, lb_fluid_reaction *table, int *n)
-{
-    if (!first) return fail(LB_ERR_ARG, "null handle");
-    NOT_ROCKET(first, "lb_get_reactions");
-    if (first->cpu || !first->multifluid()) return fail(LB_ERR_STATE, "lb_get_reactions is for the fluids of a multicomponent set (LB_SEM_MULTIFLUID)");
-    if (n) *n = first->mc_n_react;
-    for (int t = 0; table && t < first->mc_n_react; ++t) {
-        const McReact &e = first->mc_react[t];
-        table[t] = lb_fluid_reaction{e.kind, e.a, e.b, e.p0, e.p1, e.p2};
-    }
-    return LB_OK;
-}
-
-int lb_update_forces_fluids(lb_sim **fluids, int count)
-{
-    int rc = fluid_members(fluids, count, "lb_update_forces_fluids");
-    if (rc) return rc;
-    DeviceGuard guard(fluids[0]->p.device);
-    if ((rc = coupled_join(fluids, count))) return rc;
-    lbk_mc_forces(fluids[0]->p.bc_mode, count, fluids[0]->stream, fluid_args(fluids, count));
-    HIP_TRY(hipGetLastError());
-    return coupled_release(fluids, count);
-}
-
-int lb_update_bary_fluids(lb_sim **fluids, int count)
-{
-    int rc = fluid_members(fluids, count, "lb_update_bary_fluids");
-    if (rc) return rc;
-    DeviceGuard guard(fluids[0]->p.device);
-    if ((rc = coupled_join(fluids, count))) return rc;
-    lbk_mc_bary(count, fluids[0]->stream, fluid_args(fluids, count));
-    HIP_TRY(hipGetLastError());
-    for (int i = 0; i < count; ++i) fluids[i]->feq_valid = false;
-    return coupled_release(fluids, count);
-}
-
-int lb_react_fluids(lb_sim **fluids, int count)
-{
-    int rc = fluid_members(fluids, count, "lb_react_fluids");
-    if (rc) return rc;
-    if (fluids[0]->mc_n_react == 0) return LB_OK;
-    DeviceGuard guard(fluids[0]->p.device);
-    if ((rc = coupled_join(fluids, count))) return rc;
-    McArgs m = fluid_args(fluids, count);
-    for (int i = 0; i < count; ++i) m.a[i].dst = fluids[i]->origin(fluids[i]->cur);       // in place
-    lbk_mc_react(count, fluids[0]->stream, m);
-    HIP_TRY(hipGetLastError());
-    return coupled_release(fluids, count);
-}
-
-// ---- surfactant-propelled colonies: the two members of a set, checked alike for every set call -----------------------------------
-static int rocket_members(lb_sim **f, int count, const char *what)
-{
-    if (!f) return fail(LB_ERR_ARG, "%s: null handle array", what);
-    if (count != 2) return fail(LB_ERR_ARG, "%s takes exactly 2 handles, the population and the surfactant (got a count of %d)", what, count);
-    for (int i = 0; i < 2; ++i) {
-        lb_sim *s = f[i];
-        if (!s) return fail(LB_ERR_ARG, "%s: null handle in the set", what);
-        if (s->cpu || !s->rocket()) return fail(LB_ERR_ARG, "%s: handle %d is not a lattice of a surfactant-propelled colony (a non-rocket handle: LB_SEM_ROCKET is required)", what, i);
-        if (s->stepping) return fail(LB_ERR_STATE, "%s inside a split step", what);
-    }
-    if (f[0] == f[1]) return fail(LB_ERR_ARG, "%s: a handle appears twice in the set", what);
-    if (f[1]->p.nx != f[0]->p.nx || f[1]->p.ny != f[0]->p.ny || f[1]->p.device != f[0]->p.device ||
-        (f[1]->p.flags & LB_FLAG_PLANAR) != (f[0]->p.flags & LB_FLAG_PLANAR))
-        return fail(LB_ERR_ARG, "%s: the two lattices of a colony must share grid (geometry), layout flag and device", what);
-    return LB_OK;
-}
-
-// (src = the current lattice, dst = the other one: what the fused steps read and write; the stages set dst themselves.  Every derived
-//  scalar is one float32 operation, here and nowhere else: rocket_launch.h)
-static RyArgs rocket_args(lb_sim **f)
-{
-    RyArgs m = {};
-    for (int i = 0; i < 2; ++i) m.a[i] = step_args(f[i], 0, 1, f[i]->H);
-    const lb_rocket_params &r = f[0]->ry;
-    const float cs = (float)(1.0 / sqrt(3.0));          // np.float32(1. / np.sqrt(3))
-    const float cs2 = cs * cs;
-    m.inv_cs2 = (float)(1.0 / (double)cs2);             // the kernels' `1. / (cs * cs)`: a double quotient rounded once
-    m.G = r.G; m.Gc = r.G_c;
-    m.ke = (-r.epsilon) * m.inv_cs2;
-    m.ngc = -r.G_chen;
-    m.rho_o = r.rho_o; m.c_o = r.c_o; m.alpha = r.alpha;
-    m.op = f[0]->ry_op;
-    m.Fx = f[0]->pm_G[0]; m.Fy = f[0]->pm_G[1];
-    m.Sx = f[0]->pm_ub[0]; m.Sy = f[0]->pm_ub[1];
-    return m;
-}
-
-static bool ry_finite(float x) { return fabsf(x) <= 3.0e38f; }      // (false for NaN)
-
-int lb_set_rocket(lb_sim **fields, int count, const lb_rocket_params *params)
-{
-    int rc = rocket_members(fields, count, "lb_set_rocket");
-    if (rc) return rc;
-    if (!params) return fail(LB_ERR_ARG, "lb_set_rocket: null parameters");
-    const lb_rocket_params &r = *params;
-    if (r.mode != LB_ROCKET_FLOW && r.mode != LB_ROCKET_FORCES) return fail(LB_ERR_ARG, "lb_set_rocket: unknown mode %d (LB_ROCKET_FLOW and LB_ROCKET_FORCES are built)", r.mode);
-    for (float x : {r.G, r.G_c, r.epsilon, r.rho_o, r.G_chen, r.c_o, r.alpha})
-        if (!ry_finite(x)) return fail(LB_ERR_ARG, "lb_set_rocket: the parameters must be finite");
-    if (r.mode == LB_ROCKET_FLOW && r.rho_o == 0.f) return fail(LB_ERR_ARG, "lb_set_rocket: LB_ROCKET_FLOW needs rho_o != 0");
-    if (r.mode == LB_ROCKET_FORCES && r.c_o == 0.f) return fail(LB_ERR_ARG, "lb_set_rocket: LB_ROCKET_FORCES needs c_o != 0");
-    fields[0]->ry = r;
-    return LB_OK;
-}
-
-int lb_get_rocket(lb_sim *first, lb_rocket_params *params)
-{
-    if (!first || !params) return fail(LB_ERR_ARG, "null argument");
-    if (first->cpu || !first->rocket()) return fail(LB_ERR_STATE, "lb_get_rocket is for the lattices of a surfactant-propelled colony (LB_SEM_ROCKET)");
-    *params = first->ry;
-    return LB_OK;
-}
-
-int lb_run_rocket(lb_sim **fields, int count, int n_steps)
-{
-    int rc = rocket_members(fields, count, "lb_run_rocket");
-    if (rc) return rc;
-    if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
-    if (n_steps == 0) return LB_OK;
-    lb_sim *s0 = fields[0];
-    DeviceGuard guard(s0->p.device);
-    if ((rc = coupled_join(fields, 2))) return rc;
-    const int mode = s0->ry.mode;
-    for (int it = 0; it < n_steps; ++it) {
-        const RyArgs m = rocket_args(fields);
-        const bool last = it == n_steps - 1;            // the last launch stores rho, u, v, psi / S and the forces
-        if (rocket_one_launch(s0)) {                    // (the set's first handle chooses: lb_set_variant; plan.cpp)
-            lbk_ry_step(mode, last, s0->stream, m);
-            HIP_TRY(hipGetLastError());
-        } else {
-            lbk_ry_moments(s0->stream, m);
-            HIP_TRY(hipGetLastError());
-            lbk_ry_collide(mode, last, s0->stream, m);
-            HIP_TRY(hipGetLastError());
-        }
-        for (int i = 0; i < 2; ++i) fields[i]->cur ^= 1;
-    }
-    for (int i = 0; i < 2; ++i) {
-        fields[i]->feq_valid = false;
-        fields[i]->macro_valid = true;
-    }
-    return coupled_release(fields, 2);
-}
-
-int lb_update_velocity_rocket(lb_sim **fields, int count)
-{
-    int rc = rocket_members(fields, count, "lb_update_velocity_rocket");
-    if (rc) return rc;
-    DeviceGuard guard(fields[0]->p.device);
-    if ((rc = coupled_join(fields, 2))) return rc;
-    lbk_ry_velocity(fields[0]->ry.mode, fields[0]->stream, rocket_args(fields));
-    HIP_TRY(hipGetLastError());
-    for (int i = 0; i < 2; ++i) fields[i]->feq_valid = false;
-    return coupled_release(fields, 2);
-}
-
-int lb_update_forces_rocket(lb_sim **fields, int count)
-{
-    int rc = rocket_members(fields, count, "lb_update_forces_rocket");
-    if (rc) return rc;
-    DeviceGuard guard(fields[0]->p.device);
-    if ((rc = coupled_join(fields, 2))) return rc;
-    lbk_ry_forces(fields[0]->ry.mode, fields[0]->stream, rocket_args(fields));
-    HIP_TRY(hipGetLastError());
-    return coupled_release(fields, 2);
-}
-
-int lb_collide_rocket(lb_sim **fields, int count)
-{
-    int rc = rocket_members(fields, count, "lb_collide_rocket");
-    if (rc) return rc;
-    for (int i = 0; i < 2; ++i)
-        if (!fields[i]->feq) return fail(LB_ERR_STATE, "lb_collide_rocket before lb_update_feq on both members");
-    DeviceGuard guard(fields[0]->p.device);
-    if ((rc = coupled_join(fields, 2))) return rc;
-    RyArgs m = rocket_args(fields);
-    for (int i = 0; i < 2; ++i) m.a[i].dst = fields[i]->origin(fields[i]->cur);      // relaxed in place
-    lbk_ry_relax(fields[0]->ry.mode, fields[0]->stream, m, fields[0]->feq_origin(), fields[1]->feq_origin());
-    HIP_TRY(hipGetLastError());
-    return coupled_release(fields, 2);
-}
-
-int lb_get_rocket_fields(lb_sim **fields, int count, float *psi_or_S, float *Fx, float *Fy, float *Fsx, float *Fsy)
-{
-    int rc = rocket_members(fields, count, "lb_get_rocket_fields");
-    if (rc) return rc;
-    lb_sim *s = fields[0];
-    DeviceGuard guard(s->p.device);
-    float *out[5] = {psi_or_S, Fx, Fy, Fsx, Fsy};
-    const float *from[5] = {s->ry_op, s->pm_G[0], s->pm_G[1], s->pm_ub[0], s->pm_ub[1]};
-    for (int i = 0; i < 5; ++i)
-        if (out[i] && (rc = copy_plane_d2h(s, out[i], from[i]))) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return LB_OK;
+    return set_release(sims, count);
 }
 
 // ---- health check ------------------------------------------------------------------------
@@ -1963,7 +1129,7 @@ int lb_check(lb_sim *s, int across_ranks, int64_t *n_nonfinite, float *max_mach,
             const float ux = (f[n + c] - f[3 * n + c] + f[5 * n + c] - f[6 * n + c] - f[7 * n + c] + f[8 * n + c]) * inv;
             const float uy = (f[5 * n + c] + f[2 * n + c] + f[6 * n + c] - f[7 * n + c] - f[4 * n + c] - f[8 * n + c]) * inv;
             const float usq = ux * ux + uy * uy;
-            if (fabsf(r) <= 3.0e38f && fabsf(usq) <= 3.0e38f) { sum += (double)r; mx = fmaxf(mx, usq); }
+            if (finite32(r) && finite32(usq)) { sum += (double)r; mx = fmaxf(mx, usq); }
             else ++bad;
         }
         if (n_nonfinite) *n_nonfinite = bad;

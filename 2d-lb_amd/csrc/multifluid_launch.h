@@ -1,6 +1,5 @@
-// multifluid_launch.h -- the seam between multifluid.cpp, which instantiates the kernels of multicomponent Shan-Chen fluids
-// (kernels_multifluid.h: LB_SEM_MULTIFLUID), and the host unit that launches them (porous_launch.h does the same for the one fluid
-// in a porous medium).
+// multifluid_launch.h -- what the kernels of multicomponent Shan-Chen fluids (kernels_multifluid.h: LB_SEM_MULTIFLUID), the host code that
+// launches them (multifluid.cpp) and the handle (host.h: the tables of a set) share beyond StepArgs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels_fused.h"      // StepArgs
@@ -29,19 +28,3 @@ struct McArgs {
     McReact react[MC_MAX_REACT];
     int n_inter, n_react;
 };
-
-// bc = LB_BC_PERIODIC or LB_BC_ZERO_GRADIENT; nf = 1 ... MC_MAX.
-// The two-launch step: k_mc_moments stores every fluid's post-stream rho, k_mc_collide gathers again, reads rho around the cell,
-// and runs forces -> u_b -> feq -> relaxation -> reactions; last: it also stores u, v, G and u_b.
-void lbk_mc_moments(int bc, int nf, hipStream_t st, const McArgs &m);
-void lbk_mc_collide(int bc, int nf, bool last, hipStream_t st, const McArgs &m);
-// The one-launch step k_mc_step: a workgroup owns six rows (three fluids: two) of a 256-cell tile and keeps rho_i of them, of one halo
-// row above and below and of one halo cell left and right in LDS; last: it also stores rho, u, v, G and u_b.  Bitwise the two-launch step.
-void lbk_mc_step(int bc, int nf, bool last, hipStream_t st, const McArgs &m);
-// the un-fused phases: rho, u, v of one fluid from a.src; every fluid's G from the stored rho; u_b from the lattices at a[i].src,
-// rho and G; a[i].src relaxed in place towards feq (pm_extra's scalars at epsilon = 1, G a force); the reaction table on a[i].dst in place
-void lbk_mc_hydro(hipStream_t st, const StepArgs &a);
-void lbk_mc_forces(int bc, int nf, hipStream_t st, const McArgs &m);
-void lbk_mc_bary(int nf, hipStream_t st, const McArgs &m);
-void lbk_mc_relax(hipStream_t st, const StepArgs &a, const PmExtra &e, float *f, const float *feq);
-void lbk_mc_react(int nf, hipStream_t st, const McArgs &m);

@@ -1,9 +1,9 @@
-// scalar.cpp -- the translation unit of scalar lattices: instantiates and launches the kernels of kernels_scalar.h (scalar_launch.h).
-#include "kernels_scalar.h"
+// scalar.cpp -- scalar lattices (LB_SEM_DIFFUSION): the kernels of kernels_scalar.h and their launches, the kind's row of the kind table
+// (host.h: KindOps), its run, and the entry points of the C ABI that are its own: lb_set_reaction, the edge state, lb_set_velocity_from.
+#include "kernels_scalar.h"    // (first: host.h switches floating-point contraction off for what follows it, cpu_backend.h)
+#include "host.h"
 
 namespace {
-
-dim3 cells_grid(const StepArgs &a) { return dim3((unsigned)((a.nx + 255) / 256), (unsigned)a.ny); }
 
 template <int BC>
 void ad_step_go(bool react, bool store_rho, dim3 grid, dim3 block, hipStream_t st, const StepArgs &a, const AdExtra &e)
@@ -38,41 +38,67 @@ void ad_tile_bc(bool react, bool store_rho, int shape, hipStream_t st, const Ste
     }
 }
 
-}  // namespace
-
-void lbk_ad_tile4(int bc, bool react, bool store_rho, int shape, hipStream_t st, const StepArgs &a, const AdExtra &e)
+// bc: LB_BC_PERIODIC or LB_BC_OPEN.  k_ad_tile4: four steps over the whole grid; shape 0: 32 x 16 tiles, two cells per thread; 1: 32 x 16,
+// one; 2: 16 x 16, one.  store_rho: the launch also stores rho.
+void ad_tile4(int bc, bool react, bool store_rho, int shape, hipStream_t st, const StepArgs &a, const AdExtra &e)
 {
     if (bc == LB_BC_PERIODIC) ad_tile_bc<LB_BC_PERIODIC>(react, store_rho, shape, st, a, e);
     else ad_tile_bc<LB_BC_OPEN>(react, store_rho, shape, st, a, e);
 }
 
-void lbk_ad_step(int bc, bool react, bool store_rho, hipStream_t st, const StepArgs &a, const AdExtra &e)
+// k_ad_step over the whole grid
+void ad_step(int bc, bool react, bool store_rho, hipStream_t st, const StepArgs &a, const AdExtra &e)
 {
-    const dim3 block(64, 4), grid((unsigned)((a.fpitch / 4 + 63) / 64), (unsigned)((a.ny + 3) / 4));
+    const dim3 block(64, 4), grid = step_grid(a);
     if (bc == LB_BC_PERIODIC) ad_step_go<LB_BC_PERIODIC>(react, store_rho, grid, block, st, a, e);
     else ad_step_go<LB_BC_OPEN>(react, store_rho, grid, block, st, a, e);
 }
 
-void lbk_ad_hydro(hipStream_t st, const StepArgs &a) { hipLaunchKernelGGL(k_ad_hydro, cells_grid(a), dim3(256), 0, st, a); }
-
-void lbk_ad_feq(hipStream_t st, const StepArgs &a, float *feq) { hipLaunchKernelGGL(k_ad_feq, cells_grid(a), dim3(256), 0, st, a, feq); }
-
-void lbk_ad_collide(bool react, hipStream_t st, const StepArgs &a, float *f, const float *feq, float G)
+int scalar_create(lb_sim *s)
 {
-    if (react) hipLaunchKernelGGL(k_ad_collide<true>, cells_grid(a), dim3(256), 0, st, a, f, feq, G);
-    else hipLaunchKernelGGL(k_ad_collide<false>, cells_grid(a), dim3(256), 0, st, a, f, feq, G);
+    if (s->p.bc_mode != LB_BC_OPEN) return LB_OK;
+    const size_t edge_bytes = sizeof(float) * (size_t)ad_edge_device_floats(s->pitch, s->p.ny);
+    CREATE_TRY(hipMalloc(&s->ad_edge, edge_bytes));
+    CREATE_TRY(hipMemsetAsync(s->ad_edge, 0, edge_bytes, s->stream));
+    return LB_OK;
 }
 
-void lbk_ad_edge_capture(hipStream_t st, const StepArgs &a, const float *f, float *edge)
+// f (in place) relaxed towards feq
+int scalar_collide(lb_sim *s)
 {
-    const int n = a.fpitch > a.ny ? a.fpitch : a.ny;
-    hipLaunchKernelGGL(k_ad_edge_capture, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, f, edge);
+    int rc = collide_ready(s);
+    return rc ? rc : launch_phase(s, grid_cells(s), s->ad_G != 0.f ? k_ad_collide<true> : k_ad_collide<false>, s->origin(s->cur), s->feq_origin(), s->ad_G);
 }
 
-void lbk_ad_edge_patch(hipStream_t st, const StepArgs &a, float *f, const float *edge)
+// n time steps: k_ad_tile4 / k_ad_step launch by launch, as scalar_next_advance splits the run; the last launch stores rho (with a
+// growth term rho is not a moment of the populations a run leaves behind: never rebuilt on demand)
+int run_scalar(lb_sim *s, int n_steps)
 {
-    const int n = a.nx > a.ny ? a.nx : a.ny;
-    hipLaunchKernelGGL(k_ad_edge_patch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, f, edge);
+    const AdExtra e = AdExtra{s->ad_edge, s->ad_G};
+    int left = n_steps;
+    while (left > 0) {
+        const int adv = scalar_next_advance(s, left);
+        const StepArgs a = step_args(s, 0, 1, s->H);
+        if (adv == TILE_T) ad_tile4(s->p.bc_mode, s->ad_G != 0.f, left == adv, scalar_tile_shape(s), s->stream, a, e);
+        else ad_step(s->p.bc_mode, s->ad_G != 0.f, left == adv, s->stream, a, e);
+        HIP_TRY(hipGetLastError());
+        s->cur ^= 1;
+        left -= adv;
+    }
+    if (n_steps) { s->feq_valid = false; s->macro_valid = true; }
+    return LB_OK;
+}
+
+}  // namespace
+
+int scalar_hydro(lb_sim *s) { return launch_phase(s, grid_cells(s), k_ad_hydro); }       // rho only: u, v are imposed
+int scalar_feq(lb_sim *s) { return launch_phase(s, grid_cells(s), k_ad_feq, s->feq_origin()); }
+
+void lbk_ad_edge(bool patch, hipStream_t st, const StepArgs &a, float *f, float *edge)
+{
+    const int n = std::max(patch ? a.nx : a.fpitch, a.ny);      // (the capture takes the rows' padding along)
+    if (patch) hipLaunchKernelGGL(k_ad_edge_patch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, f, (const float *)edge);
+    else hipLaunchKernelGGL(k_ad_edge_capture, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, (const float *)f, edge);
 }
 
 long long ad_check_blocks(const StepArgs &a) { return (long long)((a.nx + 255) / 256) * a.ny; }
@@ -81,3 +107,117 @@ void lbk_ad_check(hipStream_t st, const StepArgs &a, CheckPartial *part)
 {
     hipLaunchKernelGGL(k_ad_check, cells_grid(a), dim3(256), 0, st, a, part);
 }
+
+// (move_bcs: diffusion.py:326-331, `pass`)
+KIND_ROW(kind_scalar,
+    "a scalar lattice (LB_SEM_DIFFUSION)", 1u << LB_BC_PERIODIC | 1u << LB_BC_OPEN, "the families LB_BC_PERIODIC and LB_BC_OPEN only", false, false,
+    0, nullptr, 0,
+    scalar_create, nullptr, scalar_hydro, scalar_feq, scalar_collide, run_scalar)
+
+#define NEED_SCALAR(s, name)                                                                                 \
+    do {                                                                                                     \
+        if (!(s)) return fail(LB_ERR_ARG, "null handle");                                                    \
+        NOT_POROUS(s, name);                                                                                 \
+        NOT_ROCKET(s, name);                                                                                 \
+        if (!(s)->scalar()) return fail(LB_ERR_STATE, "%s is for scalar lattices (LB_SEM_DIFFUSION)", name); \
+    } while (0)
+
+// ... whose velocity is imposed: the Poisson solver has none, and its source term is lb_set_source's
+#define NOT_POISSON(s, name)                                                                                 \
+    do {                                                                                                     \
+        if ((s)->poisson()) return fail(LB_ERR_STATE, "%s is not available on the LB Poisson solver (LB_SEM_POISSON)", name); \
+    } while (0)
+
+extern "C" {
+
+int lb_set_reaction(lb_sim *s, float G)
+{
+    NEED_SCALAR(s, "lb_set_reaction");
+    NOT_POISSON(s, "lb_set_reaction");
+    if (!finite32(G)) return fail(LB_ERR_ARG, "the growth rate must be finite");
+    s->ad_G = G;
+    return LB_OK;
+}
+
+// ABI order of the edge state (include/lb_hip.h: west, east, south, north; unpadded) <-> device order (scalar_launch.h)
+int lb_edge_floats(lb_sim *s)
+{
+    NEED_SCALAR(s, "lb_edge_floats");
+    return (int)(s->ad_edge ? 6LL * (s->p.nx + s->p.ny) : 0);
+}
+
+int lb_get_edge_state(lb_sim *s, float *out)
+{
+    NEED_SCALAR(s, "lb_get_edge_state");
+    if (!s->ad_edge) return LB_OK;                  // (PERIODIC: zero floats)
+    if (!out) return fail(LB_ERR_ARG, "null argument");
+    DeviceGuard guard(s->p.device);
+    const int nx = s->p.nx, ny = s->p.ny;
+    const size_t n = (size_t)ad_edge_device_floats(s->pitch, ny);
+    float *tmp = (float *)malloc(n * sizeof(float));
+    if (!tmp) return fail(LB_ERR_ARG, "out of host memory");
+    hipError_t e = hipMemcpyAsync(tmp, s->ad_edge, n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (e != hipSuccess) {
+        free(tmp);
+        return fail(LB_ERR_HIP, "edge state download: %s", hipGetErrorString(e));
+    }
+    memcpy(out, tmp + 6 * s->pitch, sizeof(float) * 6 * (size_t)ny);
+    float *rows = out + 6 * (size_t)ny;
+    for (int r = 0; r < 6; ++r) memcpy(rows + (size_t)r * nx, tmp + (size_t)r * s->pitch, sizeof(float) * (size_t)nx);
+    // the four corner links a column and a row share: the column's entry is the one that counts
+    rows[1 * (size_t)nx] = out[1 * (size_t)ny];                                 // south f5(0,0) = west f5[0]
+    rows[2 * (size_t)nx + nx - 1] = out[4 * (size_t)ny];                        // south f6(nx-1,0) = east f6[0]
+    rows[4 * (size_t)nx + nx - 1] = out[5 * (size_t)ny + ny - 1];               // north f7(nx-1,ny-1) = east f7[ny-1]
+    rows[5 * (size_t)nx] = out[2 * (size_t)ny + ny - 1];                        // north f8(0,ny-1) = west f8[ny-1]
+    free(tmp);
+    return LB_OK;
+}
+
+int lb_set_edge_state(lb_sim *s, const float *in)
+{
+    NEED_SCALAR(s, "lb_set_edge_state");
+    if (!s->ad_edge) return LB_OK;
+    if (!in) return fail(LB_ERR_ARG, "null argument");
+    DeviceGuard guard(s->p.device);
+    const int nx = s->p.nx, ny = s->p.ny;
+    const size_t n = (size_t)ad_edge_device_floats(s->pitch, ny);
+    float *tmp = (float *)calloc(n, sizeof(float));
+    if (!tmp) return fail(LB_ERR_ARG, "out of host memory");
+    memcpy(tmp + 6 * s->pitch, in, sizeof(float) * 6 * (size_t)ny);
+    const float *rows = in + 6 * (size_t)ny;
+    for (int r = 0; r < 6; ++r) memcpy(tmp + (size_t)r * s->pitch, rows + (size_t)r * nx, sizeof(float) * (size_t)nx);
+    hipError_t e = hipStreamSynchronize(s->stream);       // (kernels of an un-waited run may still be reading it)
+    if (e == hipSuccess) e = hipMemcpy(s->ad_edge, tmp, n * sizeof(float), hipMemcpyHostToDevice);
+    free(tmp);
+    if (e != hipSuccess) return fail(LB_ERR_HIP, "edge state upload: %s", hipGetErrorString(e));
+    return LB_OK;
+}
+
+int lb_set_velocity_from(lb_sim *s, lb_sim *flow)
+{
+    NEED_SCALAR(s, "lb_set_velocity_from");
+    NOT_POISSON(s, "lb_set_velocity_from");
+    if (!flow) return fail(LB_ERR_ARG, "null flow handle");
+    if (flow->cpu || flow->scalar() || flow->multi_slab())
+        return fail(LB_ERR_ARG, "lb_set_velocity_from takes a whole-grid GPU flow handle");
+    if (flow->p.nx != s->p.nx || flow->p.ny != s->p.ny || flow->p.device != s->p.device)
+        return fail(LB_ERR_ARG, "the flow handle must have the scalar lattice's grid (%d x %d) and device", s->p.nx, s->p.ny);
+    if (flow->stepping) return fail(LB_ERR_STATE, "lb_set_velocity_from inside a split step of the flow handle");
+    DeviceGuard guard(s->p.device);
+    int rc = ensure_macro(flow);                    // the flow's lazily rebuilt rho, u, v
+    if (rc) return rc;
+    // on the FLOW handle's stream, behind its work; this handle's kernels may still read u, v, and its later ones must see the new
+    HIP_TRY(hipEventRecord(s->ev_interior, s->stream));
+    HIP_TRY(hipStreamWaitEvent(flow->stream, s->ev_interior, 0));
+    // (rho, u, v are [H][pitch] whatever the layout of the lattices: LB_FLAG_PLANAR on either handle does not matter here)
+    const long long n4 = s->pitch * s->H / 4;       // (same pitch: same nx)
+    for (int i = 0; i < 2; ++i)
+        if ((rc = copy_quads(flow->stream, i ? s->v : s->u, i ? flow->v : flow->u, n4))) return rc;
+    HIP_TRY(hipEventRecord(flow->ev_interior, flow->stream));
+    HIP_TRY(hipStreamWaitEvent(s->stream, flow->ev_interior, 0));
+    s->feq_valid = false;
+    return LB_OK;
+}
+
+}  // extern "C"
