@@ -43,15 +43,8 @@ class DeviceField(object):
         return a if dtype is None else a.astype(dtype)
 
 
-class DropIn(object):
-    """The methods of a drop-in class that only forward to its engine (``self._sim``, a ``Simulation``)."""
-
-    def _say(self, *args):
-        if self.verbose:
-            print(*args)
-
-    def _read_field(self, key):
-        return self._sim.get_fields((key,))[key]
+class Phases(object):
+    """The reference's five phase methods, forwarded to the engine (``self._sim``: a ``Simulation`` or a set of them)."""
 
     def move_bcs(self):
         self._sim.move_bcs()
@@ -67,6 +60,17 @@ class DropIn(object):
 
     def collide_particles(self):
         self._sim.collide_particles()
+
+
+class DropIn(Phases):
+    """The other methods of a drop-in class that only forward to its engine."""
+
+    def _say(self, *args):
+        if self.verbose:
+            print(*args)
+
+    def _read_field(self, key):
+        return self._sim.get_fields((key,))[key]
 
     def run(self, num_iterations):
         """num_iterations time steps, fused on the device (one phase method = one un-fused kernel)."""

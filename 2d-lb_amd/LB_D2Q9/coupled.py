@@ -17,22 +17,24 @@ from ._native import check
 from .simulation import NUM_JUMPERS, Simulation
 
 
-class Coupled_Scalars(object):
-    MAX_POPULATIONS = 4
+class _Lattice_Set(object):
+    """What the sets share: the members (one ``Simulation`` each) and the ctypes array of their handles, state as arrays shaped
+    ``(nx, ny, num_populations[, 9])``, the phases every member makes on its own, ``run`` / ``step`` through the class's entry
+    point, ``get_fields`` by the class's key lists, and the ``m<i>_`` entries of a checkpoint."""
+    _RUN = None             # the library's run entry point for this kind of set
+    _STACKED = ()           # get_fields keys that every member has: stacked along axis 2
+    _SHARED = ()            # ... that the members share: read from the first
+    _OWN = ()               # ... that the set itself keeps: _read_own
 
-    def __init__(self, nx, ny, omegas, Gs, bc="box", device=0, planar=None):
-        omegas, Gs = [float(o) for o in np.atleast_1d(omegas)], [float(g) for g in np.atleast_1d(Gs)]
-        if not 1 <= len(omegas) <= self.MAX_POPULATIONS or len(Gs) != len(omegas):
-            raise ValueError("1..%d fields, one omega and one G each" % self.MAX_POPULATIONS)
-        if bc not in ("box", "periodic"):
-            raise ValueError("bc must be 'box' or 'periodic'")
-        self.nx, self.ny, self.num_populations, self.num_jumpers = int(nx), int(ny), len(omegas), NUM_JUMPERS
-        self.omegas, self.Gs, self.bc = omegas, Gs, bc
-        self.members = [Simulation(nx, ny, om, bc=bc, semantics="multifield", device=device, planar=planar) for om in omegas]
-        for m, g in zip(self.members, Gs):
-            m.set_reaction(g)
+    def _adopt(self, nx, ny, members):
+        self.nx, self.ny, self.num_populations, self.num_jumpers = int(nx), int(ny), len(members), NUM_JUMPERS
+        self.members = members
         self._lib = _native.lib()
-        self._handles = (ct.c_void_p * len(omegas))(*[m._h for m in self.members])
+        self._handles = (ct.c_void_p * len(members))(*[m._h for m in members])
+
+    def _call(self, entry, *args):
+        """One of the library's calls on the whole set."""
+        check(getattr(self._lib, entry)(self._handles, self.num_populations, *args))
 
     def close(self):
         for m in self.members:
@@ -54,47 +56,27 @@ class Coupled_Scalars(object):
         for i, m in enumerate(self.members):
             m.set_f(f[:, :, i, :])
 
-    def set_fields(self, rho, u, v):
-        """rho: (nx, ny, num_populations); u, v: (nx, ny), written to every member."""
-        rho = self._per_field(rho)
-        for i, m in enumerate(self.members):
-            m.set_fields(rho[:, :, i], u, v)
-
-    def set_velocity_from(self, flow):
-        """u, v of a flow Simulation of the same grid become every member's imposed velocity, device to device."""
-        for m in self.members:
-            m.set_velocity_from(flow)
-
     def init_pop(self, perturb=None):
         """f = f_streamed = feq * perturb on every member; perturb None or (nx, ny, num_populations, 9)."""
         for i, m in enumerate(self.members):
             m.init_pop(None if perturb is None else np.asarray(perturb)[:, :, i, :])
 
-    def get_fields(self, which=("f", "feq", "u", "v", "rho")):
-        """f, feq: (nx, ny, num_populations, 9); rho: (nx, ny, num_populations); u, v: (nx, ny) (the first member's)."""
+    def _get_fields(self, which):
         out = {}
-        stacked = [k for k in which if k in ("f", "feq", "rho")]
+        stacked = tuple(k for k in which if k in self._STACKED)
         if stacked:
-            per = [m.get_fields(tuple(stacked)) for m in self.members]
+            per = [m.get_fields(stacked) for m in self.members]
             for k in stacked:
                 out[k] = np.asfortranarray(np.stack([g[k] for g in per], axis=2))
-        shared = tuple(k for k in which if k in ("u", "v"))
+        shared = tuple(k for k in which if k in self._SHARED)
         if shared:
             out.update(self.members[0].get_fields(shared))
+        own = [k for k in which if k in self._OWN]
+        if own:
+            self._read_own(own, out)
         return out
 
-    def get_corner_state(self):
-        """(num_populations, 8): every member's never-written corner links (bc='box'; include/lb_hip.h)."""
-        return np.stack([m.get_corner_state() for m in self.members])
-
-    def set_corner_state(self, values):
-        values = np.asarray(values, np.float32)
-        if values.shape != (self.num_populations, 8):
-            raise ValueError("corner state = (num_populations, 8) floats")
-        for m, v in zip(self.members, values):
-            m.set_corner_state(v)
-
-    # -- the fork's phases, un-fused ------------------------------------------------------------------------------------
+    # -- the phases every member makes on its own, un-fused ----------------------------------------------------------------
     def move(self):
         for m in self.members:
             m.move()
@@ -111,26 +93,100 @@ class Coupled_Scalars(object):
         for m in self.members:
             m.update_feq()
 
-    def collide_particles(self):
-        check(self._lib.lb_collide_coupled(self._handles, self.num_populations))
-        self.sync()
-
     # -- the hot path ---------------------------------------------------------------------------------------------------
     def run(self, num_iterations, wait=True):
-        """num_iterations fused time steps of all fields, one launch per step."""
-        check(self._lib.lb_run_coupled(self._handles, self.num_populations, int(num_iterations)))
+        """num_iterations fused time steps of all members, one launch per step."""
+        self._call(self._RUN, int(num_iterations))
         if wait:
             self.sync()
 
     def step(self):
         self.run(1)
 
+    # -- checkpoints: every member's arrays under 'm<i>_' ------------------------------------------------------------------
+    def _member_entries(self):
+        return {"m%d_%s" % (i, k): a for i, m in enumerate(self.members) for k, a in m.checkpoint_arrays().items()}
+
+    @staticmethod
+    def _load_entries(path):
+        """(the set's own entries, [every member's, without the prefix]) of a checkpoint file"""
+        with np.load(Simulation._ckpt_path(path)) as d:
+            per = []
+            while "m%d_version" % len(per) in d.files:
+                prefix = "m%d_" % len(per)
+                per.append({k[len(prefix):]: d[k] for k in d.files if k.startswith(prefix)})
+            return {k: d[k] for k in d.files if not any(k.startswith("m%d_" % i) for i in range(len(per)))}, per
+
+
+class _Shared_Velocity(object):
+    """Scalar lattices advected by one velocity field."""
+
+    def set_fields(self, rho, u, v):
+        """rho: (nx, ny, num_populations); u, v: (nx, ny), written to every member."""
+        rho = self._per_field(rho)
+        for i, m in enumerate(self.members):
+            m.set_fields(rho[:, :, i], u, v)
+
     def check(self):
         """Per member: Simulation.check() (non-finite cells, max Mach number of the imposed field, sum of rho)."""
         return [m.check() for m in self.members]
 
 
-class Shan_Chen_Fluids(object):
+class _Fused_Set(_Lattice_Set):
+    """A set whose step is one launch or, under ``set_variant(0)``, two; it has a checkpoint file of its own."""
+
+    def set_variant(self, variant):
+        for m in self.members:
+            m.set_variant(variant)
+
+    def hot_kernel(self):
+        return self.members[0].hot_kernel()
+
+    def save_checkpoint(self, path):
+        np.savez(Simulation._ckpt_path(path), **dict(self._own_entries(), **self._member_entries()))
+
+
+class Coupled_Scalars(_Shared_Velocity, _Lattice_Set):
+    MAX_POPULATIONS = 4
+    _RUN, _STACKED, _SHARED = "lb_run_coupled", ("f", "feq", "rho"), ("u", "v")
+
+    def __init__(self, nx, ny, omegas, Gs, bc="box", device=0, planar=None):
+        omegas, Gs = [float(o) for o in np.atleast_1d(omegas)], [float(g) for g in np.atleast_1d(Gs)]
+        if not 1 <= len(omegas) <= self.MAX_POPULATIONS or len(Gs) != len(omegas):
+            raise ValueError("1..%d fields, one omega and one G each" % self.MAX_POPULATIONS)
+        if bc not in ("box", "periodic"):
+            raise ValueError("bc must be 'box' or 'periodic'")
+        self.omegas, self.Gs, self.bc = omegas, Gs, bc
+        self._adopt(nx, ny, [Simulation(nx, ny, om, bc=bc, semantics="multifield", device=device, planar=planar) for om in omegas])
+        for m, g in zip(self.members, Gs):
+            m.set_reaction(g)
+
+    def set_velocity_from(self, flow):
+        """u, v of a flow Simulation of the same grid become every member's imposed velocity, device to device."""
+        for m in self.members:
+            m.set_velocity_from(flow)
+
+    def get_fields(self, which=("f", "feq", "u", "v", "rho")):
+        """f, feq: (nx, ny, num_populations, 9); rho: (nx, ny, num_populations); u, v: (nx, ny) (the first member's)."""
+        return self._get_fields(which)
+
+    def get_corner_state(self):
+        """(num_populations, 8): every member's never-written corner links (bc='box'; include/lb_hip.h)."""
+        return np.stack([m.get_corner_state() for m in self.members])
+
+    def set_corner_state(self, values):
+        values = np.asarray(values, np.float32)
+        if values.shape != (self.num_populations, 8):
+            raise ValueError("corner state = (num_populations, 8) floats")
+        for m, v in zip(self.members, values):
+            m.set_corner_state(v)
+
+    def collide_particles(self):
+        self._call("lb_collide_coupled")
+        self.sync()
+
+
+class Shan_Chen_Fluids(_Fused_Set):
     """A set of 1..3 fluids on one grid (``Simulation(semantics='multifluid')``, its own ``omega`` each) that relax towards
     their common barycentric velocity and act on each other through pseudopotential forces and reactions: the reference's
     ``multicomponent_multiphase/multi.py``.  ``run(n)`` advances all of them with one launch per time step and no host
@@ -143,7 +199,7 @@ class Shan_Chen_Fluids(object):
     ``('eat', eater, eatee, rate, cutoff)`` or ``('grow', fluid, min, max, rate)``, applied in order."""
     MAX_POPULATIONS = _native.MC_MAX
     POTENTIALS = {"linear": _native.LB_PSI_LINEAR, "shan_chen": _native.LB_PSI_SHAN_CHEN, "pow": _native.LB_PSI_POW}
-    _STACKED = ("f", "feq", "rho", "u", "v", "Gx", "Gy")
+    _RUN, _STACKED, _SHARED = "lb_run_fluids", ("f", "feq", "rho", "u", "v", "Gx", "Gy"), ("u_bary", "v_bary")
 
     def __init__(self, nx, ny, omegas, bc="periodic", device=0, planar=None):
         omegas = [float(o) for o in np.atleast_1d(omegas)]
@@ -151,11 +207,8 @@ class Shan_Chen_Fluids(object):
             raise NotImplementedError("1..%d fluids are built (more than %d fluids are not)" % (self.MAX_POPULATIONS, self.MAX_POPULATIONS))
         if bc not in ("periodic", "zero_gradient"):
             raise ValueError("bc must be 'periodic' or 'zero_gradient'")
-        self.nx, self.ny, self.num_populations, self.num_jumpers = int(nx), int(ny), len(omegas), NUM_JUMPERS
         self.omegas, self.bc = omegas, bc
-        self.members = [Simulation(nx, ny, om, bc=bc, semantics="multifluid", device=device, planar=planar) for om in omegas]
-        self._lib = _native.lib()
-        self._handles = (ct.c_void_p * len(omegas))(*[m._h for m in self.members])
+        self._adopt(nx, ny, [Simulation(nx, ny, om, bc=bc, semantics="multifluid", device=device, planar=planar) for om in omegas])
         self.interactions, self.reactions = [], []
 
     @classmethod
@@ -167,19 +220,11 @@ class Shan_Chen_Fluids(object):
         if len({m.bc_mode for m in members}) != 1:
             raise NotImplementedError("fluids of different families in one set are not built")
         self = cls.__new__(cls)
-        m0 = members[0]
-        self.nx, self.ny, self.num_populations, self.num_jumpers = m0.nx, m0.ny, len(members), NUM_JUMPERS
         self.omegas = [m.omega for m in members]
-        self.bc = "periodic" if m0.bc_mode == _native.LB_BC_PERIODIC else "zero_gradient"
-        self.members = members
-        self._lib = _native.lib()
-        self._handles = (ct.c_void_p * len(members))(*[m._h for m in members])
+        self.bc = "periodic" if members[0].bc_mode == _native.LB_BC_PERIODIC else "zero_gradient"
+        self._adopt(members[0].nx, members[0].ny, members)
         self.interactions, self.reactions = [], []
         return self
-
-    close, sync, _per_field = Coupled_Scalars.close, Coupled_Scalars.sync, Coupled_Scalars._per_field
-    set_f, init_pop = Coupled_Scalars.set_f, Coupled_Scalars.init_pop
-    move, move_bcs, update_hydro, update_feq = Coupled_Scalars.move, Coupled_Scalars.move_bcs, Coupled_Scalars.update_hydro, Coupled_Scalars.update_feq
 
     # -- the tables ---------------------------------------------------------------------------------------------------------
     def set_interactions(self, table):
@@ -222,24 +267,15 @@ class Shan_Chen_Fluids(object):
         self.members[int(fluid)].set_force_field(gx, gy)
 
     def get_fields(self, which=("f", "feq", "rho", "u", "v", "Gx", "Gy", "u_bary", "v_bary")):
-        out = {}
-        stacked = tuple(k for k in which if k in self._STACKED)
-        if stacked:
-            per = [m.get_fields(stacked) for m in self.members]
-            for k in stacked:
-                out[k] = np.asfortranarray(np.stack([g[k] for g in per], axis=2))
-        shared = tuple(k for k in which if k in ("u_bary", "v_bary"))
-        if shared:
-            out.update(self.members[0].get_fields(shared))
-        return out
+        return self._get_fields(which)
 
     # -- the reference's stages that involve the whole set, un-fused -------------------------------------------------------
     def update_forces(self):
-        check(self._lib.lb_update_forces_fluids(self._handles, self.num_populations))
+        self._call("lb_update_forces_fluids")
         self.sync()
 
     def update_bary_velocity(self):
-        check(self._lib.lb_update_bary_fluids(self._handles, self.num_populations))
+        self._call("lb_update_bary_fluids")
         self.sync()
 
     def collide_particles(self):
@@ -247,7 +283,7 @@ class Shan_Chen_Fluids(object):
             m.collide_particles()
 
     def react(self):
-        check(self._lib.lb_react_fluids(self._handles, self.num_populations))
+        self._call("lb_react_fluids")
         self.sync()
 
     def step_phases(self):
@@ -261,35 +297,13 @@ class Shan_Chen_Fluids(object):
         self.collide_particles()
         self.react()
 
-    # -- the hot path -----------------------------------------------------------------------------------------------------
-    def run(self, num_iterations, wait=True):
-        check(self._lib.lb_run_fluids(self._handles, self.num_populations, int(num_iterations)))
-        if wait:
-            self.sync()
-
-    def step(self):
-        self.run(1)
-
-    def set_variant(self, variant):
-        for m in self.members:
-            m.set_variant(variant)
-
-    def hot_kernel(self):
-        return self.members[0].hot_kernel()
-
     # -- checkpoints: every member's arrays under 'm<i>_', the tables with the first ----------------------------------------
-    def save_checkpoint(self, path):
-        d = {"num_populations": self.num_populations}
-        for i, m in enumerate(self.members):
-            for k, a in m.checkpoint_arrays().items():
-                d["m%d_%s" % (i, k)] = a
-        np.savez(Simulation._ckpt_path(path), **d)
+    def _own_entries(self):
+        return {"num_populations": self.num_populations}
 
     @classmethod
     def from_checkpoint(cls, path, device=0):
-        with np.load(Simulation._ckpt_path(path)) as d:
-            n = int(d["num_populations"])
-            per = [{k[len("m%d_" % i):]: d[k] for k in d.files if k.startswith("m%d_" % i)} for i in range(n)]
+        _, per = cls._load_entries(path)
         bc = {_native.LB_BC_PERIODIC: "periodic", _native.LB_BC_ZERO_GRADIENT: "zero_gradient"}[int(per[0]["bc_mode"])]
         out = cls(int(per[0]["nx"]), int(per[0]["ny"]), [float(p["omega"]) for p in per], bc=bc, device=device)
         for m, p in zip(out.members, per):
@@ -301,7 +315,7 @@ class Shan_Chen_Fluids(object):
         return out
 
 
-class Surfactant_Colony(object):
+class Surfactant_Colony(_Shared_Velocity, _Fused_Set):
     """A growing population and the surfactant it secretes, two scalar lattices in one periodic box
     (``Simulation(semantics='rocket')``, ``omega`` and ``omega_c``): the reference's ``rocket_yeast/rocket_yeast.py``
     (``mode='flow'``: the velocity that advects both is ``-epsilon / cs^2`` times the D2Q9 stencil over the surfactant, and the
@@ -313,24 +327,16 @@ class Surfactant_Colony(object):
     the population at index 0 and the surfactant at 1; ``u``, ``v``, ``psi`` / ``S`` and the forces are ``(nx, ny)``."""
     MODES = {"flow": _native.LB_ROCKET_FLOW, "forces": _native.LB_ROCKET_FORCES}
     PARAMS = ("G", "G_c", "epsilon", "rho_o", "G_chen", "c_o", "alpha")
-    _STACKED = ("f", "feq", "rho")
+    _RUN, _STACKED, _SHARED = "lb_run_rocket", ("f", "feq", "rho"), ("u", "v")
     _OWN = ("psi", "S", "pseudo_force_x", "pseudo_force_y", "surface_force_x", "surface_force_y")
 
     def __init__(self, nx, ny, omega, omega_c, mode="flow", device=0, planar=None):
         if mode not in self.MODES:
             raise ValueError("mode must be 'flow' or 'forces'")
-        self.nx, self.ny, self.num_populations, self.num_jumpers = int(nx), int(ny), 2, NUM_JUMPERS
         self.omega, self.omega_c, self.mode = float(omega), float(omega_c), mode
-        self.members = [Simulation(nx, ny, om, bc="periodic", semantics="rocket", device=device, planar=planar) for om in (omega, omega_c)]
-        self._lib = _native.lib()
-        self._handles = (ct.c_void_p * 2)(*[m._h for m in self.members])
+        self._adopt(nx, ny, [Simulation(nx, ny, om, bc="periodic", semantics="rocket", device=device, planar=planar) for om in (omega, omega_c)])
         self.params = dict(G=0., G_c=0., epsilon=0., rho_o=1., G_chen=0., c_o=1., alpha=1.)
         self.set_params()
-
-    close, sync, _per_field = Coupled_Scalars.close, Coupled_Scalars.sync, Coupled_Scalars._per_field
-    set_f, set_fields, init_pop = Coupled_Scalars.set_f, Coupled_Scalars.set_fields, Coupled_Scalars.init_pop
-    move, move_bcs, update_hydro, update_feq = Coupled_Scalars.move, Coupled_Scalars.move_bcs, Coupled_Scalars.update_hydro, Coupled_Scalars.update_feq
-    check = Coupled_Scalars.check
 
     def set_params(self, **kw):
         """G, G_c (growth and secretion rate per step), epsilon, rho_o, G_chen, c_o, alpha: float32, stored with the first member."""
@@ -339,7 +345,7 @@ class Surfactant_Colony(object):
                 raise TypeError("unknown parameter %r (one of %s)" % (k, ", ".join(self.PARAMS)))
         self.params.update({k: float(np.float32(v)) for k, v in kw.items()})
         p = _native.RocketParams(self.MODES[self.mode], *[self.params[k] for k in self.PARAMS])
-        check(self._lib.lb_set_rocket(self._handles, 2, ct.byref(p)))
+        self._call("lb_set_rocket", ct.byref(p))
 
     def get_params(self):
         p = _native.RocketParams()
@@ -349,37 +355,28 @@ class Surfactant_Colony(object):
     def get_fields(self, which=("f", "feq", "rho", "u", "v")):
         """f, feq: (nx, ny, 2, 9); rho: (nx, ny, 2); u, v: (nx, ny); 'psi' and 'pseudo_force_x/y' (flow), 'S',
         'surface_force_x/y' and 'pseudo_force_x/y' = the pressure force (forces): (nx, ny), those of the last step."""
-        out = {}
-        stacked = tuple(k for k in which if k in self._STACKED)
-        if stacked:
-            per = [m.get_fields(stacked) for m in self.members]
-            for k in stacked:
-                out[k] = np.asfortranarray(np.stack([g[k] for g in per], axis=2))
-        shared = tuple(k for k in which if k in ("u", "v"))
-        if shared:
-            out.update(self.members[0].get_fields(shared))
-        own = [k for k in which if k in self._OWN]
-        if own:
-            for k in own:
-                out[k] = np.zeros((self.nx, self.ny), np.float32, order="F")
-            ptr = lambda *ks: next((out[k].ctypes.data for k in ks if k in out), None)
-            check(self._lib.lb_get_rocket_fields(self._handles, 2, ptr("psi", "S"), ptr("pseudo_force_x"), ptr("pseudo_force_y"),
-                                                 ptr("surface_force_x"), ptr("surface_force_y")))
-            if "psi" in out and "S" in out:
-                out["S"][...] = out["psi"]
-        return out
+        return self._get_fields(which)
+
+    def _read_own(self, own, out):
+        for k in own:
+            out[k] = np.zeros((self.nx, self.ny), np.float32, order="F")
+        ptr = lambda *ks: next((out[k].ctypes.data for k in ks if k in out), None)
+        self._call("lb_get_rocket_fields", ptr("psi", "S"), ptr("pseudo_force_x"), ptr("pseudo_force_y"),
+                   ptr("surface_force_x"), ptr("surface_force_y"))
+        if "psi" in out and "S" in out:
+            out["S"][...] = out["psi"]
 
     # -- the reference's stages that involve both lattices, un-fused -----------------------------------------------------------
     def update_velocity(self):
-        check(self._lib.lb_update_velocity_rocket(self._handles, 2))
+        self._call("lb_update_velocity_rocket")
         self.sync()
 
     def update_forces(self):
-        check(self._lib.lb_update_forces_rocket(self._handles, 2))
+        self._call("lb_update_forces_rocket")
         self.sync()
 
     def collide_particles(self):
-        check(self._lib.lb_collide_rocket(self._handles, 2))
+        self._call("lb_collide_rocket")
         self.sync()
 
     def step_phases(self):
@@ -397,41 +394,20 @@ class Surfactant_Colony(object):
         self.update_feq()
         self.collide_particles()
 
-    # -- the hot path -----------------------------------------------------------------------------------------------------
-    def run(self, num_iterations, wait=True):
-        check(self._lib.lb_run_rocket(self._handles, 2, int(num_iterations)))
-        if wait:
-            self.sync()
-
-    def step(self):
-        self.run(1)
-
-    def set_variant(self, variant):
-        for m in self.members:
-            m.set_variant(variant)
-
-    def hot_kernel(self):
-        return self.members[0].hot_kernel()
-
     def use_stream(self, hip_stream):
         for m in self.members:
             m.use_stream(hip_stream)
 
     # -- checkpoints: every member's arrays under 'm<i>_', the parameters with the first -----------------------------------------
-    def save_checkpoint(self, path):
-        d = {"mode": np.array(self.mode), "params": np.array([self.params[k] for k in self.PARAMS], np.float32)}
-        for i, m in enumerate(self.members):
-            for k, a in m.checkpoint_arrays().items():
-                d["m%d_%s" % (i, k)] = a
-        np.savez(Simulation._ckpt_path(path), **d)
+    def _own_entries(self):
+        return {"mode": np.array(self.mode), "params": np.array([self.params[k] for k in self.PARAMS], np.float32)}
 
     @classmethod
     def from_checkpoint(cls, path, device=0):
-        with np.load(Simulation._ckpt_path(path)) as d:
-            per = [{k[len("m%d_" % i):]: d[k] for k in d.files if k.startswith("m%d_" % i)} for i in range(2)]
-            mode, params = str(d["mode"]), [float(x) for x in d["params"]]
-        out = cls(int(per[0]["nx"]), int(per[0]["ny"]), float(per[0]["omega"]), float(per[1]["omega"]), mode=mode, device=device)
-        out.set_params(**dict(zip(cls.PARAMS, params)))
+        own, per = cls._load_entries(path)
+        # (the members' omegas as they were given: the restored colony writes the same file)
+        out = cls(int(per[0]["nx"]), int(per[0]["ny"]), per[0]["omega"][()], per[1]["omega"][()], mode=str(own["mode"]), device=device)
+        out.set_params(**dict(zip(cls.PARAMS, [float(x) for x in own["params"]])))
         for m, p in zip(out.members, per):
             m.restore_arrays(p)
         out.update_forces()             # psi / S and the forces of the last step follow from its densities

@@ -26,12 +26,9 @@ NOT BUILT -- each raises ``NotImplementedError`` naming this list: ``potential='
 import numpy as np
 
 from .._dropin import NUM_JUMPERS, DeviceField, cs, get_divisible_global, lattice_arrays  # noqa: F401
+from .._forced import Forced_Fluid, Forced_Runner, cx, cy, int_type, num_type, w  # noqa: F401
 from ..coupled import Shan_Chen_Fluids
-from ..simulation import Simulation
-
-num_type = np.float32
-int_type = np.int32
-w, cx, cy = lattice_arrays(num_type, int_type)
+from ..simulation import Simulation  # noqa: F401
 
 _NOT_BUILT = ("not built in LB_D2Q9.multicomponent_multiphase.multi: potential='vdw'; add_interaction_force_second_belt "
               "(halo 2); add_screened_poisson_force (FFT); Simulation_RunnerD2Q25; more than 3 fluids; fluids of different "
@@ -39,59 +36,19 @@ _NOT_BUILT = ("not built in LB_D2Q9.multicomponent_multiphase.multi: potential='
 MAX_FLUIDS = Shan_Chen_Fluids.MAX_POPULATIONS
 
 
-class Fluid(object):
+class Fluid(Forced_Fluid):
     def __init__(self, sim, field_index, nu=1.0, bc='periodic', device=0, seed=None):
         if bc not in ('periodic', 'zero_gradient'):
             raise ValueError('unknown bc...')
         if not 0 <= int(field_index) < MAX_FLUIDS:
             raise NotImplementedError(_NOT_BUILT)
-        self.sim = sim
-        self.field_index = int_type(field_index)
-        self.lb_nu_e = num_type(nu)
-        self.bc = bc
-        # (the reference's float64 expression, rounded once: omega is the float32 of 1 / (0.5 + nu / cs^2))
-        self.tau = num_type(.5 + float(nu) / cs ** 2)
-        self.omega = num_type((.5 + float(nu) / cs ** 2) ** -1.)
-        assert self.omega < 2.
-        self._seed = seed
-        self._engine = Simulation(int(sim.nx), int(sim.ny), self.omega, bc=bc, semantics="multifluid", device=device)
-
-    def initialize(self, rho_arr, f_amp=0.0):
-        """ASSUMES THAT THE BARYCENTRIC VELOCITY IS ALREADY SET (Simulation_Runner.set_bary_velocity)."""
-        e = self._engine
-        g = e.get_fields(("u", "v"))
-        e.set_fields(np.asarray(rho_arr).reshape(e.nx, e.ny), g["u"], g["v"])
-        self.update_feq()
-        self.init_pop(amplitude=f_amp)
-
-    def init_pop(self, amplitude=0.001, seed=None):
-        """f = f_streamed = feq (1 + amplitude randn), seeded; amplitude 0 = exactly feq."""
-        if amplitude == 0:
-            self._engine.init_pop(None)
-            return
-        rng = np.random.default_rng(self._seed if seed is None else seed)
-        self._engine.init_pop(1. + amplitude * rng.standard_normal((int(self.sim.nx), int(self.sim.ny), NUM_JUMPERS)))
+        Forced_Fluid.__init__(self, sim, field_index, nu, bc, "multifluid", device, seed)
 
     def update_forces(self):
         """For internal forces...none in this case."""
 
-    def update_feq(self):
-        self._engine.update_feq()
 
-    def move_bcs(self):
-        self._engine.move_bcs()
-
-    def move(self):
-        self._engine.move()
-
-    def update_hydro(self):
-        self._engine.update_hydro()
-
-    def collide_particles(self):
-        self._engine.collide_particles()
-
-
-class Simulation_Runner(object):
+class Simulation_Runner(Forced_Runner):
     """Everything is in dimensionless units.  It's just easier."""
 
     _KEYS = {"rho": 3, "u": 3, "v": 3, "Gx": 3, "Gy": 3, "f": 4, "feq": 4, "u_bary": 2, "v_bary": 2}
@@ -100,36 +57,19 @@ class Simulation_Runner(object):
                  check_max_ulb=False, mach_tolerance=0.1, context=None):
         if not 1 <= int(num_populations) <= MAX_FLUIDS:
             raise NotImplementedError(_NOT_BUILT)
-        self.nx, self.ny = int_type(nx), int_type(ny)
-        self.L_lb, self.T_lb = int_type(L_lb), num_type(T_lb)
-        self.delta_x, self.delta_t = 1. / self.L_lb, 1. / self.T_lb
-        self.num_populations = int_type(num_populations)
-        self.check_max_ulb, self.mach_tolerance = check_max_ulb, mach_tolerance
-        self.two_d_local_size = two_d_local_size
-        self.two_d_global_size = get_divisible_global((self.nx, self.ny), two_d_local_size)
-        self.context, self.queue, self.kernels = context, None, None    # (OpenCL objects of the reference: kept, never used)
-        self.use_interop = use_interop
-        self.w, self.cx, self.cy = w, cx, cy
-        self.cs = num_type(cs)
-        self.num_jumpers = int_type(NUM_JUMPERS)
-        self.halo = int_type(1)
-        self.fluid_list, self.tau_arr = [], []
-        self.additional_collisions, self.additional_forces = [], []
+        Forced_Runner.__init__(self, nx, ny, L_lb, T_lb, num_populations, two_d_local_size, use_interop, check_max_ulb, mach_tolerance,
+                               context)
         self._set = None
-        self._bary = None                                   # set_bary_velocity before add_fluid: kept for the fluids to come
         self._g = {}                                        # fluid -> [gx, gy], the sum of its constant accelerations
-        self._field64 = {}                                  # fluid -> [fx, fy] float64, the sum of its radial ones
         self._inter, self._react = [], []
         self._dirty = False                                 # the tables differ from what the set's first handle holds
-        for key in self._KEYS:
-            setattr(self, key, DeviceField(self, key))
 
     @property
     def engine(self):
         """The ``Shan_Chen_Fluids`` underneath (checkpoints, hot_kernel ...); None before add_fluid."""
         return self._set
 
-    def _need_set(self):
+    def _need(self):
         if self._set is None:
             raise RuntimeError("add_fluid() first: the fluids carry the lattices")
         if self._dirty:
@@ -145,7 +85,7 @@ class Simulation_Runner(object):
         return self.fluid_list[index]
 
     def _read_field(self, key):
-        return self._need_set().get_fields((key,))[key]
+        return self._need().get_fields((key,))[key]
 
     def add_fluid(self, fluid):
         if len(self.fluid_list) >= min(MAX_FLUIDS, int(self.num_populations)):
@@ -154,27 +94,13 @@ class Simulation_Runner(object):
             raise NotImplementedError(_NOT_BUILT)
         if int(fluid.field_index) != len(self.fluid_list):
             raise ValueError("fluids are added in the order of their field_index")
-        self.fluid_list.append(fluid)
+        self._adopt(fluid)
         self._set = Shan_Chen_Fluids.of([f._engine for f in self.fluid_list])
         self._dirty = True
-        if self._bary is not None:
-            fluid._engine.set_bary_velocity(*self._bary)
-
-    def complete_setup(self):
-        self.tau_arr = np.array([f.tau for f in self.fluid_list], dtype=num_type)
-
-    def set_bary_velocity(self, u_bary_host, v_bary_host):
-        shape = (int(self.nx), int(self.ny))
-        self._bary = (np.asarray(u_bary_host).reshape(shape), np.asarray(v_bary_host).reshape(shape))
-        for f in self.fluid_list:
-            f._engine.set_bary_velocity(*self._bary)
-
-    def update_bary_velocity(self):
-        self._need_set().update_bary_velocity()
 
     def update_forces(self):
         """Gx, Gy = 0 and the additional forces: one kernel."""
-        self._need_set().update_forces()
+        self._need().update_forces()
 
     # -- additional forces ------------------------------------------------------------------------------------------------
     def add_constant_g_force(self, fluid_index, force_x, force_y):
@@ -188,15 +114,9 @@ class Simulation_Runner(object):
         """prefactor r^radial_scaling along the unit vector from (center_x, center_y): multi.cl:568-606, formed on the host in
         float64 (it depends on position only) and cast to float32 once; the kernel multiplies by rho."""
         f = self._fluid(fluid_index)
-        x, y = np.meshgrid(np.arange(int(self.nx)), np.arange(int(self.ny)), indexing="ij")
-        dx, dy = (x - int(center_x)).astype(np.float64), (y - int(center_y)).astype(np.float64)
-        radius, theta = np.sqrt(dx * dx + dy * dy), np.arctan2(dy, dx)
-        magnitude = float(prefactor) * np.power(radius, float(radial_scaling))
-        acc = self._field64.setdefault(int(fluid_index), [np.zeros_like(dx), np.zeros_like(dx)])
-        acc[0] += magnitude * np.cos(theta)
-        acc[1] += magnitude * np.sin(theta)
+        field = self._add_radial(fluid_index, center_x, center_y, prefactor, radial_scaling)
         self.additional_forces.append(["add_radial_g_force", [int(fluid_index), center_x, center_y, prefactor, radial_scaling]])
-        f._engine.set_force_field(acc[0].astype(num_type), acc[1].astype(num_type))
+        f._engine.set_force_field(*field)
 
     def add_interaction_force(self, fluid_1_index, fluid_2_index, G_int, bc='periodic', potential='linear', potential_parameters=None):
         f1, f2 = self._fluid(fluid_1_index), self._fluid(fluid_2_index)
@@ -241,16 +161,9 @@ class Simulation_Runner(object):
         self._fluid(eater_index)
         self._add_reaction(("grow", int(eater_index), num_type(min_rho_cutoff), num_type(max_rho_cutoff), num_type(eat_rate)))
 
-    def run(self, num_iterations, debug=False):
-        """num_iterations time steps, one launch each."""
-        self._need_set().run(int(num_iterations))
-
     def react(self):
         """The additional collisions, from the stored rho."""
-        self._need_set().react()
-
-    def get_fields(self):
-        return {k: self._read_field(k) for k in self._KEYS}
+        self._need().react()
 
     def check_fields(self):
         g = self.get_fields()

@@ -18,14 +18,14 @@ kernel; ``two_d_local_size`` and ``use_interop`` are accepted and ignored; nothi
 """
 import numpy as np
 
-from .._dropin import NUM_JUMPERS, DeviceField, get_divisible_global, lattice_arrays, w0, w1, w2  # noqa: F401
+from .._dropin import NUM_JUMPERS, DeviceField, Phases, get_divisible_global, lattice_arrays, w0, w1, w2  # noqa: F401
 from ..coupled import Surfactant_Colony
 
 w, cx, cy = lattice_arrays(np.float32, np.int32)
 cs = np.float32(1. / np.sqrt(3))                # Speed of sound on the lattice
 
 
-class Rocket_Yeast(object):
+class Rocket_Yeast(Phases):
     """Everything is in dimensionless units.  It's just easier."""
     _MODE = "flow"
     _KEYS = ("rho", "f", "feq", "u", "v", "psi", "pseudo_force_x", "pseudo_force_y")
@@ -71,7 +71,7 @@ class Rocket_Yeast(object):
         self.buf_nx, self.buf_ny = np.int32(two_d_local_size[0] + 2), np.int32(two_d_local_size[1] + 2)
         self.psi_local = None
         self._rng = np.random.default_rng(rng)
-        self._engine = Surfactant_Colony(int(self.nx), int(self.ny), self.omega, self.omega_c, mode=self._MODE, device=device)
+        self._sim = self._engine = Surfactant_Colony(int(self.nx), int(self.ny), self.omega, self.omega_c, mode=self._MODE, device=device)
         self._engine.set_params(**self._engine_params())
         for key in self._KEYS:
             setattr(self, key, DeviceField(self, key))
@@ -136,9 +136,6 @@ class Rocket_Yeast(object):
         self.update_feq()
         self.init_pop()
 
-    def update_feq(self):
-        self._engine.update_feq()
-
     def init_pop(self, amplitude=0):
         """f = f_streamed = feq (1 + amplitude randn), from the class's generator; amplitude 0 = exactly feq."""
         if amplitude == 0:
@@ -148,9 +145,6 @@ class Rocket_Yeast(object):
 
     def move_bcs(self):
         pass                                            # (implemented in move_periodic, as in the reference)
-
-    def move(self):
-        self._engine.move()
 
     def _warn_max_ulb(self):
         g = self._engine.get_fields(("u", "v"))
@@ -167,9 +161,6 @@ class Rocket_Yeast(object):
 
     def update_force(self):
         self._engine.update_forces()
-
-    def collide_particles(self):
-        self._engine.collide_particles()
 
     def run(self, num_iterations):
         """num_iterations time steps, one fused launch each."""

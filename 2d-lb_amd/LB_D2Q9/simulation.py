@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _native
 from ._native import LbError, check
+from .kinds import KINDS
 
 NUM_JUMPERS = 9
 
@@ -124,13 +125,10 @@ class Simulation(object):
         self.eager_macro = bool(eager_macro)
         p.flags = ((_native.LB_FLAG_HALO if halo else 0) | (_native.LB_FLAG_PLANAR if self.planar else 0) |
                    (_native.LB_FLAG_EAGER_MACRO if self.eager_macro else 0))
-        sem = {"opencl": _native.LB_SEM_OPENCL, "cython": _native.LB_SEM_CYTHON, "d2q9i": _native.LB_SEM_OPENCL_D2Q9I,
-               "diffusion": _native.LB_SEM_DIFFUSION, "multifield": _native.LB_SEM_MULTIFIELD, "poisson": _native.LB_SEM_POISSON,
-               "porous": _native.LB_SEM_POROUS, "multifluid": _native.LB_SEM_MULTIFLUID, "rocket": _native.LB_SEM_ROCKET}
-        if semantics not in sem:
-            raise ValueError("semantics must be one of %s" % sorted(sem))
-        p.semantics = sem[semantics]
-        self.semantics = semantics
+        if semantics not in KINDS:
+            raise ValueError("semantics must be one of %s" % sorted(KINDS))
+        self.semantics, self._kind = semantics, KINDS[semantics]        # (the kind's row: LB_D2Q9/kinds.py)
+        p.semantics = self._kind.sem
         self._halo = bool(halo)
         p.omega = np.float32(omega)
         p.inlet_rho, p.outlet_rho = np.float32(inlet_rho), np.float32(outlet_rho)
@@ -245,7 +243,7 @@ class Simulation(object):
         unchanged; the pass advances at most (n - 7) // 4 steps, a runner-up's longer comparison included) and keeps the
         fastest for this grid; shorter runs use the size heuristic (or call autotune())."""
         n = int(num_iterations)
-        if wait and n > 0 and self.semantics not in ("diffusion", "multifield", "poisson", "porous", "multifluid", "rocket"):      # (a scalar lattice's kernel is the planner's size rule: no tuning pass)
+        if wait and n > 0 and self._kind.tunes:
             # (the pass costs 361 steps, 889 on grids <= 768^2, some of them in configurations several times slower than
             #  the best: it only pays for itself in a run several times that long)
             used = self._lib.lb_autotune_quick(self._h, (n - 7) // 4)
@@ -343,35 +341,7 @@ class Simulation(object):
             d[k] = getattr(self, k)
         if self.bc_mode == _native.LB_BC_VELOCITY_INLET:
             d["corner_state"] = self.get_corner_state()
-        if self.semantics == "diffusion":
-            d["G"] = np.float32(self.G)
-            d["edge_state"] = self.get_edge_state()
-        if self.semantics == "multifield":
-            d["G"] = np.float32(self.G)
-            d["corner_state"] = self.get_corner_state()
-        if self.semantics == "poisson":
-            d["corner_state"] = self.get_corner_state()
-            d["source"] = self.get_source()
-            d["poisson"] = np.array([self.rho_on_boundary, self.react_factor, self.tolerance], np.float32)
-            d["solve_state"] = np.array(self.solve_state(), np.int32)
-        if self.semantics == "porous":
-            g = self.get_fields(("u_bary", "v_bary", "Gx", "Gy"))
-            d["porous"] = np.array([self.epsilon, self.nu_fluid, self.K, self.Fe], np.float32)
-            d["body_force"] = np.array(self.body_force, np.float32)
-            d["bary"] = np.stack([g["u_bary"], g["v_bary"]])
-            d["force"] = np.stack([g["Gx"], g["Gy"]])
-            if self._force_field is not None:
-                d["force_field"] = np.stack(self._force_field)
-        if self.semantics == "multifluid":
-            g = self.get_fields(("u_bary", "v_bary", "Gx", "Gy"))
-            d["body_force"] = np.array(self.body_force, np.float32)
-            d["bary"] = np.stack([g["u_bary"], g["v_bary"]])
-            d["force"] = np.stack([g["Gx"], g["Gy"]])
-            if self._force_field is not None:
-                d["force_field"] = np.stack(self._force_field)
-            # the tables as rows of float64 (exact for the int32 and float32 they hold)
-            d["interactions"] = np.array(self.interactions, np.float64).reshape(len(self.interactions), 6)
-            d["reactions"] = np.array(self.reactions, np.float64).reshape(len(self.reactions), 6)
+        self._kind.save(self, d)
         if self._mask_halo_host is not None:         # a slab: the neighbours' obstacle rows it was given
             empty = np.zeros((0, 0), np.int32)
             d["mask_halo_south"] = empty if self._mask_halo_host[0] is None else self._mask_halo_host[0]
@@ -405,7 +375,7 @@ class Simulation(object):
 
     def restore_arrays(self, d):
         self._check_compatible(d)
-        if self.semantics not in ("diffusion", "multifield", "poisson", "porous", "multifluid", "rocket"):   # (a scalar lattice has no obstacles, nor have the porous medium and the fluids of a set)
+        if self._kind.has_mask:
             self.set_obstacle_mask(d["mask"] if d["mask"].size else None)
         if "mask_halo_south" in d:
             so, no = d["mask_halo_south"], d["mask_halo_north"]
@@ -414,38 +384,15 @@ class Simulation(object):
         self.set_f(d["f"])
         if self.bc_mode == _native.LB_BC_VELOCITY_INLET:
             self.set_corner_state(d["corner_state"])           # (after set_f, which resets them to f's own corners)
-        if self.semantics == "diffusion":
-            self.set_reaction(float(d["G"]))
-            self.set_edge_state(d["edge_state"])               # (after set_f, likewise)
-        if self.semantics == "multifield":
-            self.set_reaction(float(d["G"]))
-            self.set_corner_state(d["corner_state"])           # (after set_f, likewise)
+        self._kind.restore(self, d)                            # (after set_f, likewise: edge and corner state)
 
-        if self.semantics == "poisson":
-            self.set_poisson(*[float(x) for x in d["poisson"]])
-            self.set_source(d["source"])
-            self.set_corner_state(d["corner_state"])           # (after set_f, likewise)
-            check(self._lib.lb_set_solve_state(self._h, int(d["solve_state"][0]), int(d["solve_state"][1])))
+    def _set_force(self, gx, gy):
+        """The force of the last step, two (nx, ny) arrays (a checkpoint's; update_forces and run() overwrite it)."""
+        a, b = (_f_order(x, self._shape2) for x in (gx, gy))
+        check(self._lib.lb_set_force(self._h, a.ctypes.data, b.ctypes.data))
 
-        if self.semantics == "porous":
-            self.set_porous(*[float(x) for x in d["porous"]])
-            self.set_body_force(*[float(x) for x in d["body_force"]])
-            self.set_force_field(*(d["force_field"] if "force_field" in d else (None, None)))
-            self.set_bary_velocity(d["bary"][0], d["bary"][1])
-            gx, gy = (_f_order(a, self._shape2) for a in d["force"])
-            check(self._lib.lb_set_force(self._h, gx.ctypes.data, gy.ctypes.data))
-
-        if self.semantics == "multifluid":
-            self.set_body_force(*[float(x) for x in d["body_force"]])
-            self.set_force_field(*(d["force_field"] if "force_field" in d else (None, None)))
-            self.set_bary_velocity(d["bary"][0], d["bary"][1])
-            gx, gy = (_f_order(a, self._shape2) for a in d["force"])
-            check(self._lib.lb_set_force(self._h, gx.ctypes.data, gy.ctypes.data))
-            inter, react = [tuple(r) for r in d["interactions"]], [tuple(r) for r in d["reactions"]]
-            others = [r[0] for r in inter] + [r[1] for r in inter] + [r[1] for r in react] + [r[2] for r in react]
-            if not others or max(others) == 0:      # (tables that name further fluids are restored by the set: Shan_Chen_Fluids)
-                self.set_interactions(inter)
-                self.set_reactions(react)
+    def _set_solve_state(self, iterations, stop_word):
+        check(self._lib.lb_set_solve_state(self._h, int(iterations), int(stop_word)))
 
     # -- one fluid of a set of Shan-Chen fluids (semantics='multifluid'); the calls below this block are shared -------------
     def _set_tables(self, handles, count, interactions, reactions):
@@ -627,7 +574,7 @@ class Simulation(object):
         with np.load(cls._ckpt_path(path)) as d:
             if int(d["version"]) != cls.CHECKPOINT_VERSION:
                 raise ValueError("checkpoint format %d, this build reads %d" % (int(d["version"]), cls.CHECKPOINT_VERSION))
-            sim = cls(int(d["nx"]), int(d["ny"]), float(d["omega"]), bc=int(d["bc_mode"]),
+            sim = cls(int(d["nx"]), int(d["ny"]), d["omega"][()], bc=int(d["bc_mode"]),        # (omega as it was given: the restored handle writes the same file)
                       inlet_rho=float(d["inlet_rho"]), outlet_rho=float(d["outlet_rho"]), lid_u=float(d["lid_u"]),
                       rho0=float(d["rho0"]), device=device, y0=int(d["y0"]), local_ny=int(d["local_ny"]),
                       halo=bool(int(d["halo"])), semantics=str(d["semantics"]),

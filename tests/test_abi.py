@@ -24,6 +24,26 @@ def test_every_declared_symbol_is_exported(lbhip):
     assert sorted(_native.EXPORTS) == names          # the binding covers exactly the header
 
 
+def test_every_export_has_a_row_in_the_signature_table():
+    from LB_D2Q9 import _native
+    assert [n for n in _native.EXPORTS if n not in _native.SIGNATURES] == []
+    assert list(_native.EXPORTS) == list(_native.SIGNATURES)         # (derived from it ...)
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "lb_hip.h")).read(), flags=re.S)
+    in_order = list(dict.fromkeys(re.findall(r"\b(lb_[a-z0-9_]+)\s*\(", text)))
+    assert list(_native.SIGNATURES) == in_order                      # (... and written in the header's order)
+
+
+def test_every_exported_function_is_bound_with_argtypes(lbhip):
+    from LB_D2Q9 import _native
+    assert [n for n in _native.EXPORTS if getattr(lbhip, n).argtypes is None] == []
+    for name, row in _native.SIGNATURES.items():
+        assert list(getattr(lbhip, name).argtypes) == list(row[0]), name
+
+
+def test_last_error_returns_a_string(lbhip):
+    assert lbhip.lb_last_error.restype is ct.c_char_p
+
+
 def test_abi_version_matches_header(lbhip):
     text = open(os.path.join(ROOT, "include", "lb_hip.h")).read()
     assert lbhip.lb_abi_version() == int(re.search(r"#define LB_ABI_VERSION (\d+)", text).group(1))
