@@ -12,7 +12,8 @@
 // Small kernels are emitted by the one unit that includes their header: kernels_phases.h + kernels_check.h by lb_hip.cpp,
 // kernels_halo.h by slab.cpp, kernels_scalar.h by scalar.cpp (its health check's first pass only: check_reduce.h is shared, the folding
 // pass is lb_hip.cpp's), kernels_multifield.h by multifield.cpp, kernels_poisson.h by poisson.cpp, kernels_porous.h by porous.cpp,
-// kernels_multifluid.h by multifluid.cpp, kernels_rocket.h by rocket.cpp.
+// kernels_multifluid.h by multifluid.cpp, kernels_rocket.h by rocket.cpp.  The six kind headers share kernels_lane4.h, the plan their
+// fused steps follow: device functions only, no kernel of its own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -49,7 +50,7 @@ struct lb_sim : PlanInputs {
     float *stage = nullptr;     // [H][pitch], lazily: one plane on its way between the host and interleaved rows (lattice_plane_*)
     float *ad_edge = nullptr;   // scalar lattice, OPEN family: the edge state on the device (scalar_launch.h: AdExtra)
     float ad_G = 0.f;           // scalar lattice: growth rate of the Fisher term (lb_set_reaction); 0 = plain relaxation
-    float *vi_corner = nullptr; // VELOCITY_INLET: the eight corner links nothing ever writes (bc_vel_cell), device; LB_BC_BOX, LB_BC_DIRICHLET: likewise (mf_box_cell, ps_box_cell)
+    float *vi_corner = nullptr; // VELOCITY_INLET: the eight corner links nothing ever writes (bc_vel_cell), device; LB_BC_BOX, LB_BC_DIRICHLET: likewise (MfBox, PsBox)
     // the LB Poisson solver (LB_SEM_POISSON; poisson_launch.h)
     float *ps_source = nullptr;         // [H][pitch]: the source, padding zero
     float *ps_part = nullptr;           // two floats per workgroup of k_ps_step

@@ -2,11 +2,10 @@
 // driven as advecting_range_expansion/deterministic_fisher_waves.py:436-450 does: move + copy_buffer -> move_bcs -> update_hydro ->
 // update_feq -> collide_particles, five launches and five host waits per step, each looping over the fields in every work-item).
 // Included by multifield.cpp only (multifield_launch.h: what the kernels and their host code share; host.h: what the other host units see).
-//   k_mf_step<BC, NF, RHO>   the fused step of NF fields: k_ad_step's plan (kernels_scalar.h) -- a lane owns four consecutive cells of
-//                            a row; per field nine 16-byte loads (six displaced by one element: k_step's gather) and nine aligned
-//                            16-byte stores, u and v loaded once for all fields, rho of every field when asked: 72 NF + 8 B per cell
-//                            and step.  Every field's gathered populations are live before any collision -- rho_tot comes first --:
-//                            36 registers per field.  The cell arithmetic is scalar_cell.h's: with one field the bits of k_ad_step.
+//   k_mf_step<BC, NF, RHO>   the fused step of NF fields on the lane-of-four plan (kernels_lane4.h): u and v loaded once for all fields,
+//                            rho of every field when asked: 72 NF + 8 B per cell and step.  Every field's gathered populations are
+//                            live before any collision -- rho_tot comes first --: 36 registers per field.  The cell arithmetic is
+//                            scalar_cell.h's: with one field the bits of k_ad_step.
 //   k_mf_move_bcs            the un-fused move_bcs of LB_BC_BOX, in place, edge cells only
 //   k_mf_collide<NF>         the un-fused collide_particles: stored feq and rho, rho_tot summed over the fields' stored rho in order
 // (lb_move, lb_update_hydro, lb_update_feq, lb_init_pop reuse k_move / k_ad_hydro / k_ad_feq: per field they are the same kernels.)
@@ -17,57 +16,44 @@
 #pragma once
 #include "scalar_cell.h"
 #include "multifield_launch.h"
+#include "kernels_lane4.h"
 
 namespace {
 
 // move_bcs of D2Q9_multifield_fisher.cl for one cell (w, e, s, n: it lies in column 0 / nx-1, row 0 / ny-1); st: the eight corner
 // links in the ABI's order -- f6, f8 of (0,0), f5, f7 of (nx-1,0), f5, f7 of (0,ny-1), f6, f8 of (nx-1,ny-1).  Every right-hand
 // side is a post-stream value of the cell, read before anything is written, as the kernel reads f1 ... f8 first.
-__device__ __forceinline__ void mf_box_cell(Cell &c, bool w, bool e, bool s, bool n, const float *st)
-{
-    const float f1 = c.f1, f2 = c.f2, f3 = c.f3, f4 = c.f4, f5 = c.f5, f6 = c.f6, f7 = c.f7, f8 = c.f8;
-    if (w) c.f1 = f3;
-    if (e) c.f3 = f1;
-    if (s) c.f2 = f4;
-    if (n) c.f4 = f2;
-    // a diagonal link enters from outside through either wall its velocity points away from; bounced except in the corner whose
-    // other wall it runs along
-    if (w || s) c.f5 = (w && n) ? st[4] : ((s && e) ? st[2] : f7);
-    if (e || n) c.f7 = (e && s) ? st[3] : ((n && w) ? st[5] : f5);
-    if (e || s) c.f6 = (s && w) ? st[0] : ((e && n) ? st[6] : f8);
-    if (w || n) c.f8 = (w && s) ? st[1] : ((n && e) ? st[7] : f6);
-}
-
-// ... for a lane's four gathered cells (x4 .. x4+3, row y).  The caller has checked that the lane holds a wall cell.
-__device__ __forceinline__ void mf_box_row(const float *st, int nx, int ny, int x4, int y, f4a (&q)[9])
-{
-    const bool s = (y == 0), n = (y == ny - 1);
-    const int ce = nx - 1 - x4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const bool w = (x4 == 0 && j == 0), e = (j == ce);
-        if (s || n || w || e) {
-            Cell c = row_cell(q, j);
-            mf_box_cell(c, w, e, s, n, st);
-            row_cell_put(q, j, c);
-        }
+struct MfBox {
+    __device__ __forceinline__ void rule(Cell &c, bool w, bool e, bool s, bool n, const float *st) const
+    {
+        const float f1 = c.f1, f2 = c.f2, f3 = c.f3, f4 = c.f4, f5 = c.f5, f6 = c.f6, f7 = c.f7, f8 = c.f8;
+        if (w) c.f1 = f3;
+        if (e) c.f3 = f1;
+        if (s) c.f2 = f4;
+        if (n) c.f4 = f2;
+        // a diagonal link enters from outside through either wall its velocity points away from; bounced except in the corner whose
+        // other wall it runs along
+        if (w || s) c.f5 = (w && n) ? st[4] : ((s && e) ? st[2] : f7);
+        if (e || n) c.f7 = (e && s) ? st[3] : ((n && w) ? st[5] : f5);
+        if (e || s) c.f6 = (s && w) ? st[0] : ((e && n) ? st[6] : f8);
+        if (w || n) c.f8 = (w && s) ? st[1] : ((n && e) ? st[7] : f6);
     }
-}
+};
 
 // moments of every field, rho_tot, then equilibrium, relaxation and growth of every field: a lane's four cells as two pairs, in
-// place (ad_collide_row's plan, kernels_scalar.h).  A field with G = 0 skips the growth term (wave-uniform): plain relaxation.
+// place.  A field with G = 0 skips the growth term (wave-uniform): plain relaxation.
 template <int NF>
 __device__ __forceinline__ void mf_collide_row(f4a (&q)[NF][9], f4a u4, f4a v4, const MfArgs &m, f4a (&r4)[NF])
 {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const f2a ux = h ? u4.zw : u4.xy, uy = h ? v4.zw : v4.xy;
+        const f2a ux = pair_of(u4, h), uy = pair_of(v4, h);
         f2a rho[NF];
 #pragma unroll
         for (int i = 0; i < NF; ++i) {
             f2a f[9];
 #pragma unroll
-            for (int k = 0; k < 9; ++k) f[k] = h ? q[i][k].zw : q[i][k].xy;
+            for (int k = 0; k < 9; ++k) f[k] = pair_of(q[i][k], h);
             rho[i] = ad_rho_t<f2a>(f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8]);
         }
         f2a rho_tot = rho[0];
@@ -78,7 +64,7 @@ __device__ __forceinline__ void mf_collide_row(f4a (&q)[NF][9], f4a u4, f4a v4, 
         for (int i = 0; i < NF; ++i) {
             f2a f[9];
 #pragma unroll
-            for (int k = 0; k < 9; ++k) f[k] = h ? q[i][k].zw : q[i][k].xy;
+            for (int k = 0; k < 9; ++k) f[k] = pair_of(q[i][k], h);
             ad_relax_t<f2a, false>(f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], m.a[i].omega, 0.f, rho[i], ux, uy);
             if (m.G[i] != 0.f) ad_grow_t<f2a>(f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], m.G[i], rho[i], room);
             if (h) r4[i].zw = rho[i];
@@ -92,7 +78,8 @@ __device__ __forceinline__ void mf_collide_row(f4a (&q)[NF][9], f4a u4, f4a v4, 
     }
 }
 
-// Launch: blockDim = (64, 4), grid = (ceil(fpitch / 256), ceil(ny / 4)): a wave covers 256 cells of one row (k_ad_step's launch).
+// (lane_rows, lane_gather and the nine stores written out: through the calls the BOX form tests its two bounds at once, the diagnostic
+// build orders the gather differently, the plane offsets are shared with the gather's, and the instruction text moves)
 template <int BC, int NF, bool RHO>
 __global__ __launch_bounds__(256) void k_mf_step(const MfArgs m)
 {
@@ -114,7 +101,7 @@ __global__ __launch_bounds__(256) void k_mf_step(const MfArgs m)
         const int ce = g.nx - 1 - x4;
         if (yl == 0 || yl == g.ny - 1 || x4 == 0 || (ce >= 0 && ce < 4)) {
 #pragma unroll
-            for (int i = 0; i < NF; ++i) mf_box_row(m.a[i].corner, g.nx, g.ny, x4, yl, q[i]);
+            for (int i = 0; i < NF; ++i) row_wall(MfBox{}, m.a[i].corner, g.nx, g.ny, x4, yl, q[i]);
         }
     }
     const long long m0 = (long long)yl * g.fpitch;
@@ -132,35 +119,12 @@ __global__ __launch_bounds__(256) void k_mf_step(const MfArgs m)
 }
 
 // ---- the reference's phases ----------------------------------------------------------------------------------------------------
-// move_bcs (D2Q9_multifield_fisher.cl:173-289) of one field, in place behind lb_move: one thread per index i, grid =
-// ceil(max(nx, ny) / 256): the cells (i, 0) and (i, ny-1) of the wall rows, (0, i) and (nx-1, i) of the wall columns between them.
-// The two links per corner that the rule skips keep what the lattice holds (lb_move has patched the corner state in).
-__device__ __forceinline__ void mf_bcs_cell(const StepArgs &a, float *f, int x, int y)
-{
-    float *p = f + (long long)y * a.pitch + x;
-    const long long S = a.plane;
-    Cell c = {p[0], p[S], p[2 * S], p[3 * S], p[4 * S], p[5 * S], p[6 * S], p[7 * S], p[8 * S]};
-    const float own[8] = {c.f6, c.f8, c.f5, c.f7, c.f5, c.f7, c.f6, c.f8};
-    mf_box_cell(c, x == 0, x == a.nx - 1, y == 0, y == a.ny - 1, own);
-    p[S] = c.f1; p[2 * S] = c.f2; p[3 * S] = c.f3; p[4 * S] = c.f4;
-    p[5 * S] = c.f5; p[6 * S] = c.f6; p[7 * S] = c.f7; p[8 * S] = c.f8;
-}
+// move_bcs (D2Q9_multifield_fisher.cl:173-289) of one field, in place behind lb_move (edge_walk, kernels_lane4.h).  The two links per
+// corner that the rule skips keep what the lattice holds (lb_move has patched the corner state in).
+__global__ void k_mf_move_bcs(const StepArgs a, float *f) { edge_walk(a, f, BoxEdge<MfBox>{}); }
 
-__global__ void k_mf_move_bcs(const StepArgs a, float *f)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < a.nx) {
-        mf_bcs_cell(a, f, i, 0);
-        mf_bcs_cell(a, f, i, a.ny - 1);
-    }
-    if (i >= 1 && i <= a.ny - 2) {
-        mf_bcs_cell(a, f, 0, i);
-        mf_bcs_cell(a, f, a.nx - 1, i);
-    }
-}
-
-// collide_particles (:76-124), one cell per thread: grid = (ceil(nx / 256), ny).  k_ad_collide's arithmetic (kernels_scalar.h) with
-// the room left by ALL fields in the growth term.
+// collide_particles (:76-124), one cell per thread: grid = (ceil(nx / 256), ny).  k_ad_collide's arithmetic with the room left by ALL
+// fields in the growth term.  (cell_xy written out: the call moves the instruction text for one field.)
 template <int NF>
 __global__ void k_mf_collide(const MfArgs m)
 {
@@ -168,7 +132,6 @@ __global__ void k_mf_collide(const MfArgs m)
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= g.nx) return;
     const long long o = (long long)y * g.pitch + x, c = (long long)y * g.fpitch + x;
-    const float w[9] = {4.f / 9.f, 1.f / 9.f, 1.f / 9.f, 1.f / 9.f, 1.f / 9.f, 1.f / 36.f, 1.f / 36.f, 1.f / 36.f, 1.f / 36.f};
     float rho[NF], rho_tot = 0.f;
 #pragma unroll
     for (int i = 0; i < NF; ++i) {
@@ -184,7 +147,7 @@ __global__ void k_mf_collide(const MfArgs m)
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
             float v = lb_fma(f[o + k * g.plane], keep, omega * feq[o + k * g.plane]);
-            if (G != 0.f) v = lb_fma(w[k], react, v);
+            if (G != 0.f) v = lb_fma(lb_w9(k), react, v);
             f[o + k * g.plane] = v;
         }
     }

@@ -6,16 +6,13 @@
 //
 // The step is NOT local to the cell after streaming: the interaction force on a cell reads the post-stream density of its eight
 // neighbours.  Two forms of the step, bitwise equal (one body, mc_collide_lane).  The one-launch form:
-//   k_mc_step<BC, NF, R, LAST>   a workgroup of R + 2 waves owns R rows of a 256-cell tile; every wave gathers one row of every fluid,
-//                                the two extra ones the rows above and below (the halo rows), and puts rho_i into LDS with one
-//                                halo cell left and right; after one barrier the R owned rows, their populations still in
-//                                registers, run forces -> collide.  36 NF (R + 2) / R B read + 36 NF B written per cell.
+//   k_mc_step<BC, NF, R, LAST>   the one-launch form of the lane-of-four plan (kernels_lane4.h): every wave gathers one row of every
+//                                fluid and puts rho_i into LDS; the R owned rows run forces -> collide.  36 NF (R + 2) / R B read +
+//                                36 NF B written per cell.
 // The two-launch form:
-//   k_mc_moments<BC, NF>         k_pm_step's gather (a lane owns four consecutive cells of a row; the source cell is clamped for the
-//                                zero-gradient family), sums only, stores rho_i: 36 NF B read, 4 NF B written per cell
-//   k_mc_collide<BC, NF, LAST>   gathers again, reads rho of the three rows around the cell (one 16-byte load and two 4-byte loads
-//                                per row and fluid; wrap or clamp on the INDEX, as the family says), forces -> u_b -> feq -> relaxation
-//                                -> reactions in registers (multifluid_cell.h), nine aligned 16-byte stores per fluid; LAST (a
+//   k_mc_moments<BC, NF>         the gather, sums only, stores rho_i: 36 NF B read, 4 NF B written per cell
+//   k_mc_collide<BC, NF, LAST>   gathers again, reads rho of the three rows around the cell (wrap or clamp on the INDEX, as the family
+//                                says), forces -> u_b -> feq -> relaxation -> reactions in registers (multifluid_cell.h); LAST (a
 //                                run's last step): u, v, Gx, Gy of every fluid and u_b, v_b as well
 //   k_mc_hydro, k_mc_forces, k_mc_bary, k_mc_relax, k_mc_react    the reference's stages one by one, one cell per thread;
 //                                multifluid_cell.h's functions, the same operations as the fused cell: bitwise equal to it.
@@ -25,83 +22,27 @@
 #pragma once
 #include "kernels_porous.h"
 #include "multifluid_cell.h"
+#include "kernels_lane4.h"
 
 namespace {
 
-// rho of one fluid around a lane's four cells: nb[row][col], row 0 = y - 1, col 0 = x4 - 1 ... col 5 = x4 + 4.  Every index is
-// inside the box (wrapped or clamped), so nothing outside the row's allocation is read; cells past nx-1 (row padding) get in-bounds
-// values nobody uses.
-template <int BC>
-__device__ __forceinline__ void mc_load_rho(const float *rho, int fpitch, int nx, int ny, int x4, int yl, float (&nb)[3][6])
-{
-    const int c = nx - 1 - x4;
-    int xl = x4 - 1, xr = x4 + 4;
-    if (xl < 0) xl = BC == LB_BC_PERIODIC ? nx - 1 : 0;
-    if (xr >= nx) xr = BC == LB_BC_PERIODIC ? 0 : nx - 1;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        int y = yl - 1 + r;
-        if (BC == LB_BC_PERIODIC) {
-            if (y < 0) y = ny - 1;
-            if (y >= ny) y = 0;
-        } else {
-            y = min(max(y, 0), ny - 1);
-        }
-        const float *row = rho + (long long)y * fpitch;
-        const f4a v = load4<false>(lane_ptr(row, x4));
-        const float w = row[xl], e = row[xr];
-        nb[r][0] = w;
-        nb[r][1] = v.x;
-        // the east neighbour of the cell nx-1, where that cell is not the lane's last: the wrapped cell / the cell itself
-        nb[r][2] = c == 0 ? (BC == LB_BC_PERIODIC ? e : v.x) : v.y;
-        nb[r][3] = c == 1 ? (BC == LB_BC_PERIODIC ? e : v.y) : v.z;
-        nb[r][4] = c == 2 ? (BC == LB_BC_PERIODIC ? e : v.z) : v.w;
-        nb[r][5] = e;
-    }
-}
-
-template <int BC>
-__device__ __forceinline__ bool mc_rows(const StepArgs &a, int &x4, int &yl, int &ys, int &ym, int &yp)
-{
-    x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    yl = blockIdx.y * blockDim.y + __builtin_amdgcn_readfirstlane(threadIdx.y);
-    if (x4 >= a.fpitch || yl >= a.ny) return false;
-    ys = yl;                                // the row of the source cells
-    if (BC == LB_BC_ZERO_GRADIENT) ys = min(max(yl, 1), a.ny - 2);
-    ym = ys - 1, yp = ys + 1;               // source rows of the cy = +1 / cy = -1 links
-    if (BC == LB_BC_PERIODIC) {
-        if (ym < 0) ym = a.ny - 1;
-        if (yp >= a.ny) yp = 0;
-    }
-    return true;
-}
-
-template <int BC>
-__device__ __forceinline__ void mc_gather(const StepArgs &a, int x4, int ys, int ym, int yp, f4a (&q)[9])
-{
-    uc4 mk;
-    gather_row<BC == LB_BC_PERIODIC ? LB_BC_PERIODIC : LB_BC_PIPE, false, false>(a, x4, ys, ym, yp, q, mk);
-    if (BC == LB_BC_ZERO_GRADIENT) pm_clamp_x(a, x4, ys, q);
-}
-
-// Launch (both): blockDim = (64, 4), grid = (ceil(fpitch / 256), ceil(ny / 4)): a wave covers 256 cells of one row (k_pm_step's launch).
 template <int BC, int NF>
 __global__ __launch_bounds__(256) void k_mc_moments(const McArgs m)
 {
     int x4, yl, ys, ym, yp;
-    if (!mc_rows<BC>(m.a[0], x4, yl, ys, ym, yp)) return;
+    if (!lane_rows<BC>(m.a[0], x4, yl, ys, ym, yp)) return;
     const long long m0 = (long long)yl * m.a[0].fpitch;
 #pragma unroll
     for (int i = 0; i < NF; ++i) {
         f4a q[9];
-        mc_gather<BC>(m.a[i], x4, ys, ym, yp, q);
-        const f4a r4 = q[0] + q[1] + q[2] + q[3] + q[4] + q[5] + q[6] + q[7] + q[8];
+        lane_gather<BC>(m.a[i], x4, ys, ym, yp, q);
+        const f4a r4 = sum9(q);
         store4<false>(lane_ptr(m.a[i].rho + m0, x4), r4);
     }
 }
 
 // Stages 2-7 of a lane's four cells of row yl for every fluid, and the stores: q = the gathered populations, nb = rho around the
-// cells (mc_load_rho's layout).  LAST: u, v, Gx, Gy of every fluid and u_b, v_b are stored as well; RHO: rho too (the one-launch
+// cells (lane_nb_load's layout).  LAST: u, v, Gx, Gy of every fluid and u_b, v_b are stored as well; RHO: rho too (the one-launch
 // step, whose rho never reached memory).  The one body of k_mc_collide and k_mc_step: they cannot differ in a bit.
 template <int NF, bool LAST, bool RHO>
 __device__ __forceinline__ void mc_collide_lane(const McArgs &m, int x4, int yl, f4a (&q)[NF][9], const float (&nb)[NF][3][6])
@@ -125,10 +66,10 @@ __device__ __forceinline__ void mc_collide_lane(const McArgs &m, int x4, int yl,
 #pragma unroll
         for (int i = 0; i < NF; ++i) {
 #pragma unroll
-            for (int k = 0; k < 9; ++k) f[i][k] = h ? q[i][k].zw : q[i][k].xy;
+            for (int k = 0; k < 9; ++k) f[i][k] = pair_of(q[i][k], h);
             mc_hydro_t<f2a>(f[i], rho[i], mx[i], my[i], u[i], v[i]);
-            Gx[i] = (h ? g4x[i].zw : g4x[i].xy) * rho[i];
-            Gy[i] = (h ? g4y[i].zw : g4y[i].xy) * rho[i];
+            Gx[i] = pair_of(g4x[i], h) * rho[i];
+            Gy[i] = pair_of(g4y[i], h) * rho[i];
         }
         for (int t = 0; t < m.n_inter; ++t) {
             const McInter it = m.inter[t];
@@ -180,10 +121,7 @@ __device__ __forceinline__ void mc_collide_lane(const McArgs &m, int x4, int yl,
     }
 #pragma unroll
     for (int i = 0; i < NF; ++i) {
-        float *d = m.a[i].dst + (long long)yl * m.a[i].pitch;
-        const long long S = m.a[i].plane;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) store4<false>(lane_ptr(d + k * S, x4), q[i][k]);
+        store_planes(m.a[i], yl, x4, q[i]);
         if (LAST) {
             if (RHO) store4<false>(lane_ptr(m.a[i].rho + m0, x4), r4[i]);
             store4<false>(lane_ptr(m.a[i].u + m0, x4), u4[i]);
@@ -200,48 +138,23 @@ template <int BC, int NF, bool LAST>
 __global__ __launch_bounds__(256) void k_mc_collide(const McArgs m)
 {
     int x4, yl, ys, ym, yp;
-    if (!mc_rows<BC>(m.a[0], x4, yl, ys, ym, yp)) return;
+    if (!lane_rows<BC>(m.a[0], x4, yl, ys, ym, yp)) return;
     f4a q[NF][9];
     float nb[NF][3][6];
 #pragma unroll
     for (int i = 0; i < NF; ++i) {
-        mc_gather<BC>(m.a[i], x4, ys, ym, yp, q[i]);
-        mc_load_rho<BC>(m.a[i].rho, m.a[0].fpitch, m.a[0].nx, m.a[0].ny, x4, yl, nb[i]);
+        lane_gather<BC>(m.a[i], x4, ys, ym, yp, q[i]);
+        lane_nb_load<BC>(m.a[i].rho, m.a[0].fpitch, m.a[0].nx, m.a[0].ny, x4, yl, nb[i]);
     }
     mc_collide_lane<NF, LAST, false>(m, x4, yl, q, nb);
 }
 
 // ---- the one-launch step ------------------------------------------------------------------------------------------------------
-// rho of the cell (x, row) of one fluid as k_mc_moments computes it, by nine 4-byte loads: ys, ym, yp as mc_rows gives them for the row
-template <int BC>
-__device__ __forceinline__ float mc_cell_rho(const StepArgs &a, int x, int ys, int ym, int yp)
-{
-    int xs = x;
-    if (BC == LB_BC_ZERO_GRADIENT) xs = min(max(x, 1), a.nx - 2);
-    int xm = xs - 1, xp = xs + 1;           // source columns of the cx = +1 / cx = -1 links
-    if (BC == LB_BC_PERIODIC) {
-        if (xm < 0) xm = a.nx - 1;
-        if (xp >= a.nx) xp = 0;
-    }
-    const long long P = a.pitch, S = a.plane;
-    const float *r0 = a.src + (long long)ys * P, *rm = a.src + (long long)ym * P, *rp = a.src + (long long)yp * P;
-    const float f0 = r0[xs], f1 = r0[1 * S + xm], f2 = rm[2 * S + xs], f3 = r0[3 * S + xp], f4 = rp[4 * S + xs];
-    const float f5 = rm[5 * S + xm], f6 = rm[6 * S + xp], f7 = rp[7 * S + xp], f8 = rp[8 * S + xm];
-    return f0 + f1 + f2 + f3 + f4 + f5 + f6 + f7 + f8;
-}
-
-// Launch: blockDim = (64, R + 2), grid = (ceil(fpitch / 256), ceil(ny / R)).  A workgroup owns R rows of a 256-cell tile.  Wave w
-// gathers the populations of row y0 - 1 + w (the rows above and below the owned ones wrapped or clamped into the box: the halo
-// rows) for every fluid and puts rho_i of its 256 cells into LDS, lane 0 and lane 1 also the cell west of the tile and the cell east
-// of its last cell in the box (wrapped, or the edge cell itself: the halo columns, nine 4-byte loads each).  After ONE barrier the
-// waves of the owned rows, whose populations stayed in registers, read rho around their cells from LDS and run mc_collide_lane; the
-// halo waves are done.  LDS: NF (R + 2) rows of MC_LDS_ROW floats, cell x of the tile at index 4 + x (16-byte aligned), the west
-// halo at 3, the east halo at 4 + (cells of the tile inside the box).
-constexpr int MC_LDS_ROW = 264;
+// (kernels_lane4.h has the plan.)  One LDS row of rho_i per fluid and row of the tile.
 template <int BC, int NF, int R, bool LAST>
 __global__ __launch_bounds__(64 * (R + 2)) void k_mc_step(const McArgs m)
 {
-    __shared__ __attribute__((aligned(16))) float lds[NF][R + 2][MC_LDS_ROW];
+    __shared__ __attribute__((aligned(16))) float lds[NF][R + 2][LANE4_LDS_ROW];
     const StepArgs &a0 = m.a[0];
     const int lane = threadIdx.x, w = __builtin_amdgcn_readfirstlane(threadIdx.y);
     const int x0 = blockIdx.x * 256, x4 = x0 + lane * 4;
@@ -268,16 +181,15 @@ __global__ __launch_bounds__(64 * (R + 2)) void k_mc_step(const McArgs m)
 #pragma unroll
     for (int i = 0; i < NF; ++i) {
         if (active) {
-            mc_gather<BC>(m.a[i], x4, ys, ym, yp, q[i]);
-            const f4a r4 = q[i][0] + q[i][1] + q[i][2] + q[i][3] + q[i][4] + q[i][5] + q[i][6] + q[i][7] + q[i][8];
-            *reinterpret_cast<f4a *>(&lds[i][w][4 + lane * 4]) = r4;
+            lane_gather<BC>(m.a[i], x4, ys, ym, yp, q[i]);
+            *reinterpret_cast<f4a *>(&lds[i][w][4 + lane * 4]) = sum9(q[i]);
         }
     }
     if (inside > 0 && lane < 2) {
         // (behind the rows' own writes: the east halo takes the slot of the first padding cell, and a wave's LDS writes land in order)
 #pragma unroll
         for (int i = 0; i < NF; ++i) {
-            const float r = mc_cell_rho<BC>(m.a[i], lane ? xe : xw, ys, ym, yp);
+            const float r = cell_rho<BC>(m.a[i], lane ? xe : xw, ys, ym, yp);
             lds[i][w][lane ? 4 + inside : 3] = r;
         }
     }
@@ -298,12 +210,13 @@ __global__ __launch_bounds__(64 * (R + 2)) void k_mc_step(const McArgs m)
 }
 
 // ---- the reference's stages, one cell per thread: grid = (ceil(nx / 256), ny) ----------------------------------------------------
+// (k_mc_forces and k_mc_bary write cell_xy out: the call moves their instruction text)
 __global__ void k_mc_hydro(const StepArgs a)
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= a.nx) return;
+    int x, y;
+    if (!cell_xy(a, x, y)) return;
     float f[9], rho, mx, my, u, v;
-    pm_load_cell(a.src + (long long)y * a.pitch + x, a.plane, f);
+    load_cell(a.src + (long long)y * a.pitch + x, a.plane, f);
     mc_hydro_t<float>(f, rho, mx, my, u, v);
     const long long o = (long long)y * a.fpitch + x;
     a.rho[o] = rho; a.u[o] = u; a.v[o] = v;
@@ -374,7 +287,7 @@ __global__ void k_mc_bary(const McArgs m)
 #pragma unroll
     for (int i = 0; i < NF; ++i) {
         float f[9];
-        pm_load_cell(m.a[i].src + (long long)y * m.a[i].pitch + x, m.a[i].plane, f);
+        load_cell(m.a[i].src + (long long)y * m.a[i].pitch + x, m.a[i].plane, f);
         mc_bary_add_t<float>(f, m.a[i].rho[o], m.e[i].Gx[o], m.e[i].Gy[o], sx, sy, rs);
     }
     const float ub = sx / rs, vb = sy / rs;
@@ -387,12 +300,12 @@ __global__ void k_mc_bary(const McArgs m)
 
 __global__ void k_mc_relax(const StepArgs a, const PmExtra e, float *fl, const float *feq)
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= a.nx) return;
+    int x, y;
+    if (!cell_xy(a, x, y)) return;
     const long long o = (long long)y * a.pitch + x, c = (long long)y * a.fpitch + x;
     float f[9], q[9];
-    pm_load_cell(fl + o, a.plane, f);
-    pm_load_cell(feq + o, a.plane, q);
+    load_cell(fl + o, a.plane, f);
+    load_cell(feq + o, a.plane, q);
     mc_relax_t<float>(e, f, q, a.omega, e.ub[c], e.vb[c], e.Gx[c], e.Gy[c]);
 #pragma unroll
     for (int k = 0; k < 9; ++k) fl[o + k * a.plane] = f[k];
@@ -402,13 +315,13 @@ template <int NF>
 __global__ void k_mc_react(const McArgs m)
 {
     const StepArgs &a = m.a[0];
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= a.nx) return;
+    int x, y;
+    if (!cell_xy(a, x, y)) return;
     const long long c = (long long)y * a.fpitch + x;
     float f[NF][9], rho[NF];
 #pragma unroll
     for (int i = 0; i < NF; ++i) {
-        pm_load_cell(m.a[i].dst + (long long)y * m.a[i].pitch + x, m.a[i].plane, f[i]);
+        load_cell(m.a[i].dst + (long long)y * m.a[i].pitch + x, m.a[i].plane, f[i]);
         rho[i] = m.a[i].rho[c];
     }
     mc_react_t<float, NF>(m, f, rho);

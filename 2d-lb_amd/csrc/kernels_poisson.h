@@ -2,10 +2,9 @@
 // poisson/solver.py:324-358 does: rho_before = rho, move + copy_buffer -> move_bcs (nine times over) -> update_hydro -> update_feq ->
 // collide_particles, six launches and six host waits per iteration, then two reductions and two host read-backs to decide whether to
 // stop).  Included by poisson.cpp only (poisson_launch.h: what the kernels, their host code and the handle share; host.h: what the other host units see).
-//   k_ps_step<RHO_ALWAYS>   the fused iteration on k_ad_step's plan (kernels_scalar.h): a lane owns four consecutive cells of a row; nine
-//                           16-byte loads (six displaced by one element: k_step's gather without a wrap), the prescribed-density rule
-//                           in registers on the lanes that hold a wall cell, one 16-byte load of the source, nine aligned 16-byte
-//                           stores.  RHO_ALWAYS (lb_solve's form): the first instruction reads the stop word and the whole grid
+//   k_ps_step<RHO_ALWAYS>   the fused iteration on the lane-of-four plan (kernels_lane4.h): the gather without a wrap, the
+//                           prescribed-density rule in registers on the lanes that hold a wall cell, one 16-byte load of the source.
+//                           RHO_ALWAYS (lb_solve's form): the first instruction reads the stop word and the whole grid
 //                           returns if it is set; the previous rho is loaded, the new one stored, and sum |rho_new - rho_old| and
 //                           sum rho_old over the workgroup's cells inside the box go to its slot of the partials: 72 + 4 + 8 + 4 = 88 B
 //                           per cell and iteration.  Otherwise (lb_run's form) no stop word, no sums, rho when the launch is the last.
@@ -18,10 +17,11 @@
 // the allocation, never used); on each wall and in each corner the three links pointing into the box become w_k R, R = -(sum of the
 // cell's five other non-rest links + (w0 - 1) rho_on_boundary) / (sum of the three weights), every right-hand side a post-stream value
 // of the same cell.  Two links per corner are neither streamed nor written and the corner's rule READS them: the handle's corner
-// state, the same eight links in the same order as LB_BC_BOX's (kernels_multifield.h).
+// state, the same eight links in the same order as LB_BC_BOX's (row_wall, kernels_lane4.h).
 #pragma once
 #include "scalar_cell.h"
 #include "poisson_launch.h"
+#include "kernels_lane4.h"
 
 namespace {
 
@@ -29,47 +29,34 @@ namespace {
 // wall = (w0 - 1) rho_on_boundary.  The five links read are summed in ascending order, as every branch of the reference does (a
 // written link contributes an exact + 0), and the three weights in ascending order of their links: 1/9 + 1/36 + 1/36 on a wall,
 // 1/9 + 1/9 + 1/36 in a corner.
-__device__ __forceinline__ void ps_box_cell(Cell &c, bool w, bool e, bool s, bool n, const float *st, float wall)
-{
-    if (s && w) { c.f6 = st[0]; c.f8 = st[1]; }
-    if (s && e) { c.f5 = st[2]; c.f7 = st[3]; }
-    if (n && w) { c.f5 = st[4]; c.f7 = st[5]; }
-    if (n && e) { c.f6 = st[6]; c.f8 = st[7]; }
-    // a link is written if it enters from outside -- except, in a corner, the two diagonals that run along the corner's other wall
-    const bool wr[9] = {false, w, s, e, n, (w || s) && !(e || n), (e || s) && !(w || n), (e || n) && !(w || s), (w || n) && !(e || s)};
-    const float f[9] = {0.f, c.f1, c.f2, c.f3, c.f4, c.f5, c.f6, c.f7, c.f8};
-    float sum = 0.f;
+struct PsBox {
+    float wall;
+    __device__ __forceinline__ void rule(Cell &c, bool w, bool e, bool s, bool n, const float *st) const
+    {
+        if (s && w) { c.f6 = st[0]; c.f8 = st[1]; }
+        if (s && e) { c.f5 = st[2]; c.f7 = st[3]; }
+        if (n && w) { c.f5 = st[4]; c.f7 = st[5]; }
+        if (n && e) { c.f6 = st[6]; c.f8 = st[7]; }
+        // a link is written if it enters from outside -- except, in a corner, the two diagonals that run along the corner's other wall
+        const bool wr[9] = {false, w, s, e, n, (w || s) && !(e || n), (e || s) && !(w || n), (e || n) && !(w || s), (w || n) && !(e || s)};
+        const float f[9] = {0.f, c.f1, c.f2, c.f3, c.f4, c.f5, c.f6, c.f7, c.f8};
+        float sum = 0.f;
 #pragma unroll
-    for (int k = 1; k < 9; ++k) sum = sum + (wr[k] ? 0.f : f[k]);
-    const float w1 = 1.f / 9.f, w2 = 1.f / 36.f;
-    const float den = ((w || e) && (s || n)) ? (w1 + w1) + w2 : (w1 + w2) + w2;
-    const float R = -(sum + wall) / den;
-    const float a1 = w1 * R, a2 = w2 * R;
-    c.f1 = wr[1] ? a1 : c.f1;
-    c.f2 = wr[2] ? a1 : c.f2;
-    c.f3 = wr[3] ? a1 : c.f3;
-    c.f4 = wr[4] ? a1 : c.f4;
-    c.f5 = wr[5] ? a2 : c.f5;
-    c.f6 = wr[6] ? a2 : c.f6;
-    c.f7 = wr[7] ? a2 : c.f7;
-    c.f8 = wr[8] ? a2 : c.f8;
-}
-
-// ... for a lane's four gathered cells (x4 .. x4+3, row y).  The caller has checked that the lane holds a wall cell.
-__device__ __forceinline__ void ps_box_row(const float *st, float wall, int nx, int ny, int x4, int y, f4a (&q)[9])
-{
-    const bool s = (y == 0), n = (y == ny - 1);
-    const int ce = nx - 1 - x4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const bool w = (x4 == 0 && j == 0), e = (j == ce);
-        if (s || n || w || e) {
-            Cell c = row_cell(q, j);
-            ps_box_cell(c, w, e, s, n, st, wall);
-            row_cell_put(q, j, c);
-        }
+        for (int k = 1; k < 9; ++k) sum = sum + (wr[k] ? 0.f : f[k]);
+        const float w1 = 1.f / 9.f, w2 = 1.f / 36.f;
+        const float den = ((w || e) && (s || n)) ? (w1 + w1) + w2 : (w1 + w2) + w2;
+        const float R = -(sum + wall) / den;
+        const float a1 = w1 * R, a2 = w2 * R;
+        c.f1 = wr[1] ? a1 : c.f1;
+        c.f2 = wr[2] ? a1 : c.f2;
+        c.f3 = wr[3] ? a1 : c.f3;
+        c.f4 = wr[4] ? a1 : c.f4;
+        c.f5 = wr[5] ? a2 : c.f5;
+        c.f6 = wr[6] ? a2 : c.f6;
+        c.f7 = wr[7] ? a2 : c.f7;
+        c.f8 = wr[8] ? a2 : c.f8;
     }
-}
+};
 
 // moment, equilibrium, relaxation and source term of a lane's four gathered cells as two pairs (scalar_cell.h, T = f2a), in place
 __device__ __forceinline__ void ps_collide_row(f4a (&q)[9], f4a s4, float omega, float react, f4a &r4)
@@ -78,10 +65,10 @@ __device__ __forceinline__ void ps_collide_row(f4a (&q)[9], f4a s4, float omega,
     for (int h = 0; h < 2; ++h) {
         f2a f[9], eq[9];
 #pragma unroll
-        for (int k = 0; k < 9; ++k) f[k] = h ? q[k].zw : q[k].xy;
+        for (int k = 0; k < 9; ++k) f[k] = pair_of(q[k], h);
         const f2a rho = ps_rho_t<f2a>(f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8]);
         ps_feq_t<f2a>(eq, rho);
-        ps_relax_t<f2a>(f, eq, omega, (h ? s4.zw : s4.xy) * lb_splat<f2a>(react));
+        ps_relax_t<f2a>(f, eq, omega, pair_of(s4, h) * lb_splat<f2a>(react));
         if (h) r4.zw = rho;
         else r4.xy = rho;
 #pragma unroll
@@ -92,7 +79,7 @@ __device__ __forceinline__ void ps_collide_row(f4a (&q)[9], f4a s4, float omega,
     }
 }
 
-// Launch: blockDim = (64, 4), grid = (ceil(fpitch / 256), ceil(ny / 4)): a wave covers 256 cells of one row (k_ad_step's launch).
+// (lane_rows and the nine stores written out: every lane reaches the reduction, so there is no early return; through store_planes the plane offsets are shared with the gather's and the instruction text moves.)
 // The two sums: a lane's four cells in order, the lanes of a wave through cross-lane moves, the four waves through LDS in index order;
 // padding lanes, rows >= ny and columns >= nx are left out by selection, not by a factor (whatever the padding of rho holds).
 template <bool RHO_ALWAYS>
@@ -105,13 +92,13 @@ __global__ __launch_bounds__(256) void k_ps_step(const StepArgs a, const PsExtra
     if (x4 < a.fpitch && yl < a.ny) {
         f4a q[9], r4;
         uc4 mk;
-        gather_row<LB_BC_PIPE, false, false>(a, x4, yl, yl - 1, yl + 1, q, mk);     // (k_step's gather without a wrap)
+        gather_row<LB_BC_PIPE, false, false>(a, x4, yl, yl - 1, yl + 1, q, mk);     // (lane_gather written out: the call moves the diagnostic build's text)
         const long long m0 = (long long)yl * a.fpitch;
         const f4a s4 = load4<false>(lane_ptr(e.source + m0, x4));
         f4a o4 = {0.f, 0.f, 0.f, 0.f};
         if (RHO_ALWAYS) o4 = load4<false>(lane_ptr((const float *)a.rho + m0, x4));
         const int ce = a.nx - 1 - x4;
-        if (yl == 0 || yl == a.ny - 1 || x4 == 0 || (ce >= 0 && ce < 4)) ps_box_row(a.corner, e.wall, a.nx, a.ny, x4, yl, q);
+        if (yl == 0 || yl == a.ny - 1 || x4 == 0 || (ce >= 0 && ce < 4)) row_wall(PsBox{e.wall}, a.corner, a.nx, a.ny, x4, yl, q);
         ps_collide_row(q, s4, a.omega, e.react, r4);
         float *d = a.dst + (long long)yl * a.pitch;
         const long long S = a.plane;
@@ -184,8 +171,8 @@ __global__ __launch_bounds__(PS_CHECK_THREADS) void k_ps_check(const float *part
 // ---- one cell per thread: grid = (ceil(nx / 256), ny) ---------------------------------------------------------------------------------
 __global__ void k_ps_gradient(const StepArgs a, float inv_two_dx)      // a.u := d rho / dx, a.v := d rho / dy
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= a.nx) return;
+    int x, y;
+    if (!cell_xy(a, x, y)) return;
     const long long o = (long long)y * a.fpitch + x;
     const float *r = a.rho + o;
     const float xp = x + 1 < a.nx ? r[1] : 0.f, xm = x >= 1 ? r[-1] : 0.f;
@@ -196,8 +183,8 @@ __global__ void k_ps_gradient(const StepArgs a, float inv_two_dx)      // a.u :=
 
 __global__ void k_ps_hydro(const StepArgs a)
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= a.nx) return;
+    int x, y;
+    if (!cell_xy(a, x, y)) return;
     const float *f = a.src + (long long)y * a.pitch + x;
     const long long S = a.plane;
     a.rho[(long long)y * a.fpitch + x] = ps_rho_t<float>(f[S], f[2 * S], f[3 * S], f[4 * S], f[5 * S], f[6 * S], f[7 * S], f[8 * S]);
@@ -205,8 +192,8 @@ __global__ void k_ps_hydro(const StepArgs a)
 
 __global__ void k_ps_feq(const StepArgs a, float *feq)
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= a.nx) return;
+    int x, y;
+    if (!cell_xy(a, x, y)) return;
     float e[9];
     ps_feq_t<float>(e, a.rho[(long long)y * a.fpitch + x]);
     float *o = feq + (long long)y * a.pitch + x;
@@ -214,6 +201,7 @@ __global__ void k_ps_feq(const StepArgs a, float *feq)
     for (int k = 0; k < 9; ++k) o[k * a.plane] = e[k];
 }
 
+// (cell_xy written out: the call moves the instruction text)
 __global__ void k_ps_collide(const StepArgs a, float *f, const float *feq, const float *source, float react)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
@@ -227,31 +215,8 @@ __global__ void k_ps_collide(const StepArgs a, float *f, const float *feq, const
     for (int k = 0; k < 9; ++k) f[o + k * a.plane] = c[k];
 }
 
-// move_bcs of one lattice, in place behind lb_move: one thread per index i, grid = ceil(max(nx, ny) / 256): the cells (i, 0) and
-// (i, ny-1) of the wall rows, (0, i) and (nx-1, i) of the wall columns between them (k_mf_move_bcs's plan).  The two links per corner
-// that the rule reads but never writes are what the lattice holds (lb_move has patched the corner state in).
-__device__ __forceinline__ void ps_bcs_cell(const StepArgs &a, float *f, float wall, int x, int y)
-{
-    float *p = f + (long long)y * a.pitch + x;
-    const long long S = a.plane;
-    Cell c = {p[0], p[S], p[2 * S], p[3 * S], p[4 * S], p[5 * S], p[6 * S], p[7 * S], p[8 * S]};
-    const float own[8] = {c.f6, c.f8, c.f5, c.f7, c.f5, c.f7, c.f6, c.f8};
-    ps_box_cell(c, x == 0, x == a.nx - 1, y == 0, y == a.ny - 1, own, wall);
-    p[S] = c.f1; p[2 * S] = c.f2; p[3 * S] = c.f3; p[4 * S] = c.f4;
-    p[5 * S] = c.f5; p[6 * S] = c.f6; p[7 * S] = c.f7; p[8 * S] = c.f8;
-}
-
-__global__ void k_ps_move_bcs(const StepArgs a, float *f, float wall)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < a.nx) {
-        ps_bcs_cell(a, f, wall, i, 0);
-        ps_bcs_cell(a, f, wall, i, a.ny - 1);
-    }
-    if (i >= 1 && i <= a.ny - 2) {
-        ps_bcs_cell(a, f, wall, 0, i);
-        ps_bcs_cell(a, f, wall, a.nx - 1, i);
-    }
-}
+// move_bcs of one lattice, in place behind lb_move (edge_walk, kernels_lane4.h).  The two links per corner that the rule reads but
+// never writes are what the lattice holds (lb_move has patched the corner state in).
+__global__ void k_ps_move_bcs(const StepArgs a, float *f, float wall) { edge_walk(a, f, BoxEdge<PsBox>{{wall}}); }
 
 }  // namespace

@@ -7,11 +7,9 @@
 // the surfactant (MODE = LB_ROCKET_FLOW) or the sum of two stencil forces (LB_ROCKET_FORCES), so the step is NOT local to the cell
 // after streaming: it reads two OPERANDS at the eight neighbours -- A from rho_c (FLOW: rho_c itself; FORCES: S(rho_c)) and B from
 // rho_p (FLOW: psi(rho_p); FORCES: rho_p itself).  Three forms, bitwise equal (one body, ry_collide_lane, and rocket_cell.h):
-//   k_ry_step<MODE, R, LAST>     one launch per step: a workgroup of R + 2 waves owns R rows of a 256-cell tile; every wave gathers one
-//                                row of both lattices (a lane owns four consecutive cells: 16-byte loads), the two extra ones the rows
-//                                above and below, and puts A and B of its 256 cells into LDS with one halo cell left and right; after
-//                                ONE barrier the R owned rows, their populations still in registers, run stages 3-5 and store.
-//                                72 (R + 2) / R B read + 72 B written per cell.
+// All three are on the lane-of-four plan, and the first on its one-launch form, of kernels_lane4.h:
+//   k_ry_step<MODE, R, LAST>     one launch per step: every wave gathers one row of both lattices and puts A and B of its 256 cells into
+//                                LDS; the R owned rows run stages 3-5 and store.  72 (R + 2) / R B read + 72 B written per cell.
 //   k_ry_moments                 the two-launch form: the gather, sums only, stores rho_p and rho_c: 72 B read, 8 B written per cell
 //   k_ry_collide<MODE, LAST>     gathers again, reads both densities of the three rows around the cell (wrap on the INDEX), forms the
 //                                operands and runs stages 3-5; LAST (a run's last step): u, v, psi / S and the forces as well
@@ -19,69 +17,25 @@
 //                                update_feq are the scalar lattice's k_move, k_ad_hydro and k_ad_feq: the same operations)
 #pragma once
 #include "rocket_cell.h"
+#include "kernels_lane4.h"
 
 namespace {
 
-// one density around a lane's four cells: nb[row][col], row 0 = y - 1, col 0 = x4 - 1 ... col 5 = x4 + 4 (mc_load_rho's layout,
-// kernels_multifluid.h, periodic).  Every index is inside the box; cells past nx-1 (row padding) get in-bounds values nobody uses.
-__device__ __forceinline__ void ry_load_rho(const float *rho, int fpitch, int nx, int ny, int x4, int yl, float (&nb)[3][6])
-{
-    const int c = nx - 1 - x4;
-    int xl = x4 - 1, xr = x4 + 4;
-    if (xl < 0) xl = nx - 1;
-    if (xr >= nx) xr = 0;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        int y = yl - 1 + r;
-        if (y < 0) y = ny - 1;
-        if (y >= ny) y = 0;
-        const float *row = rho + (long long)y * fpitch;
-        const f4a v = load4<false>(lane_ptr(row, x4));
-        const float w = row[xl], e = row[xr];
-        nb[r][0] = w;
-        nb[r][1] = v.x;
-        nb[r][2] = c == 0 ? e : v.y;        // the east neighbour of the cell nx-1, where that cell is not the lane's last: the wrapped cell
-        nb[r][3] = c == 1 ? e : v.z;
-        nb[r][4] = c == 2 ? e : v.w;
-        nb[r][5] = e;
-    }
-}
-
-__device__ __forceinline__ void ry_gather(const StepArgs &a, int x4, int ys, int ym, int yp, f4a (&q)[9])
-{
-    uc4 mk;
-    gather_row<LB_BC_PERIODIC, false, false>(a, x4, ys, ym, yp, q, mk);
-}
-
-__device__ __forceinline__ f4a ry_sum(const f4a (&q)[9]) { return q[0] + q[1] + q[2] + q[3] + q[4] + q[5] + q[6] + q[7] + q[8]; }
-
-// Launch (moments, collide): blockDim = (64, 4), grid = (ceil(fpitch / 256), ceil(ny / 4)): a wave covers 256 cells of one row.
-__device__ __forceinline__ bool ry_rows(const StepArgs &a, int &x4, int &yl, int &ym, int &yp)
-{
-    x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    yl = blockIdx.y * blockDim.y + __builtin_amdgcn_readfirstlane(threadIdx.y);
-    if (x4 >= a.fpitch || yl >= a.ny) return false;
-    ym = yl - 1, yp = yl + 1;               // source rows of the cy = +1 / cy = -1 links
-    if (ym < 0) ym = a.ny - 1;
-    if (yp >= a.ny) yp = 0;
-    return true;
-}
-
 __global__ __launch_bounds__(256) void k_ry_moments(const RyArgs m)
 {
-    int x4, yl, ym, yp;
-    if (!ry_rows(m.a[0], x4, yl, ym, yp)) return;
+    int x4, yl, ys, ym, yp;
+    if (!lane_rows<LB_BC_PERIODIC>(m.a[0], x4, yl, ys, ym, yp)) return;
     const long long m0 = (long long)yl * m.a[0].fpitch;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         f4a q[9];
-        ry_gather(m.a[i], x4, yl, ym, yp, q);
-        store4<false>(lane_ptr(m.a[i].rho + m0, x4), ry_sum(q));
+        lane_gather<LB_BC_PERIODIC>(m.a[i], x4, ys, ym, yp, q);
+        store4<false>(lane_ptr(m.a[i].rho + m0, x4), sum9(q));
     }
 }
 
 // Stages 2-5 of a lane's four cells of row yl for both lattices, and the stores: q = the gathered populations, na / nb = the operands A
-// and B around the cells (ry_load_rho's layout).  LAST: u, v (to both members), psi / S and the forces are stored as well; RHO: both
+// and B around the cells (lane_nb_load's layout).  LAST: u, v (to both members), psi / S and the forces are stored as well; RHO: both
 // densities too (the one-launch step, whose densities never reached memory).  The one body of k_ry_collide and k_ry_step.
 template <int MODE, bool LAST, bool RHO>
 __device__ __forceinline__ void ry_collide_lane(const RyArgs &m, int x4, int yl, f4a (&q)[2][9], const float (&na)[3][6], const float (&nb)[3][6])
@@ -93,8 +47,8 @@ __device__ __forceinline__ void ry_collide_lane(const RyArgs &m, int x4, int yl,
         f2a fp[9], fc[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
-            fp[k] = h ? q[0][k].zw : q[0][k].xy;
-            fc[k] = h ? q[1][k].zw : q[1][k].xy;
+            fp[k] = pair_of(q[0][k], h);
+            fc[k] = pair_of(q[1][k], h);
         }
         const f2a rho_p = ad_rho_t<f2a>(fp[0], fp[1], fp[2], fp[3], fp[4], fp[5], fp[6], fp[7], fp[8]);
         const f2a rho_c = ad_rho_t<f2a>(fc[0], fc[1], fc[2], fc[3], fc[4], fc[5], fc[6], fc[7], fc[8]);
@@ -132,10 +86,7 @@ __device__ __forceinline__ void ry_collide_lane(const RyArgs &m, int x4, int yl,
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        float *d = m.a[i].dst + (long long)yl * m.a[i].pitch;
-        const long long S = m.a[i].plane;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) store4<false>(lane_ptr(d + k * S, x4), q[i][k]);
+        store_planes(m.a[i], yl, x4, q[i]);
         if (LAST) {
             if (RHO) store4<false>(lane_ptr(m.a[i].rho + m0, x4), i ? rc4 : rp4);
             store4<false>(lane_ptr(m.a[i].u + m0, x4), u4);
@@ -156,14 +107,14 @@ __device__ __forceinline__ void ry_collide_lane(const RyArgs &m, int x4, int yl,
 template <int MODE, bool LAST>
 __global__ __launch_bounds__(256) void k_ry_collide(const RyArgs m)
 {
-    int x4, yl, ym, yp;
-    if (!ry_rows(m.a[0], x4, yl, ym, yp)) return;
+    int x4, yl, ys, ym, yp;
+    if (!lane_rows<LB_BC_PERIODIC>(m.a[0], x4, yl, ys, ym, yp)) return;
     f4a q[2][9];
     float na[3][6], nb[3][6];
-    ry_gather(m.a[0], x4, yl, ym, yp, q[0]);
-    ry_gather(m.a[1], x4, yl, ym, yp, q[1]);
-    ry_load_rho(m.a[1].rho, m.a[0].fpitch, m.a[0].nx, m.a[0].ny, x4, yl, na);
-    ry_load_rho(m.a[0].rho, m.a[0].fpitch, m.a[0].nx, m.a[0].ny, x4, yl, nb);
+    lane_gather<LB_BC_PERIODIC>(m.a[0], x4, ys, ym, yp, q[0]);
+    lane_gather<LB_BC_PERIODIC>(m.a[1], x4, ys, ym, yp, q[1]);
+    lane_nb_load<LB_BC_PERIODIC>(m.a[1].rho, m.a[0].fpitch, m.a[0].nx, m.a[0].ny, x4, yl, na);
+    lane_nb_load<LB_BC_PERIODIC>(m.a[0].rho, m.a[0].fpitch, m.a[0].nx, m.a[0].ny, x4, yl, nb);
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -174,33 +125,12 @@ __global__ __launch_bounds__(256) void k_ry_collide(const RyArgs m)
     ry_collide_lane<MODE, LAST, false>(m, x4, yl, q, na, nb);
 }
 
-// ---- the one-launch step ------------------------------------------------------------------------------------------------------
-// the density of the cell (x, row) of one lattice as k_ry_moments computes it, by nine 4-byte loads: ys, ym, yp the row and the source
-// rows of its cy = +1 / cy = -1 links
-__device__ __forceinline__ float ry_cell_rho(const StepArgs &a, int x, int ys, int ym, int yp)
-{
-    int xm = x - 1, xp = x + 1;             // source columns of the cx = +1 / cx = -1 links
-    if (xm < 0) xm = a.nx - 1;
-    if (xp >= a.nx) xp = 0;
-    const long long P = a.pitch, S = a.plane;
-    const float *r0 = a.src + (long long)ys * P, *rm = a.src + (long long)ym * P, *rp = a.src + (long long)yp * P;
-    const float f0 = r0[x], f1 = r0[1 * S + xm], f2 = rm[2 * S + x], f3 = r0[3 * S + xp], f4 = rp[4 * S + x];
-    const float f5 = rm[5 * S + xm], f6 = rm[6 * S + xp], f7 = rp[7 * S + xp], f8 = rp[8 * S + xm];
-    return f0 + f1 + f2 + f3 + f4 + f5 + f6 + f7 + f8;
-}
-
-// Launch: blockDim = (64, R + 2), grid = (ceil(fpitch / 256), ceil(ny / R)).  A workgroup owns R rows of a 256-cell tile.  Wave w gathers
-// the populations of row y0 - 1 + w (the rows above and below the owned ones wrapped into the box: the halo rows) of both lattices and
-// puts the operands A and B of its 256 cells into LDS, lane 0 and lane 1 also those of the cell west of the tile and of the cell east
-// of its last cell in the box (wrapped: the halo columns, nine 4-byte loads per lattice).  After ONE barrier the waves of the owned
-// rows, whose populations stayed in registers, read the operands around their cells from LDS and run ry_collide_lane; the halo waves
-// are done.  LDS: 2 (R + 2) rows of RY_LDS_ROW floats, cell x of the tile at index 4 + x (16-byte aligned), the west halo at 3, the east
-// halo at 4 + (cells of the tile inside the box).
-constexpr int RY_LDS_ROW = 264;
+// ---- the one-launch step (kernels_lane4.h has the plan and the LDS row) -----------------------------------------------------------
+// What a wave puts into LDS is not a density but the operands A and B of its cells: two LDS rows per row of the tile.
 template <int MODE, int R, bool LAST>
 __global__ __launch_bounds__(64 * (R + 2)) void k_ry_step(const RyArgs m)
 {
-    __shared__ __attribute__((aligned(16))) float lds[2][R + 2][RY_LDS_ROW];
+    __shared__ __attribute__((aligned(16))) float lds[2][R + 2][LANE4_LDS_ROW];
     const StepArgs &a0 = m.a[0];
     const int lane = threadIdx.x, w = __builtin_amdgcn_readfirstlane(threadIdx.y);
     const int x0 = blockIdx.x * 256, x4 = x0 + lane * 4;
@@ -219,9 +149,9 @@ __global__ __launch_bounds__(64 * (R + 2)) void k_ry_step(const RyArgs m)
     if (xe >= a0.nx) xe = 0;
     f4a q[2][9];
     if (active) {
-        ry_gather(m.a[0], x4, yl, ym, yp, q[0]);
-        ry_gather(m.a[1], x4, yl, ym, yp, q[1]);
-        const f4a rp = ry_sum(q[0]), rc = ry_sum(q[1]);
+        lane_gather<LB_BC_PERIODIC>(m.a[0], x4, yl, ym, yp, q[0]);
+        lane_gather<LB_BC_PERIODIC>(m.a[1], x4, yl, ym, yp, q[1]);
+        const f4a rp = sum9(q[0]), rc = sum9(q[1]);
         f4a A, B;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -234,7 +164,7 @@ __global__ __launch_bounds__(64 * (R + 2)) void k_ry_step(const RyArgs m)
     if (inside > 0 && lane < 2) {
         // (behind the rows' own writes: the east halo takes the slot of the first padding cell, and a wave's LDS writes land in order)
         const int xh = lane ? xe : xw;
-        const float rc = ry_cell_rho(m.a[1], xh, yl, ym, yp), rp = ry_cell_rho(m.a[0], xh, yl, ym, yp);
+        const float rc = cell_rho<LB_BC_PERIODIC>(m.a[1], xh, yl, ym, yp), rp = cell_rho<LB_BC_PERIODIC>(m.a[0], xh, yl, ym, yp);
         lds[0][w][lane ? 4 + inside : 3] = ry_op_a<MODE>(m, rc);
         lds[1][w][lane ? 4 + inside : 3] = ry_op_b<MODE>(m, rp);
     }
@@ -275,8 +205,8 @@ template <int MODE>
 __global__ void k_ry_velocity(const RyArgs m)
 {
     const StepArgs &a = m.a[0];
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= a.nx) return;
+    int x, y;
+    if (!cell_xy(a, x, y)) return;
     const long long o = (long long)y * a.fpitch + x;
     float u, v;
     if (MODE == LB_ROCKET_FLOW) {
@@ -296,8 +226,8 @@ template <int MODE>
 __global__ void k_ry_forces(const RyArgs m)
 {
     const StepArgs &a = m.a[0];
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= a.nx) return;
+    int x, y;
+    if (!cell_xy(a, x, y)) return;
     const long long o = (long long)y * a.fpitch + x;
     float pb[3][3], Fx, Fy;
     ry_operand_3x3<MODE, 1>(m, x, y, pb);
@@ -321,8 +251,8 @@ template <int MODE>
 __global__ void k_ry_relax(const RyArgs m, const float *feq_p, const float *feq_c)
 {
     const StepArgs &a = m.a[0];
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= a.nx) return;
+    int x, y;
+    if (!cell_xy(a, x, y)) return;
     const long long o = (long long)y * a.pitch + x, c = (long long)y * a.fpitch + x, S = a.plane;
     float *fp = m.a[0].dst + o, *fc = m.a[1].dst + o;
     float f[9], e[9];

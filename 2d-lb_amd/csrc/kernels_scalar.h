@@ -2,10 +2,9 @@
 // reaction_diffusion/diffusion.py:365-380 does: move + copy_buffer -> move_bcs (`pass`) -> update_hydro_diffusion ->
 // update_feq_diffusion -> collide_particles[_fisher], five launches and five host waits per step).  Included by scalar.cpp only: its
 // plain kernels must be emitted by exactly one translation unit (scalar_launch.h: what the kernels and their host code share; host.h: what the other host units see).
-//   k_ad_step<BC, REACT, RHO>   the fused step: pull-stream, rho = sum f, linear equilibrium with the imposed u, v, relaxation
-//                               [+ growth term]; a lane owns four consecutive cells of one row: nine 16-byte loads (six displaced
-//                               by one element: k_step's gather), one 16-byte load each of u and v, nine aligned 16-byte stores,
-//                               rho when asked: 72 B + 8 B per cell and step.  The fused multi-step kernel is held to it bitwise.
+//   k_ad_step<BC, REACT, RHO>   the fused step on the lane-of-four plan (kernels_lane4.h): pull-stream, rho = sum f, linear equilibrium
+//                               with the imposed u, v, relaxation [+ growth term]; one 16-byte load each of u and v beside the
+//                               gather, rho when asked: 72 B + 8 B per cell and step.  The fused multi-step kernel is held to it bitwise.
 //   k_ad_tile4<BC, REACT, RHO, TW, TH, CPT>   four steps per launch in LDS tiles on the plan of k_tile4 (kernels_tile.h), the region's
 //                               u, v loaded once for all four; same cell arithmetic (scalar_cell.h): bitwise equal to four k_ad_step
 //   k_ad_hydro, k_ad_feq, k_ad_collide<REACT>   the reference's phases one by one (API / test parity; lb_move is k_move + copy).  They
@@ -19,6 +18,7 @@
 #pragma once
 #include "scalar_cell.h"
 #include "scalar_launch.h"
+#include "kernels_lane4.h"
 #include "kernels_tile.h"       // TileShape, xcd_band_tile
 
 namespace {
@@ -63,8 +63,8 @@ __device__ __forceinline__ void ad_collide_row(f4a (&q)[9], f4a u4, f4a v4, floa
     for (int h = 0; h < 2; ++h) {
         f2a f[9];
 #pragma unroll
-        for (int k = 0; k < 9; ++k) f[k] = h ? q[k].zw : q[k].xy;
-        const f2a ux = h ? u4.zw : u4.xy, uy = h ? v4.zw : v4.xy;
+        for (int k = 0; k < 9; ++k) f[k] = pair_of(q[k], h);
+        const f2a ux = pair_of(u4, h), uy = pair_of(v4, h);
         const f2a rho = ad_rho_t<f2a>(f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8]);
         ad_relax_t<f2a, REACT>(f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], omega, G, rho, ux, uy);
         if (h) r4.zw = rho;
@@ -77,7 +77,8 @@ __device__ __forceinline__ void ad_collide_row(f4a (&q)[9], f4a u4, f4a v4, floa
     }
 }
 
-// Launch: blockDim = (64, 4), grid = (ceil(fpitch / 256), ceil(ny / 4)): a wave covers 256 cells of one row.
+// (lane_rows and the nine stores written out: through the calls the diagnostic build's OPEN form is scheduled differently, the plane
+// offsets are shared with the gather's, and the instruction text moves)
 template <int BC, bool REACT, bool RHO>
 __global__ __launch_bounds__(256) void k_ad_step(const StepArgs a, const AdExtra e)
 {
@@ -90,9 +91,7 @@ __global__ __launch_bounds__(256) void k_ad_step(const StepArgs a, const AdExtra
         if (yp >= a.ny) yp = 0;
     }
     f4a q[9], r4;
-    uc4 mk;
-    // (k_step's gather; its PIPE form is the one without a wrap in x)
-    gather_row<BC == LB_BC_PERIODIC ? LB_BC_PERIODIC : LB_BC_PIPE, false, false>(a, x4, yl, ym, yp, q, mk);
+    lane_gather<BC>(a, x4, yl, ym, yp, q);
     if (BC == LB_BC_OPEN) ad_edge_gather(e.edge, a.fpitch, a.nx, a.ny, x4, yl, q);
     const long long m0 = (long long)yl * a.fpitch;
     const f4a u4 = load4<false>(lane_ptr((const float *)a.u + m0, x4));
@@ -207,8 +206,8 @@ __global__ __launch_bounds__((TileShape<TW, TH, CPT>::THREADS)) void k_ad_tile4(
 // ---- the reference's phases, one cell per thread: grid = (ceil(nx / 256), ny) ---------------------------------------------------
 __global__ void k_ad_hydro(const StepArgs a)                    // D2Q9_diffusion.cl:41-68: rho only; u, v are imposed
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= a.nx) return;
+    int x, y;
+    if (!cell_xy(a, x, y)) return;
     const float *f = a.src + (long long)y * a.pitch + x;
     const long long S = a.plane;
     a.rho[(long long)y * a.fpitch + x] = ad_rho_t<float>(f[0], f[S], f[2 * S], f[3 * S], f[4 * S], f[5 * S], f[6 * S], f[7 * S], f[8 * S]);
@@ -216,8 +215,8 @@ __global__ void k_ad_hydro(const StepArgs a)                    // D2Q9_diffusio
 
 __global__ void k_ad_feq(const StepArgs a, float *feq)         // :1-38
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= a.nx) return;
+    int x, y;
+    if (!cell_xy(a, x, y)) return;
     const long long m = (long long)y * a.fpitch + x;
     float e[9];
     ad_feq_cell(e, a.rho[m], a.u[m], a.v[m]);
@@ -229,11 +228,10 @@ __global__ void k_ad_feq(const StepArgs a, float *feq)         // :1-38
 template <bool REACT>
 __global__ void k_ad_collide(const StepArgs a, float *f, const float *feq, float G)     // :70-93, :95-124
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x >= a.nx) return;
+    int x, y;
+    if (!cell_xy(a, x, y)) return;
     const long long o = (long long)y * a.pitch + x;
     const float keep = 1.f - a.omega;
-    const float w[9] = {4.f / 9.f, 1.f / 9.f, 1.f / 9.f, 1.f / 9.f, 1.f / 9.f, 1.f / 36.f, 1.f / 36.f, 1.f / 36.f, 1.f / 36.f};
     float react = 0.f;
     if (REACT) {
         const float rho = a.rho[(long long)y * a.fpitch + x];
@@ -242,7 +240,7 @@ __global__ void k_ad_collide(const StepArgs a, float *f, const float *feq, float
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
         float v = lb_fma(f[o + k * a.plane], keep, a.omega * feq[o + k * a.plane]);
-        if (REACT) v = lb_fma(w[k], react, v);
+        if (REACT) v = lb_fma(lb_w9(k), react, v);
         f[o + k * a.plane] = v;
     }
 }

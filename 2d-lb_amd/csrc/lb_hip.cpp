@@ -210,7 +210,7 @@ static int frozen_links(lb_sim *s, int which, bool patch)
         const int X = s->p.nx - 1, Y = s->p.ny - 1;
         struct Link { int k, x, y; };
         const Link vel[8] = {{1, 0, 0}, {8, 0, 0}, {1, 0, Y}, {5, 0, Y}, {3, X, 0}, {7, X, 0}, {3, X, Y}, {6, X, Y}};   // (bc_vel_cell's order)
-        const Link box[8] = {{6, 0, 0}, {8, 0, 0}, {5, X, 0}, {7, X, 0}, {5, 0, Y}, {7, 0, Y}, {6, X, Y}, {8, X, Y}};   // (mf_box_cell's and ps_box_cell's order)
+        const Link box[8] = {{6, 0, 0}, {8, 0, 0}, {5, X, 0}, {7, X, 0}, {5, 0, Y}, {7, 0, Y}, {6, X, Y}, {8, X, Y}};   // (MfBox's and PsBox's order)
         const Link *c = s->p.bc_mode == LB_BC_VELOCITY_INLET ? vel : box;
         for (int i = 0; i < 8; ++i) {
             float *in_lat = s->origin(which) + c[i].k * s->plane + (long long)c[i].y * s->rowp + c[i].x, *kept = s->vi_corner + i;
