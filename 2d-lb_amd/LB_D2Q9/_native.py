@@ -108,6 +108,11 @@ SIGNATURES = {
     "lb_autotune": ([_h],), "lb_autotune_quick": ([_h, _I],), "lb_copy_calibration": ([_h, _I, _i64p],),
     "lb_set_variant": ([_h, _I],), "lb_set_slab_cycle": ([_h, _I],), "lb_set_exchange_inline": ([_h, _I],),
     "lb_exchange_timing": ([_h, _I],), "lb_exchange_stats": ([_h, _i64p, _dp, _dp, _ip, _ip],),
+    # the spectral screened-Poisson solver (an lb_spectral is not a handle kind; which: 0 charge, 1 xgrad, 2 ygrad)
+    "lb_spectral_create": ([_I, _I, _I, _D, _hp],), "lb_spectral_destroy": ([_h],), "lb_spectral_set_lambda": ([_h, _D],),
+    "lb_spectral_set": ([_h, _I, _vp, _I],), "lb_spectral_get": ([_h, _I, _vp],),
+    "lb_spectral_transform": ([_h, _I, _I],), "lb_spectral_screen": ([_h],), "lb_spectral_grad_multiply": ([_h],),
+    "lb_spectral_solve": ([_h],), "lb_spectral_velocity": ([_h, _h, _F, _I],), "lb_run_screened": ([_h, _h, _F, _I],),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -9,10 +9,12 @@
 //                  checks, then the kind's row), the flow kind's row, lb_run_batch, what set calls share, lb_check, timers
 //   scalar.cpp, multifield.cpp, poisson.cpp, porous.cpp, multifluid.cpp, rocket.cpp
 //                  one handle kind each: its kernels, their launches, its row of the kind table, its own entry points of the C ABI
+//   spectral.cpp   the spectral screened-Poisson solver (lb_spectral_*: not a handle kind) and its coupling to a scalar lattice;
+//                  spectral_plan.cpp its plan (spectral_plan.h): no HIP
 // Small kernels are emitted by the one unit that includes their header: kernels_phases.h + kernels_check.h by lb_hip.cpp,
 // kernels_halo.h by slab.cpp, kernels_scalar.h by scalar.cpp (its health check's first pass only: check_reduce.h is shared, the folding
 // pass is lb_hip.cpp's), kernels_multifield.h by multifield.cpp, kernels_poisson.h by poisson.cpp, kernels_porous.h by porous.cpp,
-// kernels_multifluid.h by multifluid.cpp, kernels_rocket.h by rocket.cpp.  The six kind headers share kernels_lane4.h, the plan their
+// kernels_multifluid.h by multifluid.cpp, kernels_rocket.h by rocket.cpp, kernels_spectral.h by spectral.cpp.  The six kind headers share kernels_lane4.h, the plan their
 // fused steps follow: device functions only, no kernel of its own.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -281,6 +283,10 @@ int run_whole_grid(lb_sim *s, int n_steps, bool final_macro = true);
 // the un-fused phases the coupled lattices and the colonies share with the scalar lattice: rho = sum f; feq from rho, u, v
 int scalar_hydro(lb_sim *s);
 int scalar_feq(lb_sim *s);
+// what spectral.cpp steps a scalar lattice (LB_SEM_DIFFUSION) with: the density after streaming into s->rho, nothing moved
+// (k_ad_moments); one k_ad_step with the velocity u, v hold now
+int scalar_moments(lb_sim *s);
+int scalar_step(lb_sim *s, bool store_rho);
 // OPEN: the edge state copied out of (k_ad_edge_capture) / patch: written back into (k_ad_edge_patch) the lattice at `f`
 void lbk_ad_edge(bool patch, hipStream_t st, const StepArgs &a, float *f, float *edge);
 // the health check's first pass over the lattice at a.src and the fields a.u, a.v: one record per workgroup, ad_check_blocks(a) of

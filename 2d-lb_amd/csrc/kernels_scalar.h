@@ -104,6 +104,32 @@ __global__ __launch_bounds__(256) void k_ad_step(const StepArgs a, const AdExtra
     if (RHO) store4<false>(lane_ptr(a.rho + m0, x4), r4);
 }
 
+// The density the populations will have after streaming -- k_ad_step's gather and sum, the same bits -- stored in rho; nothing moves.
+// For a velocity that is a function of that density (lb_spectral_velocity, lb_run_screened: spectral.cpp).
+template <int BC>
+__global__ __launch_bounds__(256) void k_ad_moments(const StepArgs a, const AdExtra e)
+{
+    const int x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const int yl = blockIdx.y * blockDim.y + __builtin_amdgcn_readfirstlane(threadIdx.y);
+    if (x4 >= a.fpitch || yl >= a.ny) return;
+    int ym = yl - 1, yp = yl + 1;
+    if (BC == LB_BC_PERIODIC) {
+        if (ym < 0) ym = a.ny - 1;
+        if (yp >= a.ny) yp = 0;
+    }
+    f4a q[9], r4;
+    lane_gather<BC>(a, x4, yl, ym, yp, q);
+    if (BC == LB_BC_OPEN) ad_edge_gather(e.edge, a.fpitch, a.nx, a.ny, x4, yl, q);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const f2a rho = ad_rho_t<f2a>(pair_of(q[0], h), pair_of(q[1], h), pair_of(q[2], h), pair_of(q[3], h), pair_of(q[4], h),
+                                      pair_of(q[5], h), pair_of(q[6], h), pair_of(q[7], h), pair_of(q[8], h));
+        if (h) r4.zw = rho;
+        else r4.xy = rho;
+    }
+    store4<false>(lane_ptr(a.rho + (long long)yl * a.fpitch, x4), r4);
+}
+
 // ---- four time steps per launch in LDS tiles -----------------------------------------------------------------------------------------
 // k_tile4's plan (kernels_tile.h): a workgroup loads a region -- a TW x TH tile + TILE_T halo cells a side -- of the nine planes AND of
 // u, v into LDS once, steps it four times there -- after step s the outermost s rings are stale and no longer computed --, and stores

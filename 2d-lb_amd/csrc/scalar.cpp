@@ -94,7 +94,25 @@ int run_scalar(lb_sim *s, int n_steps)
 int scalar_hydro(lb_sim *s) { return launch_phase(s, grid_cells(s), k_ad_hydro); }       // rho only: u, v are imposed
 int scalar_feq(lb_sim *s) { return launch_phase(s, grid_cells(s), k_ad_feq, s->feq_origin()); }
 
-void lbk_ad_edge(bool patch, hipStream_t st, const StepArgs &a, float *f, float *edge)
+int scalar_moments(lb_sim *s)
+{
+    const StepArgs a = step_args(s, 0, 1, s->H);
+    const AdExtra e = AdExtra{s->ad_edge, s->ad_G};
+    if (s->p.bc_mode == LB_BC_PERIODIC) hipLaunchKernelGGL(k_ad_moments<LB_BC_PERIODIC>, step_grid(a), dim3(64, 4), 0, s->stream, a, e);
+    else hipLaunchKernelGGL(k_ad_moments<LB_BC_OPEN>, step_grid(a), dim3(64, 4), 0, s->stream, a, e);
+    HIP_TRY(hipGetLastError());
+    return LB_OK;
+}
+
+int scalar_step(lb_sim *s, bool store_rho)
+{
+    ad_step(s->p.bc_mode, s->ad_G != 0.f, store_rho, s->stream, step_args(s, 0, 1, s->H), AdExtra{s->ad_edge, s->ad_G});
+    HIP_TRY(hipGetLastError());
+    s->cur ^= 1;
+    return LB_OK;
+}
+
+void lbk_ad_edge(bool patch,hipStream_t st, const StepArgs &a, float *f, float *edge)
 {
     const int n = std::max(patch ? a.nx : a.fpitch, a.ny);      // (the capture takes the rows' padding along)
     if (patch) hipLaunchKernelGGL(k_ad_edge_patch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, f, (const float *)edge);

@@ -683,6 +683,44 @@ int lb_set_exchange_inline(lb_sim *s, int on);
 int lb_exchange_timing(lb_sim *s, int enable);
 int lb_exchange_stats(lb_sim *s, int64_t *n_exchanges, double *total_ms, double *max_ms, int *cycle_depth, int *band_rows);
 
+/* ---- the spectral screened-Poisson solver (the reference's spectral_poisson/screened_poisson.py: gpyfft plans and whole-array
+ *      passes with a host wait behind each; reaction_diffusion/screened_poisson_waves.py couples it to a scalar lattice) ------------
+ * An lb_spectral is NOT a handle kind (no semantics value, no lb_create): a periodic nx x ny box of complex float32, three arrays --
+ * charge, xgrad, ygrad -- laid out [ny][nx], interleaved (re, im), and a screening length lambda.  It solves
+ * (1 - lambda^2 laplace) phi = charge and returns grad phi, with the reference's conventions: wave indices are the integers of
+ * numpy's fftfreq (the Nyquist index of an even axis is -n/2), the gradient multipliers are 2 pi i kx and 2 pi i ky, the inverse
+ * carries 1 / (nx ny).  Each axis has 1 ... 4096 points and no prime factor other than 2, 3 and 5; any other length is refused with
+ * LB_ERR_ARG before a device is touched.  The transform is the library's own (LDS Stockham passes of radix 5, 3, 4, 2; csrc/
+ * kernels_spectral.h); work is enqueued on the solver's own stream, lb_spectral_get waits for it. */
+typedef struct lb_spectral lb_spectral;
+typedef enum { LB_SPECTRAL_CHARGE = 0, LB_SPECTRAL_XGRAD = 1, LB_SPECTRAL_YGRAD = 2 } lb_spectral_array;
+int lb_spectral_create(int nx, int ny, int device, double lam, lb_spectral **out);
+int lb_spectral_destroy(lb_spectral *sp);
+int lb_spectral_set_lambda(lb_spectral *sp, double lam);
+/* re_im: 2 nx ny floats on the host, or (on_device != 0) on the solver's device */
+int lb_spectral_set(lb_spectral *sp, int which, const float *re_im, int on_device);
+int lb_spectral_get(lb_spectral *sp, int which, float *re_im);
+/* The phases of the reference, one by one.  lb_spectral_transform: the 2-D transform of one array in place (forward: rows, then
+ * columns; inverse: columns, then rows and 1 / (nx ny)).  lb_spectral_screen: charge /= lambda^2 (kx^2 + ky^2) + 1.
+ * lb_spectral_grad_multiply: xgrad = 2 pi i kx charge, ygrad = 2 pi i ky charge. */
+int lb_spectral_transform(lb_spectral *sp, int which, int forward);
+int lb_spectral_screen(lb_spectral *sp);
+int lb_spectral_grad_multiply(lb_spectral *sp);
+/* The whole solve in three launches (x-FFT of the rows; per block of columns the y-FFT, the screening, both multipliers and two
+ * inverse y-FFTs in LDS; the inverse x-FFT of both gradients): charge ends as the screened spectrum, xgrad and ygrad as the complex
+ * gradients, BITWISE what transform(charge, 1), screen, grad_multiply, transform(xgrad, 0), transform(ygrad, 0) leave. */
+int lb_spectral_solve(lb_spectral *sp);
+/* The solve with a scalar lattice's density as the charge and its velocity as the result: s is a whole-grid LB_SEM_DIFFUSION GPU
+ * handle (either family) of the solver's grid and device.  streamed = 0: the charge is the handle's stored rho; 1: the density the
+ * populations will have after streaming, which one launch (k_ad_moments) stores in the handle's rho first, moving nothing.  u and v
+ * of s become scale x Re xgrad, scale x Re ygrad -- bitwise the float32 product with lb_spectral_solve's gradients --, cells x < nx
+ * only; the solver's xgrad and ygrad are left half transformed.  On s's stream, behind the solver's own work, without a host wait;
+ * feq of s is no longer current. */
+int lb_spectral_velocity(lb_spectral *sp, lb_sim *s, float scale, int streamed);
+/* n_steps times: k_ad_moments, the three launches of the solve, k_ad_step (never the LDS tiles: the velocity changes every step);
+ * only the last step stores rho.  No host wait.  BITWISE n_steps x (lb_spectral_velocity(sp, s, scale, 1); lb_run(s, 1)). */
+int lb_run_screened(lb_spectral *sp, lb_sim *s, float scale, int n_steps);
+
 #ifdef __cplusplus
 }
 #endif
