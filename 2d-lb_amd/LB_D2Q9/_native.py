@@ -55,6 +55,10 @@ class RocketParams(ct.Structure):        # lb_rocket_params
                 ("G_chen", ct.c_float), ("c_o", ct.c_float), ("alpha", ct.c_float)]
 
 
+class NutrientParams(ct.Structure):      # lb_nutrient_params
+    _fields_ = [("G", ct.c_float), ("scale", ct.c_float), ("clumpy", ct.c_int32), ("rho_o", ct.c_float), ("G_chen", ct.c_float)]
+
+
 class LbError(RuntimeError):
     pass
 
@@ -113,6 +117,10 @@ SIGNATURES = {
     "lb_spectral_set": ([_h, _I, _vp, _I],), "lb_spectral_get": ([_h, _I, _vp],),
     "lb_spectral_transform": ([_h, _I, _I],), "lb_spectral_screen": ([_h],), "lb_spectral_grad_multiply": ([_h],),
     "lb_spectral_solve": ([_h],), "lb_spectral_velocity": ([_h, _h, _F, _I],), "lb_run_screened": ([_h, _h, _F, _I],),
+    # a population and its nutrient under the solver's velocity (two scalar lattices and an lb_spectral; the parameters: NutrientParams)
+    "lb_run_nutrient": ([_h, _hp, _I, ct.POINTER(NutrientParams), _I],), "lb_nutrient_velocity": ([_h, _hp, _I, _F, _I],),
+    "lb_update_forces_nutrient": ([_hp, _I, ct.POINTER(NutrientParams)],), "lb_collide_nutrient": ([_hp, _I, ct.POINTER(NutrientParams)],),
+    "lb_get_nutrient_fields": ([_hp, _I, _vp, _vp, _vp],),
 }
 EXPORTS = tuple(SIGNATURES)
 

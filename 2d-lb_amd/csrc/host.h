@@ -11,10 +11,12 @@
 //                  one handle kind each: its kernels, their launches, its row of the kind table, its own entry points of the C ABI
 //   spectral.cpp   the spectral screened-Poisson solver (lb_spectral_*: not a handle kind) and its coupling to a scalar lattice;
 //                  spectral_plan.cpp its plan (spectral_plan.h): no HIP
+//   nutrient.cpp   a population and its nutrient under the solver's velocity (lb_*_nutrient: two scalar lattices and an lb_spectral,
+//                  no handle kind of its own); emits kernels_nutrient.h
 // Small kernels are emitted by the one unit that includes their header: kernels_phases.h + kernels_check.h by lb_hip.cpp,
 // kernels_halo.h by slab.cpp, kernels_scalar.h by scalar.cpp (its health check's first pass only: check_reduce.h is shared, the folding
 // pass is lb_hip.cpp's), kernels_multifield.h by multifield.cpp, kernels_poisson.h by poisson.cpp, kernels_porous.h by porous.cpp,
-// kernels_multifluid.h by multifluid.cpp, kernels_rocket.h by rocket.cpp, kernels_spectral.h by spectral.cpp.  The six kind headers share kernels_lane4.h, the plan their
+// kernels_multifluid.h by multifluid.cpp, kernels_rocket.h by rocket.cpp, kernels_spectral.h by spectral.cpp, kernels_nutrient.h by nutrient.cpp.  The six kind headers and kernels_nutrient.h share kernels_lane4.h, the plan their
 // fused steps follow: device functions only, no kernel of its own.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -75,6 +77,7 @@ struct lb_sim : PlanInputs {
     // first handle -- pm_G the pseudo-force (FLOW) / the pressure force (FORCES), pm_ub the surface force, ry_op psi / S
     lb_rocket_params ry = {LB_ROCKET_FLOW, 0.f, 0.f, 0.f, 1.f, 0.f, 1.f, 1.f};
     float *ry_op = nullptr;     // [H][pitch]
+    // (a scalar lattice that is the first of a clumpy nutrient set, nutrient.cpp, keeps psi in ry_op and F in pm_G, made at first use)
     uint8_t *mask_raw = nullptr, *mask = nullptr;   // [H+2*MASK_GHOST][pitch] + guards; mask -> row 0
     bool feq_valid = false;     // feq buffer consistent with rho,u,v
     bool macro_valid = true;    // rho,u,v hold the last step's fields (false: to be rebuilt from the populations, ensure_macro)
@@ -293,6 +296,13 @@ void lbk_ad_edge(bool patch, hipStream_t st, const StepArgs &a, float *f, float 
 // them, into part (k_check_final, lb_hip.cpp, folds them)
 long long ad_check_blocks(const StepArgs &a);
 void lbk_ad_check(hipStream_t st, const StepArgs &a, CheckPartial *part);
+
+// ---- spectral.cpp: what a set coupled to the spectral solver (nutrient.cpp) runs it with ---------------------------------------------
+struct lb_spectral;
+int sp_borrow(lb_spectral *sp, hipStream_t st);     // the solver's arrays handed to another stream behind the solver's own work ...
+int sp_return(lb_spectral *sp, hipStream_t st);     // ... and back
+int sp_coupled_ready(const lb_spectral *sp, const lb_sim *s, const char *name);    // a whole-grid GPU scalar lattice of the solver's grid and device, or the refusal
+int sp_velocity_on(const lb_spectral *sp, const lb_sim *s, float scale);           // the three launches on s's stream: s's stored rho -> s's u, v
 
 // ---- porous.cpp: what a fluid of a multicomponent set shares with the porous-medium fluid (and a colony: the four planes) -------------
 PmExtra pm_extra(const lb_sim *s);

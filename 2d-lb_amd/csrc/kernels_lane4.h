@@ -1,5 +1,6 @@
 // kernels_lane4.h -- the lane-of-four plan of every handle kind beyond flow, once.  Included after kernels_fused.h by the kind kernel
-// headers (kernels_scalar.h, kernels_multifield.h, kernels_poisson.h, kernels_porous.h, kernels_multifluid.h, kernels_rocket.h).  Device
+// headers (kernels_scalar.h, kernels_multifield.h, kernels_poisson.h, kernels_porous.h, kernels_multifluid.h, kernels_rocket.h) and by
+// kernels_nutrient.h, the set of two scalar lattices that is no kind.  Device
 // functions only: no kernel is emitted from here.
 // The plan: a lane owns four consecutive cells (x4 .. x4+3) of one row and a wave 256 cells of it; launch blockDim = (64, 4), grid =
 // (ceil(fpitch / 256), ceil(ny / 4)).  The source rows are wrapped or clamped as the boundary family says (lane_rows), the nine planes
@@ -150,7 +151,8 @@ __device__ __forceinline__ float cell_rho(const StepArgs &a, int x, int ys, int 
 // of its last cell in the box (wrapped, or the edge cell itself: the halo columns, cell_rho).  After ONE barrier the waves of the owned
 // rows, whose populations stayed in registers, read the density around their cells from LDS (lane_nb_load's layout); the halo waves
 // are done.  An LDS row: LANE4_LDS_ROW floats, cell x of the tile at index 4 + x (16-byte aligned), the west halo at 3, the east halo at
-// 4 + (cells of the tile inside the box).  k_mc_step and k_ry_step each write the index arithmetic out.
+// 4 + (cells of the tile inside the box).  k_mc_step and k_ry_step each write the index arithmetic out; so does k_sn_step, whose LDS rows hold an
+// operand of a STORED plane: its halo rows are read by the owned rows' waves, no wave gathers for them.
 constexpr int LANE4_LDS_ROW = 264;
 
 // ---- the reference's phases, one cell per thread: grid = (ceil(nx / 256), ny) -------------------------------------------------------

@@ -90,6 +90,18 @@ int solve_on(const lb_spectral *sp, hipStream_t st, const SpArgs &a, bool vel)
     return rows_inv(sp, st, a, true, vel);
 }
 
+SpArgs velocity_args(const lb_spectral *sp, const lb_sim *s, float scale)
+{
+    SpArgs a = sp_args(sp);
+    a.real_in = s->rho; a.u = s->u; a.v = s->v;
+    a.rpitch = (int)s->pitch;
+    a.scale = scale;
+    return a;
+}
+
+}  // namespace
+
+// ---- what nutrient.cpp couples its set with (host.h) ---------------------------------------------------------------------------------
 // the solver's arrays handed to another stream behind the solver's own work, and back
 int sp_borrow(lb_spectral *sp, hipStream_t st)
 {
@@ -105,7 +117,7 @@ int sp_return(lb_spectral *sp, hipStream_t st)
 }
 
 // what the coupled calls refuse, in the style of NEED_SCALAR
-int coupled_ready(const lb_spectral *sp, const lb_sim *s, const char *name)
+int sp_coupled_ready(const lb_spectral *sp, const lb_sim *s, const char *name)
 {
     if (!sp) return fail(LB_ERR_ARG, "null spectral solver");
     if (!s) return fail(LB_ERR_ARG, "null handle");
@@ -118,14 +130,10 @@ int coupled_ready(const lb_spectral *sp, const lb_sim *s, const char *name)
     return LB_OK;
 }
 
-SpArgs velocity_args(const lb_spectral *sp, const lb_sim *s, float scale)
-{
-    SpArgs a = sp_args(sp);
-    a.real_in = s->rho; a.u = s->u; a.v = s->v;
-    a.rpitch = (int)s->pitch;
-    a.scale = scale;
-    return a;
-}
+// the three launches of the solve on s's stream: the charge is s's stored rho, u and v of s become scale x Re grad phi
+int sp_velocity_on(const lb_spectral *sp, const lb_sim *s, float scale) { return solve_on(sp, s->stream, velocity_args(sp, s, scale), true); }
+
+namespace {
 
 #define NEED_SPECTRAL(sp)                                                        \
     do {                                                                         \
@@ -261,7 +269,7 @@ int lb_spectral_solve(lb_spectral *sp)
 
 int lb_spectral_velocity(lb_spectral *sp, lb_sim *s, float scale, int streamed)
 {
-    int rc = coupled_ready(sp, s, "lb_spectral_velocity");
+    int rc = sp_coupled_ready(sp, s, "lb_spectral_velocity");
     if (rc) return rc;
     if (!finite32(scale)) return fail(LB_ERR_ARG, "the velocity's factor must be finite");
     DeviceGuard guard(s->p.device);
@@ -276,7 +284,7 @@ int lb_spectral_velocity(lb_spectral *sp, lb_sim *s, float scale, int streamed)
 
 int lb_run_screened(lb_spectral *sp, lb_sim *s, float scale, int n_steps)
 {
-    int rc = coupled_ready(sp, s, "lb_run_screened");
+    int rc = sp_coupled_ready(sp, s, "lb_run_screened");
     if (rc) return rc;
     if (!finite32(scale)) return fail(LB_ERR_ARG, "the velocity's factor must be finite");
     if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");

@@ -721,6 +721,39 @@ int lb_spectral_velocity(lb_spectral *sp, lb_sim *s, float scale, int streamed);
  * only the last step stores rho.  No host wait.  BITWISE n_steps x (lb_spectral_velocity(sp, s, scale, 1); lb_run(s, 1)). */
 int lb_run_screened(lb_spectral *sp, lb_sim *s, float scale, int n_steps);
 
+/* ---- a population and the nutrient it eats under the solver's velocity (the reference's reaction_diffusion/
+ *      surfactant_nutrient_waves.py and .cl: Surfactant_Nutrient_Wave and Clumpy_Surfactant_Nutrient_Wave) ----------------------------
+ * NOT a handle kind either: a set is exactly two whole-grid LB_SEM_DIFFUSION, LB_BC_PERIODIC GPU handles of one geometry, layout flag
+ * and device -- fields[0] the population p, fields[1] the nutrient n, each with its own omega -- and an lb_spectral of their grid.
+ * The parameters travel with every call; nothing is stored in a handle except psi and F, which live with the first member, are made
+ * at first use and freed by lb_destroy.  LB_ERR_ARG, with the reason, before any launch: a count other than 2, a handle given twice,
+ * a member that is no scalar lattice on the GPU or not periodic, members of different geometry, layout or device, a grid the solver
+ * was not created for, non-finite parameters, clumpy with nx or ny < 3 or with rho_o == 0, a negative n_steps; LB_ERR_STATE for slabs.  With cs = float32(1 / sqrt(3)) and 1 / cs^2 = float32(1. / (cs cs)) in the force term (the convention of the
+ * colonies above), one time step (surfactant_nutrient_waves.py: run) is
+ *   1. both lattices stream, periodic wrap (move_periodic + copy)                                              lb_move on each member
+ *   2. rho_i = sum_k f_ik                                                                                      lb_update_hydro on each
+ *   3. (u, v) = scale Re grad phi, (1 - lam^2 laplace) phi = rho_p; one velocity for both (update_u_and_v)     lb_nutrient_velocity
+ *   4. clumpy: psi = rho_o (1 - exp(-max(rho_p, 0) / rho_o)),                                                  lb_update_forces_nutrient
+ *        F = ((-cs cs) G_chen) psi(x) sum_k w_k c_k psi(x + c_k), periodic wrap
+ *   5. feq_ik = w_k rho_i (1 + c_k.u / cs^2)                                                                   lb_update_feq on each
+ *   6. population: f_k (1 - omega) + omega feq_k + w_k G rho_p rho_n [clumpy: + (w_k c_k.F) / cs^2];           lb_collide_nutrient
+ *      nutrient:   f_k (1 - omega_n) + omega_n feq_k - w_k G rho_p rho_n.  No floor at zero.
+ * lb_run_nutrient(n) = n steps on the first member's stream without a host wait, of FIVE launches each: k_ad_moments on the
+ * population (its density after streaming, nothing moved), the three launches of the solve, and k_sn_step, which gathers both
+ * lattices, relaxes them with the scalar lattice's cell arithmetic (with G = 0, scale = 0 and clumpy = 0 a member gets k_ad_step's
+ * bits) and, clumpy, stages psi of a workgroup's rows and their halo in LDS.  It leaves f post-collision, rho, u, v (on both
+ * members), psi and F those of the last step before its collision, feq not current.  The fused step and the stages are held to each
+ * other by the contract's tolerance, not bitwise: the stages store feq, the fused cell lets omega enter through rho (as lb_run and the
+ * phases of a scalar lattice differ). */
+typedef struct { float G, scale; int32_t clumpy; float rho_o, G_chen; } lb_nutrient_params;   /* clumpy: rho_o != 0 */
+int lb_run_nutrient(lb_spectral *sp, lb_sim **fields, int count, const lb_nutrient_params *p, int n_steps);
+/* stage 3: lb_spectral_velocity on fields[0] (streamed as there), then u, v copied into fields[1] device to device, same stream */
+int lb_nutrient_velocity(lb_spectral *sp, lb_sim **fields, int count, float scale, int streamed);
+int lb_update_forces_nutrient(lb_sim **fields, int count, const lb_nutrient_params *p);      /* stage 4 from the stored rho_p (clumpy only) */
+int lb_collide_nutrient(lb_sim **fields, int count, const lb_nutrient_params *p);            /* stage 6: stored feq, rho, F */
+/* psi, Fx, Fy of the last step / the last lb_update_forces_nutrient: [ny][nx] each, any may be NULL; zero before either */
+int lb_get_nutrient_fields(lb_sim **fields, int count, float *psi, float *Fx, float *Fy);
+
 #ifdef __cplusplus
 }
 #endif
