@@ -65,6 +65,7 @@ class LbError(RuntimeError):
 
 _h, _hp, _vp, _I, _F, _D = ct.c_void_p, ct.POINTER(ct.c_void_p), ct.c_void_p, ct.c_int, ct.c_float, ct.c_double
 _ip, _fp, _dp, _i64p = ct.POINTER(ct.c_int), ct.POINTER(ct.c_float), ct.POINTER(ct.c_double), ct.POINTER(ct.c_int64)
+_U64, _u64p = ct.c_uint64, ct.POINTER(ct.c_uint64)
 
 # every function include/lb_hip.h declares, in its order: name -> (argtypes[, restype]); tests/test_abi.py holds the names to the header
 SIGNATURES = {
@@ -77,6 +78,9 @@ SIGNATURES = {
     # scalar lattices
     "lb_set_reaction": ([_h, _F],), "lb_edge_floats": ([_h],), "lb_get_edge_state": ([_h, _vp],),
     "lb_set_edge_state": ([_h, _vp],), "lb_set_velocity_from": ([_h, _h],),
+    # ... their noisy collision
+    "lb_set_noise": ([_h, _F, _U64],), "lb_get_noise": ([_h, _fp, _u64p, _u64p],), "lb_set_noise_counter": ([_h, _U64],),
+    "lb_noise_fill": ([_h, _U64, _vp, _I],), "lb_set_noise_field": ([_h, _vp, _I],),
     # the LB Poisson solver
     "lb_set_poisson": ([_h, _F, _F, _F],), "lb_set_source": ([_h, _vp, _I],), "lb_get_source": ([_h, _vp],),
     "lb_solve": ([_h, _I, _ip, _ip, _fp],), "lb_solve_reset": ([_h],), "lb_get_solve_state": ([_h, _ip, _ip],),

@@ -30,11 +30,20 @@ def _restore_growth(sim, d):
 def _save_diffusion(sim, d):
     _save_growth(sim, d)
     d["edge_state"] = sim.get_edge_state()
+    # the noisy collision: [Dg as its float32 bit pattern, seed, noise counter], uint64 -- only where it is on (a checkpoint of a
+    # handle without noise keeps its entries); a supplied noise field is not part of a checkpoint
+    dg, seed, t = sim._noise()
+    if dg != 0.:
+        d["noise"] = np.array([int(np.float32(dg).view(np.uint32)), seed, t], np.uint64)
 
 
 def _restore_diffusion(sim, d):
     _restore_growth(sim, d)
     sim.set_edge_state(d["edge_state"])
+    if "noise" in d:
+        bits, seed, t = (int(x) for x in d["noise"])
+        sim._set_noise(float(np.uint32(bits).view(np.float32)), seed)
+        sim._set_noise_counter(t)
 
 
 def _save_multifield(sim, d):

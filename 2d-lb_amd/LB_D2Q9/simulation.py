@@ -528,6 +528,40 @@ class Simulation(object):
         check(self._lib.lb_set_reaction(self._h, float(np.float32(G))))
         self.G = float(np.float32(G))
 
+    # (the noisy collision: public on LB_D2Q9.noisy_simulation.NoisySimulation; the kind row's checkpoint code reaches it from here)
+    def _set_noise(self, Dg, seed=0):
+        """The noisy collision (D2Q9_diffusion.cl:127-167): react = G rho (1 - rho) + sqrt(Dg rho (1 - rho)) z, f_k < 0 -> 0, with
+        z a standard normal per cell and collision drawn inside the kernels from a counter-based stream (Philox4x32-10 under the
+        64-bit `seed`; include/lb_hip.h has the definition).  Dg > 0 switches it on and resets the noise counter; 0 switches back to
+        the plain cell.  rho outside [0, 1] gives NaN, as in the reference: check() counts such cells."""
+        check(self._lib.lb_set_noise(self._h, float(np.float32(Dg)), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def _noise(self):
+        """(Dg, seed, t): t = the noise counter, the number of noisy collisions since set_noise."""
+        dg, seed, t = ct.c_float(), ct.c_uint64(), ct.c_uint64()
+        check(self._lib.lb_get_noise(self._h, ct.byref(dg), ct.byref(seed), ct.byref(t)))
+        return dg.value, seed.value, t.value
+
+    def _set_noise_counter(self, t):
+        check(self._lib.lb_set_noise_counter(self._h, int(t)))
+
+    def _noise_fill(self, t):
+        """The (nx, ny) normals the kernels draw at noise counter t under the handle's seed (lb_noise_fill)."""
+        out = np.zeros(self._shape2, np.float32, order="F")
+        check(self._lib.lb_noise_fill(self._h, int(t), out.ctypes.data, 0))
+        return out
+
+    def _set_noise_field(self, z):
+        """A supplied (nx, ny) field of normals that collide_particles() uses in place of the stream (the reference's random_normal
+        buffer); None drops it.  While one is set run() refuses: a field is never used twice."""
+        if z is None:
+            check(self._lib.lb_set_noise_field(self._h, None, 0))
+            return
+        a = np.asfortranarray(z, np.float32)
+        if a.shape != self._shape2:
+            raise ValueError("noise field must have shape (nx, ny)")
+        check(self._lib.lb_set_noise_field(self._h, a.ctypes.data, 0))
+
     def set_velocity_from(self, flow):
         """Take the imposed velocity from a flow Simulation of the same grid on the same device: its current u, v,
         copied device to device behind the flow's enqueued work (lb_set_velocity_from)."""

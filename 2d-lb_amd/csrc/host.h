@@ -54,6 +54,9 @@ struct lb_sim : PlanInputs {
     float *stage = nullptr;     // [H][pitch], lazily: one plane on its way between the host and interleaved rows (lattice_plane_*)
     float *ad_edge = nullptr;   // scalar lattice, OPEN family: the edge state on the device (scalar_launch.h: AdExtra)
     float ad_G = 0.f;           // scalar lattice: growth rate of the Fisher term (lb_set_reaction); 0 = plain relaxation
+    float ad_Dg = 0.f;          // LB_SEM_DIFFUSION: strength of the noisy collision (lb_set_noise); 0 = the plain cell
+    uint64_t ad_seed = 0, ad_t = 0;     // ... its stream's key and its noise counter: noisy collisions since the seed was set (philox.h)
+    float *ad_noise_field = nullptr;    // ... a supplied [ny][nx] field of normals for lb_collide_particles (lb_set_noise_field), device
     float *vi_corner = nullptr; // VELOCITY_INLET: the eight corner links nothing ever writes (bc_vel_cell), device; LB_BC_BOX, LB_BC_DIRICHLET: likewise (MfBox, PsBox)
     // the LB Poisson solver (LB_SEM_POISSON; poisson_launch.h)
     float *ps_source = nullptr;         // [H][pitch]: the source, padding zero

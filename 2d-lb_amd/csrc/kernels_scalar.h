@@ -11,6 +11,9 @@
 //                               keep the reference's un-fused order -- feq stored, then f (1 - omega) + omega feq -- and so round
 //                               differently from the fused cell, where omega enters through rho: held to it by the contract's
 //                               tolerance, not bitwise
+//   k_ad_step / k_ad_tile4 / k_ad_collide<..., AdNoise>   the noisy instantiations (lb_set_noise; collide_particles_noisy_fisher): an AdNoise
+//                               behind the other arguments, the normals drawn in registers from philox.h's stream (scalar_cell.h);
+//                               k_ad_tile4<..., AdNoise> bitwise equal to four k_ad_step<..., AdNoise>.  k_ad_noise_fill: lb_noise_fill
 //   k_ad_edge_capture / k_ad_edge_patch, k_ad_check (the health check's first pass: check_reduce.h)
 // The OPEN family (the reference's box, whose move_bcs does nothing): a link that would enter from outside keeps the value it had
 // when the populations were last set -- the handle's edge state, scalar_launch.h.  The gather reads whatever lies beside the box
@@ -77,10 +80,38 @@ __device__ __forceinline__ void ad_collide_row(f4a (&q)[9], f4a u4, f4a v4, floa
     }
 }
 
+// The noisy instantiations take an AdNoise behind their other arguments (a pack that is empty or that one struct: the plain
+// instantiations keep their signature, their name and their instruction text).
+__device__ __forceinline__ const AdNoise &ad_nz(const AdNoise &n) { return n; }
+
+// ... with the noisy collision: ONE Philox call for the lane (box cells x4 .. x4+3 of row y, counter n.t), its four normals in registers
+__device__ __forceinline__ void ad_collide_row_noisy(f4a (&q)[9], f4a u4, f4a v4, float omega, float G, const AdNoise &n, int x4, int y,
+                                                     f4a &r4)
+{
+    float z[4];
+    ad_lane_normals(n.seed, x4, y, n.t, z);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        f2a f[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) f[k] = pair_of(q[k], h);
+        const f2a ux = pair_of(u4, h), uy = pair_of(v4, h);
+        const f2a rho = ad_rho_t<f2a>(f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8]);
+        ad_relax_noisy_t<f2a>(f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], omega, G, n.Dg, rho, ux, uy, f2a{z[2 * h], z[2 * h + 1]});
+        if (h) r4.zw = rho;
+        else r4.xy = rho;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            if (h) q[k].zw = f[k];
+            else q[k].xy = f[k];
+        }
+    }
+}
+
 // (lane_rows and the nine stores written out: through the calls the diagnostic build's OPEN form is scheduled differently, the plane
 // offsets are shared with the gather's, and the instruction text moves)
-template <int BC, bool REACT, bool RHO>
-__global__ __launch_bounds__(256) void k_ad_step(const StepArgs a, const AdExtra e)
+template <int BC, bool REACT, bool RHO, typename... NZ>
+__global__ __launch_bounds__(256) void k_ad_step(const StepArgs a, const AdExtra e, const NZ... nz)
 {
     const int x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int yl = blockIdx.y * blockDim.y + __builtin_amdgcn_readfirstlane(threadIdx.y);
@@ -96,7 +127,8 @@ __global__ __launch_bounds__(256) void k_ad_step(const StepArgs a, const AdExtra
     const long long m0 = (long long)yl * a.fpitch;
     const f4a u4 = load4<false>(lane_ptr((const float *)a.u + m0, x4));
     const f4a v4 = load4<false>(lane_ptr((const float *)a.v + m0, x4));
-    ad_collide_row<REACT>(q, u4, v4, a.omega, e.G, r4);
+    if constexpr (sizeof...(NZ) != 0) ad_collide_row_noisy(q, u4, v4, a.omega, e.G, ad_nz(nz...), x4, yl, r4);
+    else ad_collide_row<REACT>(q, u4, v4, a.omega, e.G, r4);
     float *d = a.dst + (long long)yl * a.pitch;
     const long long S = a.plane;
 #pragma unroll
@@ -138,8 +170,53 @@ __global__ __launch_bounds__(256) void k_ad_moments(const StepArgs a, const AdEx
 // un-wrapped tile cells are stored.  OPEN: a region cell outside the box is never stepped (it is loaded from the nearest cell inside,
 // so that no address leaves the lattice, and never used); a cell on the box's edge takes its outside links from the edge state, rows
 // first, then the columns, as ad_edge_gather does.
-template <int BC, bool REACT, bool RHO, int TW, int TH, int CPT>
-__global__ __launch_bounds__((TileShape<TW, TH, CPT>::THREADS)) void k_ad_tile4(const StepArgs a, const AdExtra e, int tiles_x, int n_tiles)
+// Noisy (an AdNoise or an AdNoiseCell last): step s of the launch draws at counter t + s - 1, in BOX coordinates -- a halo cell and a
+// periodic image get the bits their owner gets.  Two plans (DESIGN.md section 17 has both measured):
+//   AdNoise      the noise plane: before each step one thread per four region cells (the region's width and origin are multiples of 4:
+//                a region four is a box lane-of-four) calls Philox once, as a lane of k_ad_step does, and writes the four normals into
+//                an LDS plane beside the populations -- between the two barriers a step has anyway.  A four of a periodic image that is
+//                no box lane (nx no multiple of 4, at the seam) falls back to four per-cell draws.
+//   AdNoiseCell  every cell calls Philox for the lane of its box coordinates and takes its own word pair (ad_cell_normal): no LDS,
+//                four times the integer rounds and twice the transcendental work.  Kept for the A/B measurement.
+template <typename... N> struct ad_noise_plan { static constexpr int value = 0; };
+template <> struct ad_noise_plan<AdNoise> { static constexpr int value = 1; };
+template <> struct ad_noise_plan<AdNoiseCell> { static constexpr int value = 2; };
+
+template <int CELLS>
+__device__ __forceinline__ float *ad_noise_plane()
+{
+    __shared__ float lz[CELLS];
+    return lz;
+}
+
+template <int BC, int L, int CELLS, int THREADS>
+__device__ __forceinline__ void ad_noise_plane_fill(float *lz, const AdNoise &n, unsigned long long t, int gx0, int gy0, int nx, int ny, int tid)
+{
+    static_assert(L % 4 == 0 && CELLS % 4 == 0, "a region row is whole fours");
+    for (int l = tid; l < CELLS / 4; l += THREADS) {
+        const int c0 = 4 * l;
+        int x = gx0 + c0 % L, y = gy0 + c0 / L;
+        if (BC == LB_BC_PERIODIC) {
+            x %= nx; if (x < 0) x += nx;
+            y %= ny; if (y < 0) y += ny;
+            if ((x & 3) != 0 || x + 3 >= nx) {      // not a whole box lane: cell by cell, each wrapped on its own
+#pragma unroll 1
+                for (int j = 0; j < 4; ++j) lz[c0 + j] = ad_cell_normal(n.seed, (x + j) % nx, y, t);
+                continue;
+            }
+        } else if (x < 0 || x >= nx || y < 0 || y >= ny) {
+            continue;                               // outside the box: never stepped
+        }
+        float z[4];
+        ad_lane_normals(n.seed, x, y, t, z);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) lz[c0 + j] = z[j];
+    }
+}
+
+template <int BC, bool REACT, bool RHO, int TW, int TH, int CPT, typename... NZ>
+__global__ __launch_bounds__((TileShape<TW, TH, CPT>::THREADS)) void k_ad_tile4(const StepArgs a, const AdExtra e, int tiles_x, int n_tiles,
+                                                                                const NZ... nz)
 {
     constexpr int L = TileShape<TW, TH, CPT>::LW, LH = TileShape<TW, TH, CPT>::LH;
     constexpr int CELLS = TileShape<TW, TH, CPT>::CELLS, THREADS = TileShape<TW, TH, CPT>::THREADS;
@@ -182,6 +259,12 @@ __global__ __launch_bounds__((TileShape<TW, TH, CPT>::THREADS)) void k_ad_tile4(
             lv[c] = a.v[m];
         }
     }
+    constexpr int NOISE_PLAN = ad_noise_plan<NZ...>::value;
+    float *lz = nullptr;
+    if constexpr (NOISE_PLAN == 1) {
+        lz = ad_noise_plane<CELLS>();
+        ad_noise_plane_fill<BC, L, CELLS, THREADS>(lz, ad_nz(nz...), ad_nz(nz...).t, gx0, gy0, nx, ny, tid);
+    }
     __syncthreads();
 
 #pragma unroll 1
@@ -204,7 +287,15 @@ __global__ __launch_bounds__((TileShape<TW, TH, CPT>::THREADS)) void k_ad_tile4(
                 if (gx == nx - 1) { f3 = col[3 * ny]; f6 = col[4 * ny]; f7 = col[5 * ny]; }
             }
             const float rho = ad_rho_t<float>(f0, f1, f2, f3, f4, f5, f6, f7, f8);
-            ad_relax_t<float, REACT>(f0, f1, f2, f3, f4, f5, f6, f7, f8, a.omega, e.G, rho, lu[c], lv[c]);
+            if constexpr (sizeof...(NZ) != 0) {
+                const AdNoise &n = ad_nz(nz...);
+                float z;
+                if constexpr (NOISE_PLAN == 1) z = lz[c];
+                else z = ad_cell_normal(n.seed, gx, gy, n.t + (unsigned long long)(s - 1));
+                ad_relax_noisy_t<float>(f0, f1, f2, f3, f4, f5, f6, f7, f8, a.omega, e.G, n.Dg, rho, lu[c], lv[c], z);
+            } else {
+                ad_relax_t<float, REACT>(f0, f1, f2, f3, f4, f5, f6, f7, f8, a.omega, e.G, rho, lu[c], lv[c]);
+            }
             if (last) {
                 if (mine[i]) {
                     float *d = a.dst + (long long)gy * P + gx;
@@ -225,6 +316,8 @@ __global__ __launch_bounds__((TileShape<TW, TH, CPT>::THREADS)) void k_ad_tile4(
 #pragma unroll
                 for (int k = 0; k < 9; ++k) lds[k][cc[i]] = q[i][k];
             }
+        if constexpr (NOISE_PLAN == 1)              // the next step's normals (everyone has read this step's: the barrier above)
+            ad_noise_plane_fill<BC, L, CELLS, THREADS>(lz, ad_nz(nz...), ad_nz(nz...).t + (unsigned long long)s, gx0, gy0, nx, ny, tid);
         __syncthreads();
     }
 }
@@ -251,15 +344,20 @@ __global__ void k_ad_feq(const StepArgs a, float *feq)         // :1-38
     for (int k = 0; k < 9; ++k) o[k * a.plane] = e[k];
 }
 
-template <bool REACT>
-__global__ void k_ad_collide(const StepArgs a, float *f, const float *feq, float G)     // :70-93, :95-124
+// Noisy (an AdNoise last; :127-167): z from the supplied field where there is one (lb_set_noise_field), else from the stream
+template <bool REACT, typename... NZ>
+__global__ void k_ad_collide(const StepArgs a, float *f, const float *feq, float G, const NZ... nz)     // :70-93, :95-124
 {
     int x, y;
     if (!cell_xy(a, x, y)) return;
     const long long o = (long long)y * a.pitch + x;
     const float keep = 1.f - a.omega;
     float react = 0.f;
-    if (REACT) {
+    if constexpr (sizeof...(NZ) != 0) {
+        const AdNoise &n = ad_nz(nz...);
+        const float z = n.field ? n.field[(long long)y * a.nx + x] : ad_cell_normal(n.seed, x, y, n.t);
+        react = ad_noisy_react_t<float>(G, n.Dg, a.rho[(long long)y * a.fpitch + x], z);
+    } else if (REACT) {
         const float rho = a.rho[(long long)y * a.fpitch + x];
         react = (G * rho) * (1.f - rho);
     }
@@ -267,8 +365,22 @@ __global__ void k_ad_collide(const StepArgs a, float *f, const float *feq, float
     for (int k = 0; k < 9; ++k) {
         float v = lb_fma(f[o + k * a.plane], keep, a.omega * feq[o + k * a.plane]);
         if (REACT) v = lb_fma(lb_w9(k), react, v);
+        if constexpr (sizeof...(NZ) != 0) v = ad_clamp0(v);
         f[o + k * a.plane] = v;
     }
+}
+
+// lb_noise_fill: the normals of noise counter n.t as dense [ny][nx] floats, one lane-of-four per thread as k_ad_step draws them;
+// grid = (ceil(nx / 1024), ny), 256 threads
+__global__ __launch_bounds__(256) void k_ad_noise_fill(const AdNoise n, int nx, float *out)
+{
+    const int x4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y;
+    if (x4 >= nx) return;
+    float z[4];
+    ad_lane_normals(n.seed, x4, y, n.t, z);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (x4 + j < nx) out[(long long)y * nx + x4 + j] = z[j];
 }
 
 // ---- OPEN: edge state <-> lattice.  One thread per column / row index: grid = ceil(max(fpitch, ny) / 256) --------------------------

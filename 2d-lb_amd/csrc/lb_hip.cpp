@@ -606,7 +606,7 @@ int lb_destroy(lb_sim *s)
         }
     if (s->peer_flags) (void)hipFree(s->peer_flags);
     if (s->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(s->comm);
-    for (float *p : {s->lat[0], s->lat[1], s->feq, s->rho, s->u, s->v, s->halo_buf, s->vi_corner, s->stage, s->ad_edge, s->ps_source, s->ps_part,
+    for (float *p : {s->lat[0], s->lat[1], s->feq, s->rho, s->u, s->v, s->halo_buf, s->vi_corner, s->stage, s->ad_edge, s->ad_noise_field, s->ps_source, s->ps_part,
                      s->pm_G[0], s->pm_G[1], s->pm_ub[0], s->pm_ub[1], s->pm_field[0], s->pm_field[1], s->ry_op})
         if (p) (void)hipFree(p);
     if (s->mask_raw) (void)hipFree(s->mask_raw);

@@ -39,6 +39,7 @@ int nutrient_members(lb_sim **f, int count, const char *what)
     for (int i = 0; i < 2; ++i) {
         if (f[i]->p.bc_mode != LB_BC_PERIODIC) return fail(LB_ERR_ARG, "%s: handle %d is not periodic (the family LB_BC_PERIODIC only)", what, i);
         if (f[i]->multi_slab()) return fail(LB_ERR_STATE, "%s is only available on handles that own the whole grid", what);
+        if (f[i]->noisy) return fail(LB_ERR_STATE, "%s: handle %d has the noisy collision on (lb_set_noise), which the set's kernels do not draw", what, i);
     }
     return LB_OK;
 }

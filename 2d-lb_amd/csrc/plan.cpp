@@ -492,6 +492,7 @@ bool tune_entry_runs_here(const PlanInputs *s, int steps, int wpc)
 // The shape by size as for k_tile4 (tile_shape_of) is the sweep's best one at 256^2 (16 x 16), 512^2 (32 x 16, one cell per thread) and
 // from 2048^2 (two per thread); at 1024^2 it is the periodic family's best and 5 % behind the other 32 x 16 shape in the OPEN family.
 static const double SCALAR_TILE_MIN_CELLS = 256.0 * 256.0, SCALAR_TILE_MAX_CELLS = 8192.0 * 8192.0;
+static const double SCALAR_NOISY_OPEN_TILE_END_CELLS = 1024.0 * 1024.0;     // (noisy handles of the OPEN family: tiles below, k_ad_step from here)
 // Multicomponent Shan-Chen fluids: variant 0 = the two-launch step, 1 = the one-launch step.  The planner's choice (-1) is the
 // one-launch step at every size: on one MI355X it is 1.00-1.21 x the two-launch step at 256^2 ... 8192^2 with one, two and three
 // fluids, but for 0.97 x at 1024^2 with two (profiles/multifluid_bench.txt, tools/multifluid_bench.py) -- no size rule to draw from that.
@@ -505,6 +506,13 @@ bool scalar_use_tiles(const PlanInputs *s)
     if (s->multifield() || s->poisson() || s->porous() || s->multifluid() || s->rocket()) return false;      // (no tiles for coupled sets, the Poisson solver and the porous-medium fluid: k_mf_step / k_ps_step / k_pm_step, one step per launch)
     if (s->variant >= 0) return (s->variant & LB_VAR_TILES) != 0;
     const double cells = (double)s->p.nx * s->H;
+    // The noisy collision (lb_set_noise; profiles/scalar_bench.txt, the noise column: 256^2 ... 8192^2, all six sizes, both families).
+    // k_ad_step draws one Philox block per lane-of-four and keeps 0.97-1.00 x its noiseless rate from 1024^2 up; k_ad_tile4 with its noise
+    // plane in LDS falls to 0.43-0.63 x its own.  Best noisy tile shape over the noisy k_ad_step, 256^2, 512^2, ... 8192^2:
+    //   PERIODIC  2.15  1.57  1.33  1.58  1.57  1.62   faster at every size measured: the noiseless range stands
+    //   OPEN      2.10  1.39  0.99  1.03  0.98  0.97   faster at 256^2 and 512^2; from 1024^2 up within the samples' spread of 1 (0.2-4.9 %),
+    //                                                   not faster: k_ad_step
+    if (s->noisy && s->p.bc_mode != LB_BC_PERIODIC && cells >= SCALAR_NOISY_OPEN_TILE_END_CELLS) return false;
     return cells >= SCALAR_TILE_MIN_CELLS && cells <= SCALAR_TILE_MAX_CELLS;
 }
 

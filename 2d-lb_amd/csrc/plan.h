@@ -18,6 +18,7 @@ struct PlanInputs {
     long long pitch = 0, rowp = 0, plane = 0, lat_floats = 0;   // padded row width; lattice row / plane strides; floats per lattice
     bool has_mask = false;
     bool has_field = false;     // LB_SEM_POROUS: a force field is set (lb_set_force_field)
+    bool noisy = false;         // LB_SEM_DIFFUSION: the noisy collision is on (lb_set_noise with Dg > 0)
     int cu_count = 256;
     int min_h = 0;              // smallest slab height over the ranks (every rank must pick the same schedule)
     int nranks = 1;             // slabs of the run (lb_comm_init / lb_peer_connect): with min_h, the tallest slab the run can hold

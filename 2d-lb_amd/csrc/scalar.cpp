@@ -1,5 +1,6 @@
 // scalar.cpp -- scalar lattices (LB_SEM_DIFFUSION): the kernels of kernels_scalar.h and their launches, the kind's row of the kind table
-// (host.h: KindOps), its run, and the entry points of the C ABI that are its own: lb_set_reaction, the edge state, lb_set_velocity_from.
+// (host.h: KindOps), its run, and the entry points of the C ABI that are its own: lb_set_reaction, the edge state, lb_set_velocity_from,
+// the noisy collision (lb_set_noise ...: the stream is philox.h's, the noise counter ad_t advances by one per noisy collision).
 #include "kernels_scalar.h"    // (first: host.h switches floating-point contraction off for what follows it, cpu_backend.h)
 #include "host.h"
 
@@ -25,6 +26,56 @@ void ad_tile_go(int shape, hipStream_t st, const StepArgs &a, const AdExtra &e)
         hipLaunchKernelGGL((k_ad_tile4<BC, REACT, RHO, T::TW, T::TH, T::CPT>), t.grid, t.block, 0, st, a, e, t.tiles_x, t.n_tiles);
     });
 }
+
+// the noisy instantiations (always with the growth term: G = 0 adds nothing)
+template <int BC, bool RHO, typename NZ>
+void ad_noisy_tile_go(int shape, hipStream_t st, const StepArgs &a, const AdExtra &e, const NZ &nz)
+{
+    with_tile_shape(shape, a.nx, a.ny, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_ad_tile4<BC, true, RHO, T::TW, T::TH, T::CPT, NZ>), t.grid, t.block, 0, st, a, e, t.tiles_x, t.n_tiles, nz);
+    });
+}
+
+template <typename NZ>
+void ad_noisy_tile_plan(int bc, bool store_rho, int shape, hipStream_t st, const StepArgs &a, const AdExtra &e, const NZ &nz)
+{
+    if (bc == LB_BC_PERIODIC) {
+        if (store_rho) ad_noisy_tile_go<LB_BC_PERIODIC, true>(shape, st, a, e, nz);
+        else ad_noisy_tile_go<LB_BC_PERIODIC, false>(shape, st, a, e, nz);
+    } else {
+        if (store_rho) ad_noisy_tile_go<LB_BC_OPEN, true>(shape, st, a, e, nz);
+        else ad_noisy_tile_go<LB_BC_OPEN, false>(shape, st, a, e, nz);
+    }
+}
+
+// per_cell: the per-cell plan (an explicit variant with LB_VAR_STEP4_NO_AHEAD: the A/B switch) instead of the noise plane in LDS
+void ad_noisy_tile4(int bc, bool store_rho, int shape, bool per_cell, hipStream_t st, const StepArgs &a, const AdExtra &e, const AdNoise &nz)
+{
+    if (per_cell) {
+        AdNoiseCell c;
+        static_cast<AdNoise &>(c) = nz;
+        ad_noisy_tile_plan(bc, store_rho, shape, st, a, e, c);
+    } else {
+        ad_noisy_tile_plan(bc, store_rho, shape, st, a, e, nz);
+    }
+}
+
+void ad_noisy_step(int bc, bool store_rho, hipStream_t st, const StepArgs &a, const AdExtra &e, const AdNoise &nz)
+{
+    const dim3 block(64, 4), grid = step_grid(a);
+    if (bc == LB_BC_PERIODIC) {
+        if (store_rho) hipLaunchKernelGGL((k_ad_step<LB_BC_PERIODIC, true, true, AdNoise>), grid, block, 0, st, a, e, nz);
+        else hipLaunchKernelGGL((k_ad_step<LB_BC_PERIODIC, true, false, AdNoise>), grid, block, 0, st, a, e, nz);
+    } else {
+        if (store_rho) hipLaunchKernelGGL((k_ad_step<LB_BC_OPEN, true, true, AdNoise>), grid, block, 0, st, a, e, nz);
+        else hipLaunchKernelGGL((k_ad_step<LB_BC_OPEN, true, false, AdNoise>), grid, block, 0, st, a, e, nz);
+    }
+}
+
+// the handle's noise as a launch takes it: the stream at the handle's counter
+AdNoise ad_noise_of(const lb_sim *s) { return AdNoise{s->ad_Dg, s->ad_seed, s->ad_t, nullptr}; }
+const char *const NOISE_FIELD_SET = "a noise field is set (lb_set_noise_field): only lb_collide_particles uses one; drop it with NULL first";
 
 template <int BC>
 void ad_tile_bc(bool react, bool store_rho, int shape, hipStream_t st, const StepArgs &a, const AdExtra &e)
@@ -67,7 +118,15 @@ int scalar_create(lb_sim *s)
 int scalar_collide(lb_sim *s)
 {
     int rc = collide_ready(s);
-    return rc ? rc : launch_phase(s, grid_cells(s), s->ad_G != 0.f ? k_ad_collide<true> : k_ad_collide<false>, s->origin(s->cur), s->feq_origin(), s->ad_G);
+    if (rc) return rc;
+    if (s->ad_Dg != 0.f && s->p.semantics == LB_SEM_DIFFUSION) {       // the stream, or the supplied field in its place; either way one noisy collision
+        AdNoise nz = ad_noise_of(s);
+        nz.field = s->ad_noise_field;
+        if ((rc = launch_phase(s, grid_cells(s), k_ad_collide<true, AdNoise>, s->origin(s->cur), s->feq_origin(), s->ad_G, nz))) return rc;
+        s->ad_t += 1;
+        return LB_OK;
+    }
+    return launch_phase(s, grid_cells(s), s->ad_G != 0.f ? k_ad_collide<true> : k_ad_collide<false>, s->origin(s->cur), s->feq_origin(), s->ad_G);
 }
 
 // n time steps: k_ad_tile4 / k_ad_step launch by launch, as scalar_next_advance splits the run; the last launch stores rho (with a
@@ -75,14 +134,20 @@ int scalar_collide(lb_sim *s)
 int run_scalar(lb_sim *s, int n_steps)
 {
     const AdExtra e = AdExtra{s->ad_edge, s->ad_G};
+    const bool noisy = s->ad_Dg != 0.f;
+    if (noisy && s->ad_noise_field) return fail(LB_ERR_STATE, "lb_run: %s", NOISE_FIELD_SET);
     int left = n_steps;
     while (left > 0) {
         const int adv = scalar_next_advance(s, left);
         const StepArgs a = step_args(s, 0, 1, s->H);
-        if (adv == TILE_T) ad_tile4(s->p.bc_mode, s->ad_G != 0.f, left == adv, scalar_tile_shape(s), s->stream, a, e);
+        if (noisy) {            // step i of a launch draws at counter t + i
+            if (adv == TILE_T) ad_noisy_tile4(s->p.bc_mode, left == adv, scalar_tile_shape(s), s->variant >= 0 && (s->variant & LB_VAR_STEP4_NO_AHEAD), s->stream, a, e, ad_noise_of(s));
+            else ad_noisy_step(s->p.bc_mode, left == adv, s->stream, a, e, ad_noise_of(s));
+        } else if (adv == TILE_T) ad_tile4(s->p.bc_mode, s->ad_G != 0.f, left == adv, scalar_tile_shape(s), s->stream, a, e);
         else ad_step(s->p.bc_mode, s->ad_G != 0.f, left == adv, s->stream, a, e);
         HIP_TRY(hipGetLastError());
         s->cur ^= 1;
+        if (noisy) s->ad_t += (unsigned long long)adv;
         left -= adv;
     }
     if (n_steps) { s->feq_valid = false; s->macro_valid = true; }
@@ -106,7 +171,13 @@ int scalar_moments(lb_sim *s)
 
 int scalar_step(lb_sim *s, bool store_rho)
 {
-    ad_step(s->p.bc_mode, s->ad_G != 0.f, store_rho, s->stream, step_args(s, 0, 1, s->H), AdExtra{s->ad_edge, s->ad_G});
+    if (s->ad_Dg != 0.f) {
+        if (s->ad_noise_field) return fail(LB_ERR_STATE, "%s", NOISE_FIELD_SET);
+        ad_noisy_step(s->p.bc_mode, store_rho, s->stream, step_args(s, 0, 1, s->H), AdExtra{s->ad_edge, s->ad_G}, ad_noise_of(s));
+        s->ad_t += 1;
+    } else {
+        ad_step(s->p.bc_mode, s->ad_G != 0.f, store_rho, s->stream, step_args(s, 0, 1, s->H), AdExtra{s->ad_edge, s->ad_G});
+    }
     HIP_TRY(hipGetLastError());
     s->cur ^= 1;
     return LB_OK;
@@ -209,6 +280,76 @@ int lb_set_edge_state(lb_sim *s, const float *in)
     if (e == hipSuccess) e = hipMemcpy(s->ad_edge, tmp, n * sizeof(float), hipMemcpyHostToDevice);
     free(tmp);
     if (e != hipSuccess) return fail(LB_ERR_HIP, "edge state upload: %s", hipGetErrorString(e));
+    return LB_OK;
+}
+
+// ---- the noisy collision (collide_particles_noisy_fisher): LB_SEM_DIFFUSION handles only ------------------------------------------
+#define NEED_DIFFUSION(s, name)                                                                              \
+    do {                                                                                                     \
+        NEED_SCALAR(s, name);                                                                                \
+        if ((s)->p.semantics != LB_SEM_DIFFUSION)                                                            \
+            return fail(LB_ERR_STATE, "%s is for scalar lattices on their own (LB_SEM_DIFFUSION)", name);    \
+    } while (0)
+
+int lb_set_noise(lb_sim *s, float Dg, uint64_t seed)
+{
+    NEED_DIFFUSION(s, "lb_set_noise");
+    if (!finite32(Dg) || Dg < 0.f) return fail(LB_ERR_ARG, "the noise strength must be finite and not negative");
+    s->ad_Dg = Dg;
+    s->noisy = Dg != 0.f;       // (the planner's: automatic runs of a noisy handle stay on k_ad_step, plan.cpp)
+    s->ad_seed = seed;
+    s->ad_t = 0;
+    return LB_OK;
+}
+
+int lb_get_noise(lb_sim *s, float *Dg, uint64_t *seed, uint64_t *t)
+{
+    NEED_DIFFUSION(s, "lb_get_noise");
+    if (Dg) *Dg = s->ad_Dg;
+    if (seed) *seed = s->ad_seed;
+    if (t) *t = s->ad_t;
+    return LB_OK;
+}
+
+int lb_set_noise_counter(lb_sim *s, uint64_t t)
+{
+    NEED_DIFFUSION(s, "lb_set_noise_counter");
+    s->ad_t = t;
+    return LB_OK;
+}
+
+int lb_noise_fill(lb_sim *s, uint64_t t, float *out, int on_device)
+{
+    NEED_DIFFUSION(s, "lb_noise_fill");
+    if (!out) return fail(LB_ERR_ARG, "null argument");
+    DeviceGuard guard(s->p.device);
+    const int nx = s->p.nx, ny = s->p.ny;
+    const size_t bytes = sizeof(float) * (size_t)nx * ny;
+    float *dev = out;
+    if (!on_device) HIP_TRY(hipMalloc(&dev, bytes));
+    hipLaunchKernelGGL(k_ad_noise_fill, dim3((unsigned)((nx + 1023) / 1024), (unsigned)ny), dim3(256), 0, s->stream,
+                       AdNoise{s->ad_Dg, s->ad_seed, t, nullptr}, nx, dev);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && !on_device) e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (!on_device) (void)hipFree(dev);
+    if (e != hipSuccess) return fail(LB_ERR_HIP, "lb_noise_fill: %s", hipGetErrorString(e));
+    return LB_OK;
+}
+
+int lb_set_noise_field(lb_sim *s, const float *z, int on_device)
+{
+    NEED_DIFFUSION(s, "lb_set_noise_field");
+    DeviceGuard guard(s->p.device);
+    HIP_TRY(hipStreamSynchronize(s->stream));       // (a collision in flight may still be reading the field)
+    if (!z) {
+        if (s->ad_noise_field) (void)hipFree(s->ad_noise_field);
+        s->ad_noise_field = nullptr;
+        return LB_OK;
+    }
+    const size_t bytes = sizeof(float) * (size_t)s->p.nx * s->p.ny;
+    if (!s->ad_noise_field) HIP_TRY(hipMalloc(&s->ad_noise_field, bytes));
+    HIP_TRY(hipMemcpy(s->ad_noise_field, z, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     return LB_OK;
 }
 

@@ -8,6 +8,7 @@
 // ad_feq_t below): no division in the cell.  A numpy model with the constant 3 followed the reference's C to 1.0e-7 after 1000 steps.
 #pragma once
 #include "d2q9_cell.h"
+#include "philox.h"
 
 namespace {
 
@@ -69,6 +70,78 @@ __device__ __forceinline__ void ad_relax_t(T &f0, T &f1, T &f2, T &f3, T &f4, T 
     f8 = lb_fma(f8, keep, e8);
     f6 = lb_fma(f6, keep, e6);
     if (REACT) ad_grow_t<T>(f0, f1, f2, f3, f4, f5, f6, f7, f8, G, rho, lb_splat<T>(1.f) - rho);
+}
+
+// ---- the noisy collision: collide_particles_noisy_fisher, D2Q9_diffusion.cl:127-167 --------------------------------------------------
+// Two normals from two words of the stream (philox.h): R cos(theta), R sin(theta), R = sqrt(-2 ln u(ra)), theta = 2 pi u(rb).  The one
+// place where the logarithm, the square root and the sine / cosine are written: every kernel inlines it, so a cell's normal is the same
+// bits wherever it is (re)computed.  Library routines throughout (the argument of sincospif, 2 u, is exact): held to a float64 model by
+// tests/test_gpu_noise.py.
+__device__ __forceinline__ void ad_normal_pair(uint32_t ra, uint32_t rb, float &zc, float &zs)
+{
+    const float radius = sqrtf(-2.f * logf(philox_uniform(ra)));
+    float sn, cs;
+    sincospif(2.f * philox_uniform(rb), &sn, &cs);
+    zc = radius * cs;
+    zs = radius * sn;
+}
+
+// the normals of the lane-of-four at box cells x4 .. x4+3 of row y
+__device__ __forceinline__ void ad_lane_normals(unsigned long long seed, int x4, int y, unsigned long long t, float (&z)[4])
+{
+    uint32_t r[4];
+    philox_lane_words(seed, x4, y, t, r);
+    ad_normal_pair(r[0], r[1], z[0], z[1]);
+    ad_normal_pair(r[2], r[3], z[2], z[3]);
+}
+
+// ... of the one box cell (x, y): its lane's words, its pair, its half of the pair
+__device__ __forceinline__ float ad_cell_normal(unsigned long long seed, int x, int y, unsigned long long t)
+{
+    uint32_t r[4];
+    philox_lane_words(seed, x, y, t, r);
+    const bool second = (x & 2) != 0;
+    float zc, zs;
+    ad_normal_pair(second ? r[2] : r[0], second ? r[3] : r[1], zc, zs);
+    return (x & 1) ? zs : zc;
+}
+
+__device__ __forceinline__ float ad_sqrt(float x) { return sqrtf(x); }
+__device__ __forceinline__ f2a ad_sqrt(f2a x) { return f2a{sqrtf(x.x), sqrtf(x.y)}; }
+// new_f < 0 -> 0 as a compare-and-select: false for NaN, which stays (the reference's `if (new_f < 0) new_f = 0`; not fmaxf)
+__device__ __forceinline__ float ad_clamp0(float x) { return x < 0.f ? 0.f : x; }
+__device__ __forceinline__ f2a ad_clamp0(f2a x) { return f2a{x.x < 0.f ? 0.f : x.x, x.y < 0.f ? 0.f : x.y}; }
+
+// react = G rho (1 - rho) + sqrt(Dg rho (1 - rho)) z, each product and the sum rounded on its own as the reference's C does; rho
+// outside [0, 1] makes the root, react and all nine links NaN, as there
+template <typename T>
+__device__ __forceinline__ T ad_noisy_react_t(float G, float Dg, T rho, T z)
+{
+    const T room = lb_splat<T>(1.f) - rho;
+    const T grow = (lb_splat<T>(G) * rho) * room;
+    const T root = ad_sqrt((lb_splat<T>(Dg) * rho) * room);
+    const T kick = root * z;
+    return grow + kick;
+}
+
+// The noisy form of ad_relax_t: the plain relaxation, then fl(w_k) react added last as the growth term is (ad_grow_t's order), then
+// the clamp.
+template <typename T>
+__device__ __forceinline__ void ad_relax_noisy_t(T &f0, T &f1, T &f2, T &f3, T &f4, T &f5, T &f6, T &f7, T &f8, float omega, float G,
+                                                 float Dg, T rho, T ux, T uy, T z)
+{
+    ad_relax_t<T, false>(f0, f1, f2, f3, f4, f5, f6, f7, f8, omega, G, rho, ux, uy);
+    const T react = ad_noisy_react_t<T>(G, Dg, rho, z);
+    const T w0 = lb_splat<T>(4.f / 9.f), w1 = lb_splat<T>(1.f / 9.f), w2 = lb_splat<T>(1.f / 36.f);
+    f0 = ad_clamp0(lb_fma(w0, react, f0));
+    f1 = ad_clamp0(lb_fma(w1, react, f1));
+    f3 = ad_clamp0(lb_fma(w1, react, f3));
+    f2 = ad_clamp0(lb_fma(w1, react, f2));
+    f4 = ad_clamp0(lb_fma(w1, react, f4));
+    f5 = ad_clamp0(lb_fma(w2, react, f5));
+    f7 = ad_clamp0(lb_fma(w2, react, f7));
+    f8 = ad_clamp0(lb_fma(w2, react, f8));
+    f6 = ad_clamp0(lb_fma(w2, react, f6));
 }
 
 // feq_k itself (the un-fused update_feq_diffusion): ad_relax_t's equilibrium with omega = 1

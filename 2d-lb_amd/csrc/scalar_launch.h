@@ -12,4 +12,12 @@ struct AdExtra {
     float *edge;        // nullptr in the PERIODIC family
     float G;            // growth rate of the Fisher term; used by the REACT instantiations only
 };
+// The noisy collision (lb_set_noise; philox.h has the stream): taken, behind AdExtra, by the noisy instantiations only.
+struct AdNoise {
+    float Dg;                   // the noise strength: react = G rho (1 - rho) + sqrt(Dg rho (1 - rho)) z
+    unsigned long long seed;    // the key
+    unsigned long long t;       // the noise counter of the launch's first collision
+    const float *field;         // the un-fused collision only: a supplied [ny][nx] field of normals in place of the stream, or nullptr
+};
+struct AdNoiseCell : AdNoise {};     // k_ad_tile4 only: the per-cell plan instead of the noise plane (kernels_scalar.h)
 inline long long ad_edge_device_floats(long long fpitch, int ny) { return 6 * fpitch + 6LL * ny; }

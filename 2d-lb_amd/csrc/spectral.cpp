@@ -288,6 +288,9 @@ int lb_run_screened(lb_spectral *sp, lb_sim *s, float scale, int n_steps)
     if (rc) return rc;
     if (!finite32(scale)) return fail(LB_ERR_ARG, "the velocity's factor must be finite");
     if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
+    // (scalar_step would refuse this too, but only with the solver borrowed and rho, u, v of the first step written)
+    if (s->noisy && s->ad_noise_field)
+        return fail(LB_ERR_STATE, "lb_run_screened: a noise field is set (lb_set_noise_field): only lb_collide_particles uses one; drop it with NULL first");
     if (n_steps == 0) return LB_OK;
     DeviceGuard guard(s->p.device);
     if ((rc = sp_borrow(sp, s->stream))) return rc;

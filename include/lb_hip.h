@@ -267,6 +267,29 @@ int lb_get_edge_state(lb_sim *s, float *out);
 int lb_set_edge_state(lb_sim *s, const float *in);
 int lb_set_velocity_from(lb_sim *s, lb_sim *flow);
 
+/* ---- the noisy collision of a scalar lattice (LB_SEM_DIFFUSION only: LB_ERR_STATE on a field of a coupled set, the Poisson
+ *      solver and every other kind) -- collide_particles_noisy_fisher, D2Q9_diffusion.cl:127-167, as reaction_diffusion/
+ *      noisy_fisher_wave.py drives it:  react = G rho (1 - rho) + sqrt(Dg rho (1 - rho)) z,  f_k = relaxed f_k + w_k react,
+ *      f_k < 0 -> 0 (a compare: rho outside [0, 1] makes all nine links NaN, as in the reference; lb_check counts such cells).
+ * z is a standard normal per cell and collision from a counter-based stream, drawn in registers inside the kernels: Philox4x32-10,
+ * key = the low and high word of `seed`, counter = (x / 4, y, t_lo, t_hi) for the four cells x = 4j .. 4j+3 of row y, t = the noise
+ * counter: the number of noisy collisions since the seed was set.  Word r -> u = float(r >> 9) 2^-23 + 2^-24; cells 0, 1 of the
+ * four get R cos(theta), R sin(theta), R = sqrt(-2 ln u(r0)), theta = 2 pi u(r1); cells 2, 3 the same from r2, r3.  The same
+ * bits in every kernel form, however a run is split, and after a checkpoint.  Not pyopencl's generator (the reference draws unseeded).
+ * lb_set_noise: Dg > 0 switches the handle to the noisy cell and sets t = 0; Dg == 0 switches back to the plain cell; a
+ *   negative or non-finite Dg: LB_ERR_ARG.  lb_run, lb_run_screened and lb_collide_particles honour it, one count of t per collision.
+ * lb_get_noise / lb_set_noise_counter: for checkpoints (any of Dg, seed, t may be NULL).
+ * lb_noise_fill: the [ny][nx] normals of noise counter t under the handle's seed, by the device function the kernels inline;
+ *   on_device != 0: out is a device pointer.  Waits for the handle's work.
+ * lb_set_noise_field: a supplied [ny][nx] field (on_device != 0: a device pointer; copied) that lb_collide_particles uses in
+ *   place of the stream -- the reference's random_normal buffer; NULL drops it.  While one is set lb_run returns LB_ERR_STATE
+ *   (the reference's run never uses a field twice).  Not part of a checkpoint. */
+int lb_set_noise(lb_sim *s, float Dg, uint64_t seed);
+int lb_get_noise(lb_sim *s, float *Dg, uint64_t *seed, uint64_t *t);
+int lb_set_noise_counter(lb_sim *s, uint64_t t);
+int lb_noise_fill(lb_sim *s, uint64_t t, float *out, int on_device);
+int lb_set_noise_field(lb_sim *s, const float *z, int on_device);
+
 /* ---- the LB Poisson solver (LB_SEM_POISSON; LB_ERR_STATE on every other handle) --------------------------------------
  * A fresh handle is the reference's start: f = 0, rho = 0, source = 0, corner state = 0, iteration counter = 0.
  * lb_set_poisson: rho_on_boundary, the value prescribed on the walls (default 0); react_factor, the `delta_t * D` of the
@@ -631,7 +654,8 @@ typedef enum {
     LB_VAR_STEP4 = 1 << 8,              /* four time steps per pass (nx >= 512; whole-grid handles of >= 128 rows, slabs of >= 64) */
     LB_VAR_TILES = 1 << 9,              /* four time steps per pass through 32 x 16 LDS tiles (k_tile4: whole-grid handles of
                                          * >= 64 x 64 cells; for small grids) */
-    LB_VAR_STEP4_NO_AHEAD = 1 << 10,    /* A/B switch of a thing on by default: k_step4 without its one-row-ahead gather */
+    LB_VAR_STEP4_NO_AHEAD = 1 << 10,    /* A/B switch of a thing on by default: k_step4 without its one-row-ahead gather; a noisy
+                                         * scalar lattice with LB_VAR_TILES: k_ad_tile4 draws per cell, without its noise plane in LDS */
     LB_VAR_NO_PRIO_TURNS = 1 << 11,     /* A/B switch of a thing on by default: k_step4 / k_step5 without the priority turns of
                                          * the two waves of a SIMD */
     LB_VAR_STEP5 = 1 << 12,             /* five time steps per pass on overlapping strips (k_step5: whole-grid handles where
