@@ -7,6 +7,8 @@
 //   S3_lds             rows, cols >= 1; 16 x rows x nx and 16 x cols x ny are what the plan says and <= SP_LDS_BYTES
 //   S4_coverage        the row blocks cover every row once, the column blocks every column once, no block is empty
 //   S5_twiddles        per admissible length: entry 0 is (1, 0), every entry within 6e-8 of exp(-2 pi i k / n) in double, inside the table
+// `--plan nx ny [nx ny ...]`: no sweep; one line per pair, "PLAN nx ny rows R cols C row_lds L col_lds L x r,r,... y r,r,..." ("-" for
+// an axis without a pass), so that a test can hold the shapes it lists to the plan the library makes of them.
 #include "spectral_plan.h"
 
 #include <math.h>
@@ -31,6 +33,22 @@ static bool smooth(int n)
 
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "--plan")) {
+        if (argc < 4 || argc % 2) return 2;
+        for (int i = 2; i + 1 < argc; i += 2) {
+            int nx = 0, ny = 0;
+            SpPlan p;
+            if (sscanf(argv[i], "%d", &nx) != 1 || sscanf(argv[i + 1], "%d", &ny) != 1 || !sp_plan(nx, ny, &p)) return 2;
+            printf("PLAN %d %d rows %d cols %d row_lds %d col_lds %d", nx, ny, p.rows, p.cols, p.row_lds_bytes, p.col_lds_bytes);
+            for (const SpAxis *a : {&p.x, &p.y}) {
+                printf(a == &p.x ? " x " : " y ");
+                if (!a->npass) printf("-");
+                for (int k = 0; k < a->npass; ++k) printf(k ? ",%d" : "%d", a->radix[k]);
+            }
+            printf("\n");
+        }
+        return 0;
+    }
     const bool thin = argc > 1 && !strcmp(argv[1], "--thin");
     Prop s1{"S1_admissible"}, s2{"S2_radix_product"}, s3{"S3_lds"}, s4{"S4_coverage"}, s5{"S5_twiddles"};
     std::vector<int> lens;

@@ -5,7 +5,9 @@ drop-in classes.
 Shapes: 3x3 and 5x4 (a row narrower than one lane-of-four group plus its tail; every stencil neighbour wraps), 30x18 (nx % 4 == 2,
 mixed radices, five workgroups of SN_ROWS = 4 rows, the last one ragged), 270x12 (k_sn_step's tile is k_ry_step's 256 cells: the row
 crosses it, so the LDS halo columns of the first tile come from the second tile and from the wrap, those of the second from the first
-and from the wrap; 12 rows are three workgroups, so every halo row is another workgroup's or the wrap), 20x12 for the phases.
+and from the wrap; 12 rows are three workgroups, so every halo row is another workgroup's or the wrap), 20x12 for the phases; 1000x12
+and 12x1000 (the solver's batched passes, which begin at 512 points an axis: column blocks of cols = 3 with the last one a column
+short, row blocks of rows = 3 with the last one a row short -- tests/test_spectral_cpu.py asks sp_plan for both; four tiles a row).
 Bounds: the project's parity contract (contract_tol) in f, feq, rho, u, v and nutrient_bounds in psi and F, as tests/test_nutrient_cpu.py
 states them."""
 import ctypes as ct
@@ -29,6 +31,7 @@ pytestmark = pytest.mark.gpu
 F = np.float32
 # model / fixture name -> Nutrient_Set.get_fields key
 KEYS = dict(f="f", feq="feq", rho="rho", u="u", v="v", psi="psi", Fx="pseudo_force_x", Fy="pseudo_force_y")
+BOXES = ((270, 12), (1000, 12), (12, 1000))                           # test_row_across_the_tile_boundary_follows_the_model's
 CASE = dict(G=0.01, scale=-0.05, rho_o=1., G_chen=-1., lam=1.)        # the issue's case at N = 10, vc = 0.5
 
 
@@ -91,10 +94,12 @@ def test_run_follows_reference_fixture(lbhip, name, planar):
     s.close()
 
 
+@pytest.mark.parametrize("box", BOXES, ids=lambda b: "%dx%d" % b)
 @pytest.mark.parametrize("clumpy", (False, True))
-def test_row_across_the_tile_boundary_follows_the_model(lbhip, clumpy):
-    """270 x 12: no fixture; the float64 model from the same float32 start, within the contract at 1, 10 and 50 steps."""
-    nx, ny = 270, 12
+def test_row_across_the_tile_boundary_follows_the_model(lbhip, clumpy, box):
+    """270 x 12, 1000 x 12, 12 x 1000: no fixture; the float64 model from the same float32 start, within the contract at 1, 10 and 50
+    steps."""
+    nx, ny = box
     m = droplet_case(nx, ny, clumpy)
     s = set_of(nx, ny, (0.8, 1.25), CASE, clumpy, m.f)
     done = 0
@@ -102,7 +107,7 @@ def test_row_across_the_tile_boundary_follows_the_model(lbhip, clumpy):
         s.run(n - done), m.run(n - done)
         done = n
         assert float(np.sqrt(m.u ** 2 + m.v ** 2).max()) < 0.15
-        compare("270x12 %s after %d steps / float64 model" % ("clumpy" if clumpy else "plain", n), m.params, n, got_of(s, all_keys(clumpy)), m.state())
+        compare("%dx%d %s after %d steps / float64 model" % (nx, ny, "clumpy" if clumpy else "plain", n), m.params, n, got_of(s, all_keys(clumpy)), m.state())
     s.close()
 
 
@@ -133,7 +138,7 @@ def test_stages_follow_phases_fixture_and_the_fused_step(lbhip, variant):
 
 
 # ---- what the product computes twice: bitwise ------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", ((5, 4), (30, 18), (270, 12)))
+@pytest.mark.parametrize("shape", ((5, 4), (30, 18), (270, 12), (1000, 12)))
 @pytest.mark.parametrize("clumpy", (False, True))
 def test_one_run_equals_single_steps_bitwise(lbhip, shape, clumpy):
     m = droplet_case(shape[0], shape[1], clumpy)

@@ -4,7 +4,27 @@
 Shapes -- the smallest at which each thing can go wrong: (2, 3), (5, 3) one pass per radix; (4, 4), (8, 6) mixed radices; (30, 18)
 mixed, not square, a lattice pitch above nx; (50, 50) the reference's default; (64, 48) a row of exactly one wave; (256, 5), (5, 256) a
 long row over a short column and the other way round; (96, 250) mixed radices, both axes longer than a wave; (4096, 4), (4, 4096)
-the limit on each axis.
+the limit on each axis.  Of these only the last two have a batch (cols = 16, rows = 16), and their batched axis is one radix-4 pass
+whose every twiddle is tw[0].
+
+Batched shapes (BATCHED) -- a workgroup takes `rows` whole rows or `cols` adjacent columns where an axis has 512 points or more
+(spectral_plan.cpp); each is the smallest that reaches its case; rows (ny % rows), cols (nx % cols), x passes, y passes, as
+tests/test_spectral_cpu.py asks sp_plan itself:
+    1 x 1, 1 x 6, 6 x 1   1, 1             an axis of one point: no pass at all
+    625 x 48     1, 2 (1)   [5,5,5,5] [3,4,4]           the smallest ragged column batch; x = 5^4
+    1000 x 30    1, 3 (1)   [5,5,5,4,2] [5,3,2]         an everyday width, ragged
+    800 x 640    1, 3 (2)   [5,5,4,4,2] [5,4,4,4,2]     two columns missing from the last block; an odd number of batched passes
+    48 x 1000    3 (1), 1   [3,4,4] [5,5,5,4,2]         a ragged row batch
+    250 x 625    2 (1), 1   [5,5,5,2] [5,5,5,5]         a row batch of four passes; y = 5^4
+    64 x 3750    14 (12), 1 [4,4,4] [5,5,5,5,3,2]       a large ragged row batch; 60000 B of column LDS
+    6 x 2187     8 (3), 1   [3,2] [3 x 7]               y = 3^7
+    3125 x 6     1, 12 (5)  [5 x 5] [3,2]               x = 5^5; a wide ragged column batch
+    3600 x 3     1, 14 (2)  [5,5,3,3,4,4] [3]           every radix but 2 in one axis
+    4096 x 250   1, 16 (0)  [4 x 6] [5,5,5,2]           the widest batch there is: 64000 B of column LDS, 65536 B of row LDS
+    512 x 2048   2 (0), 2 (0) [4,4,4,4,2] [4,4,4,4,4,2] both passes batched; column LDS exactly 65536 B with two columns
+The ragged ones also: a charge that lives in the last column or row only, and transforms of one array beside sentinels in the two others.
+The coupled calls (the real plane in, u and v out: k_sp_rows_fwd<true>, k_sp_rows_inv<true>) at 48 x 1000, 1000 x 30 and 250 x 625,
+bitwise where the small shapes are and against the float64 model within the contract.
 
 Accuracy: E = max |got - m64| / max |m64| against the float64 model, for the screened spectrum, for the gradient (both components
 over max |grad phi|: it is one vector field, and one component of a single mode is exactly zero) and for a forward / inverse round
@@ -31,7 +51,11 @@ from scalar_model import contract_tol
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(2, 3), (5, 3), (4, 4), (8, 6), (30, 18), (50, 50), (64, 48), (256, 5), (5, 256), (96, 250), (4096, 4), (4, 4096)]
+PLAIN = [(2, 3), (5, 3), (4, 4), (8, 6), (30, 18), (50, 50), (64, 48), (256, 5), (5, 256), (96, 250), (4096, 4), (4, 4096)]
+BATCHED = [(1, 1), (1, 6), (6, 1), (625, 48), (1000, 30), (800, 640), (48, 1000), (250, 625), (64, 3750), (6, 2187), (3125, 6), (3600, 3),
+           (4096, 250), (512, 2048)]
+SHAPES = PLAIN + BATCHED
+RAGGED = [(625, 48), (48, 1000), (64, 3750), (3125, 6)]          # a last column block / row block with padding, narrow and wide
 EPS = 2. ** -23
 LAM = 1.0
 
@@ -111,13 +135,19 @@ def inputs(nx, ny):
                 nyquist=nyq.astype(np.float32))
 
 
+def over(err, top):
+    """err / top; a field the model has identically zero (the gradient on a 1 x 1 box: its only wave index is 0) is held to err itself, the
+    charges being of order one."""
+    return err / top if top > 0 else err
+
+
 def rel(got, want):
-    return np.abs(np.asarray(got, np.complex128) - want).max() / np.abs(want).max()
+    return over(np.abs(np.asarray(got, np.complex128) - want).max(), np.abs(want).max())
 
 
 def grad_rel(gx, gy, wx, wy):
     top = max(np.abs(wx).max(), np.abs(wy).max())
-    return max(np.abs(np.asarray(gx, np.complex128) - wx).max(), np.abs(np.asarray(gy, np.complex128) - wy).max()) / top
+    return over(max(np.abs(np.asarray(gx, np.complex128) - wx).max(), np.abs(np.asarray(gy, np.complex128) - wy).max()), top)
 
 
 @pytest.mark.parametrize("nx,ny", SHAPES)
@@ -158,6 +188,44 @@ def test_the_nyquist_gradient_keeps_its_imaginary_part(solvers):
     assert np.abs(xg.real).max() <= 8 * EPS * want and abs(np.abs(xg.imag).max() - want) <= 8 * EPS * want
 
 
+def sentinel(nx, ny, k):
+    """(nx, ny) complex64 without a NaN, no two elements alike, none like another k's."""
+    a = (np.arange(2 * nx * ny, dtype=np.float64) + 1.) * (k + 2) + 0.25 * (k + 1)
+    a = np.where(np.arange(2 * nx * ny) % 2, -a, a).astype(np.float32)
+    return np.asfortranarray(a.view(np.complex64).reshape((nx, ny), order='F'))
+
+
+@pytest.mark.parametrize("nx,ny", RAGGED)
+def test_a_ragged_last_batch_neither_leaks_its_padding_nor_leaves_the_array(solvers, nx, ny):
+    """The last block of the batched axis is zero-filled past the array and guarded on the way out.  A charge that lives in the last
+    column only, and one in the last row only -- the padding's neighbours in LDS --, solve to the float64 model within the accuracy
+    test's bound; a transform of one array, forward or inverse, leaves the two other arrays' bits alone and changes its own."""
+    sp = solvers(nx, ny)
+    rng = np.random.RandomState(nx + ny)
+    bad = []
+    for name, sel in (("last column", (nx - 1, slice(None))), ("last row", (slice(None), ny - 1))):
+        charge = np.zeros((nx, ny), np.float32)
+        charge[sel] = 1. + 0.5 * rng.standard_normal(charge[sel].shape)
+        w, n32, g = M.solve(charge, LAM), M.solve(charge, LAM, np.complex64), sp.solve(charge)
+        for what, e_gpu, e_np in (("spectrum", rel(g[0], w[0]), rel(n32[0], w[0])),
+                                  ("gradient", grad_rel(g[1], g[2], w[1], w[2]), grad_rel(n32[1], n32[2], w[1], w[2]))):
+            print("ACCURACY %4d x %-4d %-11s %-10s E_gpu %.3e E_numpy32 %.3e ratio %.2f bound %.3e"
+                  % (nx, ny, name, what, e_gpu, e_np, e_gpu / max(e_np, 1e-30), 4 * max(e_np, EPS)))
+            if not e_gpu <= 4 * max(e_np, EPS):
+                bad.append((name, what, e_gpu, e_np))
+    assert bad == []
+    marks = [sentinel(nx, ny, k) for k in range(3)]
+    for which in range(3):
+        for forward in (1, 0):
+            for k in range(3):
+                sp.put(k, marks[k])
+            sp.check(sp.L.lb_spectral_transform(sp.h, which, forward))
+            after = sp.all()
+            for k in range(3):
+                same = after[k].tobytes() == marks[k].tobytes()
+                assert same == (k != which), (which, forward, k)
+
+
 # ---- the coupling to a scalar lattice ---------------------------------------------------------------------------------------
 FIELDS = ("f", "rho", "u", "v")
 
@@ -182,7 +250,7 @@ def case(nx, ny):
     return p["omega"], p["lb_G"], p["scale"], M.noisy_droplet(nx, ny, max(nx, ny) / 3., 0.5, 7 * nx + ny)
 
 
-@pytest.mark.parametrize("nx,ny", [(30, 18), (5, 3), (64, 48)])
+@pytest.mark.parametrize("nx,ny", [(30, 18), (5, 3), (64, 48), (48, 1000), (1000, 30)])
 def test_the_velocity_is_the_float32_product_with_the_solves_gradient(solvers, nx, ny):
     from LB_D2Q9 import _native
     sp = solvers(nx, ny)
@@ -210,7 +278,7 @@ def test_the_velocity_is_the_float32_product_with_the_solves_gradient(solvers, n
 
 @pytest.mark.parametrize("bc", ["open", "periodic"])
 @pytest.mark.parametrize("n", [1, 5])
-@pytest.mark.parametrize("nx,ny", [(30, 18), (5, 3)])
+@pytest.mark.parametrize("nx,ny", [(30, 18), (5, 3), (48, 1000), (1000, 30)])
 def test_run_screened_equals_the_pairs_of_calls_bitwise(solvers, nx, ny, n, bc):
     from LB_D2Q9 import _native
     sp = solvers(nx, ny)
@@ -263,6 +331,32 @@ def test_run_screened_follows_the_fixture(solvers, bc):
         # (lb_check sums the populations the step left: its growth term is in them)
         after = rho51.sum() + float(g["G"]) * (rho51 * (1. - rho51)).sum()
         assert abs(sim.check()["sum_rho"] - after) <= 2 * rho50.size * contract_tol(1)["rho"]
+    sim.close()
+
+
+@pytest.mark.parametrize("bc", ["open", "periodic"])
+@pytest.mark.parametrize("nx,ny", [(1000, 30), (48, 1000), (250, 625)])
+def test_run_screened_follows_the_model_through_the_batched_kernels(solvers, nx, ny, bc):
+    """No fixture at these sizes: the float64 model from the same float32 droplet, started as lattice() starts, after 1 and 5 steps
+    within the contract.  The real plane in and u, v out go through row batches of 3 (ragged) and 2 (ragged), the columns through a
+    ragged batch of 3."""
+    from LB_D2Q9 import _native
+    sp = solvers(nx, ny)
+    omega, G, scale, rho0 = case(nx, ny)
+    m = M.ScreenedFisherModel(nx, ny, omega, G, LAM, scale, bc=bc, dtype=np.float64)
+    m.redo_initial_condition(rho0)
+    sim = lattice(nx, ny, omega, G, bc, rho0, sp, scale)
+    bad, done = [], 0
+    for n in (1, 5):
+        _native.check(sp.L.lb_run_screened(sp.h, sim._h, float(scale), n - done))
+        m.run(n - done)
+        done = n
+        top = float(np.sqrt(m.u ** 2 + m.v ** 2).max())
+        print("MODEL %d x %d %s step %d max |u| %.3f" % (nx, ny, bc, n, top))
+        assert top < 0.2
+        want = {"%s_%s_%d" % (bc, k, n): getattr(m, k) for k in FIELDS}
+        bad += within_contract(sim.get_fields(FIELDS), want, bc, n, "run_screened %dx%d" % (nx, ny))
+    assert bad == []
     sim.close()
 
 

@@ -195,6 +195,48 @@ def test_the_plan_keeps_its_invariants_under_the_sanitizers(tmp_path):
     _assert_all_hold(run)
 
 
+# (nx, ny) -> (rows, cols, ny % rows, nx % cols, x passes, y passes): what tests/test_gpu_spectral.py's docstring says of its batched shapes
+# and tests/test_gpu_nutrient.py's of its two wide boxes
+BATCHED_PLANS = {
+    (1, 1): (1, 1, 0, 0, [], []), (1, 6): (1, 1, 0, 0, [], [3, 2]), (6, 1): (1, 1, 0, 0, [3, 2], []),
+    (625, 48): (1, 2, 0, 1, [5, 5, 5, 5], [3, 4, 4]), (1000, 30): (1, 3, 0, 1, [5, 5, 5, 4, 2], [5, 3, 2]),
+    (800, 640): (1, 3, 0, 2, [5, 5, 4, 4, 2], [5, 4, 4, 4, 2]), (48, 1000): (3, 1, 1, 0, [3, 4, 4], [5, 5, 5, 4, 2]),
+    (250, 625): (2, 1, 1, 0, [5, 5, 5, 2], [5, 5, 5, 5]), (64, 3750): (14, 1, 12, 0, [4, 4, 4], [5, 5, 5, 5, 3, 2]),
+    (6, 2187): (8, 1, 3, 0, [3, 2], [3] * 7), (3125, 6): (1, 12, 0, 5, [5] * 5, [3, 2]),
+    (3600, 3): (1, 14, 0, 2, [5, 5, 3, 3, 4, 4], [3]), (4096, 250): (1, 16, 0, 0, [4] * 6, [5, 5, 5, 2]),
+    (512, 2048): (2, 2, 0, 0, [4, 4, 4, 4, 2], [4, 4, 4, 4, 4, 2]),
+    (4096, 4): (1, 16, 0, 0, [4] * 6, [4]), (4, 4096): (16, 1, 0, 0, [4], [4] * 6),
+    (1000, 12): (1, 3, 0, 1, [5, 5, 5, 4, 2], [3, 4]), (12, 1000): (3, 1, 1, 0, [3, 4], [5, 5, 5, 4, 2]),
+}
+
+
+def test_the_batched_shapes_of_the_gpu_tests_have_the_plans_their_docstrings_state(tmp_path):
+    """sp_plan itself (spectral_plan_props --plan), not a restatement: rows, cols, what the last block lacks, the passes of both axes and
+    the LDS of each batched shape the GPU tests list; every other shape of theirs has no batch."""
+    import test_gpu_nutrient as TN
+    import test_gpu_spectral as TG
+    assert set(TG.BATCHED) <= set(BATCHED_PLANS) and set(TG.SHAPES) == set(TG.PLAIN) | set(TG.BATCHED)
+    assert {(1000, 12), (12, 1000)} <= set(TN.BOXES)
+    shapes = sorted(set(BATCHED_PLANS) | set(TG.SHAPES) | set(TN.BOXES))
+    exe = _compile(str(tmp_path / "spectral_plan_props"), ["-O2"])
+    run = subprocess.run([exe, "--plan"] + [str(n) for s in shapes for n in s], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0, run.stderr[-2000:]
+    print(run.stdout)
+    got = {}
+    for m in re.finditer(r"^PLAN (\d+) (\d+) rows (\d+) cols (\d+) row_lds (\d+) col_lds (\d+) x (\S+) y (\S+)$", run.stdout, re.M):
+        nx, ny, rows, cols, row_lds, col_lds = (int(m.group(i)) for i in range(1, 7))
+        px, py = ([] if m.group(i) == "-" else [int(r) for r in m.group(i).split(",")] for i in (7, 8))
+        got[(nx, ny)] = (rows, cols, ny % rows, nx % cols, px, py)
+        assert row_lds == 16 * rows * nx <= 65536 and col_lds == 16 * cols * ny <= 65536
+        assert px == M.radix_passes(nx) and py == M.radix_passes(ny)
+    assert sorted(got) == shapes
+    for s in shapes:
+        if s in BATCHED_PLANS:
+            assert got[s] == BATCHED_PLANS[s], (s, got[s])
+        else:
+            assert got[s][:2] == (1, 1), (s, got[s])
+
+
 def test_the_model_restates_the_plans_passes():
     """radix_passes (the model's) is the order spectral_plan.cpp writes: 5s, 3s, 4s, a 2."""
     src = open(os.path.join(CSRC, "spectral_plan.cpp")).read()
