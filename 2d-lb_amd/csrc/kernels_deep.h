@@ -366,6 +366,26 @@ __device__ __forceinline__ void deep_row_take_lds(const f4a (*S)[64], int lane, 
     }
 }
 
+// A row taken by nine 16-byte LDS reads is nine <4 x float> values whose halves collide_row (kernels_fused.h) then works on as pairs.
+// The optimiser sees the same operation on both halves of one 16-byte value and widens it to four floats; the back end splits a
+// four-float add, multiply or fma into two packed instructions, but a four-float SUBTRACTION into four scalar ones: 20 v_sub_f32
+// per row in the first collision of a front wave -- and in no later stage, whose rows are put together from pairs.  So the two halves
+// of each plane pass through an empty asm, as pairs, directly in front of that collision (behind every join of the take's branches:
+// in front of one, the pairs are copied into place, 80 moves per row pair): the differences come out as v_pk_add_f32 with `neg`.
+// (Plane 0 enters sums only.)  Where: a periodic box without a mask, 670 -> 658 vector instructions per row of a front wave's rolled
+// loop.  With walls or a mask the first collision's selects and boundary rule already take the row apart cell by cell: the same
+// vector instructions with or without (pipe 984 / 984 per row, periodic + mask 791 / 791), so those kernels stay as they were.
+constexpr bool deep_pair_typed_pays(bool mask, int bc) { return !mask && bc == LB_BC_PERIODIC; }
+__device__ __forceinline__ void deep_pair_typed(f4a (&q)[9])
+{
+#pragma unroll
+    for (int k = 1; k < 9; ++k) {
+        f2a lo = q[k].xy, hi = q[k].zw;
+        asm volatile("" : "+v"(lo), "+v"(hi));
+        q[k] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
+    }
+}
+
 // store_row9 (kernels_fused.h) through a buffer resource based at the row
 __device__ __forceinline__ void deep_row_store(const StepArgs &a, int r, int x4, const f4a (&t)[9])
 {
@@ -490,6 +510,7 @@ __device__ __forceinline__ void deep_iter(const StepArgs &a, const DeepCtx &cx, 
     const uc4 mk = cur.mk;
     if (ROLE != DEEP_BACK && cur.have) {
         gather_merge<BC, true>(a, x4, q1, cur.wp);
+        if constexpr (ROLE == DEEP_FRONT && deep_pair_typed_pays(MASK, BC)) deep_pair_typed(q1);
         LB_DEEP_NOCOLLIDE collide_row<BC, MASK, true>(a, x4, a.y0 + cur.rr, q1, mk, r4, u4, v4);
     }
     if (NST == 1) {

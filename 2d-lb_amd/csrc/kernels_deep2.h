@@ -29,6 +29,19 @@
 // Issue priority.  Every front wave raises its priority once, at entry (deep2_set_prio below): without it the older of a CU's two
 // workgroups is served first on every SIMD and the younger runs a quarter of the launch alone.
 //
+// Steady trips in pairs (deep2_pairs_front / deep2_pairs_back below).  Both roles keep two stage windows in registers, and in a loop
+// whose body is one trip the values carried to the next trip sit in fixed registers: the row a stage has just produced is live beside
+// the window the next stage still gathers from, so the compiler copies -- of the 121 register moves per row in the front loop and the 83 in the back loop
+// 27 and 26 are of that kind and compute nothing.  With two trips per body the two names swap: a periodic box without a mask runs an unconditional paired loop
+// while two more trips lie inside the wave's own positions (and inside `trips`), then the guarded single-trip loop for what is left --
+// at most one more position of its own, then the other waves' trips.  Every trip, paired or not, executes the same two barriers, so
+// the four waves of a workgroup stay matched whatever loop each is in (the halves of a pair differ by a row, the back waves run F
+// trips behind).  Three things make the pair what it should be: deep2_settle (no scratch in the back wave), deep2_trip_fence (the
+// back wave's work stays between its trip's barriers) and, in the front wave, deep_pair_typed (kernels_deep.h: stage 1's twenty scalar
+// subtractions packed).  Per strip and row 1149 -> 1092.5 vector instructions (-4.9 %, profiles/deep2_pairs_isa.txt); on the device
+// SQ_INSTS_VALU 3.236e8 -> 3.068e8 per 8192^2 launch (-5.2 %).  What that is worth in time, and which instantiations pair:
+// deep2_pairs_front below, profiles/deep2_pairs_ab.txt.
+//
 // The launch moves the same 72 B per cell; same cell functions, same operations in the same order: bitwise equal to k_step.
 #pragma once
 
@@ -41,6 +54,17 @@ constexpr int deep2_split(int D) { return D >= 8 ? 4 : (D + 1) / 2; }          /
 constexpr int deep2_rw_front(int D) { return deep2_split(D) - 2 >= 2 ? 2 : 1; }
 constexpr int deep2_rw_back(int D) { return (D - deep2_split(D) + 1) - 2 >= 2 ? 2 : 1; }
 constexpr int DEEP2_WAVES = 4;
+// Which instantiations run their steady trips in pairs (see the header), per role.  Measured, 8192^2 periodic, 84 steps pinned to
+// k_deep2<7>, five rounds alternated on one box, k MLUPS (profiles/deep2_pairs_ab.txt):
+//     parent 510.7-511.9 | pair-typed stage 1 alone 511.9-512.5 | + front pairs 512.7-513.6 | + back pairs (this) 515.0-515.9
+// every line of each step above every line of the step before; +0.8 % in all, for 5.2 % fewer vector instructions on the device: the
+// launch does not follow its vector-instruction count the way its 82 % busy vector ALU suggested, what the waves wait for at the
+// barriers grows by what they save (SQ_WAIT_ANY 1.82e8 -> 1.92e8 per launch, SQ_WAVE_CYCLES 8.15e8 -> 8.10e8).  The same pairs WITHOUT
+// deep2_trip_fence: 456.8-459.6 against the parent's 505.0-505.4 on another box, -9.5 %.
+// With walls or a mask neither role can be paired without scratch (both roles 80-224 B per lane, the front alone 80-192 B, where the
+// parent has 0-64 B: profiles/deep2_pairs_isa.txt), so those instantiations stay as they were, instruction for instruction.
+constexpr bool deep2_pairs_front(bool mask, int bc) { return !mask && bc == LB_BC_PERIODIC; }
+constexpr bool deep2_pairs_back(bool mask, int bc) { return !mask && bc == LB_BC_PERIODIC; }
 
 // The trip's two barriers (see the header).  NOT __syncthreads(): that is a fence as well -- `s_waitcnt vmcnt(0)` in front of the
 // barrier --, and at every trip a back wave would wait out the nine stores it has just issued, a front wave the row it has just asked
@@ -48,6 +72,14 @@ constexpr int DEEP2_WAVES = 4;
 // 8192^2 launch where k_deep<7> takes 0.89).  What the waves hand each other goes through LDS: an LDS instruction that has completed
 // (lgkmcnt) is visible to the workgroup.
 __device__ __forceinline__ void deep2_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// (a steady trip's: the diagnostic build can run the steady state without them -- timing only, races: wrong results)
+__device__ __forceinline__ void deep2_steady_barrier(const StepArgs &a)
+{
+#ifdef LB_DIAG
+    if (a.diag & (1 << 24)) return;
+#endif
+    deep2_barrier();
+}
 
 // Static issue priority by role.  The hardware gives a SIMD's vector issue to the higher priority, then to the OLDER wave: at equal
 // priority the workgroup a CU was given first wins on all four SIMDs, runs as if alone and ends at three quarters of the launch, and
@@ -107,20 +139,35 @@ __device__ __forceinline__ void deep2_front(const StepArgs &a, const int x0, con
     deep_row_issue_lds<BC, MASK>(a, row_at(0), cx.x4, cx.dma_off, ra);
     int trip = 0;
     deep2_front_fill<BC, MASK, F, RW, DOWN, 1>(a, cx, st, ra, rb, trip);
-    if ((F - 1) & 1) ra = rb;                           // (position F - 1 is in ra or rb by its parity)
-    for (; trip < trips; ++trip) {
-#ifdef LB_DIAG
-        if (!(a.diag & (1 << 24)))                      // timing only: no barriers in the steady state (races: wrong results)
-#endif
-        deep2_barrier();
-        if (trip < cx.n_iter) {
-            deep_iter<BC, MASK, false, F, RW, 1, DOWN, F, -1, DEEP_FRONT>(a, cx, trip, st, ra, rb);
-            ra = rb;
+    if constexpr (!deep2_pairs_front(MASK, BC)) {
+        if ((F - 1) & 1) ra = rb;                       // (position F - 1 is in ra or rb by its parity)
+        for (; trip < trips; ++trip) {
+            deep2_steady_barrier(a);
+            if (trip < cx.n_iter) {
+                deep_iter<BC, MASK, false, F, RW, 1, DOWN, F, -1, DEEP_FRONT>(a, cx, trip, st, ra, rb);
+                ra = rb;
+            }
+            deep2_steady_barrier(a);
         }
-#ifdef LB_DIAG
-        if (!(a.diag & (1 << 24)))
-#endif
-        deep2_barrier();
+    } else {
+        // position i is in ra for even i, in rb for odd i: the two buffers swap roles by argument order, the parity is a constant
+        constexpr int P0 = (F - 1) & 1;
+        Row1 &r0 = P0 ? rb : ra, &r1 = P0 ? ra : rb;
+        const int paired = min(cx.n_iter, trips);
+        for (; trip + 1 < paired; trip += 2) {
+            deep2_steady_barrier(a);
+            deep_iter<BC, MASK, false, F, RW, 1, DOWN, F, P0, DEEP_FRONT>(a, cx, trip, st, r0, r1);
+            deep2_steady_barrier(a);
+            deep2_steady_barrier(a);
+            deep_iter<BC, MASK, false, F, RW, 1, DOWN, F, 1 - P0, DEEP_FRONT>(a, cx, trip + 1, st, r1, r0);
+            deep2_steady_barrier(a);
+        }
+        // the rest: at most one more position of mine (trip + 1 >= n_iter: the parity is still P0), then the other waves' trips
+        for (; trip < trips; ++trip) {
+            deep2_steady_barrier(a);
+            if (trip < cx.n_iter) deep_iter<BC, MASK, false, F, RW, 1, DOWN, F, P0, DEEP_FRONT>(a, cx, trip, st, r0, r1);
+            deep2_steady_barrier(a);
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // (the row gathered behind the last position)
 }
@@ -135,6 +182,33 @@ __device__ __forceinline__ void deep2_take(const DeepCtx &cx, Row1 &cur)
     if (MASK) cur.mk = __builtin_bit_cast(uc4, reinterpret_cast<const unsigned *>(cx.ho[9])[cx.lane]);
     cur.have = true;
 }
+
+// Between the two trips of a pair (deep2_back below).  A stage's row enters the next register window for the trips to come; nothing in
+// its own trip reads more of it than the three links pulled from ahead.  In a rolled loop the row is in the window's registers at the
+// back edge.  With two trips in one body the compiler sinks the row's last nine fma below the trip's stores, into the next trip, and
+// keeps their operands -- the row before relaxation and its equilibria, twice the registers -- live across the barrier and the take:
+// 152 B of scratch per lane, 17 scratch instructions per pair.  An empty asm on the windows' d and e rows ends the trip for them: no
+// scratch, 250 registers as before.  (Window 1 takes the row handed over, a load: nothing to sink; of an LDS window's row only link 0
+// stays in registers.)
+template <int RW, int NL>
+__device__ __forceinline__ void deep2_settle(DeepState<RW, NL> &st)
+{
+#pragma unroll
+    for (int k = 1; k < RW; ++k) {
+        Window &w = st.w[k];
+        asm volatile("" : "+v"(w.d0), "+v"(w.d1), "+v"(w.d3), "+v"(w.e2), "+v"(w.e5), "+v"(w.e6));
+    }
+#pragma unroll
+    for (int k = 0; k < NL; ++k) asm volatile("" : "+v"(st.d0[k]));
+}
+
+// Around a paired trip's work (deep2_back below).  The barriers are asm statements: vector instructions move across them freely.  In
+// the rolled loop the back edge keeps a trip's work between its two barriers and leaves the take alone between the second and the
+// next first (30 instructions).  In a two-trip body the scheduler sinks the tail of one trip and hoists the head of the next into
+// that gap, 163 and 79 instructions -- which the front waves, who have nothing to do there, spend waiting at the first barrier:
+// SQ_WAIT_ANY 1.83e8 -> 4.23e8 per 8192^2 launch, the launch 9.5 % LONGER with 5.2 % fewer vector instructions
+// (profiles/deep2_pairs_ab.txt section 1).  A scheduling fence behind the first barrier and in front of the second: 11 and 16.
+__device__ __forceinline__ void deep2_trip_fence() { __builtin_amdgcn_sched_barrier(0); }
 
 template <int BC, bool MASK, bool MACRO, int DB, int RW, bool DOWN, int NST>
 __device__ __forceinline__ void deep2_back_fill(const StepArgs &a, const DeepCtx &cx, DeepState<RW, DB - 1 - RW> &st, Row1 &cur, int &j)
@@ -173,17 +247,31 @@ __device__ __forceinline__ void deep2_back(const StepArgs &a, const int x0, cons
     }
     int j = 0;
     deep2_back_fill<BC, MASK, MACRO, DB, RW, DOWN, 1>(a, cx, st, cur, j);
+    if constexpr (deep2_pairs_back(MASK, BC)) {
+        constexpr int P0 = (DB - 1) & 1;
+        const int paired = min(cx.n_iter, trips - F);
+        for (; j + 1 < paired; j += 2) {
+            deep2_take<MASK>(cx, cur);
+            deep2_steady_barrier(a);
+            deep2_trip_fence();
+            deep_iter<BC, MASK, MACRO, DB, RW, 0, DOWN, DB, P0, DEEP_BACK>(a, cx, j, st, cur, cur);
+            deep2_settle(st);
+            deep2_trip_fence();
+            deep2_steady_barrier(a);
+            deep2_take<MASK>(cx, cur);
+            deep2_steady_barrier(a);
+            deep2_trip_fence();
+            deep_iter<BC, MASK, MACRO, DB, RW, 0, DOWN, DB, 1 - P0, DEEP_BACK>(a, cx, j + 1, st, cur, cur);
+            deep2_trip_fence();
+            deep2_steady_barrier(a);
+        }
+    }
+    // (behind a paired loop: at most one more position of mine, then the other waves' trips)
     for (; j + F < trips; ++j) {
         if (j < cx.n_iter) deep2_take<MASK>(cx, cur);
-#ifdef LB_DIAG
-        if (!(a.diag & (1 << 24)))
-#endif
-        deep2_barrier();
+        deep2_steady_barrier(a);
         if (j < cx.n_iter) deep_iter<BC, MASK, MACRO, DB, RW, 0, DOWN, DB, -1, DEEP_BACK>(a, cx, j, st, cur, cur);
-#ifdef LB_DIAG
-        if (!(a.diag & (1 << 24)))
-#endif
-        deep2_barrier();
+        deep2_steady_barrier(a);
     }
 }
 
