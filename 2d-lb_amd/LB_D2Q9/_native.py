@@ -59,6 +59,10 @@ class NutrientParams(ct.Structure):      # lb_nutrient_params
     _fields_ = [("G", ct.c_float), ("scale", ct.c_float), ("clumpy", ct.c_int32), ("rho_o", ct.c_float), ("G_chen", ct.c_float)]
 
 
+class ExpansionParams(ct.Structure):     # lb_expansion_params
+    _fields_ = [("zero_cutoff", ct.c_float)]
+
+
 class LbError(RuntimeError):
     pass
 
@@ -125,6 +129,9 @@ SIGNATURES = {
     "lb_run_nutrient": ([_h, _hp, _I, ct.POINTER(NutrientParams), _I],), "lb_nutrient_velocity": ([_h, _hp, _I, _F, _I],),
     "lb_update_forces_nutrient": ([_hp, _I, ct.POINTER(NutrientParams)],), "lb_collide_nutrient": ([_hp, _I, ct.POINTER(NutrientParams)],),
     "lb_get_nutrient_fields": ([_hp, _I, _vp, _vp, _vp],),
+    # noisy strains on a shared nutrient (2 ... 4 scalar lattices, the nutrient last; the parameters: ExpansionParams)
+    "lb_run_expansion": ([_hp, _I, ct.POINTER(ExpansionParams), _I],), "lb_update_hydro_expansion": ([_hp, _I, ct.POINTER(ExpansionParams)],),
+    "lb_collide_expansion": ([_hp, _I, ct.POINTER(ExpansionParams)],),
 }
 EXPORTS = tuple(SIGNATURES)
 

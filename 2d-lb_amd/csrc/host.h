@@ -13,10 +13,12 @@
 //                  spectral_plan.cpp its plan (spectral_plan.h): no HIP
 //   nutrient.cpp   a population and its nutrient under the solver's velocity (lb_*_nutrient: two scalar lattices and an lb_spectral,
 //                  no handle kind of its own); emits kernels_nutrient.h
+//   expansion.cpp  noisy strains on a shared nutrient (lb_*_expansion: 2 ... 4 scalar lattices, no handle kind of its own); emits
+//                  kernels_expansion.h
 // Small kernels are emitted by the one unit that includes their header: kernels_phases.h + kernels_check.h by lb_hip.cpp,
 // kernels_halo.h by slab.cpp, kernels_scalar.h by scalar.cpp (its health check's first pass only: check_reduce.h is shared, the folding
 // pass is lb_hip.cpp's), kernels_multifield.h by multifield.cpp, kernels_poisson.h by poisson.cpp, kernels_porous.h by porous.cpp,
-// kernels_multifluid.h by multifluid.cpp, kernels_rocket.h by rocket.cpp, kernels_spectral.h by spectral.cpp, kernels_nutrient.h by nutrient.cpp.  The six kind headers and kernels_nutrient.h share kernels_lane4.h, the plan their
+// kernels_multifluid.h by multifluid.cpp, kernels_rocket.h by rocket.cpp, kernels_spectral.h by spectral.cpp, kernels_nutrient.h by nutrient.cpp, kernels_expansion.h by expansion.cpp.  The six kind headers, kernels_nutrient.h and kernels_expansion.h share kernels_lane4.h, the plan their
 // fused steps follow: device functions only, no kernel of its own.
 #pragma once
 #include <hip/hip_runtime.h>

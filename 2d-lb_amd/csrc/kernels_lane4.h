@@ -1,6 +1,6 @@
 // kernels_lane4.h -- the lane-of-four plan of every handle kind beyond flow, once.  Included after kernels_fused.h by the kind kernel
 // headers (kernels_scalar.h, kernels_multifield.h, kernels_poisson.h, kernels_porous.h, kernels_multifluid.h, kernels_rocket.h) and by
-// kernels_nutrient.h, the set of two scalar lattices that is no kind.  Device
+// kernels_nutrient.h and kernels_expansion.h, the sets of scalar lattices that are no kind.  Device
 // functions only: no kernel is emitted from here.
 // The plan: a lane owns four consecutive cells (x4 .. x4+3) of one row and a wave 256 cells of it; launch blockDim = (64, 4), grid =
 // (ceil(fpitch / 256), ceil(ny / 4)).  The source rows are wrapped or clamped as the boundary family says (lane_rows), the nine planes
@@ -91,6 +91,38 @@ __device__ __forceinline__ void store_planes(const StepArgs &a, int yl, int x4, 
     const long long S = a.plane;
 #pragma unroll
     for (int k = 0; k < 9; ++k) store4<false>(lane_ptr(d + k * S, x4), q[k]);
+}
+
+// The scalar lattice's OPEN family (kernels_scalar.h, kernels_expansion.h): the links of a lane's four cells (x4 .. x4+3, row y) that enter from outside the box, from the edge state.  The column's
+// entry goes in last: it is the one that counts where a corner link belongs to a row as well.
+__device__ __forceinline__ void ad_edge_gather(const float *edge, int fpitch, int nx, int ny, int x4, int y, f4a (&q)[9])
+{
+    if (y == 0) {
+        q[2] = load4<false>(lane_ptr(edge, x4));
+        q[5] = load4<false>(lane_ptr(edge + fpitch, x4));
+        q[6] = load4<false>(lane_ptr(edge + 2 * fpitch, x4));
+    }
+    if (y == ny - 1) {
+        q[4] = load4<false>(lane_ptr(edge + 3 * fpitch, x4));
+        q[7] = load4<false>(lane_ptr(edge + 4 * fpitch, x4));
+        q[8] = load4<false>(lane_ptr(edge + 5 * fpitch, x4));
+    }
+    const float *col = edge + 6LL * fpitch + y;
+    if (x4 == 0) {
+        q[1].x = col[0];
+        q[5].x = col[ny];
+        q[8].x = col[2 * ny];
+    }
+    const int c = nx - 1 - x4;
+    if (c >= 0 && c < 4) {
+        const float e3 = col[3 * ny], e6 = col[4 * ny], e7 = col[5 * ny];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            q[3][j] = j == c ? e3 : q[3][j];
+            q[6][j] = j == c ? e6 : q[6][j];
+            q[7][j] = j == c ? e7 : q[7][j];
+        }
+    }
 }
 
 // ---- a density around a lane's four cells -----------------------------------------------------------------------------------------

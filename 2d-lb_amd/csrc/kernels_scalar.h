@@ -26,38 +26,7 @@
 
 namespace {
 
-// OPEN: the links of a lane's four cells (x4 .. x4+3, row y) that enter from outside the box, from the edge state.  The column's
-// entry goes in last: it is the one that counts where a corner link belongs to a row as well.
-__device__ __forceinline__ void ad_edge_gather(const float *edge, int fpitch, int nx, int ny, int x4, int y, f4a (&q)[9])
-{
-    if (y == 0) {
-        q[2] = load4<false>(lane_ptr(edge, x4));
-        q[5] = load4<false>(lane_ptr(edge + fpitch, x4));
-        q[6] = load4<false>(lane_ptr(edge + 2 * fpitch, x4));
-    }
-    if (y == ny - 1) {
-        q[4] = load4<false>(lane_ptr(edge + 3 * fpitch, x4));
-        q[7] = load4<false>(lane_ptr(edge + 4 * fpitch, x4));
-        q[8] = load4<false>(lane_ptr(edge + 5 * fpitch, x4));
-    }
-    const float *col = edge + 6LL * fpitch + y;
-    if (x4 == 0) {
-        q[1].x = col[0];
-        q[5].x = col[ny];
-        q[8].x = col[2 * ny];
-    }
-    const int c = nx - 1 - x4;
-    if (c >= 0 && c < 4) {
-        const float e3 = col[3 * ny], e6 = col[4 * ny], e7 = col[5 * ny];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            q[3][j] = j == c ? e3 : q[3][j];
-            q[6][j] = j == c ? e6 : q[6][j];
-            q[7][j] = j == c ? e7 : q[7][j];
-        }
-    }
-}
-
+// (ad_edge_gather, the OPEN family's edge links of a lane: kernels_lane4.h, shared with kernels_expansion.h)
 // moments, equilibrium, relaxation [, growth] of a lane's four gathered cells as two pairs (scalar_cell.h, T = f2a), in place
 template <bool REACT>
 __device__ __forceinline__ void ad_collide_row(f4a (&q)[9], f4a u4, f4a v4, float omega, float G, f4a &r4)

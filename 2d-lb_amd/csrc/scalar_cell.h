@@ -144,6 +144,54 @@ __device__ __forceinline__ void ad_relax_noisy_t(T &f0, T &f1, T &f2, T &f3, T &
     f6 = ad_clamp0(lb_fma(w2, react, f6));
 }
 
+// ---- strains on a shared nutrient: D2Q9_multifield_diffusion.cl (kernels_expansion.h) -------------------------------------------------
+// update_hydro's cutoff: rho < cut or NaN -> 0, as compares and selects (the NaN test is explicit)
+__device__ __forceinline__ float ex_cut(float rho, float cut) { return (rho < cut || rho != rho) ? 0.f : rho; }
+__device__ __forceinline__ f2a ex_cut(f2a rho, float cut) { return f2a{ex_cut(rho.x, cut), ex_cut(rho.y, cut)}; }
+// collide_particles' floor: the link becomes 0 where its field's (cut) rho < cut, where the new value < 0 or where it is NaN
+__device__ __forceinline__ float ex_floor(float v, float rho, float cut) { return (rho < cut || v < 0.f || v != v) ? 0.f : v; }
+__device__ __forceinline__ f2a ex_floor(f2a v, f2a rho, float cut) { return f2a{ex_floor(v.x, rho.x, cut), ex_floor(v.y, rho.y, cut)}; }
+
+// react of one strain on the nutrient c: growth = (G rho) c; NOISY: + sqrt((Dg rho) c) z + ((Dg c) / 4) (z z - 1), the Milstein term.
+// Each product and each sum is a float32 of its own (one operation a statement: nothing contracts); the reference's `4.` and `1.`
+// make its Milstein term a double product -- the float32 one here is inside the contract's tolerance.
+template <typename T, bool NOISY>
+__device__ __forceinline__ T ex_react_t(float G, float Dg, T rho, T c, T z)
+{
+    const T gr = lb_splat<T>(G) * rho;
+    const T growth = gr * c;
+    if (!NOISY) return growth;
+    const T dr = lb_splat<T>(Dg) * rho;
+    const T drc = dr * c;
+    const T kick = ad_sqrt(drc) * z;
+    const T dc = lb_splat<T>(Dg) * c;
+    const T quarter = dc * lb_splat<T>(0.25f);
+    const T zz = z * z;
+    const T zz1 = zz - lb_splat<T>(1.f);
+    const T mil = quarter * zz1;
+    const T fluct = kick + mil;
+    return growth + fluct;
+}
+
+// the relaxation of one member towards the equilibrium of its cut rho (ad_relax_t: omega enters through rho), fl(w_k) react added last
+// in ad_grow_t's order, then the floor
+template <typename T>
+__device__ __forceinline__ void ex_relax_t(T &f0, T &f1, T &f2, T &f3, T &f4, T &f5, T &f6, T &f7, T &f8, float omega, float cut, T rho,
+                                           T ux, T uy, T react)
+{
+    ad_relax_t<T, false>(f0, f1, f2, f3, f4, f5, f6, f7, f8, omega, 0.f, rho, ux, uy);
+    const T w0 = lb_splat<T>(4.f / 9.f), w1 = lb_splat<T>(1.f / 9.f), w2 = lb_splat<T>(1.f / 36.f);
+    f0 = ex_floor(lb_fma(w0, react, f0), rho, cut);
+    f1 = ex_floor(lb_fma(w1, react, f1), rho, cut);
+    f3 = ex_floor(lb_fma(w1, react, f3), rho, cut);
+    f2 = ex_floor(lb_fma(w1, react, f2), rho, cut);
+    f4 = ex_floor(lb_fma(w1, react, f4), rho, cut);
+    f5 = ex_floor(lb_fma(w2, react, f5), rho, cut);
+    f7 = ex_floor(lb_fma(w2, react, f7), rho, cut);
+    f8 = ex_floor(lb_fma(w2, react, f8), rho, cut);
+    f6 = ex_floor(lb_fma(w2, react, f6), rho, cut);
+}
+
 // feq_k itself (the un-fused update_feq_diffusion): ad_relax_t's equilibrium with omega = 1
 __device__ __forceinline__ void ad_feq_cell(float (&e)[9], float rho, float ux, float uy)
 {

@@ -778,6 +778,37 @@ int lb_collide_nutrient(lb_sim **fields, int count, const lb_nutrient_params *p)
 /* psi, Fx, Fy of the last step / the last lb_update_forces_nutrient: [ny][nx] each, any may be NULL; zero before either */
 int lb_get_nutrient_fields(lb_sim **fields, int count, float *psi, float *Fx, float *Fy);
 
+/* ---- noisy strains on a shared nutrient (the reference's advecting_range_expansion/stochastic_nutrients.py: Expansion, and
+ *      D2Q9_multifield_diffusion.cl) ---------------------------------------------------------------------------------------------------
+ * NOT a handle kind either: a set is count = 2 ... 4 whole-grid LB_SEM_DIFFUSION GPU handles of one geometry, layout flag, device and
+ * family -- LB_BC_OPEN, the reference's box with each member's own edge state, or LB_BC_PERIODIC.  fields[0 .. count-2] are the
+ * strains, fields[count-1] is the nutrient.  Per strain: omega from its parameters, G from lb_set_reaction, Dg, seed and the noise
+ * counter t from lb_set_noise.  The nutrient has its own omega, G == 0 and no noise.  zero_cutoff travels with every call; nothing is
+ * stored in a handle and nothing new is allocated.  The velocity every member reads is the first member's u, v.  One time step
+ * (stochastic_nutrients.py:478-496), with c the nutrient's rho:
+ *   1. every member streams; OPEN: a link that would enter from outside keeps the edge state (move + copy_buffer)   lb_move on each
+ *   2. rho_i = sum_k f_ik, left to right; rho_i < zero_cutoff or NaN: rho_i = 0 (update_hydro)                     lb_update_hydro_expansion
+ *   3. feq_ik = w_k rho_i (1 + 3 c_k.u) of the stored rho (update_feq)                                             lb_update_feq on each
+ *   4. strain i: react_i = (G_i rho_i) c + sqrt((Dg_i rho_i) c) z_i + ((Dg_i c) / 4)(z_i z_i - 1),                 lb_collide_expansion
+ *        f_ik = f_ik (1 - omega_i) + omega_i feq_ik + w_k react_i;
+ *      nutrient: ... - w_k sum_i react_i, accumulated in the strains' order;
+ *      a link becomes 0 where its member's rho < zero_cutoff, where the new value is < 0 or where it is NaN (collide_particles)
+ *   5. z_i is strain i's own stream at its noise counter t, as lb_noise_fill gives it; every noisy strain's t advances by one.  A
+ *      strain with Dg == 0 draws nothing and its t does not move.
+ * lb_run_expansion(n) = n steps on the first member's stream without a host wait, ONE launch each (k_ex_step: every member gathered,
+ * the normals drawn in registers); each member's variant is ignored.  It leaves f post-collision and rho, u, v of the last step, feq
+ * not current.  The fused step and the stages are held to each other by the contract's tolerance, not bitwise (as lb_run and the phases
+ * of a scalar lattice differ).  lb_collide_expansion takes z_i from the strain's supplied field where lb_set_noise_field set one.
+ * LB_ERR_ARG, with the reason, before any launch: a null array, handle or parameters, a count outside 2 ... 4, a handle given twice, a
+ * member that is no scalar lattice on the GPU, a family other than OPEN or PERIODIC, members of different geometry, layout, device or
+ * family, a non-finite zero_cutoff, a nutrient with G != 0, two noisy strains with equal seeds, a negative n_steps.  LB_ERR_STATE:
+ * slabs, a noisy nutrient, lb_run_expansion while any member holds a supplied noise field, lb_collide_expansion before
+ * lb_update_feq on every member. */
+typedef struct { float zero_cutoff; } lb_expansion_params;
+int lb_run_expansion(lb_sim **fields, int count, const lb_expansion_params *p, int n_steps);
+int lb_update_hydro_expansion(lb_sim **fields, int count, const lb_expansion_params *p);     /* stage 2 */
+int lb_collide_expansion(lb_sim **fields, int count, const lb_expansion_params *p);          /* stage 4: stored feq, rho */
+
 #ifdef __cplusplus
 }
 #endif
