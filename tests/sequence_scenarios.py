@@ -5,9 +5,11 @@ seeded numpy generator: the same (kind, family, seed) always gives the same list
 payload seed and `payload()` makes the array from it, the same one for every player.
 
   EFFECTIVE ops change the physics; every player makes them:  run(n), phase_step, set_f, and the kind's own state-changing
-  calls (E_OPS below).
+  calls (E_OPS below) -- among them fed_phase_step, the phases with a supplied field of normals on every noisy lattice
+  (set_noise_field(z), the phases, set_noise_field(None)).
   TRANSPARENT ops must change nothing; only the subject makes them: reads, the planner's answers, set_variant, the mask
-  uploaded again, a checkpoint round trip through a closed handle (T_OPS below), and run(n) split into run(a, wait=False); run(n - a)
+  uploaded again, a set's own solver used on an unrelated charge, a checkpoint round trip through a closed handle (T_OPS below; a set
+  without a file format of its own goes member by member into a fresh set), and run(n) split into run(a, wait=False); run(n - a)
   (the third entry of a run op; the other players ignore it).  They are shuffled and land at random places of the list, except
   that every variant word stands directly in front of a run (so that it selects something), one read at least lies behind a
   stepping op, and the mask is uploaded again or taken off and on while one is set.
@@ -18,7 +20,14 @@ flow kinds, the kind's numpy model in float64 otherwise).  tests/test_sequences_
 references alone.
 
 Amplitudes, tables and parameters are chosen so that every reference stays in the range the parity contract was established
-in (rho 0.5 ... 1.5, |u| < 0.15 for the flow kinds) over the 120 steps a sequence may take, mid-life changes included.
+in (rho 0.5 ... 1.5, |u| < 0.15 for the flow kinds) over the 120 steps a sequence may take, mid-life changes included; where a
+collision has thresholds (the noisy lattices, the strains on a nutrient, the colony) every thresholded quantity stays far from its
+threshold (STEP_CAP below), so that every cell is compared.
+
+The kinds 'rocket' (coupled.Surfactant_Colony), 'nutrient' (nutrient_set.Nutrient_Set), 'noise' (noisy_simulation.NoisySimulation),
+'expansion' (expansion_set.Expansion_Set) and 'screened' (a scalar lattice and a spectral_poisson.Screened_Poisson under
+lb_run_screened / lb_spectral_velocity: ScreenedWave below) came after the first six; their keys into the generators follow the first
+six's, whose op lists have not moved (tests/test_sequences_cpu.py holds a digest of each).
 """
 import os
 
@@ -27,10 +36,20 @@ import numpy as np
 F = np.float32
 W64 = np.array([4. / 9.] + [1. / 9.] * 4 + [1. / 36.] * 4)
 
-KINDS = ("flow", "scalar", "multifield", "poisson", "porous", "multifluid")
+KINDS = ("flow", "scalar", "multifield", "poisson", "porous", "multifluid", "rocket", "nutrient", "noise", "expansion", "screened")
 SEEDS = tuple(range(6))
 RUN_LENGTHS = (1, 2, 3, 4, 5, 6, 7, 8, 13, 16, 17, 33, 40)     # every fused depth, the 16-launch graph replay and its remainder
 MAX_E, MAX_T, MAX_STEPS = 10, 15, 120
+# The steps of a life of the kinds whose collision has thresholds (rho < zero_cutoff -> 0, a link < 0 -> 0, rho outside [0, 1] -> NaN):
+# the largest cap, at most MAX_STEPS, at which the float64 model of every one of the kind's twelve cases keeps each thresholded quantity
+# further from its threshold than twice the contract's bound (tests/test_sequences_cpu.py holds this and prints the smallest margin =
+# distance / (2 x bound) per kind).  All three hold at the full 120 -- the longest lives of these seeds take 101, 82 and 67 steps -- with margins
+#   rocket     the population's links 1.2e3
+#   noise      rho against 0 and 1  5.1e3, the links 1.8e2
+#   expansion  rho against zero_cutoff  8.2e3, the links 3.9e2
+# so no kind is cut short.  What keeps them there: entering edge links of the size w_k rho of the densities inside (payload), the
+# strengths of tests/test_gpu_noise.py's and tests/test_gpu_expansion.py's smooth cases.
+STEP_CAP = dict(rocket=120, noise=120, expansion=120)
 N_VARIANTS, VARIANT_DEPTH = 2, 8               # variant words per sequence; the steps in one call that let every word's kernel run
 
 FAMILIES = dict(
@@ -40,6 +59,11 @@ FAMILIES = dict(
     poisson=("dirichlet",),
     porous=("periodic", "zero_gradient"),
     multifluid=("periodic", "zero_gradient"),
+    rocket=("flow", "forces"),
+    nutrient=("plain", "clumpy"),                   # (the value of `clumpy` a life starts with; it is toggled both ways inside one)
+    noise=("periodic", "open"),
+    expansion=("periodic", "open"),
+    screened=("periodic", "open"),
 )
 
 # The smallest shapes at which each mechanism still engages.
@@ -52,9 +76,19 @@ FAMILIES = dict(
 #   porous: 261 x 9 (as above) and 256 x 4 (exactly one workgroup, the east edge inside a lane), alternating with the seed.
 #   multifluid: 517 x 5 with three fluids (three workgroups in x: one has neighbours on both sides of its column halo; ny = 2 * 2 + 1
 #       for the two rows a workgroup of k_mc_step owns), 261 x 9 and 6 x 13 with two (ny = 2 * 6 + 1 for its six rows), by seed % 3.
+#   noise: the scalar kind's 130 x 50 -- with it, a width that is no multiple of 4: the periodic seam of k_ad_tile4 takes the per-cell noise path.
+#   expansion: 261 x 9 (two workgroups in x, the last lane straddling the east edge) and 37 x 23 (nx % 4 == 1, several workgroups in y, the
+#       last ragged), alternating with the seed; 1 + seed % 3 strains.
+#   nutrient, screened: 270 x 12 (a second workgroup in x, 270 % 4 == 2, three workgroups of k_sn_step in y) and 30 x 18; both axes
+#       2^a 3^b 5^c, as the transform requires.
+#   rocket: 261 x 11 (k_ry_step owns RY_ROWS = 10 rows of a 256-cell tile: a second workgroup in x whose last lane straddles the edge, a
+#       second in y that owns one row) and 6 x 21 (narrower than a lane and its halo cells: both column halos are the wrap; ny = 2 * 10 + 1).
 FLOW_SHAPES = dict(periodic=(516, 130), pipe=(517, 131), cavity=(517, 131), velocity_inlet=(517, 131))
 POROUS_SHAPES = ((261, 9), (256, 4))
 MULTIFLUID_SHAPES = ((517, 5, 3), (261, 9, 2), (6, 13, 2))
+ROCKET_SHAPES = ((261, 11), (6, 21))
+EXPANSION_SHAPES = ((261, 9), (37, 23))
+SPECTRAL_SHAPES = ((270, 12), (30, 18))
 
 E_OPS = dict(
     flow=("run", "phase_step", "set_f", "init_equilibrium", "set_obstacle_mask", "clear_obstacle_mask"),
@@ -63,7 +97,15 @@ E_OPS = dict(
     poisson=("run", "phase_step", "set_f", "set_source", "solve", "solve_reset"),
     porous=("run", "phase_step", "set_f", "set_body_force", "set_force_field", "clear_force_field", "set_porous"),
     multifluid=("run", "phase_step", "set_f", "set_body_force", "set_force_field", "clear_force_field", "set_interactions", "set_reactions"),
+    rocket=("run", "phase_step", "set_f", "set_params"),
+    nutrient=("run", "phase_step", "set_f", "set_params"),
+    noise=("run", "phase_step", "set_f", "set_reaction", "set_fields", "set_edge_state", "set_noise", "fed_phase_step"),
+    expansion=("run", "phase_step", "fed_phase_step", "set_f", "set_noise", "set_reaction", "set_fields", "set_edge_state"),
+    screened=("run", "phase_step", "set_f", "redo_initial_condition", "set_reaction"),
 )
+# effective ops a life makes more than once: the parameter tables of a colony, `clumpy` there and back and two more parameters, the noise
+# switched off and back on (the periodic family, which has the slot that the open one gives to set_edge_state)
+MORE_E = dict(rocket=("set_params",), nutrient=("set_params",) * 3, noise=("set_noise",))
 _READS = ("get_fields", "hot_kernel", "plan_launches", "steps_per_launch", "layout", "sync", "checkpoint", "split_run")
 T_OPS = dict(
     flow=_READS + ("check", "set_variant", "reupload_mask", "mask_off_on"),
@@ -72,13 +114,26 @@ T_OPS = dict(
     poisson=_READS,
     porous=_READS,
     multifluid=_READS + ("set_variant",),
+    rocket=_READS + ("check", "set_variant", "get_params", "get_own"),
+    nutrient=_READS + ("check", "get_own", "solver_scribble"),
+    noise=_READS + ("check", "set_variant", "noise", "noise_fill"),
+    expansion=_READS + ("check", "noise", "noise_fill", "get_edge_state"),
+    screened=_READS + ("check", "solver_scribble"),
 )
-STEPPING = ("run", "phase_step", "solve")
+STEPPING = ("run", "phase_step", "solve", "fed_phase_step")
 FIELD_NAMES = dict(
     flow=("f", "rho", "u", "v", "feq"), scalar=("f", "rho", "u", "v", "feq"), multifield=("f", "rho", "u", "v", "feq"),
     poisson=("f", "rho", "feq"),
     porous=("f", "feq", "rho", "u", "v", "u_bary", "v_bary", "Gx", "Gy"),
     multifluid=("f", "feq", "rho", "u", "v", "Gx", "Gy", "u_bary", "v_bary"),
+    rocket=("f", "feq", "rho", "u", "v"), nutrient=("f", "feq", "rho", "u", "v"), noise=("f", "rho", "u", "v", "feq"),
+    expansion=("f", "feq", "rho", "u", "v"), screened=("f", "rho", "u", "v", "feq"),
+)
+# what a set keeps beside its members' arrays (get_own reads them; `op` is psi in mode 'flow' and S in mode 'forces')
+OWN_NAMES = dict(
+    rocket=dict(flow=dict(op="psi", Fx="pseudo_force_x", Fy="pseudo_force_y"),
+                forces=dict(op="S", Fx="pseudo_force_x", Fy="pseudo_force_y", Sx="surface_force_x", Sy="surface_force_y")),
+    nutrient=dict(psi="psi", Fx="pseudo_force_x", Fy="pseudo_force_y"),
 )
 
 
@@ -109,6 +164,27 @@ REACTIONS = {
 }
 
 
+# colony tables: every parameter its mode reads changes between them; growth, secretion and couplings gentle enough that 120 steps keep
+# the population inside (0, 1), the surfactant below 1.5 and the speed below 0.15 even in the box of six cells
+ROCKET_TABLES = dict(
+    flow=tuple(dict((k, _r32(v)) for k, v in t.items()) for t in (
+        dict(G=0.01, G_c=0.004, epsilon=0.5, rho_o=0.9, G_chen=-0.8, c_o=0.25, alpha=2.),
+        dict(G=0.005, G_c=0.002, epsilon=0.3, rho_o=1.2, G_chen=-0.5, c_o=0.25, alpha=2.),
+        dict(G=0., G_c=0.006, epsilon=0.4, rho_o=0.9, G_chen=0.4, c_o=0.25, alpha=2.))),
+    forces=tuple(dict((k, _r32(v)) for k, v in t.items()) for t in (
+        dict(G=0.01, G_c=0.004, epsilon=0.5, rho_o=0.9, G_chen=-0.8, c_o=0.25, alpha=2.),
+        dict(G=0.005, G_c=0.002, epsilon=0.3, rho_o=0.7, G_chen=0.5, c_o=0.4, alpha=1.5),
+        dict(G=0., G_c=0.006, epsilon=-0.4, rho_o=0.9, G_chen=-0.4, c_o=0.3, alpha=1.))),
+)
+ROCKET_OMEGAS = (F(0.8), F(1.1))
+# a population and its nutrient: the values set_params deals (the first of each is the one a life starts with)
+NUTRIENT_VALUES = dict(G=(0.01, 0.02, 0.), scale=(-0.05, -0.03, 0.), G_chen=(-1., -0.6, 0.5), rho_o=(1., 0.8))
+NUTRIENT_OMEGAS, NUTRIENT_LAM, NUTRIENT_DX = (F(0.8), F(1.25)), 1., 0.1
+# noisy strains (tests/test_gpu_expansion.py's OMEGAS, GS, DGS: its fixtures keep every density above twice the cutoff for 50 steps)
+EX_OMEGAS, EX_OMEGA_N, EX_GS, EX_DGS, EX_CUT = (1.1, 0.9, 1.25), 1.3, (0.01, 0.014, 0.012), (2.0e-3, 1.0e-3, 5.0e-4), 0.01
+NOISE_DGS = (1e-4, 2e-4, 5e-5)                  # (tests/test_gpu_noise.py's case: a hundred steps inside (0, 1) at 1e-4)
+
+
 def variant_words(kind):
     from LB_D2Q9.variants import (AUTO, K_DEEP2, K_DEEP6, K_DEEP7, K_STEP, K_STEP2, K_STEP3, K_STEP4, K_STEP5, K_TILE4, NT_STORES, ROWS_2,
                                   TILES, XCD_ORDER)
@@ -116,7 +192,10 @@ def variant_words(kind):
         return (AUTO, K_STEP, K_STEP2, K_STEP3, K_STEP4, K_STEP5, K_DEEP6, K_DEEP7, K_DEEP2, K_TILE4, NT_STORES | ROWS_2, XCD_ORDER)
     if kind == "scalar":
         return (AUTO, K_STEP, TILES | 1 << 2, TILES | 2 << 2, TILES | 3 << 2)
-    if kind == "multifluid":
+    if kind == "noise":                             # (the scalar kind's, and both noise plans of k_ad_tile4)
+        from LB_D2Q9.variants import STEP4_NO_AHEAD
+        return (AUTO, K_STEP, TILES | 1 << 2, TILES | 2 << 2, TILES | 3 << 2, TILES | STEP4_NO_AHEAD, TILES | 2 << 2 | STEP4_NO_AHEAD)
+    if kind in ("multifluid", "rocket"):
         return (-1, 0, 1)
     return ()
 
@@ -158,6 +237,28 @@ def case_of(kind, family, seed):
         c["nx"], c["ny"], c["nf"] = MULTIFLUID_SHAPES[seed % 3]
         c.update(bc=family, omegas=(F(1.25), F(0.9), F(1.05))[:c["nf"]], rhos=(1., 0.9, 0.8)[:c["nf"]],
                  g=((_r32(2e-3), _r32(-1e-3)), (0., _r32(1e-3)), (_r32(-1e-3), 0.))[:c["nf"]], interactions=seed % 3, reactions=(seed + 1) % 3)          # (the tables it starts with: indices into INTERACTIONS, REACTIONS)
+    elif kind == "rocket":
+        c["nx"], c["ny"] = ROCKET_SHAPES[seed % 2]
+        c.update(mode=family, omegas=ROCKET_OMEGAS, table=seed % 3)                   # (the table it starts with: an index into ROCKET_TABLES)
+    elif kind == "nutrient":
+        c["nx"], c["ny"] = SPECTRAL_SHAPES[seed % 2]
+        c.update(omegas=NUTRIENT_OMEGAS, lam=NUTRIENT_LAM, dx=NUTRIENT_DX, clumpy=family == "clumpy",
+                 params={k: _r32(v[0]) for k, v in NUTRIENT_VALUES.items()})
+    elif kind == "noise":
+        c.update(nx=130, ny=50, bc=family, omega=_r32(rng.uniform(0.8, 1.6)), G=(0., 0.01)[int(rng.integers(0, 2))], Dg=_r32(NOISE_DGS[0]),
+                 noise_seed=int(rng.integers(1, 1 << 62)))
+        c["u"], c["v"] = payload(c, "set_fields", 1000)
+    elif kind == "expansion":
+        c["nx"], c["ny"] = EXPANSION_SHAPES[seed % 2]
+        n = _nf(kind, seed)
+        c.update(bc=family, ns=n, omegas=tuple(F(o) for o in EX_OMEGAS[:n]), omega_n=F(EX_OMEGA_N), Gs=tuple(_r32(g) for g in EX_GS[:n]),
+                 Dgs=tuple(_r32(d) for d in EX_DGS[:n]), cut=_r32(EX_CUT), noise_seed=int(rng.integers(1, 1 << 62)))
+        c["u"], c["v"] = payload(c, "set_fields", 1000)
+    elif kind == "screened":
+        c["nx"], c["ny"] = SPECTRAL_SHAPES[seed % 2]
+        # (spectral_model.fisher_lattice_parameters at N = 10: omega = 0.8, G = 0.01, scale = -0.1; a gentler scale keeps |u| < 0.15)
+        c.update(bc=family, omega=_r32(0.8), G=0.01, lam=1., dx=0.1, scale=_r32(-rng.uniform(0.04, 0.07)))
+        c["rho0"] = payload(c, "redo_initial_condition", 1000)
     else:
         raise ValueError(kind)
     c["f0"] = payload(c, "set_f", 1000)
@@ -189,6 +290,42 @@ def payload(c, name, pseed):
             return (W64 * (1. + 0.1 * rng.uniform(-1., 1., (nx, ny, 9)))).astype(F)
         if kind == "multifluid":
             return (W64 * np.asarray(c["rhos"])[None, None, :, None] * (1. + 0.05 * rng.uniform(-1., 1., (nx, ny, c["nf"], 9)))).astype(F)
+        if kind == "rocket":                        # a few long waves of random phase: the population in 0.3 ... 0.9, the surfactant around 0.5
+            long_waves = lambda: sum(a * np.sin(2. * np.pi * (kx * x / nx + ky * y / ny) + rng.uniform(0., 2. * np.pi))
+                                     for a, kx, ky in ((0.12, 1, 0), (0.1, 0, 1), (0.06, 1, 1)))
+            rho = np.stack([0.6 + long_waves(), 0.5 + long_waves()], axis=2)
+            return (W64 * rho[:, :, :, None] * (1. + 0.02 * rng.uniform(-1., 1., (nx, ny, 2, 9)))).astype(F)
+        if kind == "nutrient":                      # a droplet of the population somewhere in the box on a gently waved nutrient
+            cx, cy, r = rng.uniform(0.2, 0.8) * nx, rng.uniform(0.3, 0.7) * ny, 0.5 * max(nx, ny) / 3.
+            rho = np.stack([0.05 + 0.8 * np.exp(-((x - cx) ** 2 + (y - cy) ** 2) / r ** 2), 0.9 + 0.1 * wave(phase)], axis=2)
+            return (W64 * rho[:, :, :, None] * (1. + 0.02 * rng.uniform(-1., 1., (nx, ny, 2, 9)))).astype(F)
+        if kind == "noise":                         # the scalar kind's blob, lower: rho 0.15 ... 0.75 grows and is kicked for 120 steps inside (0, 1)
+            rho = 0.15 + 0.6 * np.exp(-(((x - rng.uniform(0.3, 0.7) * nx) / (0.2 * nx)) ** 2 + ((y - 0.5 * ny) / (0.25 * ny)) ** 2))
+            return (W64 * rho[:, :, None] * (1. + 0.05 * rng.uniform(-1., 1., (nx, ny, 9)))).astype(F)
+        if kind == "expansion":                     # test_gpu_expansion.smooth_case with random phases: strains 0.15 ... 0.55, the nutrient 0.7 ... 1
+            f = np.zeros((nx, ny, c["ns"] + 1, 9), F)
+            for i in range(c["ns"] + 1):
+                p = rng.uniform(0., 1., 2)
+                bump = 0.5 + 0.5 * np.sin(2. * np.pi * (x / nx + p[0])) * np.cos(2. * np.pi * (y / ny - p[1]))
+                rho = 0.7 + 0.3 * bump if i == c["ns"] else 0.15 + 0.4 * bump
+                f[:, :, i, :] = W64 * rho[:, :, None] * (1. + 0.02 * rng.uniform(-1., 1., (nx, ny, 9)))
+            return f
+        if kind == "screened":
+            return (W64 * _droplet(rng, x, y, nx, ny)[:, :, None] * (1. + 0.02 * rng.uniform(-1., 1., (nx, ny, 9)))).astype(F)
+    if name == "redo_initial_condition":            # the density a wave starts again from
+        return _droplet(rng, x, y, nx, ny).astype(F)
+    if name == "solver_scribble":                   # an unrelated charge
+        return (rng.standard_normal((nx, ny)) + 1j * rng.standard_normal((nx, ny))).astype(np.complex64)
+    if name == "fed_phase_step":                    # the normals of one collision: one field per strain
+        return rng.standard_normal((nx, ny) if kind == "noise" else (nx, ny, c["ns"])).astype(F)
+    if kind == "expansion" and name == "set_fields":                 # (smooth_case's 0.05)
+        return (0.05 * wave(phase)).astype(F), (-0.05 * wave(phase[::-1])).astype(F)
+    # (where a collision floors its links at 0, entering links are those of a density a sequence reaches, w_k rho: an over-relaxed link
+    #  far above its equilibrium would be floored in the next collision)
+    if kind == "noise" and name == "set_edge_state":
+        return _edge_links(rng, nx, ny, 0.12, 0.22)              # (the blob's density at the edges is 0.15; omega reaches 1.6)
+    if kind == "expansion" and name == "set_edge_state":             # one row per member, the nutrient last
+        return np.stack([_edge_links(rng, nx, ny, *((0.15, 0.5) if i < c["ns"] else (0.7, 1.))) for i in range(c["ns"] + 1)])
     if name == "init_equilibrium":
         rho = 1. + 0.02 * wave(phase) + 0.002 * rng.standard_normal((nx, ny))
         u = 0.03 * wave(phase[::-1]) + 0.002 * rng.standard_normal((nx, ny))
@@ -215,17 +352,33 @@ def payload(c, name, pseed):
     raise ValueError((kind, name))
 
 
+def _edge_links(rng, nx, ny, lo, hi):
+    """An edge state (include/lb_hip.h: west k = 1, 5, 8, east 3, 6, 7 of ny links each, south 2, 5, 6, north 4, 7, 8 of nx each) of links
+    w_k rho with rho uniform in lo ... hi."""
+    return np.concatenate([W64[k] * rng.uniform(lo, hi, n) for n, ks in ((ny, (1, 5, 8, 3, 6, 7)), (nx, (2, 5, 6, 4, 7, 8))) for k in ks]).astype(F)
+
+
+def _droplet(rng, x, y, nx, ny):
+    """A Gaussian droplet (spectral_model.noisy_droplet's, R0 = 0.5 at N = max(nx, ny) / 3) of random height and place, 5 % noise."""
+    cx, cy, r = rng.uniform(0.3, 0.7) * nx, rng.uniform(0.3, 0.7) * ny, 0.5 * max(nx, ny) / 3.
+    rho = rng.uniform(0.6, 0.9) * np.exp(-((x - cx) ** 2 + (y - cy) ** 2) / r ** 2)
+    return rho * (1. + 0.05 * rng.standard_normal((nx, ny)))
+
+
 # ---- the generator ---------------------------------------------------------------------------------------------------------------------
 def generate(kind, family, seed):
     """The op list of (kind, family, seed): at most MAX_E effective and MAX_T transparent ops, at most MAX_STEPS steps, a stepping
     op last.  Every effective op of the kind that the family has occurs once, runs fill the rest."""
     rng = np.random.default_rng(_key(kind, family, seed) + [3])
     names = [n for n in E_OPS[kind] if not (n == "set_edge_state" and family != "open")]
+    if not (kind == "noise" and family == "open"):
+        names += MORE_E.get(kind, ())
     names += ["run"] * (MAX_E - 1 - len(names))
     rng.shuffle(names)
     names.append("run")
-    steps_left, pseed, ops = MAX_STEPS, 0, []
+    steps_left, pseed, ops = STEP_CAP.get(kind, MAX_STEPS), 0, []
     state = dict(table=seed % 3, react=(seed + 1) % 3)          # (as case_of)
+    state.update(noisy=True, clumpy=family == "clumpy", toggles=0, dealt={k: 0 for k in NUTRIENT_VALUES})
 
     # run lengths are dealt from one deck per kind, so that the committed seeds of a kind cover every length
     deck = [int(n) for n in np.random.default_rng([KINDS.index(kind), 5]).permutation(RUN_LENGTHS)]
@@ -246,12 +399,41 @@ def generate(kind, family, seed):
         elif name == "phase_step":
             steps_left -= 1
             ops.append((name,))
-        elif name in ("set_f", "init_equilibrium", "set_obstacle_mask", "set_fields", "set_edge_state", "set_corner_state", "set_source"):
+        elif name == "fed_phase_step":
+            steps_left -= 1
+            ops.append((name, pseed))
+        elif name in ("set_f", "init_equilibrium", "set_obstacle_mask", "set_fields", "set_edge_state", "set_corner_state", "set_source",
+                      "redo_initial_condition"):
             ops.append((name, pseed))
         elif name in ("clear_obstacle_mask", "solve_reset"):
             ops.append((name,))
+        elif name == "set_reaction" and kind == "expansion":            # one strain's growth rate
+            ops.append((name, int(rng.integers(0, _nf(kind, seed))), _r32((0.006, 0.016, 0.)[int(rng.integers(0, 3))])))
         elif name == "set_reaction":
             ops.append((name, "toggle"))
+        elif name == "set_params" and kind == "rocket":
+            state["table"] = (state["table"] + int(rng.integers(1, 3))) % 3
+            ops.append((name, state["table"]))
+        elif name == "set_params":                                      # nutrient: `clumpy` the other way, then the next value of a parameter, in turns
+            state["toggles"] += 1
+            if state["toggles"] % 2:
+                state["clumpy"] = not state["clumpy"]
+                ops.append((name, "clumpy", state["clumpy"]))
+            else:
+                k = str(rng.choice(sorted(NUTRIENT_VALUES)))
+                state["dealt"][k] += 1
+                ops.append((name, k, _r32(NUTRIENT_VALUES[k][state["dealt"][k] % len(NUTRIENT_VALUES[k])])))
+        elif name == "set_noise" and kind == "noise":                   # off where the family has a second call to switch it on again, or the seed is odd
+            nseed = int(rng.integers(1, 1 << 62))
+            off = state["noisy"] and (family == "periodic" or seed % 2 == 1)
+            state["noisy"] = not off
+            ops.append((name, 0. if off else _r32(NOISE_DGS[int(rng.integers(0, len(NOISE_DGS)))]), nseed))
+        elif name == "set_noise":                                       # expansion: the strengths dealt anew, every other time one strain without noise
+            n = _nf(kind, seed)
+            dgs = [_r32(d) for d in rng.permutation(EX_DGS)[:n]]
+            if rng.integers(0, 2):
+                dgs[int(rng.integers(0, n))] = 0.
+            ops.append((name, tuple(dgs), int(rng.integers(1, 1 << 62))))
         elif name == "set_porous":
             ops.append((name, pseed))
         elif name == "set_body_force":
@@ -311,6 +493,10 @@ def generate(kind, family, seed):
             t_ops.append((name, which + ("feq",) if "feq" not in which and rng.integers(0, 2) else which))
         elif name == "plan_launches":
             t_ops.append((name, int(rng.choice(RUN_LENGTHS))))
+        elif name == "noise_fill":                  # (a counter; on a set: a strain and a counter)
+            t_ops.append((name, int(rng.integers(0, 1000))) if kind == "noise" else (name, int(rng.integers(0, _nf(kind, seed))), int(rng.integers(0, 1000))))
+        elif name == "solver_scribble":             # (a payload seed)
+            t_ops.append((name, 2000 + len(t_ops)))
         else:
             t_ops.append((name,))
         if name in ("reupload_mask", "mask_off_on"):
@@ -334,6 +520,8 @@ def starts_masked(family, seed):
 
 
 def _nf(kind, seed):
+    if kind == "expansion":                         # (the strains: every count the engine builds)
+        return 1 + seed % 3
     return MULTIFLUID_SHAPES[seed % 3][2] if kind == "multifluid" else 1
 
 
@@ -388,20 +576,24 @@ class Player(object):
                 self.run(op[1], op[2])
             elif name == "solve":
                 self.solve(op[1])
+            elif name == "fed_phase_step":
+                self.fed_phase_step(payload(self.case, name, op[1]))
             else:
                 self.phase_step()
-            self.steps += 1 if name == "phase_step" else op[1]
+            self.steps += op[1] if name in ("run", "solve") else 1
             self.macro_steps = self.steps
         else:
-            if name in ("set_f", "init_equilibrium"):
+            if name in ("set_f", "init_equilibrium", "redo_initial_condition"):
                 self.steps = 0
-            if name == "init_equilibrium":
+            if name in ("init_equilibrium", "redo_initial_condition"):
                 self.macro_steps = 0
-            if name == "set_reaction":
+            if name == "set_reaction" and self.kind == "expansion":
+                self.set_reaction(op[1], op[2])
+            elif name == "set_reaction":
                 self.G = 0.01 if self.G == 0. else 0.
                 self.set_reaction(self.G)
             elif name in ("set_f", "init_equilibrium", "set_obstacle_mask", "set_fields", "set_edge_state", "set_corner_state", "set_source",
-                          "set_porous"):
+                          "set_porous", "redo_initial_condition"):
                 getattr(self, name)(payload(self.case, name, op[1]))
             elif name == "set_force_field":
                 getattr(self, name)(*(op[1:-1] + (payload(self.case, name, op[-1]),)))
@@ -409,8 +601,58 @@ class Player(object):
                 getattr(self, name)(*op[1:])
 
 
+def restorer(seed, saves):
+    """The class that restores the `saves`-th checkpoint (1, 2 ...) of a noise sequence."""
+    return ("Simulation", "NoisySimulation")[(int(seed) + int(saves)) % 2]
+
+
 def _flow_code(oracle, bc):
     return dict(pipe=oracle.BC_PIPE, periodic=oracle.BC_PERIODIC, cavity=oracle.BC_CAVITY, velocity_inlet=oracle.BC_VELOCITY_INLET)[bc]
+
+
+class ScreenedWave(object):
+    """A scalar lattice of either family whose velocity a Screened_Poisson solves from its density: what Screened_Fisher_Wave drives
+    (lb_run_screened, lb_spectral_velocity), with the class's un-fused sequence and its redo_initial_condition.  sim: a restored lattice
+    to go on with, behind a fresh solver."""
+
+    def __init__(self, c, sim=None):
+        from LB_D2Q9 import _native
+        from LB_D2Q9.simulation import Simulation
+        from LB_D2Q9.spectral_poisson.screened_poisson import Screened_Poisson
+        self.c, self._check = c, _native.check
+        self.sim = sim if sim is not None else Simulation(c["nx"], c["ny"], c["omega"], bc=c["bc"], semantics="diffusion")
+        self.solver = Screened_Poisson(np.zeros((c["nx"], c["ny"]), np.complex64), lam=c["lam"], dx=c["dx"])
+        self.solver.create_grad_fields()
+        self._lib = self.sim._lib
+
+    def close(self):
+        self.sim.close()
+        self.solver.close()
+
+    def update_u_and_v(self):
+        self._check(self._lib.lb_spectral_velocity(self.solver._h, self.sim._h, float(self.c["scale"]), 0))
+        self.sim.sync()
+
+    def run(self, n, wait=True):
+        self._check(self._lib.lb_run_screened(self.solver._h, self.sim._h, float(self.c["scale"]), int(n)))
+        if wait:
+            self.sim.sync()
+
+    def step_phases(self):
+        s = self.sim
+        s.move(); s.move_bcs(); s.update_hydro()
+        self.update_u_and_v()                       # (the class's update_hydro: the velocity follows the density)
+        s.update_feq(); s.collide_particles()
+
+    def redo_initial_condition(self, rho):
+        zero = np.zeros((self.c["nx"], self.c["ny"]), F)
+        self.sim.set_fields(rho, zero, zero)
+        self.update_u_and_v()
+        self.sim.update_feq()
+        self.sim.init_pop()
+
+    def __getattr__(self, name):                    # set_f, set_reaction, get_fields, check, sync, get_edge_state ...: the lattice's
+        return getattr(self.sim, name)
 
 
 class GpuPlayer(Player):
@@ -440,6 +682,20 @@ class GpuPlayer(Player):
             return Simulation(c["nx"], c["ny"], c["omega"], bc="dirichlet", semantics="poisson")
         if k == "porous":
             return Simulation(c["nx"], c["ny"], F(c["omega"]), bc=c["bc"], semantics="porous")
+        if k == "rocket":
+            from LB_D2Q9.coupled import Surfactant_Colony
+            return Surfactant_Colony(c["nx"], c["ny"], c["omegas"][0], c["omegas"][1], mode=c["mode"])
+        if k == "nutrient":
+            from LB_D2Q9.nutrient_set import Nutrient_Set
+            return Nutrient_Set(c["nx"], c["ny"], c["omegas"][0], c["omegas"][1], lam=c["lam"], dx=c["dx"])
+        if k == "noise":
+            from LB_D2Q9.noisy_simulation import NoisySimulation
+            return NoisySimulation(c["nx"], c["ny"], c["omega"], bc=c["bc"])
+        if k == "expansion":
+            from LB_D2Q9.expansion_set import Expansion_Set
+            return Expansion_Set(c["nx"], c["ny"], list(c["omegas"]), c["omega_n"], list(c["Gs"]), bc=c["bc"], zero_cutoff=c["cut"])
+        if k == "screened":
+            return ScreenedWave(c)
         return Shan_Chen_Fluids(c["nx"], c["ny"], list(c["omegas"]), bc=c["bc"])
 
     def _load(self):
@@ -466,6 +722,21 @@ class GpuPlayer(Player):
                 h.set_body_force(i, *g)
             h.set_interactions(INTERACTIONS[c["nf"]][c["interactions"]])
             h.set_reactions(REACTIONS[c["nf"]][c["reactions"]])
+        elif k == "rocket":
+            self.table = c["table"]
+            h.set_params(**ROCKET_TABLES[c["mode"]][self.table])
+        elif k == "nutrient":
+            h.set_params(clumpy=c["clumpy"], **c["params"])
+        elif k == "noise":
+            h.set_reaction(c["G"])
+            h._set_noise(c["Dg"], c["noise_seed"])
+            h.set_fields(zero, c["u"], c["v"])
+        elif k == "expansion":
+            h.set_noise(c["Dgs"], c["noise_seed"])
+            h.set_fields(np.zeros((c["nx"], c["ny"], c["ns"] + 1), F), c["u"], c["v"])
+        elif k == "screened":
+            h.set_reaction(c["G"])
+            h.redo_initial_condition(c["rho0"])     # (the velocity of the first density; set_f then replaces the populations)
         h.set_f(c["f0"])
 
     def first(self):
@@ -492,7 +763,7 @@ class GpuPlayer(Player):
 
     def phase_step(self):
         h = self.h
-        if self.kind == "multifluid":
+        if self.kind in ("multifluid", "rocket", "nutrient", "expansion", "screened"):
             h.step_phases()
         elif self.kind == "porous":
             for name in ("move", "move_bcs", "update_hydro", "update_forces", "update_bary_velocity", "update_feq", "collide_particles"):
@@ -500,8 +771,41 @@ class GpuPlayer(Player):
         else:
             h.move(); h.move_bcs(); h.update_hydro(); h.update_feq(); h.collide_particles()
 
+    def noisy_members(self):
+        """[(index, handle)] of the lattices whose collision draws just now."""
+        members = list(enumerate(self.h.strains)) if self.kind == "expansion" else [(0, self.h)]
+        return [(i, m) for i, m in members if m._noise()[0] != 0.]
+
+    def fed_phase_step(self, z):
+        """set_noise_field on every noisy lattice, the phases, the fields dropped again."""
+        fed = self.noisy_members()
+        for i, m in fed:
+            m._set_noise_field(z[:, :, i] if self.kind == "expansion" else z)
+        self.phase_step()
+        for _, m in fed:
+            m._set_noise_field(None)
+
     def set_f(self, f):
         self.h.set_f(f)
+
+    def redo_initial_condition(self, rho):
+        self.h.redo_initial_condition(rho)
+
+    def set_params(self, *a):
+        if self.kind == "rocket":
+            self.table = a[0]
+            self.h.set_params(**ROCKET_TABLES[self.case["mode"]][a[0]])
+        else:
+            self.h.set_params(**{a[0]: a[1]})
+
+    def set_noise(self, dg, seed):
+        if self.kind == "expansion":
+            self.h.set_noise(dg, seed)
+        else:
+            self.h._set_noise(dg, seed)         # (the handle may be a plain Simulation by now: a checkpoint restored by that class)
+
+    def noise_counters(self):
+        return [m._noise()[2] for m in (self.h.strains if self.kind == "expansion" else [self.h])]
 
     def init_equilibrium(self, ruv):
         self.h.init_equilibrium(*ruv)
@@ -514,11 +818,16 @@ class GpuPlayer(Player):
         self.mask = None
         self.h.set_obstacle_mask(None)
 
-    def set_reaction(self, G):
-        self.h.set_reaction(G)
+    def set_reaction(self, *a):                     # (G) or, on a set of strains, (strain, G)
+        if self.kind == "expansion":
+            self.h.strains[a[0]].set_reaction(a[1])
+        else:
+            self.h.set_reaction(a[0])
 
     def set_fields(self, uv):
-        self.h.set_fields(np.zeros((self.case["nx"], self.case["ny"]), F), uv[0], uv[1])
+        c = self.case
+        shape = (c["nx"], c["ny"], c["ns"] + 1) if self.kind == "expansion" else (c["nx"], c["ny"])
+        self.h.set_fields(np.zeros(shape, F), uv[0], uv[1])
 
     def set_edge_state(self, e):
         self.h.set_edge_state(e)
@@ -579,6 +888,21 @@ class GpuPlayer(Player):
             h.set_obstacle_mask(self.mask)
         elif name == "checkpoint":
             self.checkpoint()
+        elif name == "get_params":
+            assert h.get_params() == dict(ROCKET_TABLES[self.case["mode"]][self.table], mode=self.case["mode"])
+        elif name == "get_own":
+            own = OWN_NAMES[self.kind][self.case["mode"]] if self.kind == "rocket" else OWN_NAMES[self.kind]
+            assert set(h.get_fields(tuple(own.values()))) == set(own.values())
+        elif name == "solver_scribble":             # the set's own solver on an unrelated charge: a step solves from its density anew
+            h.solver.charge.set(payload(self.case, name, op[1]))
+            h.solver.solve_and_update_grad_fields()
+        elif name == "noise":
+            assert len(self.noise_counters()) == len(np.atleast_1d(self.case.get("Dgs", 0.)))
+        elif name == "noise_fill":                  # a pure function of (seed, counter): it draws nothing
+            z = one._noise_fill(op[1]) if self.kind == "noise" else h.strains[op[1]]._noise_fill(op[2])
+            assert z.shape == (self.case["nx"], self.case["ny"]) and np.isfinite(z).all()
+        elif name == "get_edge_state":
+            assert h.get_edge_state().shape[0] == self.case["ns"] + 1
         else:
             raise ValueError(name)
 
@@ -596,9 +920,29 @@ class GpuPlayer(Player):
             for m, a in zip(self.h.members, arrays):
                 m.restore_arrays(a)
             return
+        if self.kind == "nutrient":                 # (likewise; the parameters are the set's, psi and the force follow from the densities)
+            arrays, params = [m.checkpoint_arrays() for m in self.h.members], dict(self.h.params)
+            self.h.close()
+            self.h = self._create()
+            self.h.set_params(**params)
+            for m, a in zip(self.h.members, arrays):
+                m.restore_arrays(a)
+            self.h.update_forces()
+            return
         self.h.save_checkpoint(path)
         self.h.close()
-        if self.kind == "multifluid":
+        if self.kind == "rocket":
+            from LB_D2Q9.coupled import Surfactant_Colony
+            self.h = Surfactant_Colony.from_checkpoint(path)
+        elif self.kind == "expansion":
+            from LB_D2Q9.expansion_set import Expansion_Set
+            self.h = Expansion_Set.from_checkpoint(path)
+        elif self.kind == "noise":                  # either class restores the noise: in turns, the first by the seed
+            from LB_D2Q9.noisy_simulation import NoisySimulation
+            self.h = (NoisySimulation if restorer(self.case["seed"], self.saves) == "NoisySimulation" else Simulation).from_checkpoint(path)
+        elif self.kind == "screened":               # the lattice; a fresh solver behind it
+            self.h = ScreenedWave(self.case, Simulation.from_checkpoint(path))
+        elif self.kind == "multifluid":
             self.h = Shan_Chen_Fluids.from_checkpoint(path)
         elif self.kind == "flow":
             self.h = Simulation.from_checkpoint(path, eager_macro=c["eager"])
@@ -617,12 +961,27 @@ class GpuPlayer(Player):
         if k == "poisson":
             out["solve_state"] = np.array(h.solve_state())
             out["source"] = h.get_source()
+        if k in ("noise", "expansion", "screened"):
+            out["edge_state"] = h.get_edge_state()
+        out.update(self._own())
         return out
+
+    def _own(self):
+        """psi / S and the forces of the last step, under the models' names; a Nutrient_Set's only while `clumpy` is on (get_fields)."""
+        k = self.kind
+        if k == "rocket":
+            own = OWN_NAMES[k][self.case["mode"]]
+        elif k == "nutrient" and self.h.params["clumpy"]:
+            own = OWN_NAMES[k]
+        else:
+            return {}
+        g = self.h.get_fields(tuple(own.values()))
+        return {name: g[key] for name, key in own.items()}
 
     def fields(self):
         g = self.h.get_fields(FIELD_NAMES[self.kind])
         ren = dict(u_bary="ub", v_bary="vb") if self.kind in ("porous", "multifluid") else {}
-        return {ren.get(k, k): v for k, v in g.items()}
+        return dict({ren.get(k, k): v for k, v in g.items()}, **self._own())
 
 
 class RefPlayer(Player):
@@ -653,6 +1012,25 @@ class RefPlayer(Player):
             from porous_model import PorousModel
             m = PorousModel(c["nx"], c["ny"], F(c["omega"]), *c["porous"], bc=c["bc"], dtype=dtype)
             m.set_body_force(*c["g"])
+        elif k == "rocket":
+            from rocket_model import RocketModel
+            m = RocketModel(c["nx"], c["ny"], c["omegas"][0], c["omegas"][1], c["mode"], dtype, **ROCKET_TABLES[c["mode"]][c["table"]])
+        elif k == "nutrient":
+            from nutrient_model import NutrientModel
+            m = NutrientModel(c["nx"], c["ny"], c["omegas"][0], c["omegas"][1], clumpy=c["clumpy"], dtype=dtype, lam=c["lam"], **c["params"])
+        elif k == "noise":
+            from noise_model import NoisyScalarModel
+            m = NoisyScalarModel(c["nx"], c["ny"], c["omega"], c["G"], c["Dg"], c["noise_seed"], c["bc"], dtype)
+            m.set_fields(np.zeros((c["nx"], c["ny"]), F), c["u"], c["v"])
+        elif k == "expansion":                      # (the float32 model with the engine's arithmetic: every operation of the Milstein term in float32)
+            from expansion_model import ExpansionModel
+            m = ExpansionModel(c["nx"], c["ny"], c["omegas"], c["omega_n"], c["Gs"], c["Dgs"], [c["noise_seed"] + i for i in range(c["ns"])],
+                               c["cut"], c["bc"], dtype, milstein="single")
+            m.set_fields(np.zeros((c["nx"], c["ny"], c["ns"] + 1), F), c["u"], c["v"])
+        elif k == "screened":
+            from spectral_model import ScreenedFisherModel
+            m = ScreenedFisherModel(c["nx"], c["ny"], c["omega"], c["G"], c["lam"], c["scale"], c["bc"], dtype)
+            m.redo_initial_condition(c["rho0"])
         else:
             from multifluid_model import MultifluidModel
             m = MultifluidModel(c["nx"], c["ny"], c["omegas"], c["bc"], dtype)
@@ -671,15 +1049,48 @@ class RefPlayer(Player):
 
     def phase_step(self):
         m = self.m
-        if self.kind in ("porous", "multifluid"):
+        if self.kind in ("porous", "multifluid", "rocket", "nutrient", "expansion", "screened"):
             m.step()                                # (the model's step IS its stages in order)
-        elif self.kind == "scalar":
+        elif self.kind in ("scalar", "noise"):
             m.move(); m.update_hydro(); m.update_feq(); m.collide_particles()
         else:
             m.move(); m.move_bcs(); m.update_hydro(); m.update_feq(); m.collide_particles()
 
+    def fed_phase_step(self, z):
+        m = self.m
+        if self.kind == "expansion":
+            m.noise_fields = [z[:, :, i] if m.Dg[i] != 0 else None for i in range(m.np_)]
+            m.step()
+            m.noise_fields = [None] * m.np_
+        else:
+            m.noise_field = z
+            self.phase_step()
+            m.noise_field = None
+
     def set_f(self, f):
         self.m.set_f(f)
+
+    def redo_initial_condition(self, rho):
+        self.m.redo_initial_condition(rho)
+
+    def set_params(self, *a):
+        if self.kind == "rocket":
+            self.m.set_params(**ROCKET_TABLES[self.case["mode"]][a[0]])
+        elif a[0] == "clumpy":
+            self.m.clumpy = bool(a[1])
+        else:
+            self.m.set_params(**{a[0]: a[1]})
+
+    def set_noise(self, dg, seed):
+        """lb_set_noise: the strength and the seed, and the counter back to 0 -- also where the strength is 0."""
+        m = self.m
+        if self.kind == "expansion":
+            m.Dg, m.seeds, m.t = [m.T(F(d)) for d in dg], [int(seed) + i for i in range(m.np_)], [0] * m.np_
+        else:
+            m.Dg, m.seed, m.t = m.T(F(dg)), int(seed), 0
+
+    def noise_counters(self):
+        return list(self.m.t) if self.kind == "expansion" else [self.m.t]
 
     def init_equilibrium(self, ruv):
         self.m.set_macro(*ruv)
@@ -692,11 +1103,16 @@ class RefPlayer(Player):
     def clear_obstacle_mask(self):
         self.m.mask = None
 
-    def set_reaction(self, G):
-        self.m.set_reaction(G)
+    def set_reaction(self, *a):
+        if self.kind == "expansion":
+            self.m.G[a[0]] = self.m.T(F(a[1]))
+        else:
+            self.m.set_reaction(a[0])
 
     def set_fields(self, uv):
-        self.m.set_fields(np.zeros_like(self.m.rho), uv[0], uv[1])
+        c = self.case
+        shape = (c["nx"], c["ny"], c["ns"] + 1) if self.kind == "expansion" else (c["nx"], c["ny"])
+        self.m.set_fields(np.zeros(shape, self.m.T), uv[0], uv[1])
 
     def set_edge_state(self, e):
         self.m.set_edge_state(e)
@@ -733,6 +1149,10 @@ class RefPlayer(Player):
         m = self.m
         if self.kind in ("porous", "multifluid"):
             return dict(f=m.f, feq=m.feq, rho=m.rho, u=m.u, v=m.v, ub=m.ub, vb=m.vb, Gx=m.Gx, Gy=m.Gy)
+        if self.kind == "rocket":
+            return {k: v for k, v in m.get_fields().items() if m.mode == "forces" or k not in ("Sx", "Sy")}
+        if self.kind == "nutrient":
+            return dict(m.state(), feq=m.feq)
         return m.get_fields()
 
     def porous_header(self):
@@ -767,6 +1187,28 @@ def hold_to_contract(kind, label, have, ref):
         assert_close(have, want, nm, ("rho", "feq"), label)
         if kind != "poisson":
             assert np.array_equal(have["u"], want["u"]) and np.array_equal(have["v"], want["v"])       # imposed: no run writes them
+    elif kind in ("noise", "expansion", "screened"):        # scalar lattices: the scalar contract, in every cell -- no mask, no NaN allowance
+        from test_gpu_scalar import assert_close
+        assert all(np.isfinite(np.asarray(want[k])).all() for k in want), label
+        assert_close(have, want, n, ("f",), label)
+        assert_close(have, want, nm, ("rho", "feq"), label)
+        if kind == "screened":                      # a velocity that is computed
+            assert_close(have, want, nm, ("u", "v"), label)
+        else:
+            assert np.array_equal(have["u"], want["u"]) and np.array_equal(have["v"], want["v"])
+        if kind == "expansion":                     # the links and densities that are exactly 0 (tests/test_expansion_cpu.py's hold): there are none
+            for k in ("f", "rho"):
+                assert np.array_equal(np.asarray(have[k]) == 0, np.asarray(want[k]) == 0) and not (np.asarray(want[k]) == 0).any(), (label, k)
+    elif kind == "rocket":
+        from test_rocket_cpu import compare
+        assert all(np.isfinite(np.asarray(want[k])).all() for k in want), label
+        compare("%s after %d steps" % (label, n), ref.m, n, have, want, ["f"])
+        compare("%s after %d steps" % (label, nm), ref.m, nm, have, want, [k for k in want if k != "f"])
+    elif kind == "nutrient":
+        from test_nutrient_cpu import compare
+        assert all(np.isfinite(np.asarray(want[k])).all() for k in want) and set(have) == set(want), label
+        compare("%s after %d steps" % (label, n), ref.m.params, n, dict(f=have["f"]), dict(f=want["f"], rho=want["rho"]))
+        compare("%s after %d steps" % (label, nm), ref.m.params, nm, {k: v for k, v in have.items() if k != "f"}, {k: v for k, v in want.items() if k != "f"})
     else:
         compare = __import__("test_%s_cpu" % kind).compare
         about = ref.porous_header() if kind == "porous" else ref.m

@@ -15,7 +15,16 @@ through a seeded interleaving of its calls, and two properties are held at two c
 
 The comparisons follow a stepping op, where every array is fresh, or a set_f behind one, where the populations are new and rho, u, v,
 feq and the forces are still the last step's (the populations are then held to the bound of the steps since they were set, the rest
-to that of the steps behind it).  On a Poisson handle the iteration count is held to the model's as well.
+to that of the steps behind it).  On a Poisson handle the iteration count is held to the model's as well; on the noisy kinds the
+noise counters of the subject, the twin and the model are equal at every cut.
+
+The kinds that came later -- rocket, nutrient, noise, expansion, screened -- have host state of their own between their entry points:
+parameters stored with a set's first member or sent with every call, `clumpy` toggled in the middle of a life, psi / S and the forces
+"of the last step", a solver handle that keeps arrays between calls, one noise counter per strain that restarts on set_noise, stands
+still at Dg = 0, is advanced by a collision fed a supplied field and carried through a checkpoint by either class.  Where their twin has
+no plainer kernel to be pinned to (nutrient, expansion, screened) it differs from the subject in run(n) made as n x run(1), which puts
+"the last launch stores" on every launch.  Every cell is compared: no mask, no NaN allowance (tests/test_sequences_cpu.py holds
+the references finite and far from every threshold of the collisions).
 
 Shapes: sequence_scenarios.FLOW_SHAPES and its neighbours, with the reason for each.  That the references alone stay inside the
 contract on exactly these inputs: tests/test_sequences_cpu.py.
@@ -24,6 +33,9 @@ Measured on an MI355X, all 102 cases green, the largest share of its bound that 
 seed 5, the one step by phases behind an init_equilibrium: 2.38e-7 of 2.5e-7), rho 60 %, u 17 %, v 8 %; scalar f 43 %, rho 31 %, feq
 27 %; multifield f 12 %, rho 8 %, feq 8 %; poisson f 19 %, rho 14 %, feq 20 %; porous f 56 %, feq 40 %, rho 42 %, u, v, u_b, G 5 %;
 multifluid f 60 %, feq 40 %, rho 41 %, u, v, u_b, G 5 %.  The flow cases take up to half a second each, the others less.
+The 60 cases of the later kinds, all green: rocket f 33 %, feq 28 %, rho 29 %, u 3 %, v 2 %, psi / S 8 %, the forces 2 %; nutrient f 50 %,
+feq 36 %, rho 38 %, u 3 %, v < 1 %, psi 10 %, F 1 %; noise f 40 %, rho 26 %, feq 26 %; expansion f 52 %, rho 35 %, feq 35 %; screened f 27 %,
+rho 31 %, feq 29 %, u 2 %, v 1 %.  A kind's twelve cases take 1.6 s (noise) to 4.2 s (expansion) together: 0.35 s a case at the most.
 
 One-line defects tried against this file (value-changing only; none kept), with the cases each turned red:
   lb_set_f without its ensure_macro                                      ->  4 (flow: pipe 3, periodic 1 and 3, cavity 4 -- lazy
@@ -38,6 +50,18 @@ One-line defects tried against this file (value-changing only; none kept), with 
   lb_run_coupled storing every field's rho on the FIRST launch           -> 12 of 12 multifield
   lb_set_corner_state without its upload                                 -> 14 (5 of 6 multifield box, 5 of 6 poisson, 4 of 12 velocity
                                                                             inlet: wherever a restored handle gets its corner links)
+and against the later kinds (each run on the kind's twelve cases):
+  lb_run_expansion advancing ad_t of a strain with Dg == 0                ->  6 of 12 expansion (by the counters)
+  k_ex_step storing every rho on the FIRST launch of lb_run_expansion     -> 12 of 12 expansion
+  lb_set_noise leaving the noise counter                                  -> 11 of 12 noise, 8 of 12 expansion
+  scalar_collide (the un-fused collision) not advancing ad_t              -> 11 of 12 noise (four by the counters alone)
+  lb_run_rocket storing psi / S, u, v and the forces on the FIRST launch  -> 12 of 12 rocket
+  lb_set_rocket keeping the stored parameters unless the mode changes     -> 12 of 12 rocket
+  lb_run_nutrient staying clumpy once psi and the force exist             ->  9 of 12 nutrient
+  k_sn_step's growth rate taken from the member, not from the call        -> 12 of 12 nutrient
+  lb_run_screened solving the velocity from the stored rho, not the streamed one -> 12 of 12 screened
+Not tried: defects in the Python classes (kinds._restore_diffusion without its _set_noise_counter): a library built with a defect can
+stand in for the product's, a package cannot.
 """
 import numpy as np
 import pytest
@@ -71,6 +95,9 @@ def test_random_call_sequence(lbhip, oracle, tmp_path, kind, family, seed):
                 S.hold_to_contract(kind, "%s %s seed %d op %d, twin / reference" % (kind, family, seed, i), twin.fields(), ref)
                 if kind == "poisson":               # the iterations since the last solve_reset: run and solve count, the phases do not
                     assert twin.h.solve_state()[0] == ref.m.iterations, (what, twin.h.solve_state(), ref.m.iterations)
+                if kind in ("noise", "expansion"):  # the noisy collisions since the last set_noise, per strain: every player's the same
+                    assert subject.noise_counters() == twin.noise_counters() == ref.noise_counters(), \
+                        (what, subject.noise_counters(), twin.noise_counters(), ref.noise_counters())
     finally:
         subject.close()
         twin.close()

@@ -1,7 +1,11 @@
 """The random call sequences of tests/test_gpu_sequences.py without a GPU (tests/sequence_scenarios.py): the generator is
 deterministic and covers its tables; on exactly these inputs -- mid-life parameter, table and mask changes included -- the float32
 model of every kind that has one stays within the kind's contract of the float64 model, and
-the flow kinds' oracle stays in the range the contract was established in."""
+the flow kinds' oracle stays in the range the contract was established in; the op lists of the kinds that were here first have not
+moved; where a collision has thresholds, the float64 model keeps every thresholded quantity further from its threshold than twice the
+contract's bound, so that an implementation inside the contract cannot sit on the other side."""
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -9,7 +13,11 @@ import sequence_scenarios as S
 
 CASES = [(k, f, s) for k in S.KINDS for f in S.FAMILIES[k] for s in S.SEEDS]
 ids = lambda cases: ["%s-%s-%d" % c for c in cases]
-HAVE_DTYPE = ("scalar", "multifield", "poisson", "porous", "multifluid")
+HAVE_DTYPE = ("scalar", "multifield", "poisson", "porous", "multifluid", "rocket", "nutrient", "noise", "expansion", "screened")
+# sha1 over repr(generate(kind, family, seed)) for all families and seeds of a kind, taken before the generator learnt further kinds
+OLD_DIGESTS = dict(flow="5366cbf62836f6752d9dd508bc3f3c42b99dbceb", scalar="500005ea4af649b7af3a4fe4872ce240dc235b0b",
+                   multifield="4758ca676c4fb3b62d99f82d2ee9f5f90d6d4c26", poisson="37d28bcd89142eb087f330d50b352998b3e4d9b2",
+                   porous="7dde112a067b46efc2be02930dee8c02e2f48c68", multifluid="a0e62ab06d1ecefccb10fe759f0de28c9317e8cf")
 
 
 @pytest.mark.parametrize("kind,family,seed", CASES, ids=ids(CASES))
@@ -17,7 +25,7 @@ def test_generator_is_deterministic_and_within_its_limits(kind, family, seed):
     ops = S.generate(kind, family, seed)
     assert ops == S.generate(kind, family, seed)
     e, t, steps = S.counts(ops)
-    assert 1 <= e <= S.MAX_E and 1 <= t <= S.MAX_T and 1 <= steps <= S.MAX_STEPS, (e, t, steps)
+    assert 1 <= e <= S.MAX_E and 1 <= t <= S.MAX_T and 1 <= steps <= S.STEP_CAP.get(kind, S.MAX_STEPS) <= S.MAX_STEPS, (e, t, steps)
     assert ops[-1][0] == "run"
     for op in ops:                                      # plain values only: the lists above compare by value
         assert all(isinstance(a, (str, int, float, tuple, type(None))) and not isinstance(a, np.generic) for a in op), op
@@ -52,6 +60,40 @@ def test_every_op_of_the_tables_occurs(kind):
         assert {S.case_of(kind, f, s)["mask"] is None for f in S.FAMILIES[kind] for s in S.SEEDS} == {True, False}
     if kind == "scalar":
         assert {S.case_of(kind, f, s)["G"] for f in S.FAMILIES[kind] for s in S.SEEDS} == {0., 0.01}
+    lives = [S.generate(kind, f, s) for f in S.FAMILIES[kind] for s in S.SEEDS]
+    if kind == "rocket":
+        for f in S.FAMILIES[kind]:                      # every table of a mode, set in the middle of a life
+            assert {op[1] for s in S.SEEDS for op in S.generate(kind, f, s) if op[0] == "set_params"} == {0, 1, 2}
+        assert {S.case_of(kind, "flow", s)["nx"] for s in S.SEEDS} == {n for n, _ in S.ROCKET_SHAPES}
+    if kind == "nutrient":
+        for life in lives:                              # `clumpy` both ways inside every life
+            assert {op[2] for op in life if op[:2] == ("set_params", "clumpy")} == {True, False}
+        assert {op[1] for op in ops if op[0] == "set_params"} == {"clumpy"} | set(S.NUTRIENT_VALUES)
+    if kind == "noise":
+        switched = [[op[1] for op in life if op[0] == "set_noise"] for life in lives]
+        assert any(d[0] == 0. and any(x != 0. for x in d[1:]) for d in switched)                 # off and back on
+        assert any(d == [0.] for d in switched) and any(len(d) == 1 and d[0] != 0. for d in switched)
+        restored = {S.restorer(s, k + 1) for f in S.FAMILIES[kind] for s in S.SEEDS
+                    for k in range(sum(op[0] == "checkpoint" for op in S.generate(kind, f, s)))}
+        assert restored == {"Simulation", "NoisySimulation"}                                       # both restoring classes
+    if kind == "expansion":
+        assert {S.case_of(kind, "open", s)["ns"] for s in S.SEEDS} == {1, 2, 3}                   # every strain count
+        strengths = [op[1] for op in ops if op[0] == "set_noise"]
+        assert any(0. in d and any(x != 0. for x in d) for d in strengths) and any(0. not in d for d in strengths)
+        assert {op[1] for op in ops if op[0] == "set_reaction"} == {0, 1, 2}
+    if kind == "screened":
+        assert {S.case_of(kind, "open", s)["nx"] for s in S.SEEDS} == {n for n, _ in S.SPECTRAL_SHAPES}
+
+
+def test_the_cases_that_were_here_first_have_not_moved():
+    """Adding kinds shifts no draw of the 102 op lists that the GPU file's measured shares and defect table were recorded on."""
+    for kind, want in OLD_DIGESTS.items():
+        h = hashlib.sha1()
+        for f in S.FAMILIES[kind]:
+            for s in S.SEEDS:
+                h.update(repr(S.generate(kind, f, s)).encode())
+        assert h.hexdigest() == want, kind
+    assert sum(len(S.FAMILIES[k]) * len(S.SEEDS) for k in OLD_DIGESTS) == 102
 
 
 @pytest.mark.parametrize("kind,family,seed", CASES, ids=ids(CASES))
@@ -119,6 +161,10 @@ def test_float32_model_stays_within_the_contract_of_the_float64_model(kind, fami
         rho = np.asarray(m64.m.rho)
         speed = np.sqrt(np.asarray(m64.m.ub) ** 2 + np.asarray(m64.m.vb) ** 2)
         assert rho.min() > 0.5 and rho.max() < 1.5 and speed.max() < 0.15, (rho.min(), rho.max(), speed.max())
+    if kind in ("rocket", "nutrient", "screened"):      # the range rocket_bounds / nutrient_bounds were established in (their fixtures' and
+        rho = np.asarray(m64.m.rho)                     # droplet cases': densities 0 ... 1.5, speeds below 0.15); the screened wave's likewise
+        speed = np.sqrt(np.asarray(m64.m.u) ** 2 + np.asarray(m64.m.v) ** 2)
+        assert rho.min() > 0. and rho.max() < 1.5 and speed.max() < 0.15, (rho.min(), rho.max(), speed.max())
 
 
 FLOW_CASES = [c for c in CASES if c[0] == "flow"]
@@ -139,3 +185,51 @@ def test_flow_oracle_stays_in_the_contracts_range(oracle, kind, family, seed):
 
     S.play(o, ops, look, [i for i, op in enumerate(ops) if op[0] in S.STEPPING])
     print("%s seed %d: rho %.3f ... %.3f, max |u| %.4f" % (family, seed, worst[0], worst[1], worst[2]))
+
+
+# ---- the thresholds of the noisy collisions and of the colony -------------------------------------------------------------------------
+THRESHOLD_KINDS = ("rocket", "noise", "expansion")
+NEW_KINDS = ("rocket", "nutrient", "noise", "expansion", "screened")
+
+
+def threshold_margins(ref):
+    """{quantity: its smallest distance from its threshold / (2 x the contract's bound for it and the steps behind it)} of a float64
+    reference player right behind a stepping op.  The populations are held for ref.steps steps, the densities for ref.macro_steps.
+      noise      rho against 0 and 1 (outside: NaN), the new links against 0 (below: 0)
+      expansion  every member's rho against zero_cutoff (below: 0), the new links against 0
+      rocket     the population's new links against 0"""
+    from scalar_model import contract_tol
+    m, kind = ref.m, ref.kind
+    f2, rho2 = 2. * contract_tol(ref.steps)["f"], 2. * contract_tol(ref.macro_steps)["rho"]
+    if kind == "noise":
+        return dict(rho=float(min(m.rho.min(), (1. - m.rho).min())) / rho2, links=float(m.f.min()) / f2)
+    if kind == "expansion":
+        g = m.get_fields()
+        return dict(rho=float(np.abs(g["rho"] - float(m.cut)).min()) / rho2, links=float(g["f"].min()) / f2)
+    return dict(links=float(m.f[:, :, 0].min()) / f2)
+
+
+@pytest.mark.parametrize("kind", NEW_KINDS)
+def test_float64_model_is_finite_and_far_from_every_threshold(kind):
+    """After every stepping op of the kind's twelve sequences the float64 reference is finite in every cell of every array, and where
+    the collision has thresholds (rho < zero_cutoff -> 0, a link < 0 -> 0, rho outside [0, 1] -> NaN) every thresholded quantity lies more
+    than twice its contract bound from its threshold: a margin above 1 below.  A threshold crossed in one precision and not in the other
+    is no rounding difference; with these margins every cell can be compared, and is."""
+    worst = {}
+    for family in S.FAMILIES[kind]:
+        for seed in S.SEEDS:
+            case, ops = S.case_of(kind, family, seed), S.generate(kind, family, seed)
+            ref = S.RefPlayer(case, np.float64)
+
+            def look(i):
+                assert all(np.isfinite(np.asarray(a)).all() for a in ref.fields().values()), (family, seed, i, ops[i])
+                if kind in THRESHOLD_KINDS:
+                    for q, margin in threshold_margins(ref).items():
+                        if margin < worst.get(q, (np.inf,))[0]:
+                            worst[q] = (margin, family, seed, i, S.counts(ops[:i + 1])[2])
+
+            S.play(ref, ops, look, [i for i, op in enumerate(ops) if op[0] in S.STEPPING])
+    for q, (margin, family, seed, i, steps) in sorted(worst.items()):
+        print("%s: smallest margin of %s %.3g (x twice the bound; %s seed %d behind op %d, step %d of the life)" % (kind, q, margin, family, seed, i, steps))
+    assert set(worst) == ({"links", "rho"} if kind in ("noise", "expansion") else {"links"} if kind == "rocket" else set())
+    assert all(w[0] > 1. for w in worst.values()), worst
