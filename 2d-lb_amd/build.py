@@ -26,7 +26,9 @@ UNITS = ["deep7.cpp", "deep2.cpp", "deep6.cpp", "march5.cpp", "march4.cpp", "lb_
 # -ffp-contract=on: a*b+c fuses to an FMA only inside one source expression, so every kernel instantiation (single step,
 # multi-step, slab edge rows) -- in whichever translation unit -- rounds identically: results are bitwise independent of the
 # kernel variant and of the slab partition.
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=on", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-constant-logical-operand"]
+# -Werror=format*: every message of fail() (csrc/host.h) is a literal format the compiler checks against its arguments.
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=on", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-constant-logical-operand",
+         "-Werror=format", "-Werror=format-nonliteral"]
 
 
 def hipcc():

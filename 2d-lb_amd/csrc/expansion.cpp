@@ -40,6 +40,7 @@ int expansion_members(lb_sim **f, int count, const lb_expansion_params *p, const
     if (count < 2 || count > EX_MAX_STRAINS + 1)
         return fail(LB_ERR_ARG, "%s takes 2..%d handles, 1..%d strains and the nutrient behind them (got a count of %d)", what,
                     EX_MAX_STRAINS + 1, EX_MAX_STRAINS, count);
+    // (not set_fault's order: the family stands between the kind and the shared geometry, the split step behind the parameters)
     for (int i = 0; i < count; ++i) {
         lb_sim *s = f[i];
         if (!s) return fail(LB_ERR_ARG, "%s: null handle in the set", what);
@@ -50,8 +51,7 @@ int expansion_members(lb_sim **f, int count, const lb_expansion_params *p, const
             if (f[j] == s) return fail(LB_ERR_ARG, "%s: a handle appears twice in the set", what);
         if (s->p.bc_mode != LB_BC_OPEN && s->p.bc_mode != LB_BC_PERIODIC)
             return fail(LB_ERR_ARG, "%s: handle %d is neither open nor periodic (the families LB_BC_OPEN and LB_BC_PERIODIC only)", what, i);
-        if (s->p.nx != f[0]->p.nx || s->p.ny != f[0]->p.ny || s->p.bc_mode != f[0]->p.bc_mode || s->p.device != f[0]->p.device ||
-            (s->p.flags & LB_FLAG_PLANAR) != (f[0]->p.flags & LB_FLAG_PLANAR))
+        if (!same_geometry(s, f[0]))
             return fail(LB_ERR_ARG, "%s: the strains and the nutrient must share grid (geometry), boundary family, layout flag and device", what);
     }
     if (!finite32(p->zero_cutoff)) return fail(LB_ERR_ARG, "%s: zero_cutoff must be finite", what);
@@ -101,8 +101,8 @@ int lb_run_expansion(lb_sim **fields, int count, const lb_expansion_params *p, i
             return fail(LB_ERR_STATE, "lb_run_expansion: handle %d holds a noise field (lb_set_noise_field): only lb_collide_expansion uses one; drop it with NULL first", i);
     if (n_steps == 0) return LB_OK;
     lb_sim *s0 = fields[0];
-    DeviceGuard guard(s0->p.device);
-    if ((rc = set_join(fields, count))) return rc;
+    SetScope sc(fields, count);
+    if ((rc = sc.join())) return rc;
     for (int it = 0; it < n_steps; ++it) {
         ex_step(s0->p.bc_mode, count - 1, it == n_steps - 1, s0->stream, expansion_args(fields, count, *p));     // the last launch stores every rho
         HIP_TRY(hipGetLastError());
@@ -111,11 +111,8 @@ int lb_run_expansion(lb_sim **fields, int count, const lb_expansion_params *p, i
             if (i + 1 < count && fields[i]->ad_Dg != 0.f) fields[i]->ad_t += 1;
         }
     }
-    for (int i = 0; i < count; ++i) {
-        fields[i]->feq_valid = false;
-        fields[i]->macro_valid = true;
-    }
-    return set_release(fields, count);
+    set_ran(fields, count);
+    return sc.release();
 }
 
 int lb_update_hydro_expansion(lb_sim **fields, int count, const lb_expansion_params *p)
@@ -123,8 +120,8 @@ int lb_update_hydro_expansion(lb_sim **fields, int count, const lb_expansion_par
     int rc = expansion_members(fields, count, p, "lb_update_hydro_expansion");
     if (rc) return rc;
     lb_sim *s0 = fields[0];
-    DeviceGuard guard(s0->p.device);
-    if ((rc = set_join(fields, count))) return rc;
+    SetScope sc(fields, count);
+    if ((rc = sc.join())) return rc;
     const ExArgs m = expansion_args(fields, count, *p);
     const dim3 grid = cells_grid(m.a[0]), block(256);
     if (count == 2) hipLaunchKernelGGL(k_ex_hydro<2>, grid, block, 0, s0->stream, m);
@@ -132,7 +129,7 @@ int lb_update_hydro_expansion(lb_sim **fields, int count, const lb_expansion_par
     else hipLaunchKernelGGL(k_ex_hydro<4>, grid, block, 0, s0->stream, m);
     HIP_TRY(hipGetLastError());
     for (int i = 0; i < count; ++i) fields[i]->macro_valid = true;      // (feq keeps its previous content, as after lb_update_hydro)
-    return set_release(fields, count);
+    return sc.release();
 }
 
 int lb_collide_expansion(lb_sim **fields, int count, const lb_expansion_params *p)
@@ -142,8 +139,8 @@ int lb_collide_expansion(lb_sim **fields, int count, const lb_expansion_params *
     for (int i = 0; i < count; ++i)
         if (!fields[i]->feq) return fail(LB_ERR_STATE, "lb_collide_expansion before lb_update_feq on every member");
     lb_sim *s0 = fields[0];
-    DeviceGuard guard(s0->p.device);
-    if ((rc = set_join(fields, count))) return rc;
+    SetScope sc(fields, count);
+    if ((rc = sc.join())) return rc;
     ExArgs m = expansion_args(fields, count, *p);
     for (int i = 0; i < count; ++i) {
         m.a[i].dst = fields[i]->origin(fields[i]->cur);         // relaxed in place
@@ -157,7 +154,7 @@ int lb_collide_expansion(lb_sim **fields, int count, const lb_expansion_params *
     HIP_TRY(hipGetLastError());
     for (int i = 0; i + 1 < count; ++i)
         if (fields[i]->ad_Dg != 0.f) fields[i]->ad_t += 1;      // one noisy collision, from the stream or the supplied field
-    return set_release(fields, count);
+    return sc.release();
 }
 
 }  // extern "C"

@@ -6,7 +6,8 @@
 //   transport.cpp  the RCCL loader, lb_comm_*, lb_peer_*
 //   tune.cpp       lb_autotune* and what they found, remembered (LB_TUNE_CACHE)
 //   lb_hip.cpp     create / destroy / setters, state transfer, the entry points every kind shares (the un-fused phases, lb_run: common
-//                  checks, then the kind's row), the flow kind's row, lb_run_batch, what set calls share, lb_check, timers
+//                  checks, then the kind's row), the flow kind's row, lb_run_batch, what set calls share (SetScope's join and release,
+//                  set_fault), lb_check, timers
 //   scalar.cpp, multifield.cpp, poisson.cpp, porous.cpp, multifluid.cpp, rocket.cpp
 //                  one handle kind each: its kernels, their launches, its row of the kind table, its own entry points of the C ABI
 //   spectral.cpp   the spectral screened-Poisson solver (lb_spectral_*: not a handle kind) and its coupling to a scalar lattice;
@@ -135,7 +136,9 @@ struct DeviceGuard {
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-int fail(int code, const char *fmt, ...);       // records the message lb_last_error returns (this thread's); returns code
+// records the message lb_last_error returns (this thread's); returns code.  (Every format is a literal the compiler checks against its
+// arguments: build.py makes -Wformat and -Wformat-nonliteral errors.)
+int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
@@ -161,9 +164,10 @@ int fail(int code, const char *fmt, ...);       // records the message lb_last_e
     } while (0)
 // A lattice of a surfactant-propelled colony (LB_SEM_ROCKET) is a scalar lattice that is refused under its own name, and by more calls:
 // its velocity is the set's own, its collision needs both members.
+#define ROCKET_REFUSED(name) fail(LB_ERR_STATE, "%s is not available on a lattice of a surfactant-propelled colony (LB_SEM_ROCKET)", name)
 #define NOT_ROCKET(s, name)                                                                                 \
     do {                                                                                                    \
-        if ((s) && (s)->rocket()) return fail(LB_ERR_STATE, "%s is not available on a lattice of a surfactant-propelled colony (LB_SEM_ROCKET)", name); \
+        if ((s) && (s)->rocket()) return ROCKET_REFUSED(name);                                              \
     } while (0)
 #define NOT_POROUS(s, name)                                                                                 \
     do {                                                                                                    \
@@ -215,22 +219,42 @@ int collide_ready(lb_sim *s);                   // lb_collide_particles: feq exi
 int copy_plane_h2d(lb_sim *s, float *dev, const float *host);   // host [rows][nx] <-> device [rows][pitch], on s->stream
 int copy_plane_d2h(lb_sim *s, float *host, const float *dev);
 int copy_quads(hipStream_t st, float *dst, const float *src, long long n4);     // k_copy4 over n4 aligned float4
-// Set calls (lb_run_batch, lb_*_coupled, lb_*_fluids, lb_*_rocket): the members checked, everything enqueued on the first member's
-// stream behind whatever the others still have in flight (set_join), the other members' streams made to see the result (set_release).
-struct SetRules {
-    int semantics, min, max;
-    const char *null_array, *count;     // (what, max, max)
-    const char *null_member;            // (what)
-    bool rocket_named;                  // a rocket handle is refused under its own name first (NOT_ROCKET)
-    int kind_code;
-    const char *kind;                   // (what, index)
-    const char *share;                  // (what): grid, boundary family, layout flag, device
-    bool split_checked;                 // "<what> inside a split step"
-    const char *twice;                  // (what)
+// Set calls (lb_run_batch, lb_*_coupled, lb_*_fluids, lb_*_rocket, lb_*_nutrient, lb_*_expansion; lb_set_velocity_from with {flow,
+// lattice}): the members checked, then everything enqueued on the first member's stream inside a SetScope.  The scope keeps the members'
+// device current; join() puts the first member's stream behind whatever the others still have in flight, release() makes the others'
+// streams see the result.  A call ends with `return sc.release();`.  One that leaves after a successful join without it -- a launch that
+// failed -- is released by the destructor, which drops its own status and records no message: the failure that caused the return is the
+// one reported.  (guard is the first member: the previous device comes back after the release.)
+struct SetScope {
+    DeviceGuard guard;
+    lb_sim **f;
+    int count;
+    bool joined = false;
+    SetScope(lb_sim **f_, int count_) : guard(f_[0]->p.device), f(f_), count(count_) {}
+    SetScope(const SetScope &) = delete;
+    ~SetScope();
+    int join();
+    int release();
 };
-int set_members(lb_sim **f, int count, const char *what, const SetRules &r);
-int set_join(lb_sim **f, int count);
-int set_release(lb_sim **f, int count);
+// after a run of a set: feq is stale; rho, u, v are the last step's
+inline void set_ran(lb_sim **f, int count)
+{
+    for (int i = 0; i < count; ++i) {
+        f[i]->feq_valid = false;
+        f[i]->macro_valid = true;
+    }
+}
+// What the coupled, fluid, rocket and nutrient sets test member by member, in this order; set_fault names the first rule broken and the
+// member (*at) that breaks it, the family's own *_members says it in the family's sentence.
+enum SetFault { SET_FINE, SET_NULL_MEMBER, SET_ROCKET_NAMED, SET_KIND, SET_GEOMETRY, SET_SPLIT_STEP, SET_TWICE };
+// rocket_named: a rocket handle is refused under its own name before its kind is looked at; split_checked: a member inside a split step is refused
+SetFault set_fault(lb_sim **f, int count, int semantics, bool rocket_named, bool split_checked, int *at);
+// what the members of such a set, and of an expansion, share: grid, boundary family, layout flag, device
+inline bool same_geometry(const lb_sim *a, const lb_sim *b)
+{
+    return a->p.nx == b->p.nx && a->p.ny == b->p.ny && a->p.bc_mode == b->p.bc_mode && a->p.device == b->p.device &&
+           (a->p.flags & LB_FLAG_PLANAR) == (b->p.flags & LB_FLAG_PLANAR);
+}
 
 // ---- transport.cpp: RCCL, loaded lazily so that single-GPU use never touches librccl ---------------------------------------------
 struct Rccl {

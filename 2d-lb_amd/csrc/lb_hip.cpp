@@ -380,40 +380,46 @@ static int kind_refusals(const KindOps &k, const lb_params *p)
 }
 
 // ---- what set calls share (host.h) ---------------------------------------------------------------------------------------------------
-int set_members(lb_sim **f, int count, const char *what, const SetRules &r)
+SetFault set_fault(lb_sim **f, int count, int semantics, bool rocket_named, bool split_checked, int *at)
 {
-    if (!f) return fail(LB_ERR_ARG, r.null_array, what, r.max, r.max);
-    if (count < r.min || count > r.max) return fail(LB_ERR_ARG, r.count, what, r.max, r.max);
     for (int i = 0; i < count; ++i) {
-        lb_sim *s = f[i];
-        if (!s) return fail(LB_ERR_ARG, r.null_member, what);
-        if (r.rocket_named) NOT_ROCKET(s, what);
-        if (s->cpu || s->p.semantics != r.semantics) return fail(r.kind_code, r.kind, what, i);
-        if (s->p.nx != f[0]->p.nx || s->p.ny != f[0]->p.ny || s->p.bc_mode != f[0]->p.bc_mode || s->p.device != f[0]->p.device ||
-            (s->p.flags & LB_FLAG_PLANAR) != (f[0]->p.flags & LB_FLAG_PLANAR))
-            return fail(LB_ERR_ARG, r.share, what);
-        if (r.split_checked && s->stepping) return fail(LB_ERR_STATE, "%s inside a split step", what);
+        const lb_sim *s = f[i];
+        *at = i;
+        if (!s) return SET_NULL_MEMBER;
+        if (rocket_named && s->rocket()) return SET_ROCKET_NAMED;
+        if (s->cpu || s->p.semantics != semantics) return SET_KIND;
+        if (!same_geometry(s, f[0])) return SET_GEOMETRY;
+        if (split_checked && s->stepping) return SET_SPLIT_STEP;
         for (int j = 0; j < i; ++j)
-            if (f[j] == s) return fail(LB_ERR_ARG, r.twice, what);
+            if (f[j] == s) return SET_TWICE;
     }
-    return LB_OK;
+    return SET_FINE;
 }
 
-int set_join(lb_sim **f, int count)
+int SetScope::join()
 {
     for (int i = 1; i < count; ++i) {
         HIP_TRY(hipEventRecord(f[i]->ev_interior, f[i]->stream));
         HIP_TRY(hipStreamWaitEvent(f[0]->stream, f[i]->ev_interior, 0));
     }
+    joined = true;
     return LB_OK;
 }
 
-int set_release(lb_sim **f, int count)
+int SetScope::release()
 {
+    joined = false;
     if (count < 2) return LB_OK;
     HIP_TRY(hipEventRecord(f[0]->ev_interior, f[0]->stream));
     for (int i = 1; i < count; ++i) HIP_TRY(hipStreamWaitEvent(f[i]->stream, f[0]->ev_interior, 0));
     return LB_OK;
+}
+
+SetScope::~SetScope()
+{
+    if (!joined || count < 2) return;
+    (void)hipEventRecord(f[0]->ev_interior, f[0]->stream);
+    for (int i = 1; i < count; ++i) (void)hipStreamWaitEvent(f[i]->stream, f[0]->ev_interior, 0);
 }
 
 // The buffers every GPU handle has, the kind's own among them (KindOps::create).  A failure leaves what was allocated to lb_destroy.
@@ -1076,6 +1082,7 @@ int lb_run_batch(lb_sim **sims, int count, int n_steps)
     for (int i = 0; sims && i < count; ++i) SCALAR_UNSUPPORTED(sims[i], "lb_run_batch");
     if (!sims || count < 1 || count > BATCH_MAX || n_steps < 0)
         return fail(LB_ERR_ARG, "lb_run_batch takes 1..%d handles and a non-negative step count", BATCH_MAX);
+    // (not set_fault's rules: the kind is a whole-grid periodic flow handle, and what the members share is grid, device and mask presence)
     for (int i = 0; i < count; ++i) {
         lb_sim *s = sims[i];
         if (!s) return fail(LB_ERR_ARG, "null handle in batch");
@@ -1090,9 +1097,8 @@ int lb_run_batch(lb_sim **sims, int count, int n_steps)
     }
     if (n_steps == 0) return LB_OK;
     lb_sim *s0 = sims[0];
-    DeviceGuard guard(s0->p.device);
-    int rc = set_join(sims, count);
-    if (rc) return rc;
+    SetScope sc(sims, count);
+    if (int rc = sc.join()) return rc;
     const dim3 block(256, 1);
     const dim3 grid((unsigned)((s0->pitch / 4 + 255) / 256), (unsigned)s0->H, (unsigned)count);
     bool lazy = true;              // (one launch serves all members: rho, u, v are stored unless every member rebuilds them on demand)
@@ -1109,7 +1115,7 @@ int lb_run_batch(lb_sim **sims, int count, int n_steps)
         sims[i]->feq_valid = false;
         sims[i]->macro_valid = !lazy;
     }
-    return set_release(sims, count);
+    return sc.release();
 }
 
 // ---- health check ------------------------------------------------------------------------

@@ -49,10 +49,19 @@ int multifield_collide(lb_sim *s) { return s->feq ? lb_collide_coupled(&s, 1) : 
 int multifield_run(lb_sim *s, int n_steps) { return lb_run_coupled(&s, 1, n_steps); }
 
 // the members of a set, checked alike for lb_run_coupled and lb_collide_coupled
-const SetRules COUPLED = {
-    LB_SEM_MULTIFIELD, 1, MF_MAX, "%s takes 1..%d handles", "%s takes 1..%d handles", "null handle in the coupled set", false,
-    LB_ERR_ARG, "the members of a coupled set must be LB_SEM_MULTIFIELD handles",
-    "the members of a coupled set must share grid, boundary family, layout flag and device", true, "a handle appears twice in the coupled set"};
+int coupled_members(lb_sim **f, int count, const char *what)
+{
+    if (!f || count < 1 || count > MF_MAX) return fail(LB_ERR_ARG, "%s takes 1..%d handles", what, MF_MAX);
+    int at = 0;
+    switch (set_fault(f, count, LB_SEM_MULTIFIELD, false, true, &at)) {
+    case SET_NULL_MEMBER: return fail(LB_ERR_ARG, "null handle in the coupled set");
+    case SET_KIND: return fail(LB_ERR_ARG, "the members of a coupled set must be LB_SEM_MULTIFIELD handles");
+    case SET_GEOMETRY: return fail(LB_ERR_ARG, "the members of a coupled set must share grid, boundary family, layout flag and device");
+    case SET_SPLIT_STEP: return fail(LB_ERR_STATE, "%s inside a split step", what);
+    case SET_TWICE: return fail(LB_ERR_ARG, "a handle appears twice in the coupled set");
+    default: return LB_OK;
+    }
+}
 
 }  // namespace
 
@@ -67,13 +76,13 @@ int lb_run_coupled(lb_sim **fields, int count, int n_steps)
 {
     for (int i = 0; fields && i < count; ++i) NOT_POROUS(fields[i], "lb_run_coupled");
     for (int i = 0; fields && i < count; ++i) NOT_ROCKET(fields[i], "lb_run_coupled");
-    int rc = set_members(fields, count, "lb_run_coupled", COUPLED);
+    int rc = coupled_members(fields, count, "lb_run_coupled");
     if (rc) return rc;
     if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
     if (n_steps == 0) return LB_OK;
     lb_sim *s0 = fields[0];
-    DeviceGuard guard(s0->p.device);
-    if ((rc = set_join(fields, count))) return rc;
+    SetScope sc(fields, count);
+    if ((rc = sc.join())) return rc;
     for (int it = 0; it < n_steps; ++it) {
         MfArgs m = {};
         for (int i = 0; i < count; ++i) {
@@ -84,22 +93,19 @@ int lb_run_coupled(lb_sim **fields, int count, int n_steps)
         HIP_TRY(hipGetLastError());
         for (int i = 0; i < count; ++i) fields[i]->cur ^= 1;
     }
-    for (int i = 0; i < count; ++i) {
-        fields[i]->feq_valid = false;
-        fields[i]->macro_valid = true;
-    }
-    return set_release(fields, count);
+    set_ran(fields, count);
+    return sc.release();
 }
 
 int lb_collide_coupled(lb_sim **fields, int count)
 {
-    int rc = set_members(fields, count, "lb_collide_coupled", COUPLED);
+    int rc = coupled_members(fields, count, "lb_collide_coupled");
     if (rc) return rc;
     for (int i = 0; i < count; ++i)
         if (!fields[i]->feq) return fail(LB_ERR_STATE, "lb_collide_coupled before lb_update_feq on every member");
     lb_sim *s0 = fields[0];
-    DeviceGuard guard(s0->p.device);
-    if ((rc = set_join(fields, count))) return rc;
+    SetScope sc(fields, count);
+    if ((rc = sc.join())) return rc;
     MfArgs m = {};
     for (int i = 0; i < count; ++i) {
         m.a[i] = step_args(fields[i], 0, 1, fields[i]->H);
@@ -109,7 +115,7 @@ int lb_collide_coupled(lb_sim **fields, int count)
     }
     mf_collide(count, s0->stream, m);
     HIP_TRY(hipGetLastError());
-    return set_release(fields, count);
+    return sc.release();
 }
 
 }  // extern "C"

@@ -92,16 +92,19 @@ int multifluid_collide(lb_sim *s)
 int multifluid_run(lb_sim *s, int n_steps) { return lb_run_fluids(&s, 1, n_steps); }
 
 // the members of a set, checked alike for every set call
-const SetRules FLUIDS = {
-    LB_SEM_MULTIFLUID, 1, MC_MAX, "%s: null handle array", "%s takes 1..%d handles (more than %d fluids are not built)", "null handle in the set of fluids", true,
-    LB_ERR_STATE, "%s is for the fluids of a multicomponent set (LB_SEM_MULTIFLUID)",
-    "the fluids of a set must share grid, boundary family, layout flag and device (fluids of different families in one set are not built)", false,
-    "a handle appears twice in the set of fluids"};
-
 int fluid_members(lb_sim **f, int count, const char *what)
 {
-    int rc = set_members(f, count, what, FLUIDS);
-    if (rc) return rc;
+    if (!f) return fail(LB_ERR_ARG, "%s: null handle array", what);
+    if (count < 1 || count > MC_MAX) return fail(LB_ERR_ARG, "%s takes 1..%d handles (more than %d fluids are not built)", what, MC_MAX, MC_MAX);
+    int at = 0;
+    switch (set_fault(f, count, LB_SEM_MULTIFLUID, true, false, &at)) {
+    case SET_NULL_MEMBER: return fail(LB_ERR_ARG, "null handle in the set of fluids");
+    case SET_ROCKET_NAMED: return ROCKET_REFUSED(what);
+    case SET_KIND: return fail(LB_ERR_STATE, "%s is for the fluids of a multicomponent set (LB_SEM_MULTIFLUID)", what);
+    case SET_GEOMETRY: return fail(LB_ERR_ARG, "the fluids of a set must share grid, boundary family, layout flag and device (fluids of different families in one set are not built)");
+    case SET_TWICE: return fail(LB_ERR_ARG, "a handle appears twice in the set of fluids");
+    default: break;
+    }
     // the tables name fluids by their place in the set
     for (int t = 0; t < f[0]->mc_n_inter; ++t)
         if (f[0]->mc_inter[t].i >= count || f[0]->mc_inter[t].j >= count)
@@ -144,8 +147,8 @@ int lb_run_fluids(lb_sim **fluids, int count, int n_steps)
     if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
     if (n_steps == 0) return LB_OK;
     lb_sim *s0 = fluids[0];
-    DeviceGuard guard(s0->p.device);
-    if ((rc = set_join(fluids, count))) return rc;
+    SetScope sc(fluids, count);
+    if ((rc = sc.join())) return rc;
     for (int it = 0; it < n_steps; ++it) {
         const McArgs m = fluid_args(fluids, count);
         if (multifluid_one_launch(s0)) {            // (the set's first handle chooses: lb_set_variant; plan.cpp)
@@ -159,11 +162,8 @@ int lb_run_fluids(lb_sim **fluids, int count, int n_steps)
         }
         for (int i = 0; i < count; ++i) fluids[i]->cur ^= 1;
     }
-    for (int i = 0; i < count; ++i) {
-        fluids[i]->feq_valid = false;
-        fluids[i]->macro_valid = true;
-    }
-    return set_release(fluids, count);
+    set_ran(fluids, count);
+    return sc.release();
 }
 
 int lb_set_interactions(lb_sim **fluids, int count, const lb_interaction *table, int n)
@@ -240,23 +240,23 @@ int lb_update_forces_fluids(lb_sim **fluids, int count)
 {
     int rc = fluid_members(fluids, count, "lb_update_forces_fluids");
     if (rc) return rc;
-    DeviceGuard guard(fluids[0]->p.device);
-    if ((rc = set_join(fluids, count))) return rc;
+    SetScope sc(fluids, count);
+    if ((rc = sc.join())) return rc;
     mc_forces(fluids[0]->p.bc_mode, count, fluids[0]->stream, fluid_args(fluids, count));
     HIP_TRY(hipGetLastError());
-    return set_release(fluids, count);
+    return sc.release();
 }
 
 int lb_update_bary_fluids(lb_sim **fluids, int count)
 {
     int rc = fluid_members(fluids, count, "lb_update_bary_fluids");
     if (rc) return rc;
-    DeviceGuard guard(fluids[0]->p.device);
-    if ((rc = set_join(fluids, count))) return rc;
+    SetScope sc(fluids, count);
+    if ((rc = sc.join())) return rc;
     mc_bary(count, fluids[0]->stream, fluid_args(fluids, count));
     HIP_TRY(hipGetLastError());
     for (int i = 0; i < count; ++i) fluids[i]->feq_valid = false;
-    return set_release(fluids, count);
+    return sc.release();
 }
 
 int lb_react_fluids(lb_sim **fluids, int count)
@@ -264,13 +264,13 @@ int lb_react_fluids(lb_sim **fluids, int count)
     int rc = fluid_members(fluids, count, "lb_react_fluids");
     if (rc) return rc;
     if (fluids[0]->mc_n_react == 0) return LB_OK;
-    DeviceGuard guard(fluids[0]->p.device);
-    if ((rc = set_join(fluids, count))) return rc;
+    SetScope sc(fluids, count);
+    if ((rc = sc.join())) return rc;
     McArgs m = fluid_args(fluids, count);
     for (int i = 0; i < count; ++i) m.a[i].dst = fluids[i]->origin(fluids[i]->cur);       // in place
     mc_react(count, fluids[0]->stream, m);
     HIP_TRY(hipGetLastError());
-    return set_release(fluids, count);
+    return sc.release();
 }
 
 }  // extern "C"

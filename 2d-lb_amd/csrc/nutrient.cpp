@@ -25,17 +25,20 @@ void sn_step(bool clumpy, bool last, hipStream_t st, const SnArgs &m)
 }
 
 // the two members of a set, checked alike for every set call
-const SetRules NUTRIENT = {
-    LB_SEM_DIFFUSION, 2, 2, "%s: null handle array", "", "%s: null handle in the set", true,
-    LB_ERR_ARG, "%s: handle %d is not a scalar lattice on the GPU (LB_SEM_DIFFUSION is required)",
-    "%s: the population and the nutrient must share grid (geometry), layout flag and device", true, "%s: a handle appears twice in the set"};
-
 int nutrient_members(lb_sim **f, int count, const char *what)
 {
     if (!f) return fail(LB_ERR_ARG, "%s: null handle array", what);
     if (count != 2) return fail(LB_ERR_ARG, "%s takes exactly 2 handles, the population and the nutrient (got a count of %d)", what, count);
-    int rc = set_members(f, count, what, NUTRIENT);
-    if (rc) return rc;
+    int at = 0;
+    switch (set_fault(f, count, LB_SEM_DIFFUSION, true, true, &at)) {
+    case SET_NULL_MEMBER: return fail(LB_ERR_ARG, "%s: null handle in the set", what);
+    case SET_ROCKET_NAMED: return ROCKET_REFUSED(what);
+    case SET_KIND: return fail(LB_ERR_ARG, "%s: handle %d is not a scalar lattice on the GPU (LB_SEM_DIFFUSION is required)", what, at);
+    case SET_GEOMETRY: return fail(LB_ERR_ARG, "%s: the population and the nutrient must share grid (geometry), layout flag and device", what);
+    case SET_SPLIT_STEP: return fail(LB_ERR_STATE, "%s inside a split step", what);
+    case SET_TWICE: return fail(LB_ERR_ARG, "%s: a handle appears twice in the set", what);
+    case SET_FINE: break;
+    }
     for (int i = 0; i < 2; ++i) {
         if (f[i]->p.bc_mode != LB_BC_PERIODIC) return fail(LB_ERR_ARG, "%s: handle %d is not periodic (the family LB_BC_PERIODIC only)", what, i);
         if (f[i]->multi_slab()) return fail(LB_ERR_STATE, "%s is only available on handles that own the whole grid", what);
@@ -100,9 +103,9 @@ int lb_run_nutrient(lb_spectral *sp, lb_sim **fields, int count, const lb_nutrie
     if ((rc = nutrient_params(fields, p, "lb_run_nutrient"))) return rc;
     if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
     if (n_steps == 0) return LB_OK;
-    DeviceGuard guard(s0->p.device);
+    SetScope sc(fields, 2);
     if (p->clumpy && (rc = nutrient_planes(s0))) return rc;
-    if ((rc = set_join(fields, 2))) return rc;
+    if ((rc = sc.join())) return rc;
     if ((rc = sp_borrow(sp, s0->stream))) return rc;
     for (int it = 0; it < n_steps; ++it) {
         if ((rc = scalar_moments(s0))) return rc;                   // rho_p after streaming; nothing moves
@@ -111,12 +114,9 @@ int lb_run_nutrient(lb_spectral *sp, lb_sim **fields, int count, const lb_nutrie
         HIP_TRY(hipGetLastError());
         for (int i = 0; i < 2; ++i) fields[i]->cur ^= 1;
     }
-    for (int i = 0; i < 2; ++i) {
-        fields[i]->feq_valid = false;
-        fields[i]->macro_valid = true;
-    }
+    set_ran(fields, 2);
     if ((rc = sp_return(sp, s0->stream))) return rc;
-    return set_release(fields, 2);
+    return sc.release();
 }
 
 int lb_nutrient_velocity(lb_spectral *sp, lb_sim **fields, int count, float scale, int streamed)
@@ -126,8 +126,8 @@ int lb_nutrient_velocity(lb_spectral *sp, lb_sim **fields, int count, float scal
     lb_sim *s0 = fields[0], *s1 = fields[1];
     if ((rc = sp_coupled_ready(sp, s0, "lb_nutrient_velocity"))) return rc;
     if (!finite32(scale)) return fail(LB_ERR_ARG, "the velocity's factor must be finite");
-    DeviceGuard guard(s0->p.device);
-    if ((rc = set_join(fields, 2))) return rc;
+    SetScope sc(fields, 2);
+    if ((rc = sc.join())) return rc;
     if (streamed) rc = scalar_moments(s0);
     else rc = ensure_macro(s0);
     if (rc) return rc;
@@ -139,7 +139,7 @@ int lb_nutrient_velocity(lb_spectral *sp, lb_sim **fields, int count, float scal
     if ((rc = copy_quads(s0->stream, s1->v, s0->v, n4))) return rc;
     for (int i = 0; i < 2; ++i) fields[i]->feq_valid = false;
     if ((rc = sp_return(sp, s0->stream))) return rc;
-    return set_release(fields, 2);
+    return sc.release();
 }
 
 int lb_update_forces_nutrient(lb_sim **fields, int count, const lb_nutrient_params *p)
@@ -149,13 +149,13 @@ int lb_update_forces_nutrient(lb_sim **fields, int count, const lb_nutrient_para
     if ((rc = nutrient_params(fields, p, "lb_update_forces_nutrient"))) return rc;
     if (!p->clumpy) return fail(LB_ERR_ARG, "lb_update_forces_nutrient: psi and F exist in the clumpy variant only");
     lb_sim *s0 = fields[0];
-    DeviceGuard guard(s0->p.device);
+    SetScope sc(fields, 2);
     if ((rc = nutrient_planes(s0))) return rc;
-    if ((rc = set_join(fields, 2))) return rc;
+    if ((rc = sc.join())) return rc;
     const SnArgs m = nutrient_args(fields, *p);
     hipLaunchKernelGGL(k_sn_forces, cells_grid(m.a[0]), dim3(256), 0, s0->stream, m);
     HIP_TRY(hipGetLastError());
-    return set_release(fields, 2);
+    return sc.release();
 }
 
 int lb_collide_nutrient(lb_sim **fields, int count, const lb_nutrient_params *p)
@@ -167,15 +167,15 @@ int lb_collide_nutrient(lb_sim **fields, int count, const lb_nutrient_params *p)
         if (!fields[i]->feq) return fail(LB_ERR_STATE, "lb_collide_nutrient before lb_update_feq on both members");
     lb_sim *s0 = fields[0];
     if (p->clumpy && !s0->ry_op) return fail(LB_ERR_STATE, "lb_collide_nutrient (clumpy) before lb_update_forces_nutrient");
-    DeviceGuard guard(s0->p.device);
-    if ((rc = set_join(fields, 2))) return rc;
+    SetScope sc(fields, 2);
+    if ((rc = sc.join())) return rc;
     SnArgs m = nutrient_args(fields, *p);
     for (int i = 0; i < 2; ++i) m.a[i].dst = fields[i]->origin(fields[i]->cur);      // relaxed in place
     const float *feq_p = fields[0]->feq_origin(), *feq_n = fields[1]->feq_origin();
     if (p->clumpy) hipLaunchKernelGGL(k_sn_collide<true>, cells_grid(m.a[0]), dim3(256), 0, s0->stream, m, feq_p, feq_n);
     else hipLaunchKernelGGL(k_sn_collide<false>, cells_grid(m.a[0]), dim3(256), 0, s0->stream, m, feq_p, feq_n);
     HIP_TRY(hipGetLastError());
-    return set_release(fields, 2);
+    return sc.release();
 }
 
 int lb_get_nutrient_fields(lb_sim **fields, int count, float *psi, float *Fx, float *Fy)

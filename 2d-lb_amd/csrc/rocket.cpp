@@ -61,16 +61,19 @@ int rocket_collide(lb_sim *s) { NOT_ROCKET(s, "lb_collide_particles (the collisi
 int rocket_run(lb_sim *s, int) { NOT_ROCKET(s, "lb_run (a colony advances as a set of two: lb_run_rocket)"); return LB_OK; }
 
 // the two members of a set, checked alike for every set call
-const SetRules COLONY = {
-    LB_SEM_ROCKET, 2, 2, "%s: null handle array", "", "%s: null handle in the set", false,
-    LB_ERR_ARG, "%s: handle %d is not a lattice of a surfactant-propelled colony (a non-rocket handle: LB_SEM_ROCKET is required)",
-    "%s: the two lattices of a colony must share grid (geometry), layout flag and device", true, "%s: a handle appears twice in the set"};
-
 int rocket_members(lb_sim **f, int count, const char *what)
 {
     if (!f) return fail(LB_ERR_ARG, "%s: null handle array", what);
     if (count != 2) return fail(LB_ERR_ARG, "%s takes exactly 2 handles, the population and the surfactant (got a count of %d)", what, count);
-    return set_members(f, count, what, COLONY);
+    int at = 0;
+    switch (set_fault(f, count, LB_SEM_ROCKET, false, true, &at)) {
+    case SET_NULL_MEMBER: return fail(LB_ERR_ARG, "%s: null handle in the set", what);
+    case SET_KIND: return fail(LB_ERR_ARG, "%s: handle %d is not a lattice of a surfactant-propelled colony (a non-rocket handle: LB_SEM_ROCKET is required)", what, at);
+    case SET_GEOMETRY: return fail(LB_ERR_ARG, "%s: the two lattices of a colony must share grid (geometry), layout flag and device", what);
+    case SET_SPLIT_STEP: return fail(LB_ERR_STATE, "%s inside a split step", what);
+    case SET_TWICE: return fail(LB_ERR_ARG, "%s: a handle appears twice in the set", what);
+    default: return LB_OK;
+    }
 }
 
 // (src = the current lattice, dst = the other one: what the fused steps read and write; the stages set dst themselves.  Every derived
@@ -133,8 +136,8 @@ int lb_run_rocket(lb_sim **fields, int count, int n_steps)
     if (n_steps < 0) return fail(LB_ERR_ARG, "negative step count");
     if (n_steps == 0) return LB_OK;
     lb_sim *s0 = fields[0];
-    DeviceGuard guard(s0->p.device);
-    if ((rc = set_join(fields, 2))) return rc;
+    SetScope sc(fields, 2);
+    if ((rc = sc.join())) return rc;
     const int mode = s0->ry.mode;
     for (int it = 0; it < n_steps; ++it) {
         const RyArgs m = rocket_args(fields);
@@ -150,11 +153,8 @@ int lb_run_rocket(lb_sim **fields, int count, int n_steps)
         }
         for (int i = 0; i < 2; ++i) fields[i]->cur ^= 1;
     }
-    for (int i = 0; i < 2; ++i) {
-        fields[i]->feq_valid = false;
-        fields[i]->macro_valid = true;
-    }
-    return set_release(fields, 2);
+    set_ran(fields, 2);
+    return sc.release();
 }
 
 // The un-fused stage 3 and stage 5, from the stored densities: u, v (FLOW: the stencil over rho_c; FORCES: F_p + F_s from the stored
@@ -163,27 +163,27 @@ int lb_update_velocity_rocket(lb_sim **fields, int count)
 {
     int rc = rocket_members(fields, count, "lb_update_velocity_rocket");
     if (rc) return rc;
-    DeviceGuard guard(fields[0]->p.device);
-    if ((rc = set_join(fields, 2))) return rc;
+    SetScope sc(fields, 2);
+    if ((rc = sc.join())) return rc;
     const RyArgs m = rocket_args(fields);
     if (fields[0]->ry.mode == LB_ROCKET_FLOW) hipLaunchKernelGGL(k_ry_velocity<LB_ROCKET_FLOW>, cells_grid(m.a[0]), dim3(256), 0, fields[0]->stream, m);
     else hipLaunchKernelGGL(k_ry_velocity<LB_ROCKET_FORCES>, cells_grid(m.a[0]), dim3(256), 0, fields[0]->stream, m);
     HIP_TRY(hipGetLastError());
     for (int i = 0; i < 2; ++i) fields[i]->feq_valid = false;
-    return set_release(fields, 2);
+    return sc.release();
 }
 
 int lb_update_forces_rocket(lb_sim **fields, int count)
 {
     int rc = rocket_members(fields, count, "lb_update_forces_rocket");
     if (rc) return rc;
-    DeviceGuard guard(fields[0]->p.device);
-    if ((rc = set_join(fields, 2))) return rc;
+    SetScope sc(fields, 2);
+    if ((rc = sc.join())) return rc;
     const RyArgs m = rocket_args(fields);
     if (fields[0]->ry.mode == LB_ROCKET_FLOW) hipLaunchKernelGGL(k_ry_forces<LB_ROCKET_FLOW>, cells_grid(m.a[0]), dim3(256), 0, fields[0]->stream, m);
     else hipLaunchKernelGGL(k_ry_forces<LB_ROCKET_FORCES>, cells_grid(m.a[0]), dim3(256), 0, fields[0]->stream, m);
     HIP_TRY(hipGetLastError());
-    return set_release(fields, 2);
+    return sc.release();
 }
 
 int lb_collide_rocket(lb_sim **fields, int count)
@@ -192,15 +192,15 @@ int lb_collide_rocket(lb_sim **fields, int count)
     if (rc) return rc;
     for (int i = 0; i < 2; ++i)
         if (!fields[i]->feq) return fail(LB_ERR_STATE, "lb_collide_rocket before lb_update_feq on both members");
-    DeviceGuard guard(fields[0]->p.device);
-    if ((rc = set_join(fields, 2))) return rc;
+    SetScope sc(fields, 2);
+    if ((rc = sc.join())) return rc;
     RyArgs m = rocket_args(fields);
     for (int i = 0; i < 2; ++i) m.a[i].dst = fields[i]->origin(fields[i]->cur);      // relaxed in place
     const float *feq_p = fields[0]->feq_origin(), *feq_c = fields[1]->feq_origin();
     if (fields[0]->ry.mode == LB_ROCKET_FLOW) hipLaunchKernelGGL(k_ry_relax<LB_ROCKET_FLOW>, cells_grid(m.a[0]), dim3(256), 0, fields[0]->stream, m, feq_p, feq_c);
     else hipLaunchKernelGGL(k_ry_relax<LB_ROCKET_FORCES>, cells_grid(m.a[0]), dim3(256), 0, fields[0]->stream, m, feq_p, feq_c);
     HIP_TRY(hipGetLastError());
-    return set_release(fields, 2);
+    return sc.release();
 }
 
 int lb_get_rocket_fields(lb_sim **fields, int count, float *psi_or_S, float *Fx, float *Fy, float *Fsx, float *Fsy)

@@ -363,20 +363,19 @@ int lb_set_velocity_from(lb_sim *s, lb_sim *flow)
     if (flow->p.nx != s->p.nx || flow->p.ny != s->p.ny || flow->p.device != s->p.device)
         return fail(LB_ERR_ARG, "the flow handle must have the scalar lattice's grid (%d x %d) and device", s->p.nx, s->p.ny);
     if (flow->stepping) return fail(LB_ERR_STATE, "lb_set_velocity_from inside a split step of the flow handle");
-    DeviceGuard guard(s->p.device);
+    // a set of two, the flow handle first: on ITS stream, behind its work; this handle's kernels may still read u, v, and its later ones
+    // must see the new
+    lb_sim *pair[2] = {flow, s};
+    SetScope sc(pair, 2);
     int rc = ensure_macro(flow);                    // the flow's lazily rebuilt rho, u, v
     if (rc) return rc;
-    // on the FLOW handle's stream, behind its work; this handle's kernels may still read u, v, and its later ones must see the new
-    HIP_TRY(hipEventRecord(s->ev_interior, s->stream));
-    HIP_TRY(hipStreamWaitEvent(flow->stream, s->ev_interior, 0));
+    if ((rc = sc.join())) return rc;
     // (rho, u, v are [H][pitch] whatever the layout of the lattices: LB_FLAG_PLANAR on either handle does not matter here)
     const long long n4 = s->pitch * s->H / 4;       // (same pitch: same nx)
     for (int i = 0; i < 2; ++i)
         if ((rc = copy_quads(flow->stream, i ? s->v : s->u, i ? flow->v : flow->u, n4))) return rc;
-    HIP_TRY(hipEventRecord(flow->ev_interior, flow->stream));
-    HIP_TRY(hipStreamWaitEvent(s->stream, flow->ev_interior, 0));
     s->feq_valid = false;
-    return LB_OK;
+    return sc.release();
 }
 
 }  // extern "C"

@@ -4,8 +4,8 @@ behind it without a host wait, one synchronisation, a bitwise comparison with a 
 lb_run_expansion.
 
 The chain: two noisy strains and the nutrient; the NUTRIENT's handle on S, the strains on their own streams.  Behind the delay on S: a
-plain run(3) of the nutrient alone on S; lb_run_expansion(4) on the first strain's stream, which must wait for it (set_join); a run(2)
-of the nutrient alone on S again, which must wait for the set's launches (set_release).  (No control of its own, as for the coupled
+plain run(3) of the nutrient alone on S; lb_run_expansion(4) on the first strain's stream, which must wait for it (SetScope::join); a run(2)
+of the nutrient alone on S again, which must wait for the set's launches (SetScope::release).  (No control of its own, as for the coupled
 set: these handles take no device buffer a torch op could poison.)
 """
 from stream_scenarios import EPILOGUE, PRELUDE  # noqa: F401
