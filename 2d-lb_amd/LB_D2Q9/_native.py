@@ -132,6 +132,8 @@ SIGNATURES = {
     # noisy strains on a shared nutrient (2 ... 4 scalar lattices, the nutrient last; the parameters: ExpansionParams)
     "lb_run_expansion": ([_hp, _I, ct.POINTER(ExpansionParams), _I],), "lb_update_hydro_expansion": ([_hp, _I, ct.POINTER(ExpansionParams)],),
     "lb_collide_expansion": ([_hp, _I, ct.POINTER(ExpansionParams)],),
+    # a flow and the scalars it carries (flow, scalars, count, n_steps, form); the name of what runs (count, form, cells, buf, buflen)
+    "lb_run_advected": ([_h, _hp, _I, _I, _I],), "lb_advected_kernel": ([_I, _I, ct.c_int64, ct.c_char_p, _I],),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -7,6 +7,8 @@ per step.  Here every field is one engine lattice (``Simulation(semantics='multi
 towards ``w_k rho_i (1 + 3 c_k.u)`` and grows by ``w_k G_i rho_i (1 - sum_j rho_j)``.  ``bc='box'`` is the fork's closed
 box (on-node bounce-back on all four walls), ``bc='periodic'`` wraps.  The phase methods run the fork's kernels one by
 one.  The velocity the fused step reads is the first member's; ``set_fields`` / ``set_velocity_from`` write every member.
+
+``Advected_Scalars`` at the end pairs a live flow with the scalar lattices it carries (``lb_run_advected``).
 """
 import ctypes as ct
 
@@ -412,3 +414,104 @@ class Surfactant_Colony(_Shared_Velocity, _Fused_Set):
             m.restore_arrays(p)
         out.update_forces()             # psi / S and the forces of the last step follow from its densities
         return out
+
+
+class Advected_Scalars(_Shared_Velocity, _Lattice_Set):
+    """A flow and the concentrations it carries -- a dye, a temperature, a growing population under a live velocity field: one periodic
+    flow ``Simulation`` (``semantics='opencl'``, no obstacles) and one or two periodic scalar lattices (``semantics='diffusion'``, their
+    own ``omega`` and ``G``) of its grid and device, made of existing objects, which stay their owners'.  ``run(n)`` advances all of
+    them in lock step without a host wait (``lb_run_advected``): in every step each scalar is advected by the velocity the flow's
+    step forms from its streamed populations -- what an ``eager_macro=True`` flow stores --, handed from the flow's collision to the
+    scalars' in registers (``form=1``: one launch per step) or read from the flow's own u, v planes (``form=0``: one launch per
+    lattice, no copy); the same bits, and those of ``flow.run(1)`` / ``s.set_velocity_from(flow)`` / ``s.run(1)`` step by step.
+    ``members`` holds the scalars, ``flow`` the flow beside them.  Afterwards the flow's rho, u, v are stored (also on a handle that
+    otherwise rebuilds them on demand) and every scalar's u, v hold the last step's velocity.  The set has no state of its own."""
+    MAX_SCALARS = 2
+    _STACKED, _SHARED = ("f", "feq", "rho"), ("u", "v")
+    _FLOW_KEYS = {"rho_flow": "rho", "f_flow": "f", "feq_flow": "feq"}
+
+    def __init__(self, flow, scalars):
+        scalars = list(scalars)
+        if not 1 <= len(scalars) <= self.MAX_SCALARS:
+            raise ValueError("1..%d scalars are built (got %d)" % (self.MAX_SCALARS, len(scalars)))
+        if flow.semantics != "opencl":
+            raise ValueError("the flow must have semantics='opencl' (got %r)" % (flow.semantics,))
+        if flow.bc_mode != _native.LB_BC_PERIODIC:
+            raise ValueError("the flow must have bc='periodic': the scalar lattice has no wall rule")
+        if flow.local_ny != flow.ny:
+            raise ValueError("the flow must own its whole grid")
+        for i, s in enumerate(scalars):
+            if s.semantics != "diffusion":
+                raise ValueError("scalar %d must have semantics='diffusion' (got %r)" % (i, s.semantics))
+            if s.bc_mode != _native.LB_BC_PERIODIC:
+                raise ValueError("scalar %d must have bc='periodic'" % i)
+            if (s.nx, s.ny) != (flow.nx, flow.ny):
+                raise ValueError("scalar %d has a %dx%d grid, the flow %dx%d" % (i, s.nx, s.ny, flow.nx, flow.ny))
+            if s.device != flow.device:
+                raise ValueError("scalar %d is on device %d, the flow on %d" % (i, s.device, flow.device))
+            if any(s is t for t in scalars[:i]):
+                raise ValueError("scalar %d appears twice" % i)
+        self.flow = flow
+        self._adopt(flow.nx, flow.ny, scalars)
+
+    def close(self):
+        self.flow.close()
+        _Lattice_Set.close(self)
+
+    def sync(self):
+        self.flow.sync()
+        _Lattice_Set.sync(self)
+
+    def use_stream(self, hip_stream):
+        """The stream everything is enqueued on is the flow's; the scalars' own streams are joined and released."""
+        self.flow.use_stream(hip_stream)
+
+    # -- the hot path ---------------------------------------------------------------------------------------------------------
+    def run(self, num_iterations, wait=True, form=-1):
+        """num_iterations time steps of the flow and every scalar; form 1: one launch per step, 0: one per lattice, -1: the planner's."""
+        check(self._lib.lb_run_advected(self.flow._h, self._handles, self.num_populations, int(num_iterations), int(form)))
+        if wait:
+            self.sync()
+
+    def hot_kernel(self, form=-1):
+        """Name of what run(form=form) launches for this grid and number of scalars (lb_advected_kernel)."""
+        buf = ct.create_string_buffer(512)
+        check(self._lib.lb_advected_kernel(self.num_populations, int(form), self.nx * self.ny, buf, len(buf)))
+        return buf.value.decode()
+
+    def get_fields(self, which=("f", "rho", "u", "v", "rho_flow")):
+        """f: (nx, ny, NS, 9) and rho: (nx, ny, NS) of the scalars; u, v: (nx, ny), the flow's; rho_flow, f_flow, feq_flow: the flow's."""
+        out = self._get_fields(tuple(k for k in which if k in self._STACKED))
+        keys = tuple(k for k in which if k in self._SHARED) + tuple(v for k, v in self._FLOW_KEYS.items() if k in which)
+        if keys:
+            g = self.flow.get_fields(keys)
+            out.update({k: g[k] for k in self._SHARED if k in which})
+            out.update({k: g[v] for k, v in self._FLOW_KEYS.items() if k in which})
+        return out
+
+    def check(self):
+        """{'flow': the flow's Simulation.check(), 'scalars': [every scalar's]}."""
+        return {"flow": self.flow.check(), "scalars": _Shared_Velocity.check(self)}
+
+    # -- checkpoints: every scalar's arrays under 'm<i>_', the flow's under 'flow_' ---------------------------------------------------
+    def save_checkpoint(self, path):
+        own = {"flow_" + k: a for k, a in self.flow.checkpoint_arrays().items()}
+        own["flow_eager_macro"] = int(self.flow.eager_macro)
+        np.savez(Simulation._ckpt_path(path), **dict(own, **self._member_entries()))
+
+    @classmethod
+    def from_checkpoint(cls, path, device=0):
+        own, per = cls._load_entries(path)
+        d = {k[len("flow_"):]: a for k, a in own.items() if k.startswith("flow_")}
+        # (omegas as they were given: the restored set writes the same file)
+        flow = Simulation(int(d["nx"]), int(d["ny"]), d["omega"][()], bc=int(d["bc_mode"]), inlet_rho=float(d["inlet_rho"]),
+                          outlet_rho=float(d["outlet_rho"]), lid_u=float(d["lid_u"]), rho0=float(d["rho0"]), device=device,
+                          semantics=str(d["semantics"]), inlet_u=float(d["inlet_u"]), outlet_u=float(d["outlet_u"]),
+                          eager_macro=bool(int(d["eager_macro"])))
+        flow.restore_arrays(d)
+        scalars = []
+        for p in per:
+            s = Simulation(int(p["nx"]), int(p["ny"]), p["omega"][()], bc=int(p["bc_mode"]), device=device, semantics=str(p["semantics"]))
+            s.restore_arrays(p)
+            scalars.append(s)
+        return cls(flow, scalars)

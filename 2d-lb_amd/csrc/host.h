@@ -16,6 +16,8 @@
 //                  no handle kind of its own); emits kernels_nutrient.h
 //   expansion.cpp  noisy strains on a shared nutrient (lb_*_expansion: 2 ... 4 scalar lattices, no handle kind of its own); emits
 //                  kernels_expansion.h
+//   advected.cpp   a flow and the scalars it carries (lb_run_advected: one flow handle and 1 ... 2 scalar lattices, no handle kind of
+//                  its own); emits kernels_advected.h
 // Small kernels are emitted by the one unit that includes their header: kernels_phases.h + kernels_check.h by lb_hip.cpp,
 // kernels_halo.h by slab.cpp, kernels_scalar.h by scalar.cpp (its health check's first pass only: check_reduce.h is shared, the folding
 // pass is lb_hip.cpp's), kernels_multifield.h by multifield.cpp, kernels_poisson.h by poisson.cpp, kernels_porous.h by porous.cpp,
@@ -319,6 +321,9 @@ int scalar_feq(lb_sim *s);
 // (k_ad_moments); one k_ad_step with the velocity u, v hold now
 int scalar_moments(lb_sim *s);
 int scalar_step(lb_sim *s, bool store_rho);
+// what advected.cpp's 1 + NS launch form steps a periodic, noiseless scalar lattice with: one k_ad_step on the FLOW's stream whose
+// u, v are the flow handle's planes (no copy)
+int scalar_step_carried(lb_sim *s, const lb_sim *flow, bool store_rho);
 // OPEN: the edge state copied out of (k_ad_edge_capture) / patch: written back into (k_ad_edge_patch) the lattice at `f`
 void lbk_ad_edge(bool patch, hipStream_t st, const StepArgs &a, float *f, float *edge);
 // the health check's first pass over the lattice at a.src and the fields a.u, a.v: one record per workgroup, ad_check_blocks(a) of

@@ -500,6 +500,18 @@ bool multifluid_one_launch(const PlanInputs *s) { return s->variant != 0; }
 // Surfactant-propelled colonies: the same two variants.  The planner's choice (-1) is the one-launch step at every size: on one MI355X
 // it is 1.19-1.61 x the two-launch step at 256^2 ... 8192^2 in both modes (profiles/rocket_bench.txt, tools/rocket_bench.py).
 bool rocket_one_launch(const PlanInputs *s) { return s->variant != 0; }
+// A flow and the `count` scalars it carries (lb_run_advected): form 1, the one-launch step k_fa_step, or form 0, k_step<MACRO> and one
+// k_ad_step per scalar.  The planner's choice (-1) is whichever tools/advected_bench.py measured faster at the size, per count
+// (profiles/advected_bench.txt; DESIGN.md section 19 has the table).  On one MI355X that is form 1 at every size measured, 256^2 ...
+// 8192^2, with one scalar and with two: 1.10-1.42 x form 0 with one scalar, 1.13-1.67 x with two (the byte ratio is 164 / 144 and
+// 244 / 216; below 1024^2 a step is its launches), and 1.24-1.38 x today's sequence of existing calls from 2048^2 up.  The sizes and
+// the count stay arguments: a box on which form 0 wins somewhere gets its threshold here.
+int advected_form(long long cells, int count, int form)
+{
+    if (form >= 0) return form;
+    (void)cells; (void)count;
+    return 1;
+}
 
 bool scalar_use_tiles(const PlanInputs *s)
 {

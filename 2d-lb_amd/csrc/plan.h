@@ -96,6 +96,8 @@ bool scalar_use_tiles(const PlanInputs *s);
 bool multifluid_one_launch(const PlanInputs *s);
 // a surfactant-propelled colony (s = its first handle): the one-launch step k_ry_step, not k_ry_moments + k_ry_collide
 bool rocket_one_launch(const PlanInputs *s);
+// a flow and the `count` scalars it carries (lb_run_advected) on a grid of `cells` cells: the form that runs for the caller's `form` (-1: the planner's)
+int advected_form(long long cells, int count, int form);
 int scalar_tile_shape(const PlanInputs *s);
 int scalar_next_advance(const PlanInputs *s, int left);
 

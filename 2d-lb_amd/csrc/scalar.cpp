@@ -183,6 +183,17 @@ int scalar_step(lb_sim *s, bool store_rho)
     return LB_OK;
 }
 
+int scalar_step_carried(lb_sim *s, const lb_sim *flow, bool store_rho)
+{
+    StepArgs a = step_args(s, 0, 1, s->H);
+    a.u = flow->u;              // (same pitch: same nx)
+    a.v = flow->v;
+    ad_step(LB_BC_PERIODIC, s->ad_G != 0.f, store_rho, flow->stream, a, AdExtra{s->ad_edge, s->ad_G});
+    HIP_TRY(hipGetLastError());
+    s->cur ^= 1;
+    return LB_OK;
+}
+
 void lbk_ad_edge(bool patch,hipStream_t st, const StepArgs &a, float *f, float *edge)
 {
     const int n = std::max(patch ? a.nx : a.fpitch, a.ny);      // (the capture takes the rows' padding along)

@@ -809,6 +809,32 @@ int lb_run_expansion(lb_sim **fields, int count, const lb_expansion_params *p, i
 int lb_update_hydro_expansion(lb_sim **fields, int count, const lb_expansion_params *p);     /* stage 2 */
 int lb_collide_expansion(lb_sim **fields, int count, const lb_expansion_params *p);          /* stage 4: stored feq, rho */
 
+/* ---- a flow and the scalars it carries (a dye, a temperature, a growing population under a live velocity field) ----------------------
+ * NOT a handle kind either: `flow` is a whole-grid LB_SEM_OPENCL GPU handle of the family LB_BC_PERIODIC without an obstacle mask and
+ * without LB_FLAG_HALO, scalars[0 .. count-1], count = 1 ... 2, are whole-grid LB_SEM_DIFFUSION GPU handles of the family LB_BC_PERIODIC
+ * with the flow's nx, ny and device, the noisy collision off and no noise field set.  Every scalar keeps its own omega and its own G
+ * (lb_set_reaction); LB_FLAG_PLANAR may be set on any member.  One time step: the flow streams and forms rho, u, v of every cell from its
+ * streamed populations; every scalar streams and relaxes towards w_k rho_i (1 + 3 c_k.u) with THAT u, v -- the moments of the flow's
+ * step t, what a LB_FLAG_EAGER_MACRO flow handle stores, not the velocity rebuilt from the post-collision populations, which differs by
+ * rounding --; the flow relaxes.  lb_run_advected(n) is bitwise equal to n x (lb_run(flow, 1) on an eager flow handle; for each i
+ * lb_set_velocity_from(scalars[i], flow) and lb_run(scalars[i], 1) under lb_set_variant(scalars[i], 0)).  Everything is enqueued on the
+ * flow's stream, without a host wait; the scalars' streams are joined before and released behind.
+ *   form 1: ONE launch per step (k_fa_step: every lattice gathered, u, v handed from the flow's collision to the scalars' in registers;
+ *           72 (1 + count) B per cell and step);
+ *   form 0: 1 + count launches per step (the flow's k_step with its rho, u, v epilogue, then one k_ad_step per scalar reading the flow
+ *           handle's u, v planes: no copy; 84 + 80 count B);
+ *   form -1: the planner's choice by grid size (advected_form, csrc/plan.cpp, from profiles/advected_bench.txt).  The same bits.
+ * Afterwards the flow's rho, u, v are stored and current -- as on an eager handle, also on one that rebuilds them on demand --, every
+ * scalar's rho is stored, every scalar's u, v hold the velocity of the last step, and feq is not current on any member.  n_steps == 0
+ * does nothing.  lb_hot_kernel on the flow handle keeps naming lb_run's kernel; lb_advected_kernel names what lb_run_advected runs for
+ * `count` scalars on a grid of `cells` cells under `form`.
+ * LB_ERR_ARG, with the reason, before anything is enqueued: a null flow, array or member ("null"), a count outside 1 ... 2, a flow of
+ * another kind, backend or family, a member that is no LB_SEM_DIFFUSION GPU handle (the flow itself or a field of a coupled set
+ * included) or not periodic, a handle given twice, another grid or device, a form outside -1 ... 1, a negative n_steps.  LB_ERR_STATE:
+ * slabs and LB_FLAG_HALO, a flow with an obstacle mask, a member inside a split step, a noisy scalar, a scalar with a noise field. */
+int lb_run_advected(lb_sim *flow, lb_sim **scalars, int count, int n_steps, int form);
+int lb_advected_kernel(int count, int form, int64_t cells, char *buf, int buflen);
+
 #ifdef __cplusplus
 }
 #endif
