@@ -28,6 +28,10 @@ The kinds 'rocket' (coupled.Surfactant_Colony), 'nutrient' (nutrient_set.Nutrien
 'expansion' (expansion_set.Expansion_Set) and 'screened' (a scalar lattice and a spectral_poisson.Screened_Poisson under
 lb_run_screened / lb_spectral_velocity: ScreenedWave below) came after the first six; their keys into the generators follow the first
 six's, whose op lists have not moved (tests/test_sequences_cpu.py holds a digest of each).
+
+The kind 'advected' (coupled.Advected_Scalars under lb_run_advected: a flow and the scalars it carries) came last, its key behind the
+others'.  Its members are unlike lattices that also step alone between the set's runs, so it has a generator (_generate_advected), players
+(AdvectedGpu, AdvectedRef) and a hold (hold_advected) of its own; cut_points, counts and the tables above serve it as they are.
 """
 import os
 
@@ -36,7 +40,7 @@ import numpy as np
 F = np.float32
 W64 = np.array([4. / 9.] + [1. / 9.] * 4 + [1. / 36.] * 4)
 
-KINDS = ("flow", "scalar", "multifield", "poisson", "porous", "multifluid", "rocket", "nutrient", "noise", "expansion", "screened")
+KINDS = ("flow", "scalar", "multifield", "poisson", "porous", "multifluid", "rocket", "nutrient", "noise", "expansion", "screened", "advected")
 SEEDS = tuple(range(6))
 RUN_LENGTHS = (1, 2, 3, 4, 5, 6, 7, 8, 13, 16, 17, 33, 40)     # every fused depth, the 16-launch graph replay and its remainder
 MAX_E, MAX_T, MAX_STEPS = 10, 15, 120
@@ -64,6 +68,7 @@ FAMILIES = dict(
     noise=("periodic", "open"),
     expansion=("periodic", "open"),
     screened=("periodic", "open"),
+    advected=("eager", "lazy"),                     # (the flow handle's flag)
 )
 
 # The smallest shapes at which each mechanism still engages.
@@ -89,6 +94,9 @@ MULTIFLUID_SHAPES = ((517, 5, 3), (261, 9, 2), (6, 13, 2))
 ROCKET_SHAPES = ((261, 11), (6, 21))
 EXPANSION_SHAPES = ((261, 9), (37, 23))
 SPECTRAL_SHAPES = ((270, 12), (30, 18))
+#   advected: tests/test_gpu_advected.py's 37 x 23 (padding lanes, a ragged last block row) and 260 x 6 (a second workgroup in x, the x-wrap across
+#       the tile seam), alternating with the seed, the other way round in the second family: 1 + seed % 2 scalars meet both.
+ADVECTED_SHAPES = ((37, 23), (260, 6))
 
 E_OPS = dict(
     flow=("run", "phase_step", "set_f", "init_equilibrium", "set_obstacle_mask", "clear_obstacle_mask"),
@@ -102,6 +110,7 @@ E_OPS = dict(
     noise=("run", "phase_step", "set_f", "set_reaction", "set_fields", "set_edge_state", "set_noise", "fed_phase_step"),
     expansion=("run", "phase_step", "fed_phase_step", "set_f", "set_noise", "set_reaction", "set_fields", "set_edge_state"),
     screened=("run", "phase_step", "set_f", "redo_initial_condition", "set_reaction"),
+    advected=("run", "member_run", "set_f", "init_equilibrium", "set_reaction", "set_fields"),
 )
 # effective ops a life makes more than once: the parameter tables of a colony, `clumpy` there and back and two more parameters, the noise
 # switched off and back on (the periodic family, which has the slot that the open one gives to set_edge_state)
@@ -119,8 +128,9 @@ T_OPS = dict(
     noise=_READS + ("check", "set_variant", "noise", "noise_fill"),
     expansion=_READS + ("check", "noise", "noise_fill", "get_edge_state"),
     screened=_READS + ("check", "solver_scribble"),
+    advected=("get_fields", "member_fields", "hot_kernel", "sync", "checkpoint", "split_run", "check", "set_variant"),
 )
-STEPPING = ("run", "phase_step", "solve", "fed_phase_step")
+STEPPING = ("run", "phase_step", "solve", "fed_phase_step", "member_run")
 FIELD_NAMES = dict(
     flow=("f", "rho", "u", "v", "feq"), scalar=("f", "rho", "u", "v", "feq"), multifield=("f", "rho", "u", "v", "feq"),
     poisson=("f", "rho", "feq"),
@@ -128,7 +138,9 @@ FIELD_NAMES = dict(
     multifluid=("f", "feq", "rho", "u", "v", "Gx", "Gy", "u_bary", "v_bary"),
     rocket=("f", "feq", "rho", "u", "v"), nutrient=("f", "feq", "rho", "u", "v"), noise=("f", "rho", "u", "v", "feq"),
     expansion=("f", "feq", "rho", "u", "v"), screened=("f", "rho", "u", "v", "feq"),
+    advected=("f", "feq", "rho", "u", "v", "rho_flow", "f_flow", "feq_flow"),      # (the set's own get_fields; a member's: MEMBER_FIELDS)
 )
+MEMBER_FIELDS = ("f", "rho", "u", "v", "feq")
 # what a set keeps beside its members' arrays (get_own reads them; `op` is psi in mode 'flow' and S in mode 'forces')
 OWN_NAMES = dict(
     rocket=dict(flow=dict(op="psi", Fx="pseudo_force_x", Fy="pseudo_force_y"),
@@ -197,7 +209,20 @@ def variant_words(kind):
         return (AUTO, K_STEP, TILES | 1 << 2, TILES | 2 << 2, TILES | 3 << 2, TILES | STEP4_NO_AHEAD, TILES | 2 << 2 | STEP4_NO_AHEAD)
     if kind in ("multifluid", "rocket"):
         return (-1, 0, 1)
+    if kind == "advected":
+        return tuple(sorted(set(sum(advected_words(), ()))))
     return ()
+
+
+def advected_words():
+    """(the flow's words in front of a set run, the flow's in front of a run of its own, a scalar's in front of a run of its own).  The
+    first: what flow_step_macro (form 0) takes from the flow handle's word -- the block shape, the non-temporal bits -- and a marching
+    word it must not act on; the second: the marching words and the tiles, which these shapes decline; the third: the three tile shapes
+    of k_ad_tile4."""
+    from LB_D2Q9.variants import (K_DEEP2, K_DEEP6, K_DEEP7, K_STEP2, K_STEP3, K_STEP4, K_STEP5, K_TILE4, NT_LOADS, NT_STORES, ROWS_1, ROWS_2,
+                                  TILES)
+    return ((ROWS_1, ROWS_2, NT_STORES | NT_LOADS, K_DEEP7), (K_STEP2, K_STEP3, K_STEP4, K_STEP5, K_DEEP6, K_DEEP2, K_TILE4),
+            (TILES | 1 << 2, TILES | 2 << 2, TILES | 3 << 2))
 
 
 def _key(kind, family, seed):
@@ -259,20 +284,60 @@ def case_of(kind, family, seed):
         # (spectral_model.fisher_lattice_parameters at N = 10: omega = 0.8, G = 0.01, scale = -0.1; a gentler scale keeps |u| < 0.15)
         c.update(bc=family, omega=_r32(0.8), G=0.01, lam=1., dx=0.1, scale=_r32(-rng.uniform(0.04, 0.07)))
         c["rho0"] = payload(c, "redo_initial_condition", 1000)
+    elif kind == "advected":
+        fi = FAMILIES[kind].index(family)
+        c["nx"], c["ny"] = nx, ny = ADVECTED_SHAPES[(seed + fi) % 2]
+        ns = 1 + seed % 2
+        c.update(ns=ns, eager=family == "eager", planar_flow=bool(rng.integers(0, 2)), planar_scalars=bool(rng.integers(0, 2)),
+                 omega=_r32(rng.uniform(1.0, 1.6)), omegas=ADVECTED_OMEGAS[:ns], Gs=advected_rates(family, seed)[0])
+        # tests/test_gpu_advected.py's start with the case's own draws: a shear layer with a transverse kick (|u| <= 0.05), a striped dye
+        # per scalar, every population perturbed
+        x, y = np.meshgrid(np.arange(nx), np.arange(ny), indexing="ij")
+        c["u"] = (0.04 * np.tanh((y - 0.5 * ny + 0.5) / max(ny / 8., 1.))).astype(F)
+        c["v"] = (0.01 * np.sin(2 * np.pi * (x + 0.5) / nx)).astype(F)
+        assert float(np.max(np.hypot(c["u"], c["v"]))) <= 0.05
+        c["rho"] = np.ones((nx, ny), F)
+        # (stripes of 0.25 and 0.55: at omega = 1.6 a step of the dye overshoots by a third of its height in the first steps, and a growing
+        #  dye must stay below 1 for MAX_STEPS steps)
+        c["dyes"] = [((0.4 + 0.15 * np.sign(np.sin(2 * np.pi * (x + 2 * i) / max(nx / 3., 2.)))).astype(F),
+                      (1 + 0.01 * rng.standard_normal((nx, ny, 9))).astype(F)) for i in range(ns)]
+        c["f0"] = (1 + 0.01 * rng.standard_normal((nx, ny, 9))).astype(F)      # (here: the factors on the flow's first equilibrium)
+        return c
     else:
         raise ValueError(kind)
     c["f0"] = payload(c, "set_f", 1000)
     return c
 
 
-def payload(c, name, pseed):
-    """The array(s) of op `name` with payload seed `pseed` on case c."""
+# a flow and the scalars it carries: the scalars' rates as in tests/test_gpu_advected.py; growth switched between 0 and ADVECTED_G, gentle
+# enough that a dye of 0.2 ... 0.8 stays inside (0, 1) for MAX_STEPS steps (tests/test_sequences_cpu.py holds that and prints the margin)
+ADVECTED_OMEGAS, ADVECTED_G = (F(1.6), F(1.1)), 0.01
+
+
+def advected_rates(family, seed):
+    """(the growth rate every scalar starts with, the scalar whose rate set_reaction switches -- to the other of 0 and ADVECTED_G,
+    between the life's first and second set run, and back between the second and the third).  Over the seeds every scalar starts both
+    ways; with two scalars the other one has either rate."""
+    fi, ns = FAMILIES["advected"].index(family), 1 + seed % 2
+    who = (seed // 2) % ns
+    gs = [_r32(ADVECTED_G) if (seed // 2 + fi + i) % 2 else 0. for i in range(ns)]
+    gs[who] = _r32(ADVECTED_G) if (seed + fi) % 2 else 0.
+    return tuple(gs), who
+
+
+def payload(c, name, pseed, who=None):
+    """The array(s) of op `name` with payload seed `pseed` on case c; who: the member of a set of unlike lattices (-1: the flow)."""
     kind, nx, ny = c["kind"], c["nx"], c["ny"]
     rng = np.random.default_rng(_key(kind, c["family"], c["seed"]) + [2, int(pseed)])
     x, y = np.meshgrid(np.arange(nx), np.arange(ny), indexing="ij")
     phase = rng.uniform(0., 2. * np.pi, 2)
     wave = lambda p: np.sin(2. * np.pi * y / ny + p[0]) * np.cos(2. * np.pi * x / nx + p[1])
     if name == "set_f":
+        if kind == "advected" and who == -1:        # the flow kind's
+            return (W64 * (1. + 0.02 * rng.standard_normal((nx, ny, 9)))).astype(F)
+        if kind == "advected":                      # the noise kind's blob: rho 0.15 ... 0.75 grows for 120 steps inside (0, 1)
+            rho = 0.15 + 0.6 * np.exp(-(((x - rng.uniform(0.3, 0.7) * nx) / (0.2 * nx)) ** 2 + ((y - 0.5 * ny) / (0.25 * ny)) ** 2))
+            return (W64 * rho[:, :, None] * (1. + 0.05 * rng.uniform(-1., 1., (nx, ny, 9)))).astype(F)
         if kind == "flow":
             return (W64 * (1. + 0.02 * rng.standard_normal((nx, ny, 9)))).astype(F)
         if kind == "scalar":
@@ -369,6 +434,8 @@ def _droplet(rng, x, y, nx, ny):
 def generate(kind, family, seed):
     """The op list of (kind, family, seed): at most MAX_E effective and MAX_T transparent ops, at most MAX_STEPS steps, a stepping
     op last.  Every effective op of the kind that the family has occurs once, runs fill the rest."""
+    if kind == "advected":
+        return _generate_advected(family, seed)
     rng = np.random.default_rng(_key(kind, family, seed) + [3])
     names = [n for n in E_OPS[kind] if not (n == "set_edge_state" and family != "open")]
     if not (kind == "noise" and family == "open"):
@@ -514,6 +581,102 @@ def generate(kind, family, seed):
     return out
 
 
+ADVECTED_FLOW_RUNS = (17, 33, 40)                  # a flow run of its own: longer than the 16 steps of the captured graph
+ADVECTED_SCALAR_RUNS = ((1, 2, 3, 5), (8, 13, 16))  # a scalar's: short, or at least VARIANT_DEPTH steps behind a tile word
+
+
+def _generate_advected(family, seed):
+    """The life of a flow and the 1 + seed % 2 scalars it carries.  Ten effective ops: three runs of the set, the last one last; between
+    the first and the second, and between the second and the third, set_reaction switches one scalar's growth rate to the other of 0 and
+    ADVECTED_G and back (advected_rates); at random places around them a run of the flow alone (ADVECTED_FLOW_RUNS), set_fields on a
+    scalar with that scalar's own run directly behind it -- the next set run replaces the velocity --, set_f on one member,
+    init_equilibrium on the flow.  Ops: ('run', n, split, form) -- split and form are the subject's alone --, ('member_run', n, 0, who),
+    ('set_f', payload seed, who), ('init_equilibrium', payload seed), ('set_reaction', who, G), ('set_fields', payload seed, who); who:
+    -1 the flow, else the scalar.  Two variant words: one of the flow's in front of its own run; the other either one of the flow's in
+    front of the longest set run, at least VARIANT_DEPTH steps in one call and of form 0, which alone reads the word, or a tile shape on
+    the scalar in front of its own run.  The other transparent ops as in generate(): get_fields is the set's own, member_fields reads
+    every member."""
+    kind = "advected"
+    fi, seed = FAMILIES[kind].index(family), int(seed)
+    rng = np.random.default_rng(_key(kind, family, seed) + [3])
+    sequence, ns = fi * len(SEEDS) + seed, 1 + seed % 2
+    gs, who = advected_rates(family, seed)
+    set_words, own_words, scalar_words = advected_words()
+    scalar_word = (seed // 2 + fi) % 2 == 1
+    turn = (sequence // 4) * 2 + sequence % 2       # 0 ... 5 among the six lives with either kind of second word
+
+    fl_len = ADVECTED_FLOW_RUNS[sequence % len(ADVECTED_FLOW_RUNS)]
+    sc_len = ADVECTED_SCALAR_RUNS[1][turn % 3] if scalar_word else int(rng.choice(ADVECTED_SCALAR_RUNS[0]))
+    steps_left = MAX_STEPS - fl_len - sc_len
+    deck = [int(n) for n in np.random.default_rng([KINDS.index(kind), 5]).permutation(RUN_LENGTHS)]
+    lengths = []
+    for k in range(3):                              # (one step is kept for every set run still to come)
+        n, room = deck[(3 * sequence + k) % len(deck)], steps_left - (2 - k)
+        n = n if n <= room else max(m for m in RUN_LENGTHS if m <= room)
+        lengths.append(n)
+        steps_left -= n
+    if not scalar_word and max(lengths) < VARIANT_DEPTH:
+        steps_left -= VARIANT_DEPTH - max(lengths)
+        lengths[lengths.index(max(lengths))] = VARIANT_DEPTH
+    assert steps_left >= 0
+    word_run = None if scalar_word else lengths.index(max(lengths))
+    forms = [0 if k == word_run else (-1, 0, 1)[(sequence + k) % 3] for k in range(3)]
+
+    pseed = iter(range(1, 100))
+    sc_who = int(rng.integers(0, ns))
+    members = [-1] + list(range(ns))
+    other = ADVECTED_G if gs[who] == 0. else 0.
+    blocks = dict(FL=[("member_run", fl_len, 0, -1)], SC=[("set_fields", next(pseed), sc_who), ("member_run", sc_len, 0, sc_who)],
+                  SF=[("set_f", next(pseed), members[(sequence // 2) % len(members)])], IE=[("init_equilibrium", next(pseed))],
+                  SR1=[("set_reaction", who, _r32(other))], SR2=[("set_reaction", who, gs[who])])
+    gaps = [[], ["SR1"], ["SR2"]]                   # in front of the first set run, of the second, of the third
+    for name in ("FL", "SC", "SF", "IE"):
+        gaps[int(rng.integers(0, 3))].append(name)
+    ops, run_at = [], []
+    for k, gap in enumerate(gaps):
+        for j in rng.permutation(len(gap)):
+            ops += blocks[gap[int(j)]]
+        run_at.append(len(ops))
+        ops.append(("run", lengths[k], 0, forms[k]))
+    assert len(ops) == MAX_E
+
+    splittable = [i for k, i in enumerate(run_at) if lengths[k] >= 2 and k != word_run]
+    if splittable:
+        i = int(rng.choice(splittable))
+        ops[i] = ("run", ops[i][1], int(rng.integers(1, ops[i][1])), ops[i][3])
+
+    variants = {ops.index(blocks["FL"][0]): (int(own_words[sequence % len(own_words)]), -1)}
+    if scalar_word:
+        variants[ops.index(blocks["SC"][1])] = (int(scalar_words[turn % len(scalar_words)]), sc_who)
+    else:
+        variants[run_at[word_run]] = (int(set_words[turn % len(set_words)]), -1)
+
+    t_names = [n for n in T_OPS[kind] if n not in ("split_run", "set_variant")]
+    t_names = (t_names + ["get_fields", "member_fields", "checkpoint"])[:MAX_T - 1 - len(variants)]
+    rng.shuffle(t_names)
+    first_step = min(i for i, op in enumerate(ops) if op[0] in STEPPING)
+    t_ops, where = [], []
+    for name in t_names:
+        if name in ("get_fields", "member_fields"):
+            names = FIELD_NAMES[kind] if name == "get_fields" else MEMBER_FIELDS
+            k = int(rng.integers(1, len(names) + 1))
+            which = tuple(sorted(str(s) for s in rng.choice(names, size=k, replace=False)))
+            t_ops.append((name, which + ("feq",) if "feq" not in which and rng.integers(0, 2) else which))
+        else:
+            t_ops.append((name,))
+        if name == "get_fields" and "get_fields" not in [t[0] for t in t_ops[:-1]]:
+            where.append(int(rng.integers(first_step + 1, len(ops))))
+        else:
+            where.append(int(rng.integers(0, len(ops))))
+    out = []
+    for i, op in enumerate(ops):
+        out += [t for t, p in zip(t_ops, where) if p == i]
+        if i in variants:                           # (last: a set restored from a checkpoint has fresh handles, which choose anew)
+            out.append(("set_variant",) + variants[i])
+        out.append(op)
+    return out
+
+
 def starts_masked(family, seed):
     """Whether the flow case (family, seed) starts with an obstacle mask."""
     return bool(np.random.default_rng(_key("flow", family, seed) + [6]).integers(0, 2))
@@ -555,7 +718,7 @@ def counts(ops):
     """(effective ops, transparent ops -- a split run counts as one --, steps)"""
     e = [op for op in ops if is_effective(op)]
     t = len(ops) - len(e) + sum(1 for op in e if op[0] == "run" and op[2])
-    steps = sum(op[1] if op[0] in ("run", "solve") else 1 for op in e if op[0] in STEPPING)
+    steps = sum(op[1] if op[0] in ("run", "solve", "member_run") else 1 for op in e if op[0] in STEPPING)
     return len(e), t, steps
 
 
@@ -1158,6 +1321,278 @@ class RefPlayer(Player):
     def porous_header(self):
         m = self.m
         return dict(epsilon=m.eps, nu_fluid=m.nu, K=m.K, Fe=m.Fe)
+
+
+# ---- a flow and the scalars it carries (kind 'advected'): a set of unlike lattices whose members also live on their own ------------------
+class Clock(object):
+    """The steps since a member's populations were set and the steps behind its rho, u, v, feq (Player's two counters, per member)."""
+
+    def __init__(self):
+        self.steps = self.macro_steps = 0
+
+    def stepped(self, n):
+        self.steps += n
+        self.macro_steps = self.steps
+
+
+class Held(object):
+    """What hold_to_contract asks of a reference player, for one member."""
+
+    def __init__(self, fields, clock):
+        self._fields, self.steps, self.macro_steps = fields, clock.steps, clock.macro_steps
+
+    def fields(self):
+        return self._fields
+
+
+class AdvectedPlayer(object):
+    def __init__(self, case):
+        self.case, self.kind, self.ns = case, case["kind"], case["ns"]
+        self.G = list(case["Gs"])
+
+    def effective(self, op):
+        name, c = op[0], self.case
+        if name == "run":
+            self.set_run(op[1], op[2], op[3])
+        elif name == "member_run":
+            self.member_run(op[3], op[1])
+        elif name == "set_f":
+            self.set_f(op[2], payload(c, name, op[1], who=op[2]))
+        elif name == "init_equilibrium":
+            self.init_equilibrium(payload(c, name, op[1]))
+        elif name == "set_reaction":
+            self.G[op[1]] = op[2]
+            self.set_reaction(op[1], op[2])
+        elif name == "set_fields":
+            self.set_fields(op[2], payload(c, name, op[1]))
+        else:
+            raise ValueError(name)
+
+
+class AdvectedGpu(AdvectedPlayer):
+    """The subject: an Advected_Scalars with the case's flag and layouts, every op.  plain: the twin -- separately created handles in the
+    default layout, the flow with eager_macro=True, every member under set_variant(0); a set step is lb_run(flow, 1), then per scalar
+    set_velocity_from(flow) and lb_run(scalar, 1), and it records the u, v the flow stored for that step (`history`, of the last set
+    run); a member's run(n) is n x run(1).  In the lazy family the twin also keeps what a fresh lazy flow handle makes of its populations
+    over the flow's last own run (`alone`): there the subject rebuilds rho, u, v from the post-collision populations -- the same moments
+    as the eager twin's stored ones, not the same bits -- and its feq follows them."""
+
+    def __init__(self, case, plain=False, tmpdir=None):
+        AdvectedPlayer.__init__(self, case)
+        from LB_D2Q9 import _native
+        from LB_D2Q9.coupled import Advected_Scalars
+        self.plain, self.tmpdir, self.saves, self._check = plain, tmpdir, 0, _native.check
+        self.flow_fields_from, self.alone, self.history = "init", None, []
+        c = case
+        flow = self._flow(True if plain else c["eager"], False if plain else c["planar_flow"])
+        flow.init_equilibrium(c["rho"], c["u"], c["v"], c["f0"])
+        scalars = []
+        for om, G, (dye, factors) in zip(c["omegas"], c["Gs"], c["dyes"]):
+            s = self._simulation()(c["nx"], c["ny"], om, bc="periodic", semantics="diffusion", planar=False if plain else c["planar_scalars"])
+            s.set_reaction(G)
+            s.init_equilibrium(dye, c["u"], c["v"], factors)
+            scalars.append(s)
+        if plain:
+            self._members = [flow] + scalars
+            for m in self._members:
+                m.set_variant(0)
+        else:
+            self.set = Advected_Scalars(flow, scalars)
+
+    @staticmethod
+    def _simulation():
+        from LB_D2Q9.simulation import Simulation
+        return Simulation
+
+    def _flow(self, eager, planar):
+        c = self.case
+        return self._simulation()(c["nx"], c["ny"], c["omega"], bc="periodic", eager_macro=eager, planar=planar)
+
+    def member(self, who):
+        """who: -1 the flow, else the scalar"""
+        if self.plain:
+            return self._members[1 + who]
+        return self.set.flow if who == -1 else self.set.members[who]
+
+    def members(self):
+        return [self.member(w) for w in range(-1, self.ns)]
+
+    def close(self):
+        if self.plain:
+            for m in self._members:
+                m.close()
+        else:
+            self.set.close()
+
+    # -- effective ops ------------------------------------------------------------------------------------------------------------------
+    def set_run(self, n, split=0, form=-1):
+        if not self.plain:
+            if split:
+                self.set.run(split, wait=False, form=form)
+                self.set.run(n - split, form=form)
+            else:
+                self.set.run(n, form=form)
+        else:
+            flow, lib = self.member(-1), self.member(-1)._lib
+            self.history = []
+            for _ in range(n):
+                self._check(lib.lb_run(flow._h, 1))
+                for s in self._members[1:]:
+                    s.set_velocity_from(flow)
+                    self._check(lib.lb_run(s._h, 1))
+                for m in self._members:
+                    m.sync()
+                g = flow.get_fields(("u", "v"))
+                self.history.append((g["u"], g["v"]))
+        self.flow_fields_from = "set"
+
+    def member_run(self, who, n):
+        m = self.member(who)
+        if not self.plain:
+            m.run(n)
+        else:
+            if who == -1 and not self.case["eager"]:
+                lazy = self._flow(False, False)
+                lazy.set_variant(0)
+                lazy.set_f(m.get_fields(("f",))["f"])
+                for _ in range(n):
+                    lazy.run(1)
+                self.alone = lazy.get_fields(MEMBER_FIELDS)
+                lazy.close()
+            for _ in range(n):
+                m.run(1)
+            if who == -1 and not self.case["eager"]:
+                assert np.array_equal(self.alone["f"], m.get_fields(("f",))["f"]), "the twin's lazy and eager flow handles part in f"
+        if who == -1:
+            self.flow_fields_from = "own"
+
+    def set_f(self, who, f):
+        self.member(who).set_f(f)
+
+    def init_equilibrium(self, ruv):
+        self.member(-1).init_equilibrium(*ruv)
+        self.flow_fields_from = "init"
+
+    def set_reaction(self, who, G):
+        self.member(who).set_reaction(G)
+
+    def set_fields(self, who, uv):
+        self.member(who).set_fields(np.zeros((self.case["nx"], self.case["ny"]), F), uv[0], uv[1])
+
+    # -- transparent ops (the subject's) ----------------------------------------------------------------------------------------------------
+    def transparent(self, op):
+        name, st = op[0], self.set
+        if name == "get_fields":
+            assert set(st.get_fields(op[1])) == set(op[1])
+        elif name == "member_fields":
+            for m in self.members():
+                assert set(m.get_fields(op[1])) == set(op[1])
+        elif name == "check":
+            r = st.check()
+            assert r["flow"]["n_nonfinite"] == 0 and all(x["n_nonfinite"] == 0 for x in r["scalars"]) and len(r["scalars"]) == self.ns
+        elif name == "hot_kernel":
+            assert st.hot_kernel() and st.hot_kernel(0) and st.hot_kernel(1) and all(m.hot_kernel() for m in self.members())
+        elif name == "sync":
+            st.sync()
+        elif name == "set_variant":
+            self.member(op[2]).set_variant(op[1])
+        elif name == "checkpoint":                  # through a closed set: fresh handles, the flag from the file, the default layout
+            from LB_D2Q9.coupled import Advected_Scalars
+            self.saves += 1
+            path = os.path.join(str(self.tmpdir), "ck%d" % self.saves)
+            st.save_checkpoint(path)
+            st.close()
+            self.set = Advected_Scalars.from_checkpoint(path)
+            assert self.set.flow.eager_macro == self.case["eager"] and self.set.num_populations == self.ns
+            assert [float(m.G) for m in self.set.members] == [float(F(g)) for g in self.G]
+        else:
+            raise ValueError(name)
+
+    # -- read-back ------------------------------------------------------------------------------------------------------------------------
+    def snapshot(self):
+        """Every member's f, rho, u, v, feq.  The twin's, in the lazy family while the flow's fields are those of its own run: the flow's
+        rho, u, v, feq of the lazy handle that made the same run (`alone`)."""
+        out = {}
+        for who, m in zip(range(-1, self.ns), self.members()):
+            prefix = "flow_" if who == -1 else "s%d_" % who
+            out.update({prefix + k: a for k, a in m.get_fields(MEMBER_FIELDS).items()})
+        if self.plain and not self.case["eager"] and self.flow_fields_from == "own":
+            out.update({"flow_" + k: self.alone[k] for k in ("rho", "u", "v", "feq")})
+        return out
+
+
+class AdvectedRef(AdvectedPlayer):
+    """The references: oracle.O2Sim for the flow, a float64 ScalarModel per scalar.  A set step is a step of the flow and, per scalar, a
+    step under the velocity of `feed` for that step -- what the GPU twin stored (AdvectedGpu.history): the scalar contract was
+    established for an imposed velocity with the same bits on both sides, the velocity itself is the flow's hold --; without a feed,
+    O2Sim's own."""
+
+    def __init__(self, case, oracle):
+        AdvectedPlayer.__init__(self, case)
+        from scalar_model import ScalarModel
+        c = case
+        self.flow = oracle.O2Sim(c["nx"], c["ny"], c["omega"], oracle.BC_PERIODIC, 1., 1.)
+        self.flow.set_macro(c["rho"], c["u"], c["v"])
+        self.flow.update_feq()
+        self.flow.init_pop(c["f0"])
+        self.scalars = []
+        for om, G, (dye, factors) in zip(c["omegas"], c["Gs"], c["dyes"]):
+            m = ScalarModel(c["nx"], c["ny"], om, G, "periodic", np.float64)
+            m.set_fields(dye, c["u"], c["v"])
+            m.update_feq()
+            m.set_f(m.feq * factors)
+            self.scalars.append(m)
+        self.clocks = [Clock() for _ in range(1 + self.ns)]         # the flow's, then every scalar's
+        self.feed = None
+
+    def clock(self, who):
+        return self.clocks[1 + who]
+
+    def set_run(self, n, split=0, form=-1):
+        assert self.feed is None or len(self.feed) == n
+        for k in range(n):
+            self.flow.run(1)
+            u, v = self.feed[k] if self.feed is not None else (self.flow.u.T, self.flow.v.T)
+            for m in self.scalars:
+                m.u, m.v = np.array(u, np.float64), np.array(v, np.float64)
+                m.step()
+        self.feed = None
+        for c in self.clocks:
+            c.stepped(n)
+
+    def member_run(self, who, n):
+        (self.flow if who == -1 else self.scalars[who]).run(n)
+        self.clock(who).stepped(n)
+
+    def set_f(self, who, f):
+        (self.flow if who == -1 else self.scalars[who]).set_f(f)
+        self.clock(who).steps = 0
+
+    def init_equilibrium(self, ruv):
+        self.flow.set_macro(*ruv)
+        self.flow.update_feq()
+        self.flow.init_pop(None)
+        self.clock(-1).steps = self.clock(-1).macro_steps = 0
+
+    def set_reaction(self, who, G):
+        self.scalars[who].set_reaction(G)
+
+    def set_fields(self, who, uv):
+        self.scalars[who].set_fields(np.zeros((self.case["nx"], self.case["ny"])), uv[0], uv[1])
+
+
+def hold_advected(label, twin, ref):
+    """Property B of a carried set, by the two existing contracts: the twin's flow against O2Sim under the flow contract
+    (hold_to_contract('flow')), every scalar of the twin against its float64 model under the scalar contract (test_gpu_scalar.assert_close:
+    f for the steps since it was set, rho and feq for the steps behind them), u, v -- imposed, with the same bits -- equal.  Every cell."""
+    from test_gpu_scalar import assert_close
+    hold_to_contract("flow", label + ", the flow", twin.member(-1).get_fields(MEMBER_FIELDS), Held(ref.flow.get_fields(), ref.clock(-1)))
+    for i, m in enumerate(ref.scalars):
+        have, want, what = twin.member(i).get_fields(MEMBER_FIELDS), m.get_fields(), "%s, scalar %d" % (label, i)
+        assert all(np.isfinite(np.asarray(want[k])).all() for k in want), what
+        assert_close(have, want, ref.clock(i).steps, ("f",), what)
+        assert_close(have, want, ref.clock(i).macro_steps, ("rho", "feq"), what)
+        assert np.array_equal(have["u"], want["u"]) and np.array_equal(have["v"], want["v"]), what
 
 
 def play(player, ops, at=None, cuts=(), transparent=False):

@@ -5,6 +5,7 @@ import os
 import re
 import types
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -57,6 +58,37 @@ def test_kernel_names(lbhip):
             assert lbhip.lb_advected_kernel(count, -1, cells, buf, len(buf)) == 0 and buf.value.startswith((b"k_fa_step", b"k_step<MACRO> + "))
     assert lbhip.lb_advected_kernel(3, 1, 100, buf, len(buf)) == -1 and b"takes 1..2" in lbhip.lb_last_error()
     assert lbhip.lb_advected_kernel(1, 2, 100, buf, len(buf)) == -1 and b"form must be -1" in lbhip.lb_last_error()
+
+
+def test_the_growth_rate_matrix_reaches_every_instantiation():
+    """What lb_run_advected launches for every case of tests/test_gpu_advected.py's growth-rate matrix, by the rule of advected.cpp --
+    react = some scalar has G != 0, LAST = the call's last launch, inside <NS, true> member i takes the growth cell where G[i] != 0; form 0:
+    one k_ad_step<PERIODIC, REACT = G[i] != 0, RHO = the last step> per scalar --: all eight k_fa_step<NS, REACT, LAST>, all four orders of
+    the per-member branch with two scalars, and in form 0 either cell for the scalar in either place.  A case taken out of the matrix's
+    lists fails here."""
+    import test_gpu_advected as T
+    source = open(os.path.join(ROOT, "2d-lb_amd", "csrc", "advected.cpp")).read()
+    assert "react = react || scalars[i]->ad_G != 0.f;" in source and "fa_step(count, react, it == n_steps - 1, flow->stream, m);" in source
+    assert "scalar_step_carried(scalars[i], flow, it == n_steps - 1)" in source
+    triples, orders, carried = set(), set(), set()
+    for gs, form, n in T.MATRIX:
+        ns, react = len(gs), any(np.float32(g) != 0 for g in gs)
+        for it in range(n):
+            last = it == n - 1
+            if form == 1:
+                triples.add((ns, react, last))
+                if ns == 2:
+                    orders.add(tuple("react" if react and np.float32(g) != 0 else "plain" for g in gs))
+            else:
+                carried |= {(ns, i, np.float32(g) != 0, last) for i, g in enumerate(gs)}
+    assert triples == {(ns, react, last) for ns in (1, 2) for react in (False, True) for last in (False, True)}, triples
+    assert orders == {("plain", "plain"), ("react", "plain"), ("plain", "react"), ("react", "react")}, orders
+    assert carried == {(ns, i, react, last) for ns in (1, 2) for i in range(ns) for react in (False, True) for last in (False, True)}, carried
+    assert set(T.MATRIX_SHAPES) == {(37, 23), (260, 6)} and set(T.MATRIX_FORMS) == {0, 1}
+    assert len(T.MATRIX) == len(set(T.MATRIX)) == 24
+    # the variant-word cases: two scalars, the FIRST with the growth cell while it reads the flow handle's planes
+    assert len(T.WORD_GS) == 2 and T.WORD_GS[0] != 0. and T.WORD_GS[1] == 0. and T.WORD_STEPS in T.SNAPS and T.WORD_STEPS % 2 == 1
+    assert set(T.MATRIX_STEPS) | set(T.STEPS) <= set(T.SNAPS)
 
 
 def test_build_lists_the_unit():

@@ -2,13 +2,41 @@
 
 The yardstick is the sequence the call replaces, on separately created handles: per step ``lb_run(flow, 1)`` on an ``eager_macro=True``
 flow, then for every scalar ``set_velocity_from(flow)`` and ``lb_run(scalar, 1)`` under ``set_variant(0)``.  Both forms of the set are
-held to it with ``np.array_equal`` -- populations, rho, u, v of the flow and of every scalar -- and so to each other.  The twin of a
-shape and a number of scalars is run once, to seven steps with copies at 1, 2 and 7, and shared by every case that needs it.
+held to it with ``np.array_equal`` -- populations, rho, u, v and feq of the flow and of every scalar -- and so to each other.  The twin of
+a shape and a tuple of growth rates is run once, to seven steps with copies at 1, 2, 3 and 7, and shared by every case that needs it.
 
 Shapes: 6 x 5 (the wrap in both directions inside one lane-row), 37 x 23 (nx and ny no multiples of 4: padding lanes), 256 x 4 (exactly
 one wave and one block row), 260 x 6 (a second workgroup in x holding four cells, the x-wrap across the tile seam).  Initial state: a
 shear layer with a transverse kick (|u| <= 0.05), a striped dye, and a seeded perturbation of every population, so that no symmetry
 hides a swapped link.
+
+The growth-rate matrix (MATRIX_GS x both forms x 1 and 2 steps at 37 x 23 and 260 x 6) launches every k_fa_step<NS, REACT, LAST> and takes
+the per-member branch inside <2, true> in every order; tests/test_advected_cpu.py derives that census from the lists here.  Form 0
+runs under the flow handle's variant word (ROWS_1, ROWS_2, NT_STORES | NT_LOADS, K_DEEP7), which form 1 must ignore.  A lazy flow handle
+goes on alone behind a set run from either parity of its lattices, the second time through the captured 16-step graph.
+
+One-line defects tried against this file and the carried set's sequences (tests/test_gpu_sequences.py) in a scratch copy of the library,
+value-changing only, none kept, each run once on an MI355X; the cases each turned red, and what the 72 in-process cases of this file
+before the matrix (test_external_stream aside) made of the same library:
+  fa_step() sends ns == 1 && react to the plain instantiation   ->  test_growth_rate_matrix 4 (G0.05, form 1), the sequences 4; before: none
+  the branch in k_fa_step tests m.G[0] for every member         ->  test_growth_rate_matrix 4 (G0_0.05, form 1) and 23 earlier cases; before: 23
+                                                                    (G = (0, 0.05) takes the plain cell twice; no sequence: the one life
+                                                                    with rates (0, g) in a run of form 1 sets the scalar's f behind it)
+  fa_scalar_row<true> is given m.G[1 - i]                       ->  test_growth_rate_matrix 16, test_flow_variant_word 8, the sequences 6, 23
+                                                                    earlier cases; before: 23
+  LAST skips store_moments of scalar 1                          ->  test_growth_rate_matrix 16, test_flow_variant_word 8, the sequences 6, 23
+                                                                    earlier cases; before: 23
+  form 0 passes store_rho = false on the last step              ->  test_growth_rate_matrix 24, test_flow_variant_word 8, the lazy-flow tests 4,
+                                                                    the sequences 8, 32 earlier cases; before: 34
+  set_ran leaves a lazy flow's rho, u, v marked stale           ->  test_lazy_flow_handle 4, test_lazy_flow_graph_replay_behind_an_odd_set_run 4,
+                                                                    the sequences 6 (every lazy life); before: test_lazy_flow_handle 4
+  flow_step_macro sizes the grid for four rows a block whatever
+  the ROWS field says, the block by the field (fewer rows
+  written, none outside the lattice)                            ->  test_flow_variant_word 4 (ROWS_1, ROWS_2, form 0), the sequences 4; before: none
+  lb_set_macro on a scalar lattice drops u, v while feq is
+  stale (a scalar's own run behind set_fields keeps the set's
+  velocity)                                                     ->  the sequences 12 of 12; before: none
+Three of the eight passed every earlier case.  No defective build faulted or hung.
 """
 import ctypes as ct
 import os
@@ -22,9 +50,19 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = ((6, 5), (37, 23), (256, 4), (260, 6))
 STEPS = (1, 2, 7)
+SNAPS = (1, 2, 3, 7)                        # the steps the twin is copied at
 OMEGA_FLOW = 1.3
 SCALARS = ((1.6, 0.0), (1.1, 0.05))         # (omega, G) per scalar: different rates, one without growth
-KEYS = ("f", "rho", "u", "v")
+KEYS = ("f", "rho", "u", "v", "feq")
+# the growth-rate matrix: with react = any G != 0 and LAST = the call's last launch (advected.cpp) these reach every k_fa_step<NS, REACT,
+# LAST> and, inside <2, true>, every order of the per-member branch; in form 0 every k_ad_step<PERIODIC, REACT> per member
+# (tests/test_advected_cpu.py derives the census from these lists and fails when a case leaves them)
+MATRIX_GS = {1: ((0.,), (0.05,)), 2: ((0., 0.), (0.05, 0.), (0., 0.05), (0.05, 0.03))}
+MATRIX_SHAPES = ((37, 23), (260, 6))        # padding lanes and a ragged last block row; a second workgroup in x and the x-wrap across the seam
+MATRIX_STEPS = (1, 2)                       # LAST alone; one launch that is not the last, then LAST
+MATRIX_FORMS = (0, 1)
+MATRIX = [(gs, form, n) for ns in sorted(MATRIX_GS) for gs in MATRIX_GS[ns] for form in MATRIX_FORMS for n in MATRIX_STEPS]
+WORD_GS, WORD_STEPS = (0.05, 0.), 3         # form 0 under the flow handle's variant word
 LB_ERR_ARG, LB_ERR_STATE = -1, -3
 
 
@@ -43,13 +81,16 @@ def start(nx, ny, ns):
     return flow, dyes
 
 
-def make(nx, ny, ns, eager=True, planar_flow=False, planar_scalars=False):
+def make(nx, ny, ns, eager=True, planar_flow=False, planar_scalars=False, gs=None):
+    """gs: the growth rates, one per scalar (None: SCALARS')"""
     from LB_D2Q9.simulation import Simulation
     (rho, u, v, pf), dyes = start(nx, ny, ns)
     flow = Simulation(nx, ny, OMEGA_FLOW, bc="periodic", eager_macro=eager, planar=planar_flow)
     flow.init_equilibrium(rho, u, v, pf)
     scalars = []
-    for (om, G), (c, pc) in zip(SCALARS[:ns], dyes):
+    assert gs is None or len(gs) == ns
+    rates = SCALARS[:ns] if gs is None else [(om, g) for (om, _), g in zip(SCALARS, gs)]
+    for (om, G), (c, pc) in zip(rates, dyes):
         s = Simulation(nx, ny, om, bc="periodic", semantics="diffusion", planar=planar_scalars)
         s.set_reaction(G)
         s.init_equilibrium(c, u, v, pc)
@@ -83,21 +124,22 @@ def assert_same(got, want, what):
 _TWINS = {}
 
 
-def twin(lbhip, nx, ny, ns):
-    """{n: state} for n in STEPS, of the sequence through the existing calls; computed once per shape and number of scalars."""
-    key = (nx, ny, ns)
+def twin(lbhip, nx, ny, ns, gs=None):
+    """{n: state} for n in SNAPS, of the sequence through the existing calls; computed once per shape and growth rates."""
+    gs = tuple(float(g) for _, g in SCALARS[:ns]) if gs is None else tuple(float(g) for g in gs)
+    key = (nx, ny, gs)
     if key not in _TWINS:
         from LB_D2Q9._native import check
-        flow, scalars = make(nx, ny, ns, eager=True)
+        flow, scalars = make(nx, ny, ns, eager=True, gs=gs)
         for s in scalars:
             s.set_variant(0)
         snaps = {}
-        for n in range(1, max(STEPS) + 1):
+        for n in range(1, max(SNAPS) + 1):
             check(lbhip.lb_run(flow._h, 1))
             for s in scalars:
                 s.set_velocity_from(flow)
                 check(lbhip.lb_run(s._h, 1))
-            if n in STEPS:
+            if n in SNAPS:
                 flow.sync()
                 for s in scalars:
                     s.sync()
@@ -125,6 +167,46 @@ def test_bitwise_twin(lbhip, shape, ns, form, n):
     assert_same(got, want, "%dx%d, %d scalar(s), form %d, %d step(s)" % (shape + (ns, form, n)))
 
 
+def _gs_id(gs):
+    return "G" + "_".join("%g" % g for g in gs)
+
+
+@pytest.mark.parametrize("gs,form,n", MATRIX, ids=["%s-form%d-n%d" % (_gs_id(gs), form, n) for gs, form, n in MATRIX])
+@pytest.mark.parametrize("shape", MATRIX_SHAPES, ids=lambda s: "%dx%d" % s)
+def test_growth_rate_matrix(lbhip, shape, gs, form, n):
+    """Every k_fa_step<NS, REACT, LAST> and every order of the per-member branch (form 1), every k_ad_step<PERIODIC, REACT> reading the
+    flow's planes (form 0), against the sequence of existing calls with the same growth rates: f, rho, u, v and feq of the flow and of
+    every scalar, bit for bit."""
+    want = twin(lbhip, shape[0], shape[1], len(gs), gs)[n]
+    st = make_set(shape[0], shape[1], len(gs), gs=gs)
+    assert [float(m.G) for m in st.members] == [float(np.float32(g)) for g in gs]
+    st.run(n, form=form)
+    got = set_state(st)
+    st.close()
+    assert_same(got, want, "%dx%d, G %r, form %d, %d step(s)" % (shape + (gs, form, n)))
+
+
+def flow_words():
+    from LB_D2Q9 import variants as V
+    return (("ROWS_1", V.ROWS_1), ("ROWS_2", V.ROWS_2), ("NT_STORES_NT_LOADS", V.NT_STORES | V.NT_LOADS), ("K_DEEP7", V.K_DEEP7))
+
+
+@pytest.mark.parametrize("form", (0, 1))
+@pytest.mark.parametrize("word", range(4), ids=("ROWS_1", "ROWS_2", "NT_STORES_NT_LOADS", "K_DEEP7"))
+@pytest.mark.parametrize("shape", MATRIX_SHAPES, ids=lambda s: "%dx%d" % s)
+def test_flow_variant_word(lbhip, shape, word, form):
+    """Form 0 takes the flow's block shape and its non-temporal bits from the flow handle's variant word (flow_step_macro), form 1 ignores
+    the word: no bit moves against the twin either way."""
+    name, bits = flow_words()[word]
+    want = twin(lbhip, shape[0], shape[1], 2, WORD_GS)[WORD_STEPS]
+    st = make_set(shape[0], shape[1], 2, gs=WORD_GS)
+    st.flow.set_variant(bits)
+    st.run(WORD_STEPS, form=form)
+    got = set_state(st)
+    st.close()
+    assert_same(got, want, "%dx%d, the flow under %s, form %d" % (shape + (name, form)))
+
+
 @pytest.mark.parametrize("form", (-1, 0, 1))
 def test_default_form_and_split_runs(lbhip, form):
     """run(3) then run(4) equals run(7); form -1 is one of the two and has the same bits; step() is run(1)."""
@@ -144,18 +226,46 @@ def test_default_form_and_split_runs(lbhip, form):
     st.close()
 
 
+def lazy_flow_alone(f, nx, ny, n):
+    """f, rho, u, v of a fresh flow handle that rebuilds its fields on demand, given the populations f and run n x run(1)"""
+    from LB_D2Q9.simulation import Simulation
+    flow = Simulation(nx, ny, OMEGA_FLOW, bc="periodic", eager_macro=False)
+    flow.set_f(f)
+    for _ in range(n):
+        flow.run(1)
+    out = {"flow_" + k: a for k, a in flow.get_fields(("f", "rho", "u", "v")).items()}
+    flow.close()
+    return out
+
+
+def lazy_flow_goes_on(lbhip, shape, form, set_steps, own_steps):
+    want = twin(lbhip, shape[0], shape[1], 1)[set_steps]
+    st = make_set(shape[0], shape[1], 1, eager=False)
+    st.run(set_steps, form=form)
+    got = set_state(st)
+    assert_same(got, want, "lazy flow, form %d" % form)
+    st.flow.run(own_steps)
+    got = {"flow_" + k: a for k, a in st.flow.get_fields(("f", "rho", "u", "v")).items()}
+    st.close()
+    assert_same(got, lazy_flow_alone(want["flow_f"], shape[0], shape[1], own_steps),
+                "lazy flow alone for %d steps behind %d set steps, form %d" % (own_steps, set_steps, form))
+
+
 @pytest.mark.parametrize("form", (0, 1))
 @pytest.mark.parametrize("shape", ((37, 23), (260, 6)), ids=lambda s: "%dx%d" % s)
 def test_lazy_flow_handle(lbhip, shape, form):
-    """A flow handle that rebuilds rho, u, v on demand: the same populations, and after the call the STORED fields of the eager twin."""
-    want = twin(lbhip, shape[0], shape[1], 1)[7]
-    st = make_set(shape[0], shape[1], 1, eager=False)
-    st.run(7, form=form)
-    got = set_state(st)
-    assert_same(got, want, "lazy flow, form %d" % form)
-    st.flow.run(2)                      # the handle goes on as a lazy one
-    assert np.isfinite(st.flow.get_fields(("u",))["u"]).all()
-    st.close()
+    """A flow handle that rebuilds rho, u, v on demand: the same populations, and after the call the STORED fields of the eager twin.  Then
+    the handle goes on alone as a lazy one: run(2) behind the seven set steps, bit for bit -- f, rho, u, v -- what a fresh lazy handle makes
+    of the twin's seven-step populations in two single steps."""
+    lazy_flow_goes_on(lbhip, shape, form, 7, 2)
+
+
+@pytest.mark.parametrize("form", (0, 1))
+@pytest.mark.parametrize("shape", ((37, 23), (260, 6)), ids=lambda s: "%dx%d" % s)
+def test_lazy_flow_graph_replay_behind_an_odd_set_run(lbhip, shape, form):
+    """One set step leaves every member on the other lattice of its pair; the flow's run(33) behind it -- two replays of the captured
+    16-step graph, whose key holds that parity, and a single step -- against 33 x run(1) from the twin's one-step populations."""
+    lazy_flow_goes_on(lbhip, shape, form, 1, 33)
 
 
 @pytest.mark.parametrize("form", (0, 1))

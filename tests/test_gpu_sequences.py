@@ -37,6 +37,19 @@ The 60 cases of the later kinds, all green: rocket f 33 %, feq 28 %, rho 29 %, u
 feq 36 %, rho 38 %, u 3 %, v < 1 %, psi 10 %, F 1 %; noise f 40 %, rho 26 %, feq 26 %; expansion f 52 %, rho 35 %, feq 35 %; screened f 27 %,
 rho 31 %, feq 29 %, u 2 %, v 1 %.  A kind's twelve cases take 1.6 s (noise) to 4.2 s (expansion) together: 0.35 s a case at the most.
 
+The kind 'advected' (a flow and the 1 ... 2 scalars it carries: lb_run_advected, coupled.Advected_Scalars) has a driver of its own,
+test_random_call_sequence_of_a_carried_set, since its members are unlike lattices that also live as ordinary handles between the set's
+runs: runs of the set in either form and of one member alone (a flow run of more than 16 steps in every life: the captured graph
+replays behind a set run of either parity), set_f on a member, init_equilibrium on the flow, a scalar's growth rate switched between 0
+and non-zero and back between set runs, set_fields on a scalar with its own run behind it; variant words on the flow in front of a set
+run of form 0 and of its own run, tile shapes on a scalar, reads of every member and of the set, a checkpoint through a closed set.
+Families: the flow handle's flag.  A lazy flow whose fields are those of its own run holds rho, u, v rebuilt from the post-collision
+populations -- the eager twin's moments, not its bits --: there, and only there, the flow's rho, u, v, feq are held bitwise to a fresh lazy
+handle given the twin's populations.  Property B uses the two existing contracts unchanged: the flow against O2Sim, every scalar against
+its float64 model fed, step by step, the velocity the twin stored.  Measured on an MI355X, twelve cases green in 2.6 s (0.27 s at the
+most), the largest share of its bound: the flow's f 60 %, rho 48 %, u 6 %, v 6 %; a scalar's f 50 %, rho 28 %, feq 26 %.  The defects tried
+against it: the table in tests/test_gpu_advected.py.
+
 One-line defects tried against this file (value-changing only; none kept), with the cases each turned red:
   lb_set_f without its ensure_macro                                      ->  4 (flow: pipe 3, periodic 1 and 3, cavity 4 -- lazy
                                                                             families, compared behind a set_f; one by A, three by B)
@@ -71,7 +84,8 @@ from kernel_variants import same_bits
 
 pytestmark = pytest.mark.gpu
 
-CASES = [(k, f, s) for k in S.KINDS for f in S.FAMILIES[k] for s in S.SEEDS]
+CASES = [(k, f, s) for k in S.KINDS for f in S.FAMILIES[k] for s in S.SEEDS if k != "advected"]       # (a driver of its own: below)
+ADVECTED_CASES = [("advected", f, s) for f in S.FAMILIES["advected"] for s in S.SEEDS]
 
 
 @pytest.mark.parametrize("kind,family,seed", CASES, ids=["%s-%s-%d" % c for c in CASES])
@@ -98,6 +112,39 @@ def test_random_call_sequence(lbhip, oracle, tmp_path, kind, family, seed):
                 if kind in ("noise", "expansion"):  # the noisy collisions since the last set_noise, per strain: every player's the same
                     assert subject.noise_counters() == twin.noise_counters() == ref.noise_counters(), \
                         (what, subject.noise_counters(), twin.noise_counters(), ref.noise_counters())
+    finally:
+        subject.close()
+        twin.close()
+
+
+@pytest.mark.parametrize("kind,family,seed", ADVECTED_CASES, ids=["%s-%s-%d" % c for c in ADVECTED_CASES])
+def test_random_call_sequence_of_a_carried_set(lbhip, oracle, tmp_path, kind, family, seed):
+    """A flow and the scalars it carries (lb_run_advected) through a life in which the members are ordinary handles between the set's
+    runs.  A: the subject (an Advected_Scalars, the family's flag on the flow, drawn layouts, forms, variant words, reads, a checkpoint
+    through a closed set) equals the twin (S.AdvectedGpu: the three existing calls per set step) in f, rho, u, v and feq of every member --
+    in the lazy family, while the flow's fields are those of a run of its own, the flow's rho, u, v, feq equal those of a lazy handle
+    given the twin's populations.  B: the twin's flow against O2Sim under the flow contract, every scalar against its float64 model under the scalar
+    contract, the model fed the velocity the twin stored step by step (S.hold_advected)."""
+    case, ops = S.case_of(kind, family, seed), S.generate(kind, family, seed)
+    cuts = S.cut_points(ops, kind, family, seed)
+    subject, twin = S.AdvectedGpu(case, tmpdir=tmp_path), S.AdvectedGpu(case, plain=True)
+    ref = S.AdvectedRef(case, oracle)
+    try:
+        for i, op in enumerate(ops):
+            if S.is_effective(op):
+                subject.effective(op)
+                twin.effective(op)
+                if op[0] == "run":
+                    ref.feed = twin.history
+                ref.effective(op)
+            else:
+                subject.transparent(op)
+            if i in cuts:
+                what = "%s %s seed %d, behind op %d %r of %r" % (kind, family, seed, i, op, ops[:i + 1])
+                want = twin.snapshot()
+                assert subject.flow_fields_from == twin.flow_fields_from
+                same_bits(subject.snapshot(), want, what, fields=tuple(sorted(want)))
+                S.hold_advected("%s %s seed %d op %d, twin / reference" % (kind, family, seed, i), twin, ref)
     finally:
         subject.close()
         twin.close()

@@ -3,7 +3,9 @@ deterministic and covers its tables; on exactly these inputs -- mid-life paramet
 model of every kind that has one stays within the kind's contract of the float64 model, and
 the flow kinds' oracle stays in the range the contract was established in; the op lists of the kinds that were here first have not
 moved; where a collision has thresholds, the float64 model keeps every thresholded quantity further from its threshold than twice the
-contract's bound, so that an implementation inside the contract cannot sit on the other side."""
+contract's bound, so that an implementation inside the contract cannot sit on the other side.  For a flow and the scalars it carries
+(kind 'advected') the references are played alone, step by step and on to the full 120 steps: the flow stays in the contract's range,
+every growing dye inside (0, 1)."""
 import hashlib
 
 import numpy as np
@@ -18,6 +20,10 @@ HAVE_DTYPE = ("scalar", "multifield", "poisson", "porous", "multifluid", "rocket
 OLD_DIGESTS = dict(flow="5366cbf62836f6752d9dd508bc3f3c42b99dbceb", scalar="500005ea4af649b7af3a4fe4872ce240dc235b0b",
                    multifield="4758ca676c4fb3b62d99f82d2ee9f5f90d6d4c26", poisson="37d28bcd89142eb087f330d50b352998b3e4d9b2",
                    porous="7dde112a067b46efc2be02930dee8c02e2f48c68", multifluid="a0e62ab06d1ecefccb10fe759f0de28c9317e8cf")
+# the same for the five kinds that came next, taken before 'advected' was added, and for 'advected' itself once its lists were final
+LATER_DIGESTS = dict(rocket="6462665ec6f23e8e42e49e5536dd108d8803ba98", nutrient="35e0203670bb7504135cc5a04a14e97133def6f9",
+                     noise="d82ce5212a4895d2d2fd06112cc098e57d49089a", expansion="de72f120ec9b31fa0e26774899ae7637fc92deee",
+                     screened="6c2e4dd2df30d3a102ce3ddddbe1d024d195ca16", advected="39e2dddd2b63b87ae25c6278b327b3bddd0d9cab")
 
 
 @pytest.mark.parametrize("kind,family,seed", CASES, ids=ids(CASES))
@@ -51,7 +57,7 @@ def test_every_op_of_the_tables_occurs(kind):
     assert {op[1] for op in ops if op[0] in ("run", "solve")} == set(S.RUN_LENGTHS)
     assert any("feq" in op[1] for op in ops if op[0] == "get_fields")
     behind = {S.generate(kind, f, s)[i][0] for f in S.FAMILIES[kind] for s in S.SEEDS for i in S.cut_points(S.generate(kind, f, s), kind, f, s)}
-    assert behind >= {"run", "phase_step", "set_f"}, behind                                   # what a comparison follows
+    assert behind >= ({"run", "member_run", "set_f"} if kind == "advected" else {"run", "phase_step", "set_f"}), behind     # what a comparison follows
     if kind == "multifluid":
         for name in ("set_interactions", "set_reactions"):
             assert {op[1] for op in ops if op[0] == name} == {0, 1, 2}
@@ -83,6 +89,43 @@ def test_every_op_of_the_tables_occurs(kind):
         assert {op[1] for op in ops if op[0] == "set_reaction"} == {0, 1, 2}
     if kind == "screened":
         assert {S.case_of(kind, "open", s)["nx"] for s in S.SEEDS} == {n for n, _ in S.SPECTRAL_SHAPES}
+    if kind == "advected":
+        the_set_words, own_words, scalar_words = S.advected_words()
+        crossed, met = set(), set()                     # (scalar, its rate in three set runs one after the other); (shape, scalars)
+        for f in S.FAMILIES[kind]:
+            cases = [S.case_of(kind, f, s) for s in S.SEEDS]
+            assert [c["ns"] for c in cases] == [1 + s % 2 for s in S.SEEDS] and {c["eager"] for c in cases} == {f == "eager"}
+            assert [(c["nx"], c["ny"]) for c in cases[:2]] in (list(S.ADVECTED_SHAPES), list(S.ADVECTED_SHAPES[::-1]))      # alternating
+            met.update((c["nx"], c["ny"], c["ns"]) for c in cases)
+            for c, s in zip(cases, S.SEEDS):
+                life, rates, seen = S.generate(kind, f, s), list(c["Gs"]), [[] for _ in range(c["ns"])]
+                assert S.advected_rates(f, s)[0] == c["Gs"] and all(g in (0., S._r32(S.ADVECTED_G)) for g in rates)
+                assert any(op[0] == "member_run" and op[3] == -1 and op[1] > 16 for op in life)              # the graph replays
+                for op, nxt in zip(life, life[1:] + [None]):
+                    if op[0] == "set_reaction":
+                        assert op[2] in (0., S._r32(S.ADVECTED_G)) and op[2] != rates[op[1]]
+                        rates[op[1]] = op[2]
+                    if op[0] == "run":
+                        for i, g in enumerate(rates):
+                            seen[i].append(g != 0.)
+                    if op[0] == "set_fields":           # the scalar's own run uses the velocity, a set run behind it replaces it
+                        behind = [o for o in life[life.index(op) + 1:] if S.is_effective(o)]
+                        assert behind[0][0] == "member_run" and behind[0][3] == op[2] and any(o[0] == "run" for o in behind)
+                    if op[0] == "set_variant":          # each word in front of the run that reads it; the set's run of form 0
+                        if nxt[0] == "run":
+                            assert op[2] == -1 and op[1] in the_set_words and nxt[3] == 0 and not nxt[2], (op, nxt)
+                        else:
+                            assert nxt[0] == "member_run" and nxt[3] == op[2] and op[1] in (own_words if op[2] == -1 else scalar_words), (op, nxt)
+                for i, marks in enumerate(seen):
+                    crossed |= {(i, tuple(marks[k:k + 3])) for k in range(len(marks) - 2)}
+        assert met == {(nx, ny, ns) for nx, ny in S.ADVECTED_SHAPES for ns in (1, 2)}, met                # either count of scalars at either shape
+        assert crossed >= {(i, way) for i in (0, 1) for way in ((False, True, False), (True, False, True))}, crossed
+        assert {c["planar_flow"] for f in S.FAMILIES[kind] for c in [S.case_of(kind, f, s) for s in S.SEEDS]} == {True, False}
+        assert {c["planar_scalars"] for f in S.FAMILIES[kind] for c in [S.case_of(kind, f, s) for s in S.SEEDS]} == {True, False}
+        assert {op[3] for op in ops if op[0] == "run"} == {-1, 0, 1}                                    # every form
+        assert {op[2] for op in ops if op[0] in ("set_f", "set_fields")} == {-1, 0, 1}                      # set_f on the flow and on either scalar
+        assert {op[3] for op in ops if op[0] == "member_run"} == {-1, 0, 1}
+        assert any("feq_flow" in op[1] for op in ops if op[0] == "get_fields") and any("feq" in op[1] for op in ops if op[0] == "member_fields")
 
 
 def test_the_cases_that_were_here_first_have_not_moved():
@@ -96,6 +139,18 @@ def test_the_cases_that_were_here_first_have_not_moved():
     assert sum(len(S.FAMILIES[k]) * len(S.SEEDS) for k in OLD_DIGESTS) == 102
 
 
+def test_the_later_kinds_have_not_moved_either():
+    """The 60 op lists of rocket ... screened as they were before the carried set joined, and the twelve of the carried set that
+    tests/test_gpu_sequences.py's defect table was recorded on."""
+    for kind, want in LATER_DIGESTS.items():
+        h = hashlib.sha1()
+        for f in S.FAMILIES[kind]:
+            for s in S.SEEDS:
+                h.update(repr(S.generate(kind, f, s)).encode())
+        assert h.hexdigest() == want, kind
+    assert set(OLD_DIGESTS) | set(LATER_DIGESTS) == set(S.KINDS) and S.KINDS[-1] == "advected"
+
+
 @pytest.mark.parametrize("kind,family,seed", CASES, ids=ids(CASES))
 def test_transparent_ops_sit_where_they_can_matter(kind, family, seed):
     """In every sequence: a read lies behind a stepping op (only there can it find macro_valid / feq_valid stale, and only from there
@@ -106,7 +161,7 @@ def test_transparent_ops_sit_where_they_can_matter(kind, family, seed):
     assert any(op[0] == "get_fields" and stepped[i] for i, op in enumerate(ops))
     words = [i for i, op in enumerate(ops) if op[0] == "set_variant"]
     assert len(words) == (S.N_VARIANTS if S.variant_words(kind) else 0)
-    assert all(ops[i + 1][0] == "run" for i in words)
+    assert all(ops[i + 1][0] in (("run", "member_run") if kind == "advected" else ("run",)) for i in words)     # (a set's run or a member's own)
     has_mask = kind == "flow" and S.case_of(kind, family, seed)["mask"] is not None
     for op in ops:
         if op[0] in ("reupload_mask", "mask_off_on"):
@@ -185,6 +240,56 @@ def test_flow_oracle_stays_in_the_contracts_range(oracle, kind, family, seed):
 
     S.play(o, ops, look, [i for i, op in enumerate(ops) if op[0] in S.STEPPING])
     print("%s seed %d: rho %.3f ... %.3f, max |u| %.4f" % (family, seed, worst[0], worst[1], worst[2]))
+
+
+ADVECTED_CASES = [c for c in CASES if c[0] == "advected"]
+
+
+@pytest.mark.parametrize("kind,family,seed", ADVECTED_CASES, ids=ids(ADVECTED_CASES))
+def test_carried_set_references_stay_in_the_contracts_range(oracle, kind, family, seed):
+    """The references of a carried set alone, O2Sim's own u, v standing in for the GPU twin's history, looked at after EVERY step of the
+    life and after every other effective op (set_f, init_equilibrium, set_reaction in the middle of it included): the flow inside the
+    range the flow contract was established in (rho 0.5 ... 1.5, |u| < 0.15); every scalar finite, and the density of its populations
+    inside (0, 1) while its G != 0 (the growth term's fixed points).  Prints the smallest margins of the life."""
+    case, ops = S.case_of(kind, family, seed), S.generate(kind, family, seed)
+    ref = S.AdvectedRef(case, oracle)
+    worst = dict(rho=np.inf, speed=np.inf, dye=np.inf)
+    steps = [0]
+
+    def look(op):
+        g = ref.flow
+        speed = float(np.sqrt(g.u.astype(np.float64) ** 2 + g.v.astype(np.float64) ** 2).max())
+        lo, hi = float(g.rho.min()), float(g.rho.max())
+        assert 0.5 < lo and hi < 1.5 and speed < 0.15, (steps[0], op, lo, hi, speed)
+        worst["rho"], worst["speed"] = min(worst["rho"], lo - 0.5, 1.5 - hi), min(worst["speed"], 0.15 - speed)
+        for i, m in enumerate(ref.scalars):
+            assert all(np.isfinite(a).all() for a in m.get_fields().values()), (steps[0], op, i)
+            if m.G != 0:
+                rho = m.f.sum(axis=2)
+                assert 0. < rho.min() and rho.max() < 1., (steps[0], op, i, float(rho.min()), float(rho.max()))
+                worst["dye"] = min(worst["dye"], float(rho.min()), 1. - float(rho.max()))
+
+    look(None)
+    for op in ops:
+        if not S.is_effective(op):
+            continue
+        if op[0] in ("run", "member_run"):              # step by step
+            for _ in range(op[1]):
+                ref.effective((op[0], 1) + tuple(op[2:]))
+                steps[0] += 1
+                look(op)
+        else:
+            ref.effective(op)
+            look(op)
+    assert steps[0] == S.counts(ops)[2] <= S.MAX_STEPS and all(c.steps <= steps[0] for c in ref.clocks)
+    life = steps[0]
+    while steps[0] < S.MAX_STEPS:                       # ... and on to the full MAX_STEPS, had the last run been that long
+        ref.effective(("run", 1, 0, -1))
+        steps[0] += 1
+        look(("run", 1, 0, -1))
+    print("(the life has %d steps)" % life, end=" ")
+    print("%s seed %d, %d steps: smallest margins: the flow's rho %.3f from 0.5 / 1.5, |u| %.4f below 0.15, a growing dye's rho %.3f from 0 / 1"
+          % (family, seed, steps[0], worst["rho"], worst["speed"], worst["dye"]))
 
 
 # ---- the thresholds of the noisy collisions and of the colony -------------------------------------------------------------------------
