@@ -28,6 +28,8 @@ LB_REACT_EAT, LB_REACT_GROW = 0, 1
 MC_MAX, MC_MAX_INTER, MC_MAX_REACT = 3, 6, 4
 LB_ROCKET_FLOW, LB_ROCKET_FORCES = 0, 1
 RY_ROWS = 10             # rows of a 256-cell tile a workgroup of k_ry_step owns (csrc/plan_consts.h; lb_hot_kernel names it)
+MC_ROWS = {1: 6, 2: 6, 3: 2}    # ... of k_mc_step, by the number of fluids (csrc/multifluid.cpp, step_rows)
+SN_ROWS = 4              # ... of k_sn_step (csrc/nutrient_launch.h)
 
 ABI_VERSION = 11
 
